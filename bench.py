@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoising-steps/sec of the score-GPT forward at the Franka-kitchen shape.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE denoising step = one GCDenoiser.forward (score-GPT forward + Karras preconditioning)
@@ -14,7 +14,19 @@ ranks / max-over-ranks time.
 `torch.distributed.run` (one process per GPU, RCCL); the ranks verify the group with an all-reduce of their rank
 numbers before anything is timed.  A world size that disagrees with --gpus, or fewer visible GPUs than N, is an error.
 
-Rank 0 prints ONE JSON line with the driver's fields plus
+A plain run does only what the headline needs: set up, W warm-up steps, the untimed clock-settle loop, K timed steps,
+and rank 0 prints ONE JSON line with the driver's fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` = milliseconds of one timed step, ...).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed as DIR/<name>.npy (float32 /
+float64, at most 64 MB in all; a larger array is cut to a fixed, seeded sample of its rows):
+  forward: `denoised` = GCDenoiser.forward's output (rank 0's shard);
+  train:   `loss` and `params` = the model's flat parameters after the step (the untimed settle loop runs a
+           clock-dependent number of train steps before them: pass --settle-ms 0 so that every run takes the same steps).
+The inputs are seeded, so the same arguments give the same inputs on every run.
+
+`--full` adds everything else the benchmark measures, in the same run and after the headline's timed region; rank 0's
+line then also carries
   "roofline":     the dominant kernel's achieved TFLOP/s (algorithmic FLOPs / HIP-event time on the
                   launch stream) against the dense bf16 MFMA peak; `traffic` = HBM bytes per launch from two
                   rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of this very script, run as child processes;
@@ -25,7 +37,10 @@ Rank 0 prints ONE JSON line with the driver's fields plus
   "cold_ms_per_step" / "long_run": the K steps timed straight behind the W warm-up steps (before the clock-settle loop),
                   and >= 200 steps of the settled loop -- `value` itself is exactly K steps behind the settle loop;
   "cpu_baseline": the reference's CPU path (ATen restatement in oracle/beso_oracle_torch.py) timed on this box's
-                  host cores on a bounded sample of the same workload.
+                  host cores on a bounded sample of the same workload;
+  "other_configs": short runs of BASELINE.json configs 0, 2, 3 and 4 and of the small batches.
+The kernel timing of "roofline" comes from K more steps of its own with HIP events on the dominant launch site, so that
+`value` is measured the same way with and without --full.
 
 `--workload train` times BASELINE configs[2]'s per-GPU share instead: BesoAgent.train_step (score-matching loss,
 backward, AdamW, EMA; kitchen dropouts and cond_mask_prob = 0.1) at 1024 samples per GPU, gradients all-reduced over
@@ -350,7 +365,8 @@ def timed(step, steps, world):
     return time.perf_counter() - t0, out
 
 
-def run_forward(args, world, rank, dev):
+def run_forward(args, world, rank, dev, outputs=None):
+    """`outputs` (a dict, or None): receives what the last timed step returned, for --dump-outputs."""
     from beso_amd import synthetic as S
     cfg = S.SHAPES[args.config]
     w = S.make_weights(cfg, seed=0, std=0.02)
@@ -367,36 +383,45 @@ def run_forward(args, world, rank, dev):
         # (score_wrappers.py:81-96) -- incl. the packed-weight cache check of every call, not a pre-fetched image
         return model(state, action, goal, sigma)
 
+    full = getattr(args, "full", False)
     with torch.no_grad():
         for _ in range(args.warmup):
             out = step()
         torch.cuda.synchronize()
-        # the driver's protocol taken literally: K steps straight behind the W warm-up steps (a cold MI355X is still ramping)
-        cold_elapsed, _ = timed(step, args.steps, world)
+        cold_elapsed = None
+        if full:
+            # the driver's protocol taken literally: K steps straight behind the W warm-up steps (a cold MI355X is still ramping)
+            cold_elapsed, _ = timed(step, args.steps, world)
         settled = settle(step, args.settle_ms)
-        # which launch site dominates?  time each once, then instrument the dominant one
-        sites = ["fused_layer", "gemm_fc1", "gemm_fc2", "gemm_qkv", "gemm_proj", "attention", "layernorm"]
-        site_ms = {}
-        for site in sites:
-            rt.profile_enable(site)
-            step()
-            torch.cuda.synchronize()
-            ms, n = rt.profile_read()
-            if n:
-                site_ms[site] = (ms, n)
-        rt.profile_enable("off")
-        dominant = args.site or max(site_ms, key=lambda k: site_ms[k][0])
-        rt.profile_enable(dominant)
+        # the headline: K steps behind the settle loop, nothing instrumented
         elapsed, out = timed(step, args.steps, world)
-        kern_ms, kern_n = rt.profile_read()
-        rt.profile_enable("off")
         assert torch.isfinite(out).all()
-        # ... and a region long enough to carry a sub-percent margin (>= 200 steps of the same settled loop)
-        long_steps = max(200, args.steps)
-        long_elapsed, _ = timed(step, long_steps, world)
-        # the parity mode of the same kernel, timed beside the headline (rank 0, N = 1: it is not part of `value`)
+        if outputs is not None and rank == 0:
+            outputs["denoised"] = out.float().cpu().numpy()
+        site_ms = {}
         parity = fp16 = None
-        if world == 1 and not args.no_parity_line and args.precision == "bf16" and args.config in ("kitchen", "block_push"):
+        if full:
+            # which launch site dominates?  time each once, then instrument the dominant one over K steps of its own
+            sites = ["fused_layer", "gemm_fc1", "gemm_fc2", "gemm_qkv", "gemm_proj", "attention", "layernorm"]
+            for site in sites:
+                rt.profile_enable(site)
+                step()
+                torch.cuda.synchronize()
+                ms, n = rt.profile_read()
+                if n:
+                    site_ms[site] = (ms, n)
+            rt.profile_enable("off")
+            dominant = args.site or max(site_ms, key=lambda k: site_ms[k][0])
+            rt.profile_enable(dominant)
+            timed(step, args.steps, world)
+            kern_ms, kern_n = rt.profile_read()
+            rt.profile_enable("off")
+            # ... and a region long enough to carry a sub-percent margin (>= 200 steps of the same settled loop)
+            long_steps = max(200, args.steps)
+            long_elapsed, _ = timed(step, long_steps, world)
+        # the parity mode of the same kernel, timed beside the headline (rank 0, N = 1: it is not part of `value`)
+        if (full and world == 1 and not args.no_parity_line and args.precision == "bf16"
+                and args.config in ("kitchen", "block_push")):
             mx = build_model(cfg, w, "bf16x3", dev)
             ix = mx.inner_model
             rtx = ix.runtime(cfg.sigma_data)
@@ -437,13 +462,39 @@ def run_forward(args, world, rank, dev):
                             "v_mfma_f32_16x16x32_f16, the bf16 MFMA rate, 11-bit significands); vs the reference's vectors "
                             "1.3e-3 .. 1.8e-3 where bf16 measures 7e-3 .. 1.2e-2 (tests/test_gpu_parity.py)"}
     if world > 1:
-        tmax = torch.tensor([elapsed, cold_elapsed, long_elapsed], device=dev, dtype=torch.float64)
+        tmax = torch.tensor([elapsed] + ([cold_elapsed, long_elapsed] if full else []), device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
-        elapsed, cold_elapsed, long_elapsed = (float(v) for v in tmax.tolist())
+        elapsed, *rest = (float(v) for v in tmax.tolist())
+        if full:
+            cold_elapsed, long_elapsed = rest
     if rank != 0:
         return None
     F = cfg.flops_per_sample()
     D, T, t = cfg.embed_dim, cfg.block_size, cfg.obs_seq_len
+    steps_per_s = world * args.steps / elapsed
+    fwd_tflops = B * F * args.steps / elapsed / 1e12          # per GPU
+    peak = PEAK_TFLOPS[args.precision]
+    result = {
+        "metric": "denoising-steps/sec (score-GPT fwd) at kitchen obs-dim",
+        "value": steps_per_s, "unit": f"denoise-steps/s (one step = GCDenoiser.forward over B={B} samples per GPU)",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+        "config": {"workload": f"BASELINE.json configs[1]: Franka {args.config} score-GPT fwd "
+                               f"(GCDenoiser.forward), batch={B} synthetic obs/goal per GPU, 1 NFE per step",
+                   "obs_dim": cfg.obs_dim, "act_dim": cfg.act_dim, "window": cfg.obs_seq_len,
+                   "goal_seq_len": cfg.goal_seq_len, "embed_dim": D, "n_layers": cfg.n_layers,
+                   "n_heads": cfg.n_heads, "tokens_per_sample": T, "batch_per_gpu": B,
+                   "parallelism": f"batch-sharded x{world}, no collective in the loop",
+                   "weights": "seeded N(0,0.02) recipe (no trained checkpoints shipped)", "sigma": 0.3},
+        "untimed_settle_steps": settled,
+        "sample_nfe_per_s": steps_per_s * B,
+        "flops_per_sample_forward": F,
+        "forward_tflops_per_gpu": fwd_tflops,
+        "forward_frac_of_mfma_peak": fwd_tflops / peak,
+    }
+    if not full:
+        return result
     M = B * T
     # algorithmic FLOPs of ONE launch of each launch site: the REFERENCE's work
     layers_flops = (24.0 * T * D * D + 4.0 * T * T * D) * B * cfg.n_layers
@@ -460,12 +511,9 @@ def run_forward(args, world, rank, dev):
         # out-projection and the MLP (nothing else reaches the head): 18 D^2 per skipped token
         executed["fused_layer"] = layers_flops - 18.0 * (T - t) * D * D * B
         kernel_symbol = "beso::layers_kernel<3,12> (all transformer layers, one launch)"
-    steps_per_s = world * args.steps / elapsed
-    fwd_tflops = B * F * args.steps / elapsed / 1e12          # per GPU
     avg_ms = kern_ms / max(kern_n, 1)
     ach = site_flops.get(dominant, 0.0) / (avg_ms * 1e-3) / 1e12 if kern_n else 0.0
     ach_x = executed.get(dominant, 0.0) / (avg_ms * 1e-3) / 1e12 if kern_n else 0.0
-    peak = PEAK_TFLOPS[args.precision]
     traffic, traffic_detail = (None, {"source": "not measured (N > 1 or --no-traffic)"})
     if world == 1 and not args.no_traffic and dominant == "fused_layer":
         traffic, traffic_detail = measure_traffic(args)
@@ -473,27 +521,10 @@ def run_forward(args, world, rank, dev):
         parity["forward_frac_of_bf16_mfma_peak"] = B * F / (parity["ms_per_step"] * 1e-3) / 1e12 / PEAK_TFLOPS["bf16"]
         parity["executed_mfma_flops_over_algorithmic"] = 3.0
         parity["forward_frac_ceiling"] = B * F / (1e3 * elapsed / args.steps * 1e-3) / 1e12 / PEAK_TFLOPS["bf16"] / 3.0
-    result = {
-        "metric": "denoising-steps/sec (score-GPT fwd) at kitchen obs-dim",
-        "value": steps_per_s, "unit": f"denoise-steps/s (one step = GCDenoiser.forward over B={B} samples per GPU)",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-        "config": {"workload": f"BASELINE.json configs[1]: Franka {args.config} score-GPT fwd "
-                               f"(GCDenoiser.forward), batch={B} synthetic obs/goal per GPU, 1 NFE per step",
-                   "obs_dim": cfg.obs_dim, "act_dim": cfg.act_dim, "window": cfg.obs_seq_len,
-                   "goal_seq_len": cfg.goal_seq_len, "embed_dim": D, "n_layers": cfg.n_layers,
-                   "n_heads": cfg.n_heads, "tokens_per_sample": T, "batch_per_gpu": B,
-                   "parallelism": f"batch-sharded x{world}, no collective in the loop",
-                   "weights": "seeded N(0,0.02) recipe (no trained checkpoints shipped)", "sigma": 0.3},
-        "untimed_settle_steps": settled,
+    result.update({
         "cold_ms_per_step": 1e3 * cold_elapsed / args.steps,
         "long_run": {"steps": long_steps, "ms_per_step": 1e3 * long_elapsed / long_steps,
                      "frac_of_mfma_peak": B * F / (long_elapsed / long_steps) / 1e12 / peak},
-        "sample_nfe_per_s": steps_per_s * B,
-        "flops_per_sample_forward": F,
-        "forward_tflops_per_gpu": fwd_tflops,
-        "forward_frac_of_mfma_peak": fwd_tflops / peak,
         "roofline": {"bound": "mfma", "kernel": dominant, "achieved": ach, "peak": peak, "unit": "TFLOP/s",
                      "frac": ach / peak, "traffic": traffic,
                      "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE*2 + WRITE_SIZE)", "traffic_detail": traffic_detail,
@@ -502,7 +533,7 @@ def run_forward(args, world, rank, dev):
                      "executed_flops_per_launch": executed.get(dominant, 0.0), "achieved_executed": ach_x,
                      "frac_executed": ach_x / peak,
                      "site_ms_one_forward": {k: v[0] for k, v in site_ms.items()}},
-    }
+    })
     if parity is not None:
         result["parity_mode"] = parity
     if fp16 is not None:
@@ -615,8 +646,9 @@ def small_batches(dev):
 
 
 
-def run_train(args, world, rank, dev):
-    """BASELINE configs[2] per-GPU share: kitchen train_step, 1024 samples per GPU, shipped dropouts, cond_mask_prob 0.1."""
+def run_train(args, world, rank, dev, outputs=None):
+    """BASELINE configs[2] per-GPU share: kitchen train_step, 1024 samples per GPU, shipped dropouts, cond_mask_prob 0.1.
+    `outputs` (a dict, or None): receives the last timed step's loss and the parameters it left, for --dump-outputs."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from _agent import build_agent
     from beso_amd import distributed as bdist
@@ -651,6 +683,9 @@ def run_train(args, world, rank, dev):
     if rank != 0:
         return None
     assert np.isfinite(loss) and (getattr(agent, "_hip_step", None) is not None or str(dev) == "cpu")
+    if outputs is not None:
+        outputs["loss"] = np.array([loss], dtype=np.float64)
+        outputs["params"] = torch.cat([q.detach().reshape(-1).float() for q in agent.model.get_params()]).cpu().numpy()
     flops = 3.0 * cfg.flops_per_sample() * B                # forward + data gradients + weight gradients, per GPU
     ms = 1e3 * elapsed / args.steps
     ach = flops / (ms * 1e-3) / 1e12
@@ -675,6 +710,28 @@ def run_train(args, world, rank, dev):
     }
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """DIR/<name>.npy for every array, float32 (float64 stays float64), at most `budget` bytes in all: smallest first, each
+    array gets an equal share of what is left; one that does not fit its share is cut to a fixed, seeded sample of its
+    leading rows, kept in order."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    left = budget
+    for i, name in enumerate(sorted(arrays, key=lambda k: arrays[k].nbytes)):
+        a = arrays[name]
+        share = left // (len(arrays) - i)
+        if a.nbytes > share and a.ndim > 0:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--cpu-worker":
         return cpu_worker(sys.argv[2:])
@@ -693,6 +750,12 @@ def main():
     ap.add_argument("--no-traffic", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of BASELINE configs 0, 2, 3, 4 behind the headline")
     ap.add_argument("--site", default=None, help="launch site timed for the roofline object")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline and HBM traffic, cold and long runs, the "
+                         "parity and fp16 modes, the CPU baseline, the other BASELINE configurations (the --no-* options "
+                         "drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--dry-run-backend", default=None, choices=["gloo"],
                     help="launcher self-test without GPUs: spawn the ranks, verify the group over this backend, print n_gpus")
     args = ap.parse_args()
@@ -700,6 +763,8 @@ def main():
         args.batch = 4096 if args.workload == "forward" else 1024
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     maybe_relaunch(args)
     world, rank, local_rank, verified = init_ranks(args)
     if args.dry_run_backend is not None:
@@ -715,7 +780,11 @@ def main():
     torch.cuda.set_device(dev)
     from beso_amd import distributed as bdist
     numa = bdist.pin_to_gpu_numa_node(local_rank) if world > 1 else None       # one rank per GPU: host threads beside it
-    result = run_forward(args, world, rank, dev) if args.workload == "forward" else run_train(args, world, rank, dev)
+    outputs = {} if args.dump_outputs else None
+    run = run_forward if args.workload == "forward" else run_train
+    result = run(args, world, rank, dev, outputs)
+    if rank == 0 and outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         result["ranks_verified"] = verified
         result["numa_node_of_rank0"] = numa

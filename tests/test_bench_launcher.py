@@ -40,3 +40,26 @@ def test_world_size_that_disagrees_with_gpus_is_an_error():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run-backend", "gloo"], capture_output=True, text=True,
                        env=_env(WORLD_SIZE="4", RANK="0", LOCAL_RANK="0"), timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE=4" in r.stderr
+
+
+def test_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (float64 kept), the whole under the byte budget; an array
+    that does not fit is cut to the same seeded sample of rows on every call."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    big = np.arange(4096 * 90, dtype=np.float64).reshape(4096, 90).astype(np.float32)
+    loss = np.array([0.25], dtype=np.float64)
+    budget = 256 << 10
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"denoised": big, "loss": loss, "params": np.ones(1000, np.float16)}, budget=budget)
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(a) == ["denoised.npy", "loss.npy", "params.npy"]
+    assert a["loss.npy"].dtype == np.float64 and a["loss.npy"].tolist() == [0.25]
+    assert a["params.npy"].dtype == np.float32 and a["params.npy"].shape == (1000,)
+    d = a["denoised.npy"]
+    assert d.dtype == np.float32 and d.shape[1] == 90 and 0 < d.shape[0] < 4096
+    assert sum(v.nbytes for v in a.values()) <= budget
+    rows = d[:, 0] / 90                                          # rows are a sorted sample of the original ones
+    assert np.array_equal(d, big[rows.astype(np.int64)]) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(d, np.load(tmp_path / "b" / "denoised.npy"))

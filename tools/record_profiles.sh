@@ -7,7 +7,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-traffic --no-other-configs"       # (bench.py runs its own PMC passes otherwise)
+BENCH="python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-traffic --no-other-configs"       # (bench.py runs its own PMC passes otherwise)
 BENCHP="$BENCH --no-parity-line"                                                         # counter passes: the bf16 instance only
 cd /tmp
 rm -rf $OUT/prof_${TAG}_stats $OUT/prof_${TAG}_fetch $OUT/prof_${TAG}_write $OUT/prof_${TAG}_sq
@@ -19,5 +19,5 @@ cd $REPO
 # traffic.json first (bench.py quotes it), then the bench line of the same box
 python tools/pmc_summary.py $TAG --out gpurun_out/profiles_$TAG
 cp gpurun_out/profiles_$TAG/traffic.json profiles/traffic.json
-python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 python tools/pmc_summary.py $TAG --out gpurun_out/profiles_$TAG
