@@ -726,4 +726,132 @@ def _out_of_scope(name, why):
 # the reference's sample_dpmpp_2m_sde cannot run (it reads undefined names, gc_sampling.py:817-820) and nothing
 # dispatches to it (beso_agent.py:452 maps 'dpmpp_2m_sde' to sample_dpmpp_sde): there is no behaviour to reproduce
 sample_dpmpp_2m_sde = _out_of_scope('sample_dpmpp_2m_sde', 'the reference function raises NameError; use sample_dpmpp_sde')
-log_likelihood = _out_of_scope('log_likelihood', 'needs the torchdiffeq ODE integrator')
+
+
+# ------------------------------------------------------------------------------------------------
+# log-likelihood (:471-497): the probability-flow ODE from sigma_min to sigma_max with Hutchinson's trace estimate
+# ------------------------------------------------------------------------------------------------
+# Dormand-Prince 5(4) (Hairer, Norsett & Wanner, Solving ODEs I, II.5): nodes, stage weights, 5th-order weights and the
+# difference of the 5th- and 4th-order weights (the error estimate)
+_DP_C = (0., 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1., 1.)
+_DP_A = ((),
+         (1 / 5,),
+         (3 / 40, 9 / 40),
+         (44 / 45, -56 / 15, 32 / 9),
+         (19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729),
+         (9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656),
+         (35 / 384, 0., 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84))
+_DP_E = (71 / 57600, 0., -71 / 16695, 71 / 1920, -17253 / 339200, 22 / 525, -1 / 40)
+
+
+def _rms(x):
+    return x.pow(2).mean().sqrt()
+
+
+def _dopri5(fn, y0, t0, t1, atol, rtol, safety=0.9, fmin=0.2, fmax=10.):
+    """Integrate dy/dt = fn(t, y) for a tuple of tensors y from t0 to t1 (t1 > t0): adaptive Dormand-Prince 5(4) with
+    one step size for the whole state, FSAL (the 7th stage at the accepted point is the next step's 1st), Hairer's
+    initial step, the error ratio max over tensors of RMS(err / (atol + rtol max(|y0|, |y1|))) and the step factor
+    safety * ratio^(-1/5) clamped to [fmin, fmax].  Stage combinations are tensor ops on y's device; the one host read
+    per step is the error ratio.  -> (y(t1), {'steps': accepted, 'rejected': n, 'fevals': n}).
+
+    Departures from torchdiffeq's dopri5: the last step is clamped to end at t1 (no dense-output interpolation);
+    the step factor after an accepted step may also shrink; no step-size floor (a non-finite ratio raises)."""
+    t0, t1 = float(t0), float(t1)
+    stats = {'steps': 0, 'rejected': 0, 'fevals': 0}
+
+    def f(t, y):
+        stats['fevals'] += 1
+        return tuple(fn(t, y))
+
+    def comb(y, h, ks, ws):                     # y + h sum_j w_j k_j, per tensor
+        out = []
+        for i, yi in enumerate(y):
+            acc = yi
+            for w, k in zip(ws, ks):
+                if w != 0.:
+                    acc = acc + (h * w) * k[i]
+            out.append(acc)
+        return tuple(out)
+
+    y = tuple(y0)
+    k1 = f(t0, y)
+    # initial step (Hairer's HINIT, as torchdiffeq's _select_initial_step)
+    scale = [atol + rtol * yi.abs() for yi in y]
+    d0 = max(float(_rms(yi / s)) for yi, s in zip(y, scale))
+    d1 = max(float(_rms(ki / s)) for ki, s in zip(k1, scale))
+    h0 = 0.01 * d0 / d1 if (d0 >= 1e-5 and d1 >= 1e-5) else 1e-6
+    f1 = f(t0 + h0, comb(y, h0, (k1,), (1.,)))
+    d2 = max(float(_rms((a - b) / s)) for a, b, s in zip(f1, k1, scale)) / h0
+    h1 = max(1e-6, h0 * 1e-3) if max(d1, d2) <= 1e-15 else (0.01 / max(d1, d2)) ** (1. / 5)
+    h = min(100 * h0, h1, t1 - t0)
+    t = t0
+    while t < t1:
+        last = t + h >= t1 or (t1 - (t + h)) <= 1e-12 * max(1., abs(t1))
+        if last:
+            h = t1 - t
+        ks = [k1]
+        for j in range(1, 7):
+            ks.append(f(t + _DP_C[j] * h, comb(y, h, ks, _DP_A[j])))
+        y_new = comb(y, h, ks[:6], _DP_A[6])
+        err = comb(tuple(torch.zeros_like(yi) for yi in y), h, ks, _DP_E)
+        ratio = torch.stack([_rms(e / (atol + rtol * torch.maximum(a.abs(), b.abs())))
+                             for e, a, b in zip(err, y, y_new)]).max()
+        ratio = float(ratio)                    # the step's one host read
+        if not math.isfinite(ratio):
+            raise FloatingPointError("dopri5: non-finite error estimate")
+        if ratio <= 1.:
+            t = t1 if last else t + h
+            y, k1 = y_new, ks[6]                # FSAL
+            stats['steps'] += 1
+        else:
+            stats['rejected'] += 1
+        factor = fmax if ratio == 0. else min(fmax, max(fmin, safety * ratio ** (-1. / 5)))
+        h = h * factor
+    return y, stats
+
+
+def _log_likelihood_ode(rhs, action, sigma_min, sigma_max, atol, rtol):
+    """The ODE of log_likelihood: state (x, ll), integrated in sigma from sigma_min to sigma_max; ``rhs(x, sigma) ->
+    (dx/dsigma, dll/dsigma [B])``.  -> (ll [B], latent, stats): the Gaussian prior N(0, sigma_max^2) of the latent plus
+    the accumulated log-density change (:487-496)."""
+    y0 = (action, action.new_zeros([action.shape[0]]))
+    (latent, delta_ll), stats = _dopri5(lambda s, y: rhs(y[0], s), y0, sigma_min, sigma_max, atol, rtol)
+    ll_prior = torch.distributions.Normal(0, sigma_max).log_prob(latent).flatten(1).sum(1)
+    return ll_prior + delta_ll, latent, stats
+
+
+@torch.no_grad()
+def log_likelihood(model, state, action, goal, sigma_min, sigma_max, extra_args=None, atol=1e-4, rtol=1e-4):
+    """Log-density of ``action`` under the probability-flow ODE of ``model`` (:471-497) -> (ll [B], {'fevals': n}).
+
+    One evaluation of the right-hand side is ONE ``GCDenoiser.denoise_vjp`` call (the denoiser and its input
+    vector-Jacobian product with the Hutchinson vector v), two for ``ClassifierFreeSampleModel`` (cond and uncond,
+    combined as lam * cond + (1 - lam) * uncond).  v is drawn once per call from the global generator of the action's
+    device, as the reference draws it.  The integrator is the self-contained ``_dopri5`` above (torchdiffeq's method,
+    the reference's atol / rtol)."""
+    extra_args = {} if extra_args is None else dict(extra_args)
+    den, lam = _fused_target(model)
+    if den is None:
+        raise NotImplementedError("log_likelihood needs a beso_amd GCDenoiser (optionally in ClassifierFreeSampleModel): "
+                                  "the input vector-Jacobian product is a HIP call of that model, there is no autograd path")
+    uncond = bool(extra_args.pop('uncond', False))
+    if extra_args:
+        raise NotImplementedError(f"log_likelihood: unsupported extra_args {sorted(extra_args)}")
+    v = torch.randint_like(action, 2) * 2 - 1
+    vv = (v * v).flatten(1).sum(1)
+    fevals = 0
+
+    def rhs(x, sigma):
+        nonlocal fevals
+        fevals += 1
+        if lam == 1.0:
+            denoised, _, dot = den.denoise_vjp(state, x, goal, sigma, v, uncond=uncond)
+        else:
+            dc, _, tc = den.denoise_vjp(state, x, goal, sigma, v)
+            du, _, tu = den.denoise_vjp(state, x, goal, sigma, v, uncond=True)
+            denoised, dot = lam * dc + (1 - lam) * du, lam * tc + (1 - lam) * tu
+        return (x - denoised) / sigma, (vv - dot) / sigma
+
+    ll, _, _ = _log_likelihood_ode(rhs, action.float(), sigma_min, sigma_max, atol, rtol)
+    return ll, {'fevals': fevals}

@@ -85,6 +85,20 @@ class GCDenoiser(nn.Module):
             step = self._train_steps[key] = HipTrainStep(inner, key)
         return step if step.eligible(state, action, goal, noise, sigma) else None
 
+    # -- input vector-Jacobian product ---------------------------------------------------------
+    def denoise_vjp(self, state, action, goal, sigma, cot, uncond: bool = False):
+        """-> (denoised, x_grad, dot): ``forward`` at ``action`` (eval mode), ``(d denoised / d action)^T cot`` and
+        ``(cot * x_grad).flatten(1).sum(1)`` -- what the reference's log_likelihood gets from torch.autograd.grad
+        (gc_sampling.py:480-485), as one HIP call (``beso_denoise_vjp``).  No parameter gradient is touched."""
+        inner = self.inner_model
+        if not isinstance(inner, DiffusionGPT):
+            raise NotImplementedError("GCDenoiser.denoise_vjp needs a beso_amd DiffusionGPT inside (the HIP kernels)")
+        key = float(self.sigma_data)
+        step = self._train_steps.get(key)
+        if step is None:
+            step = self._train_steps[key] = HipTrainStep(inner, key)
+        return step.denoise_vjp(state, action, goal, sigma, cot, uncond=uncond)
+
     def _why_no_hip_step(self, state, action, goal, noise, sigma) -> str:
         inner = self.inner_model
         if not torch.is_grad_enabled():

@@ -709,6 +709,19 @@ int beso_loss_grad(const beso_config* cfg, const float* const* params, int n_par
                                   stream, nullptr);
 }
 
+int beso_denoise_vjp(const beso_config* cfg, const float* const* params, int n_params, int precision, const float* state,
+                     const float* x, const float* goal, const float* sigma, const float* cot, float* denoised, float* x_grad,
+                     float* dot, int batch, int t, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    hipError_t e = hipSuccess;
+    int line = 0;
+    int st = train_denoise_vjp(cfg, params, n_params, precision, state, x, goal, sigma, cot, denoised, x_grad, dot, batch, t, flags,
+                               workspace, workspace_bytes, (hipStream_t)stream, &e, &line);
+    if (st == BESO_ERR_HIP) {
+        snprintf(g_last_error, sizeof(g_last_error), "%s (%d) at train.hip:%d", hipGetErrorName(e), (int)e, line);
+    }
+    return st;
+}
+
 int beso_log_logistic(const double* u, float* out, size_t n, double loc, double scale, double cdf_lo, double cdf_hi, void* stream) {
     if (!u || !out || !(scale > 0.0) || !(cdf_lo >= 0.0 && cdf_hi <= 1.0 && cdf_lo <= cdf_hi)) return BESO_ERR_BAD_ARG;
     if (n == 0) return BESO_OK;

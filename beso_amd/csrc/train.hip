@@ -1766,6 +1766,60 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ pre
     if (threadIdx.x == 0) unsafeAtomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv_count);
 }
 
+// ---------------------------------------------------------------------------------------------
+// input VJP (beso_denoise_vjp): the seed in place of loss_kernel -- denoised = c_skip x + c_out F (compact action rows), and
+// the cotangent of F, dpred = c_out u, operand typed, zero on the padding columns act..ap
+// ---------------------------------------------------------------------------------------------
+template <typename E>
+__global__ __launch_bounds__(256) void vjp_seed_kernel(const float* __restrict__ pred, const float* __restrict__ x,
+                                                       const float* __restrict__ sigma, const float* __restrict__ cot,
+                                                       E* __restrict__ dpred, float* __restrict__ denoised, int M, int act,
+                                                       int ap, int t, float sigma_data) {
+    const size_t n = (size_t)M * ap;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t m = i / ap;
+        const int a = (int)(i % ap);
+        float g = 0.f;
+        if (a < act) {
+            const float sg = sigma[m / t];
+            const float sd2 = sigma_data * sigma_data, den = sg * sg + sd2;
+            const float c_skip = sd2 / den, c_out = sg * sigma_data / sqrtf(den);
+            const size_t j = m * act + a;
+            denoised[j] = c_skip * x[j] + c_out * pred[i];
+            g = c_out * cot[j];
+        }
+        dpred[i] = Act<E>::from(g);
+    }
+}
+
+// ... and the projection of dx0 (fp32, all token rows) back onto the action input: x_grad = c_skip u + c_in dx0[row] W_act,
+// row = the action token of step i (train_embed_kernel's layout), W_act = action_emb.weight [D][act].  One workgroup per sample;
+// dot[b] = sum over (t, act) of u x_grad as a fixed-order reduction (deterministic, no atomics).
+__global__ __launch_bounds__(256) void vjp_input_kernel(const float* __restrict__ dx0, const float* __restrict__ w_act,
+                                                        const float* __restrict__ sigma, const float* __restrict__ cot,
+                                                        float* __restrict__ x_grad, float* __restrict__ dot, int t, int T,
+                                                        int G, int D, int act, float sigma_data) {
+    __shared__ float part[4];
+    const int b = blockIdx.x;
+    const float sg = sigma[b], den = sg * sg + sigma_data * sigma_data;
+    const float c_skip = sigma_data * sigma_data / den, c_in = 1.0f / sqrtf(den);
+    float acc = 0.f;
+    for (int e = threadIdx.x; e < t * act; e += 256) {
+        const int i = e / act, a = e % act;
+        const float* r = dx0 + ((size_t)b * T + G + 2 + 2 * i) * D;
+        float s = 0.f;
+        for (int d = 0; d < D; ++d) s = fmaf(r[d], w_act[(size_t)d * act + a], s);
+        const size_t j = (size_t)b * t * act + e;
+        const float u = cot[j], g = c_skip * u + c_in * s;
+        x_grad[j] = g;
+        acc = fmaf(u, g, acc);
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0 && dot) dot[b] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -2015,12 +2069,19 @@ static bool tail_forward_enabled(int rows, int flags) {
 
 #define TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { *err = _e; *err_line = __LINE__; return BESO_ERR_HIP; } } while (0)
 
+// The input-VJP mode of the step (beso_denoise_vjp): the same forward and chain of data gradients, seeded with the caller's
+// cotangent instead of the loss, ending in the projection onto the action input.  No weight gradient, no reduction of partial
+// sums, no gradient buffer: every gradient pointer of the chain is one workspace scratch slab (dw_cat: Ke D >= 8 D floats, unused
+// in this mode) -- the kernels that write bias sums as side outputs write there.
+struct VjpIo { const float* cot; float* denoised; float* x_grad; float* dot; };
+
 template <typename E>
 static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat, int precision, const float* state,
                        const float* action, const float* goal, const float* noise, const float* sigma, float* loss_out,
                        int batch, int t, int flags, float embed_p, float attn_p, float resid_p, float goal_p, uint32_t seed,
                        float grad_scale, char* ws,
-                       const TrainWs& w, hipStream_t s, hipStream_t early_stream, hipStream_t loss_stream, hipError_t* err, int* err_line) {
+                       const TrainWs& w, hipStream_t s, hipStream_t early_stream, hipStream_t loss_stream, hipError_t* err, int* err_line,
+                       const VjpIo* vjp = nullptr) {
     const int D = c->embed_dim, H = c->n_heads, hd = D / H, L = c->n_layers, G = c->goal_seq_len;
     const int obs = c->obs_dim, act = c->act_dim, seq = G + c->obs_seq_len + 1;
     const int M = w.M, T = w.T, Ke = w.Ke, ap = w.ap, D3 = 3 * D, D4 = 4 * D;
@@ -2034,7 +2095,7 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
     const float* const* q = p;
     float* g = gflat;
     struct PG { const float* p; float* g; };
-    auto take = [&](size_t n) { PG r{*q, g}; ++q; g += n; return r; };
+    auto take = [&](size_t n) { PG r{*q, g}; ++q; if (!vjp) g += n; return r; };      // (VJP: all on the scratch slab)
     const PG pos = take((size_t)seq * D), tokw = take((size_t)D * obs), tokb = take(D);
     struct LayerPG { PG ln1w, ln1b, ln2w, ln2b, kw, kb, qw, qb, vw, vb, pw, pb, f1w, f1b, f2w, f2b; };
     LayerPG lp[kMaxLayers];
@@ -2102,7 +2163,7 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
         TRY(step_event(kEvWcat, &ev_wcat));
         TRY(hipEventRecord(ev_wcat, ps));
     }
-    TRY(hipMemsetAsync(gflat, 0, sizeof(float) * n_grad, ps));
+    if (!vjp) TRY(hipMemsetAsync(gflat, 0, sizeof(float) * n_grad, ps));
 
     // (first what the forward launch needs -- its fragment image --, then the plain copies the backward pass reads)
     if (use_whole || use_tail) {
@@ -2162,8 +2223,9 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
 
     // ---- forward
     {
-        const size_t n = (size_t)batch * t * act;
-        int grid = (int)((n + 255) / 256); if (grid > 2048) grid = 2048;
+        // (VJP: the caller's x IS the noised action -- no elements to prepare, only the loss slot and the padded head bias)
+        const size_t n = vjp ? 0 : (size_t)batch * t * act;
+        int grid = (int)((n + 255) / 256); if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
         hipLaunchKernelGGL(prep_kernel, dim3(grid), dim3(256), 0, s, action, noise, sigma, F(w.noised), F(w.target),
                            t * act, n, c->sigma_data, loss_out, F(w.b_head), hb.p, act, ap);
         TRY(hipGetLastError());
@@ -2174,7 +2236,7 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
                                    actw.p, actb.p, F(w.wcat), D, obs, act, seq, Ke);
             const size_t nf = (size_t)M * Ke;
             hipLaunchKernelGGL(train_feat_kernel<E>, dim3((unsigned)((nf + 255) / 256 > 4096 ? 4096 : (nf + 255) / 256)), dim3(256), 0, s,
-                               state, (const float*)F(w.noised), goal, sigma, P(w.xemb), F(w.xemb32), M, t, T, G, obs, act, Ke,
+                               state, vjp ? action : (const float*)F(w.noised), goal, sigma, P(w.xemb), F(w.xemb32), M, t, T, G, obs, act, Ke,
                                c->sigma_data, goal_p, seed);
             TRY(hipGetLastError());
             if (wcat_side) TRY(hipStreamWaitEvent(s, ev_wcat, 0));
@@ -2270,7 +2332,13 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
     } else {
         TRY((tgemm<E, false, false>(P(w.xf), D, P(w.w_head), D, Ma, ap, D, 1, EpiStore<E>{F(w.pred), nullptr, F(w.b_head), ap}, s)));
     }
-    {
+    if (vjp) {
+        const size_t n = (size_t)Ma * ap;
+        int grid = (int)((n + 255) / 256); if (grid > 1024) grid = 1024;
+        hipLaunchKernelGGL(vjp_seed_kernel<E>, dim3(grid), dim3(256), 0, s, (const float*)F(w.pred), action, sigma, vjp->cot,
+                           P(w.dpred), vjp->denoised, Ma, act, ap, t, c->sigma_data);
+        TRY(hipGetLastError());
+    } else {
         const size_t n = (size_t)Ma * ap;
         int grid = (int)((n + 255) / 256); if (grid > 1024) grid = 1024;
         hipLaunchKernelGGL(loss_kernel<E>, dim3(grid), dim3(256), 0, s, (const float*)F(w.pred), (const float*)F(w.target),
@@ -2439,6 +2507,7 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
     // behind B's last real column (free whenever No is not a multiple of the 128-column tile: every shipped shape); otherwise
     // a colsum launch of its own.
     auto wgrad = [&](const E* A, int lda, int Mo, const E* B, int ldb, int No, int rows, float* out, float* bias = nullptr) -> hipError_t {
+        if (vjp) return hipSuccess;                       // (input VJP: no weight gradient)
         if (gt.n == kMaxGroup) { hipError_t e = flush_group(); if (e != hipSuccess) return e; }
         if (bias && No % kTileMN == 0) {
             hipError_t e = colsum(A, lda, Mo, rows, bias);
@@ -2468,7 +2537,7 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
     // head (compact rows): dW = dpred^T xf (the act real rows of dpred's ap columns, straight into the gradient tensor),
     // db = its column sums, dxf = dpred W
     if (mlp_head) {
-        TRY(colsum(P(w.dpred), ap, act, Ma, hb.g));
+        if (!vjp) TRY(colsum(P(w.dpred), ap, act, Ma, hb.g));
         // second layer: dW1 = dpred^T a, da = dpred W1 -> dz = da * SiLU'(z) (+ its column sums = db0); first layer:
         // dW0 = dz^T xf, dxf = dz W0.  Padded rows / columns are zeros all the way.
         TRY(wgrad(P(w.dpred), ap, ap, P(w.ha), Hp, Hp, Ma, F(w.dw_head)));
@@ -2575,6 +2644,13 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
         }
     }
 #undef FUSED
+    if (vjp) {
+        // F(w.dx) holds the fp32 gradient of x0 (layer 0's LayerNorm-1 backward): onto the action input
+        hipLaunchKernelGGL(vjp_input_kernel, dim3(batch), dim3(256), 0, s, (const float*)F(w.dx), actw.p, sigma, vjp->cot,
+                           vjp->x_grad, vjp->dot, t, T, G, D, act, c->sigma_data);
+        TRY(hipGetLastError());
+        return BESO_OK;
+    }
     // embeddings: dWcat[Ke][D] = Xemb^T dx0, routed to pos_emb / tok_emb / action_emb / sigma_emb after the launch
     TRY(wgrad(P(w.xemb), Ke, Ke, P(w.dx0b), D, D, M, F(w.dw_cat)));
     // The reductions of the FC1-bias slabs and of the LayerNorm / bias partial sums read what the data-gradient kernels wrote
@@ -2638,6 +2714,34 @@ int train_loss_grad(const beso_config* c, const float* const* params, int n_para
     return loss_grad_e<uint16_t>(c, params, grads_flat, precision, state, action, goal, noise, sigma, loss_out, batch, t,
                                  flags, embed_pdrop, attn_pdrop, resid_pdrop, goal_drop, seed, grad_scale,
                                  (char*)workspace, w, s, early_stream, loss_stream, err, err_line);
+}
+
+int train_denoise_vjp(const beso_config* c, const float* const* params, int n_params, int precision, const float* state,
+                      const float* x, const float* goal, const float* sigma, const float* cot, float* denoised, float* x_grad,
+                      float* dot, int batch, int t, int flags, void* workspace, size_t workspace_bytes, hipStream_t s,
+                      hipError_t* err, int* err_line) {
+    int st = train_validate(c, batch, t);
+    if (st != BESO_OK) return st;
+    if (precision != BESO_PREC_BF16 && precision != BESO_PREC_FP32) return BESO_ERR_BAD_ARG;
+    if (!params || !state || !x || !sigma || !cot || !denoised || !x_grad || !workspace) return BESO_ERR_BAD_ARG;
+    if (c->goal_seq_len > 0 && !goal) return BESO_ERR_BAD_ARG;
+    if (n_params != 3 + 16 * c->n_layers + 6 + (c->linear_output ? 2 : 4)) return BESO_ERR_BAD_ARG;
+    for (int i = 0; i < n_params; ++i) if (!params[i]) return BESO_ERR_BAD_ARG;
+    if (flags & ~(BESO_TRAIN_PLAN_PER_OP | BESO_TRAIN_PLAN_TILES)) return BESO_ERR_BAD_ARG;
+    TrainWs w;
+    make_train_ws(c, batch, t, precision, &w);
+    if (workspace_bytes < w.total) return BESO_ERR_WORKSPACE;
+    char* ws = (char*)workspace;
+    // (the step's loss slot: the target buffer, unused in this mode; the gradient pointers: the dw_cat slab, see VjpIo)
+    float* loss_slot = (float*)(ws + w.target);
+    float* scratch = (float*)(ws + w.dw_cat);
+    const VjpIo io{cot, denoised, x_grad, dot};
+    (void)hipGetLastError();
+    if (precision == BESO_PREC_FP32)
+        return loss_grad_e<float>(c, params, scratch, precision, state, x, goal, nullptr, sigma, loss_slot, batch, t, flags,
+                                  0.f, 0.f, 0.f, 0.f, 0u, 1.f, ws, w, s, nullptr, nullptr, err, err_line, &io);
+    return loss_grad_e<uint16_t>(c, params, scratch, precision, state, x, goal, nullptr, sigma, loss_slot, batch, t, flags,
+                                 0.f, 0.f, 0.f, 0.f, 0u, 1.f, ws, w, s, nullptr, nullptr, err, err_line, &io);
 }
 
 int train_goal_mask(float* mask, size_t n, float goal_drop, uint32_t seed, hipStream_t s, hipError_t* err, int* err_line) {

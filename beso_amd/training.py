@@ -184,6 +184,65 @@ class HipTrainStep:
         _lib.check(st, "loss_grad")
         return loss, flat, views
 
+    def denoise_vjp(self, state, x, goal, sigma, cot, uncond: bool = False):
+        """-> (denoised, x_grad, dot): ``GCDenoiser.forward`` in eval mode at x, the vector-Jacobian product
+        (d denoised / d x)^T cot and its per-sample dot product with cot, as ONE enqueue of ``beso_denoise_vjp``
+        (the training step's forward and data-gradient chain, no weight gradient).  The parameters need not require
+        grad and the call works under ``torch.no_grad()``; no ``.grad`` is created or changed."""
+        inner = self.inner
+        if inner.training and any(p > 0 for p in inner._pdrops):
+            raise RuntimeError("beso_amd: denoise_vjp evaluates the eval-mode function; call eval() on a model with dropout")
+        params, ptrs = self._params()
+        if self.__dict__.get("_vjp_ptrs_ok") != ptrs:
+            if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in params):
+                raise ValueError("beso_amd: denoise_vjp needs contiguous fp32 parameters on the GPU")
+            if sum(p.numel() for p in params) != self.n_grad or len(params) != self.n_params:
+                raise ValueError("beso_amd: the module's parameters do not match its HIP layout")
+            self._vjp_ptrs_ok = ptrs
+        if not self.supported(inner):
+            raise ValueError(f"beso_amd: denoise_vjp needs embed_dim % 8 == 0 (embed_dim={inner.embed_dim})")
+        dev = x.device
+        if not x.is_cuda:
+            raise ValueError("beso_amd: denoise_vjp inputs must be on the GPU (there is no CPU path)")
+        f32 = lambda v: v.detach().to(device=dev, dtype=torch.float32).contiguous()
+        state, x, cot = f32(state), f32(x), f32(cot)
+        if state.dim() != 3 or x.dim() != 3 or cot.shape != x.shape:
+            raise ValueError("state must be [B,t,obs], x and cot [B,t,act]")
+        B, t, _ = state.shape
+        if x.shape[:2] != (B, t):
+            raise ValueError("state and x disagree on [B,t]")
+        sigma = f32(torch.as_tensor(sigma)).reshape(-1)
+        if sigma.numel() == 1:
+            sigma = sigma.expand(B).contiguous()
+        if sigma.numel() != B:
+            raise ValueError("sigma must be a scalar or [B]")
+        G = inner.goal_seq_len
+        gptr = None
+        if G > 0:
+            if uncond or goal is None:
+                goal = torch.zeros(B, G, inner.obs_dim, dtype=torch.float32, device=dev)     # (score_gpts.py:301-302)
+            else:
+                goal = f32(goal)
+                if goal.dim() == 2:
+                    goal = goal.unsqueeze(0)
+                goal = goal.expand(B, G, inner.obs_dim).contiguous()
+            gptr = goal.data_ptr()
+        # (as run(): the split-bf16 and fp16 inference modes map to the fp32 / bf16 steps)
+        precision = _lib.PRECISIONS[{"bf16x3": "fp32", "fp16": "bf16"}.get(inner.precision, inner.precision)]
+        if self.__dict__.get("_arr_ptrs") != ptrs:
+            self._arr, self._arr_ptrs = (C.c_void_p * len(ptrs))(*ptrs), ptrs
+        ws = self._workspace(B, t, precision, dev)
+        denoised, x_grad = torch.empty_like(x), torch.empty_like(x)
+        dot = torch.empty(B, dtype=torch.float32, device=dev)
+        flags = train_hints() & (_lib.TRAIN_PLAN_PER_OP | _lib.TRAIN_PLAN_TILES)
+        with torch.cuda.device(dev):
+            st = self.lib.beso_denoise_vjp(C.byref(self.cfg), self._arr, len(params), precision, state.data_ptr(), x.data_ptr(),
+                                           gptr, sigma.data_ptr(), cot.data_ptr(), denoised.data_ptr(), x_grad.data_ptr(),
+                                           dot.data_ptr(), B, t, flags, ws.data_ptr(), ws.numel(),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(st, "denoise_vjp")
+        return denoised, x_grad, dot
+
     def goal_mask(self, batch: int, seed: int, goal_drop: Optional[float] = None, device=None) -> torch.Tensor:
         """The keep-mask [batch, G, obs] the kernel applies to the goals for (goal_drop, seed) (``beso_goal_mask``)."""
         inner = self.inner

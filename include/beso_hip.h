@@ -21,6 +21,7 @@
  *   beso_scale_rows     <- Scaler.scale_input / scale_output              networks/scaler/scaler_class.py:95-117 (base_agent.py:111-142)
  *   beso_loss_grad_overlap  (same, with the early gradient range for the overlapped all-reduce: SURVEY 8(e) C1)
  *   beso_loss_grad_streams  (same, plus a stream that is released as soon as the loss value is final)
+ *   beso_denoise_vjp    <- GCDenoiser.forward + torch.autograd.grad w.r.t. the action   k_diffusion/gc_sampling.py:480-485
  *   beso_adam_step      <- optimizer.step() + ema_helper.update()      beso_agent.py:236-244
  *   beso_gather_windows <- TrajectorySlicerDataset.__getitem__ x batch envs/dataloaders/trajectory_loader.py:160-197
  *
@@ -255,6 +256,24 @@ int beso_loss_grad(const beso_config* cfg, const float* const* params, int n_par
                    const float* state, const float* action, const float* goal, const float* noise, const float* sigma,
                    float* loss_out, int batch, int t, int flags, float embed_pdrop, float attn_pdrop, float resid_pdrop,
                    float goal_drop, unsigned int seed, float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
+/* GCDenoiser.forward in eval mode at (state, x, goal, sigma), and the vector-Jacobian product of that output with
+ * respect to x (reference log_likelihood's torch.autograd.grad, gc_sampling.py:480-485).  The training step's forward and
+ * chain of data gradients (beso_loss_grad), seeded with the cotangent instead of the loss and ended by a projection of the
+ * embedding gradient onto the action input; no weight gradient, no reduction of partial sums.
+ *   params      n_params DEVICE pointers, order of beso_pack_weights (as beso_loss_grad); read only
+ *   state [batch,t,obs], x [batch,t,act], goal [batch,G,obs] (may be NULL when G = 0), sigma [batch]
+ *   cot         [batch,t,act] cotangent u
+ *   denoised    [batch,t,act] out: c_skip*x + c_out*F(c_in*x, ...)
+ *   x_grad      [batch,t,act] out: (d denoised / d x)^T u
+ *   dot         [batch] out, may be NULL: sum over (t,act) of u * x_grad, per sample (a fixed-order reduction)
+ *   flags       BESO_TRAIN_PLAN_PER_OP / BESO_TRAIN_PLAN_TILES only
+ *   workspace   beso_train_workspace_bytes(cfg, batch, t, precision) bytes
+ * precision: BESO_PREC_BF16 or BESO_PREC_FP32.  No dropout, no goal masking (uncond: pass zero goals).  No parameter
+ * gradient is computed or written.  Bad shapes, embed_dim % 8 != 0, an unknown precision or flag bit, a NULL required
+ * pointer and a short workspace are rejected before anything is enqueued.                                            */
+int beso_denoise_vjp(const beso_config* cfg, const float* const* params, int n_params, int precision, const float* state,
+                     const float* x, const float* goal, const float* sigma, const float* cot, float* denoised, float* x_grad,
+                     float* dot, int batch, int t, int flags, void* workspace, size_t workspace_bytes, void* stream);
 /* The keep-mask (1.0 / 0.0 per element of goal [batch,G,obs]) that beso_loss_grad applies for (goal_drop, seed):
  * `1 - torch.bernoulli(...)` of DiffusionGPT.mask_cond (score_gpts.py:365-368) with this library's generator.       */
 int beso_goal_mask(float* mask, int batch, int goal_seq_len, int obs_dim, float goal_drop, unsigned int seed, void* stream);
