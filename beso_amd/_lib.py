@@ -19,6 +19,8 @@ PLAN_SPW2, PLAN_SPW4, PLAN_SPW8 = 0x100, 0x200, 0x300
 SAMPLE_STEPWISE = 0x1000
 TRAIN_LAST_ACTION_ONLY, TRAIN_PLAN_PER_OP, TRAIN_PLAN_TILES = 1, 2, 4
 SAMPLER_IDS = {"ddim": 0, "euler": 1, "heun": 2}
+# beso_sample_solver (include/beso_hip.h BESO_SOLVER_*): the gc_sampling.py function names without "sample_"
+SOLVER_IDS = {"dpm_2": 0, "dpm_2_ancestral": 1, "dpmpp_2s": 2, "dpmpp_2s_ancestral": 3, "dpmpp_2m": 4, "lms": 5}
 GOAL_RANDOM, GOAL_TAIL, GOAL_SEQ_END = 0, 1, 2
 STEP_DDIM, STEP_EULER, STEP_HEUN_PREDICT, STEP_HEUN_CORRECT = 0, 1, 2, 3
 SITES = {"off": 0, "gemm_qkv": 1, "gemm_proj": 2, "gemm_fc1": 3, "gemm_fc2": 4, "attention": 5,
@@ -30,7 +32,7 @@ EXPORTS = ["beso_version", "beso_status_string", "beso_last_error", "beso_num_pa
            "beso_profile_enable", "beso_profile_read", "beso_adam_step",
            "beso_train_workspace_bytes", "beso_grad_floats", "beso_loss_grad", "beso_gather_windows",
            "beso_loss_grad_overlap", "beso_grad_early_range", "beso_sample_ancestral", "beso_goal_mask",
-           "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp"]
+           "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp", "beso_sample_solver"]
 # include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
 DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm"]
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
@@ -98,6 +100,10 @@ def load() -> C.CDLL:
             lib.beso_sample_ancestral.restype = i32
             lib.beso_sample_ancestral.argtypes = [cfgp, vp, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_float), i32, f32, f32, vp,
                                                   i32, vp, sz, vp]
+        if hasattr(lib, "beso_sample_solver") or not os.environ.get("BESO_HIP_LIB"):
+            lib.beso_sample_solver.restype = i32
+            lib.beso_sample_solver.argtypes = [cfgp, vp, i32, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_float), i32, f32, f32, f32,
+                                               i32, vp, vp, i32, vp, sz, vp]
         lib.beso_profile_enable.restype = None
         lib.beso_profile_enable.argtypes = [i32]
         if hasattr(lib, "beso_adam_step") or not os.environ.get("BESO_HIP_LIB"):   # (A/B builds of older revisions)

@@ -151,6 +151,20 @@ def _try_fused(name, model, state, action, goal, sigmas, scaler, extra_args, cal
     return den.fused_sampler(name, state, action, goal, sig, cond_lambda=lam)
 
 
+def _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback):
+    """(GCDenoiser, cond_lambda, host sigmas) when a sampler call can run as one enqueue (``beso_sample_solver``), else None.
+    Checked before anything is drawn: the ancestral samplers pre-draw their noise only for a call that takes this path."""
+    if scaler is not None or callback is not None or extra_args:
+        return None
+    den, lam = _fused_target(model)
+    if den is None or not action.is_cuda or not den.can_fuse_sampler(state, action, goal):
+        return None
+    sig = _host_sigmas(sigmas)
+    if not _interior_positive(sig):
+        return None
+    return den, lam, sig
+
+
 def _interior_positive(sig) -> bool:
     """beso_sample / beso_sample_ancestral take schedules whose values are positive up to the trailing one."""
     return len(sig) >= 2 and all(float(v) > 0.0 for v in sig[:-1])
@@ -261,8 +275,13 @@ def _log_midpoint(a, b):
 @torch.no_grad()
 def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None,
                  s_churn=0., s_tmin=0., s_tmax=float('inf'), s_noise=1.):
-    """DPM-Solver-2-like midpoint steps in log sigma (:317-375)."""
+    """DPM-Solver-2-like midpoint steps in log sigma (:317-375).  With s_churn = 0 the plain call on a ``beso_amd`` denoiser
+    runs as one enqueue (``beso_sample_solver``; the generic loop's unused ``eps`` draws are not made)."""
     extra_args = {} if extra_args is None else extra_args
+    tgt = None if s_churn else _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback)
+    if tgt is not None:
+        den, lam, sig = tgt
+        return den.fused_sampler('dpm_2', state, action, goal, sig, cond_lambda=lam)
     sig = _host_sigmas(sigmas)
     n = len(sig) - 1
     for i in range(n):
@@ -290,8 +309,17 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
 @torch.no_grad()
 def sample_dpm_2_ancestral(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None,
                            disable=None, eta=1.):
-    """Ancestral variant of the DPM-Solver-2-like sampler (:378-413)."""
+    """Ancestral variant of the DPM-Solver-2-like sampler (:378-413).  The plain call on a ``beso_amd`` denoiser runs as one
+    enqueue (``beso_sample_solver``) with the loop's ``randn_like`` draws made up front, in the same order and number."""
     extra_args = {} if extra_args is None else extra_args
+    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback) if eta >= 0 else None
+    if tgt is not None:
+        den, lam, sig = tgt
+        noise = torch.zeros((len(sig) - 1,) + tuple(action.shape), dtype=torch.float32, device=action.device)
+        for i in range(len(sig) - 1):
+            if get_ancestral_step(sig[i], sig[i + 1], eta=eta)[0] != 0:
+                noise[i] = torch.randn_like(action)
+        return den.fused_sampler('dpm_2_ancestral', state, action, goal, sig, cond_lambda=lam, eta=eta, noise=noise)
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)
@@ -330,8 +358,13 @@ def linear_multistep_coeff(order, t, i, j):
 @torch.no_grad()
 def sample_lms(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None,
                order=4):
-    """Linear multistep sampler (:432-468)."""
+    """Linear multistep sampler (:432-468).  Orders up to 4 on a ``beso_amd`` denoiser run as one enqueue
+    (``beso_sample_solver``: the coefficients are the exact integrals that quad approximates)."""
     extra_args = {} if extra_args is None else extra_args
+    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback) if 1 <= order <= 4 else None
+    if tgt is not None:
+        den, lam, sig = tgt
+        return den.fused_sampler('lms', state, action, goal, sig, cond_lambda=lam, order=order)
     sig = _host_sigmas(sigmas)
     history = []
     for i in range(len(sig) - 1):
@@ -360,8 +393,12 @@ def _exp_step_coeffs(s_from, s_to):
 
 @torch.no_grad()
 def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None):
-    """DPM-Solver++(2M) (:702-736)."""
+    """DPM-Solver++(2M) (:702-736); one enqueue (``beso_sample_solver``) on a ``beso_amd`` denoiser."""
     extra_args = {} if extra_args is None else extra_args
+    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback)
+    if tgt is not None:
+        den, lam, sig = tgt
+        return den.fused_sampler('dpmpp_2m', state, action, goal, sig, cond_lambda=lam)
     sig = _host_sigmas(sigmas)
     old_denoised = None
     for i in range(len(sig) - 1):
@@ -400,8 +437,12 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
 @torch.no_grad()
 def sample_dpmpp_2s(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None,
                     eta=1.):
-    """DPM-Solver++(2S) (:928-966)."""
+    """DPM-Solver++(2S) (:928-966); one enqueue (``beso_sample_solver``) on a ``beso_amd`` denoiser."""
     extra_args = {} if extra_args is None else extra_args
+    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback)
+    if tgt is not None:
+        den, lam, sig = tgt
+        return den.fused_sampler('dpmpp_2s', state, action, goal, sig, cond_lambda=lam)
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)
@@ -429,9 +470,18 @@ def _dpmpp_2s_update(model, state, action, goal, denoised, s_from, s_to, extra_a
 @torch.no_grad()
 def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None,
                               disable=None, eta=1., s_noise=1., noise_sampler=None):
-    """Ancestral DPM-Solver++(2S) (:969-1016)."""
+    """Ancestral DPM-Solver++(2S) (:969-1016).  The plain call on a ``beso_amd`` denoiser runs as one enqueue
+    (``beso_sample_solver``) with the loop's ``noise_sampler`` calls made up front, in the same order and number."""
     extra_args = {} if extra_args is None else extra_args
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
+    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback) if eta >= 0 else None
+    if tgt is not None:
+        den, lam, sig = tgt
+        noise = torch.zeros((len(sig) - 1,) + tuple(action.shape), dtype=torch.float32, device=action.device)
+        for i in range(len(sig) - 1):
+            noise[i] = noise_sampler(sig[i], sig[i + 1])
+        return den.fused_sampler('dpmpp_2s_ancestral', state, action, goal, sig, cond_lambda=lam, eta=eta, s_noise=s_noise,
+                                 noise=noise)
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)

@@ -11,6 +11,7 @@ from torch import nn
 from ...._instantiate import instantiate
 from .score_gpts import DiffusionGPT
 from .utils import append_dims
+from .... import _lib
 from ....training import HipTrainStep, ScoreMatchingLoss
 
 
@@ -121,13 +122,22 @@ class GCDenoiser(nn.Module):
             return False            # training-mode goal masking / dropout live in DiffusionGPT.forward
         return inner._hip_eligible(*tensors)
 
+    def can_fuse_sampler(self, state, x_t, goal) -> bool:
+        """True when ``fused_sampler`` runs these inputs (and does not return None for them)."""
+        return self._fused(self.inner_model, {}, state, x_t, goal) and x_t.dim() == 3 and state.dim() == 3
+
     def fused_sampler(self, sampler: str, state, x_t, goal, sigmas, cond_lambda: float = 1.0, eta: float = 1.0, noise=None,
-                      stepwise: bool = False):
-        """Whole ddim / euler / heun / euler_ancestral loop as one enqueue (``beso_sample``, ``beso_sample_ancestral``); None
-        if not applicable."""
+                      stepwise: bool = False, s_noise: float = 1.0, order: int = 4):
+        """Whole ddim / euler / heun / euler_ancestral loop as one enqueue (``beso_sample``, ``beso_sample_ancestral``), and
+        dpm_2 / dpm_2_ancestral / dpmpp_2s / dpmpp_2s_ancestral / dpmpp_2m / lms (``beso_sample_solver``); None if not
+        applicable."""
         inner = self.inner_model
-        if not self._fused(inner, {}, state, x_t, goal) or x_t.dim() != 3 or state.dim() != 3:
+        if not self.can_fuse_sampler(state, x_t, goal):
             return None
+        if sampler in _lib.SOLVER_IDS:
+            return inner.runtime(self.sigma_data).sample_solver(inner.packed_weights(), sampler, state, x_t, goal, sigmas,
+                                                                cond_lambda=cond_lambda, eta=eta, s_noise=s_noise, order=order,
+                                                                noise=noise, stepwise=stepwise)
         if sampler == "euler_ancestral":
             return inner.runtime(self.sigma_data).sample_ancestral(inner.packed_weights(), state, x_t, goal, sigmas,
                                                                    cond_lambda=cond_lambda, eta=eta, noise=noise, stepwise=stepwise)

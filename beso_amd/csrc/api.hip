@@ -601,7 +601,7 @@ int beso_sample_ancestral(const beso_config* cfg, const void* packed, int precis
                     const float sf = sigmas[i0 + k], sn = sigmas[i0 + k + 1];
                     float down, up;
                     ancestral(sf, sn, down, up);
-                    S.rec[k] = StepRec{sf, sf, down - sf, BESO_STEP_EULER | (down > 0.f ? kStepAddNoise : 0), up};      // :240-247
+                    S.rec[k] = StepRec{sf, sf, down - sf, BESO_STEP_EULER | (down > 0.f ? kStepAddNoise : 0) | (k << kStepShift), up};      // :240-247
                 }
                 a.noise = noise + (size_t)i0 * n;
                 profile_begin(BESO_SITE_FUSED_LAYER, s);
@@ -626,6 +626,187 @@ int beso_sample_ancestral(const beso_config* cfg, const void* packed, int precis
         if (st != BESO_OK) return st;
         HIP_TRY(launch_sampler_step(BESO_STEP_EULER, x, nullptr, x, nullptr, den, sf, down - sf, n, s, sig, sn, batch));     // :240-245
         if (down > 0.f) HIP_TRY(launch_sampler_step(BESO_STEP_ADD_NOISE, x, nullptr, x, noise + (size_t)i * n, x, up, 0.f, n, s));
+    }
+    return BESO_OK;
+}
+
+// linear_multistep_coeff (gc_sampling.py:416-429): the integral over [t_i, t_{i+1}] of the Lagrange basis polynomial of node
+// t_{i-j} on t_i ... t_{i-order+1}.  The reference integrates it with scipy's quad, exact for a polynomial of degree <= 3 up to
+// rounding; so does the three-point Gauss-Legendre rule (exact to degree 5), in double.  The denominators are fp32 differences
+// of the fp32 schedule, as the reference's numpy scalars.
+static double lms_coeff(int order, const float* t, int i, int j) {
+    auto basis = [&](double tau) {
+        double prod = 1.0;
+        for (int k = 0; k < order; ++k)
+            if (k != j) prod *= (tau - (double)t[i - k]) / (double)(t[i - j] - t[i - k]);
+        return prod;
+    };
+    const double a = t[i], b = t[i + 1], mid = 0.5 * (a + b), half = 0.5 * (b - a);
+    const double xg = sqrt(0.6);
+    return half * ((5.0 / 9.0) * basis(mid - half * xg) + (8.0 / 9.0) * basis(mid) + (5.0 / 9.0) * basis(mid + half * xg));
+}
+
+int beso_sample_solver(const beso_config* cfg, const void* packed, int precision, int solver, const float* state,
+                       const float* goal, float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda,
+                       float eta, float s_noise, int order, const float* noise, float* history, int flags,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    int st = validate_config(cfg);
+    if (st != BESO_OK) return st;
+    if (solver < BESO_SOLVER_DPM_2 || solver > BESO_SOLVER_LMS || (flags & ~(BESO_SAMPLE_STEPWISE | BESO_PLAN_MASK)))
+        return BESO_ERR_BAD_ARG;
+    const bool ancestral = solver == BESO_SOLVER_DPM_2_ANCESTRAL || solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL;
+    if (solver == BESO_SOLVER_LMS && (order < 1 || order > 4)) return BESO_ERR_BAD_ARG;
+    const int n_hist = solver == BESO_SOLVER_DPMPP_2M ? 1 : solver == BESO_SOLVER_LMS ? order - 1 : 0;
+    if ((ancestral && !noise) || (n_hist > 0 && !history) || !(eta >= 0.f)) return BESO_ERR_BAD_ARG;
+    const int plan = flags & BESO_PLAN_MASK;
+    if (!sigmas || n_sigmas < 2 || !x || !workspace) return BESO_ERR_BAD_ARG;
+    if (batch < 1 || t < 1 || t > cfg->obs_seq_len) return BESO_ERR_BAD_SHAPE;
+    Layout lay;
+    Workspace ws;
+    if (!make_layout(cfg, precision, &lay)) return BESO_ERR_BAD_ARG;
+    const int two = (cond_lambda != 0.f && cond_lambda != 1.f) ? 1 : 0;
+    if (!make_workspace(cfg, lay, batch, t, precision, two, &ws)) return BESO_ERR_BAD_SHAPE;
+    if (workspace_bytes < ws.total) return BESO_ERR_WORKSPACE;
+    for (int i = 0; i + 1 < n_sigmas; ++i) if (!(sigmas[i] > 0.f)) return BESO_ERR_BAD_ARG;
+    if (!packed || !state || (cfg->goal_seq_len > 0 && !goal)) return BESO_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    char* wsp = (char*)workspace;
+    float* den = (float*)(wsp + ws.den);
+    float* x2 = (float*)(wsp + ws.x2);
+    float* sig = (float*)(wsp + ws.sig);
+    const size_t n = (size_t)batch * t * lay.act;
+
+    // The evaluations of the loop: their records (sigma, c0, c1, mode, c2), the fifth number (c3) and the step of each.
+    // Every coefficient is an fp32 scalar computed as the reference computes it (numpy float32 / 0-d tensors).
+    std::vector<StepRec> recs;
+    std::vector<float> c3s;
+    std::vector<int> rec_step, step_first;
+    auto push = [&](int i, float sigma, float c0, float c1, int mode, float c2, float c3) {
+        recs.push_back(StepRec{sigma, c0, c1, mode, c2});
+        c3s.push_back(c3);
+        rec_step.push_back(i);
+    };
+    auto ancestral_step = [&](float sf, float sn, float& down, float& up) {      // get_ancestral_step (:107-114)
+        down = sn; up = 0.f;
+        if (eta != 0.f) {
+            up = eta * sqrtf(sn * sn * (sf * sf - sn * sn) / (sf * sf));
+            if (sn < up) up = sn;
+            down = sqrtf(sn * sn - up * up);
+        }
+    };
+    auto log_midpoint = [](float a, float b) {          // exp(lerp(log a, log b, 0.5))
+        const float la = logf(a), lb = logf(b);
+        const float hm = 0.5f * (lb - la);
+        return expf(la + hm);
+    };
+    for (int i = 0; i + 1 < n_sigmas; ++i) {
+        const float si = sigmas[i], sn = sigmas[i + 1];
+        step_first.push_back((int)recs.size());
+        if (solver == BESO_SOLVER_DPM_2 || solver == BESO_SOLVER_DPM_2_ANCESTRAL) {
+            float to = sn, up = 0.f;
+            if (solver == BESO_SOLVER_DPM_2_ANCESTRAL) ancestral_step(si, sn, to, up);
+            if (to == 0.f) {
+                push(i, si, si, to - si, BESO_STEP_EULER, 0.f, 0.f);
+            } else {
+                const float mid = log_midpoint(si, to);
+                push(i, si, si, mid - si, kStepDpm2Predict, 0.f, 0.f);
+                push(i, mid, mid, to - si, kStepDpm2Correct | (solver == BESO_SOLVER_DPM_2_ANCESTRAL ? kStepAddNoise : 0), up, 0.f);
+            }
+        } else if (solver == BESO_SOLVER_DPMPP_2S || solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL) {
+            float to = sn, up = 0.f;
+            const bool anc = solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL;
+            if (anc) ancestral_step(si, sn, to, up);
+            const int nz = anc ? kStepScaledNoise : 0;       // every step of the ancestral form draws, the last one included
+            if (to == 0.f) {
+                push(i, si, si, to - si, BESO_STEP_EULER | nz, up, s_noise);
+            } else {
+                // _dpmpp_2s_update: r = 1/2, s = t + r h, stage 1 to sigma = exp(-s), stage 2 from x to sigma_to
+                const float tt = -logf(si), tn = -logf(to);
+                const float h = tn - tt;
+                const float rh = h * 0.5f;
+                const float sm = tt + rh;
+                const float smid = expf(-sm);
+                push(i, si, smid / expf(-tt), expm1f(-rh), kStepExpPredict, 0.f, 0.f);
+                push(i, smid, expf(-tn) / expf(-tt), expm1f(-h), kStepExpCorrect | nz, up, s_noise);
+            }
+        } else if (solver == BESO_SOLVER_DPMPP_2M) {
+            const float tt = -logf(si), tn = -logf(sn);        // sn == 0 -> tn = +inf -> x = den exactly
+            const float h = tn - tt;
+            const float ratio = expf(-tn) / expf(-tt), em1 = expm1f(-h);
+            if (i == 0 || sn == 0.f) {
+                push(i, si, ratio, em1, i == 0 ? kStepDpm2mFirst : BESO_STEP_DDIM, 0.f, 0.f);
+            } else {
+                const float tp = -logf(sigmas[i - 1]);
+                const float r = (tt - tp) / h;
+                const float c3 = 1.0f / (2.0f * r);
+                push(i, si, ratio, em1, kStepDpm2m, 1.0f + c3, c3);
+            }
+        } else {
+            const int cur = i + 1 < order ? i + 1 : order;
+            float c[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < cur; ++j) c[j] = (float)lms_coeff(cur, sigmas, i, j);
+            push(i, si, c[0], c[1], lms_mode(cur - 1, order - 1), c[2], c[3]);
+        }
+    }
+    step_first.push_back((int)recs.size());
+
+    FwdArgs a;
+    a.state = state; a.action = x; a.goal = goal; a.sigma = sig; a.out = x; a.aux = history; a.noise = noise;
+    a.batch = batch; a.vbatch = two ? 2 * batch : batch; a.t = t; a.T = 1 + lay.G + 2 * t;
+    a.precondition = 1;
+    a.uncond_from = two ? batch : (cond_lambda == 0.f ? 0 : a.vbatch);
+    a.cond_lambda = cond_lambda; a.sigma_data = cfg->sigma_data;
+    a.plan = precision == BESO_PREC_FP16 ? (plan & ~(BESO_PLAN_PER_OP | BESO_PLAN_BLOCKS)) : plan;
+    const bool f16 = precision == BESO_PREC_FP16;
+    // ONE launch for the whole loop where beso_sample runs one: two-evaluation steps park x in `x` between their evaluations,
+    // the multistep state lives in `history`, the noise is indexed by step; cut at step boundaries past kMaxLoopEvals
+    if (!(flags & BESO_SAMPLE_STEPWISE) && !small_wanted(lay, a, precision) &&
+        (f16 ? fused_can_loop_f16(lay, a, BESO_PREC_BF16) : fused_can_loop(lay, a, precision))) {
+        const size_t n_steps = step_first.size() - 1;
+        size_t i0 = 0;
+        while (i0 < n_steps) {
+            size_t i1 = i0 + 1;
+            while (i1 < n_steps && step_first[i1 + 1] - step_first[i0] <= kMaxLoopEvals) ++i1;
+            SampleSteps S{};
+            SampleExtra X3{};
+            S.n = step_first[i1] - step_first[i0];
+            for (int k = 0; k < S.n; ++k) {
+                const int r = step_first[i0] + k;
+                S.rec[k] = recs[r];
+                S.rec[k].mode |= (rec_step[r] - (int)i0) << kStepShift;
+                X3.c3[k] = c3s[r];
+            }
+            a.noise = noise ? noise + i0 * n : nullptr;
+            profile_begin(BESO_SITE_FUSED_LAYER, s);
+            st = f16 ? fused_layers_f16(lay, (const char*)packed, a, (float*)(wsp + ws.x), nullptr, BESO_PREC_BF16, s, &S, &X3)
+                     : fused_layers(lay, (const char*)packed, a, (float*)(wsp + ws.x), nullptr, precision, s, &S, &X3);
+            profile_end(BESO_SITE_FUSED_LAYER, s);
+            if (st != BESO_OK) return st;
+            i0 = i1;
+        }
+        return BESO_OK;
+    }
+    // step by step: per evaluation the forward (at x, or at x2 for the second stage of a step) and one update launch, which
+    // also writes the sigma vector of the next evaluation; x2 / den are the workspace's, x stays parked in place
+    {
+        uint32_t bits; memcpy(&bits, &recs[0].sigma, 4);
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)sig, (int)bits, (size_t)batch, s));
+    }
+    for (size_t k = 0; k < recs.size(); ++k) {
+        const StepRec& r = recs[k];
+        const int mode = r.mode & 0xff;
+        const bool second = mode == kStepDpm2Correct || mode == kStepExpCorrect;
+        const bool first = mode == kStepDpm2Predict || mode == kStepExpPredict;
+        st = beso_denoise_fwd(cfg, packed, precision, state, second ? x2 : x, goal, sig, den, batch, t, plan, cond_lambda,
+                              workspace, workspace_bytes, stream);
+        if (st != BESO_OK) return st;
+        SolverStepArgs sv;
+        sv.c2 = r.c2; sv.c3 = c3s[k]; sv.sigma = r.sigma;
+        sv.noise = noise ? noise + (size_t)rec_step[k] * n : nullptr;
+        sv.hist = history;
+        const bool more = k + 1 < recs.size();
+        HIP_TRY(launch_sampler_step(r.mode, first ? x2 : x, nullptr, x, x2, den, r.c0, r.c1, n, s, more ? sig : nullptr,
+                                    more ? recs[k + 1].sigma : 0.f, batch, sv));
     }
     return BESO_OK;
 }

@@ -133,6 +133,86 @@ __device__ __forceinline__ float sampler_update(int mode, float xv, float x2v, f
     return xv + s;
 }
 
+// The updates of beso_sample_solver: internal modes behind the public BESO_STEP_* (beso_sampler_step accepts none of them),
+// with the same sharing between sampler_step_kernel and the head of the sampler loop.  A step mode is
+//   (base mode) | noise flag | LMS term counts << 12 | (the step's index inside its launch) << kStepShift.
+// Two-evaluation steps park x (in `out` in the loop, in place in the step-by-step form) and feed x2 to their second evaluation;
+// the state slabs `h` (k = 0, 1, 2 at h[k * stride]) are the caller's history buffer, read and written per element.
+//   DPM2_PREDICT   d = (x - den)/c0;  x2 <- x + d*c1                c0 = sigma_i, c1 = sigma_mid - sigma_i      :317-375
+//   DPM2_CORRECT   d2 = (x2 - den)/c0;  x <- x_parked + d2*c1       c0 = sigma_mid, c1 = sigma_to - sigma_i
+//   EXP_PREDICT    x2 <- c0*x - c1*den                              DPM-Solver++(2S) stage 1 (r1, e1)            :928-966
+//   EXP_CORRECT    x <- c0*x_parked - c1*den                        stage 2 (r2, e2)
+//   DPM2M_FIRST    x <- c0*x - c1*den;  h0 <- den                   DPM-Solver++(2M), first step (DDIM)          :702-736
+//   DPM2M          bl = c2*den - c3*h0;  x <- c0*x - c1*bl;  h0 <- den
+//   LMS            d = (x - den)/sigma;  s = c0*d (+ c_j*h_{j-1}, j = 1 .. terms);  x <- x + s;  h shifts, h0 <- d   :432-468
+// Noise flags, behind the update (the caller's randn of the step): kStepAddNoise  x <- x + noise*c2 (two rounded operations),
+// kStepScaledNoise  x <- x + (noise*c3)*c2 (three: noise_sampler(...) * s_noise * sigma_up).
+enum { kStepDpm2Predict = 5, kStepDpm2Correct = 6, kStepExpPredict = 7, kStepExpCorrect = 8, kStepDpm2mFirst = 9,
+       kStepDpm2m = 10, kStepLms = 11 };
+constexpr int kStepAddNoise = 0x100, kStepScaledNoise = 0x200;
+constexpr int kStepShift = 16;
+__host__ __device__ constexpr int lms_mode(int terms, int keep) { return kStepLms | (terms << 12) | (keep << 14); }
+__device__ __forceinline__ bool step_parks(int mode) {
+    return mode == BESO_STEP_HEUN_PREDICT || mode == kStepDpm2Predict || mode == kStepExpPredict;
+}
+__device__ __forceinline__ bool step_unparks(int mode) {
+    return mode == BESO_STEP_HEUN_CORRECT || mode == kStepDpm2Correct || mode == kStepExpCorrect;
+}
+// xv: x (the parked x for the second stage of a step), x2v: the second stage's input, dv: the evaluation's denoised value
+__device__ __forceinline__ float solver_update(int mode_bits, float xv, float x2v, float dv, float* h, size_t stride, float sigma,
+                                              float c0, float c1, float c2, float c3) {
+#pragma clang fp contract(off)
+    const int mode = mode_bits & 0xff;
+    if (mode == kStepDpm2Predict) {
+        const float d = (xv - dv) / c0;
+        const float s = d * c1;
+        return xv + s;
+    }
+    if (mode == kStepDpm2Correct) {
+        const float d2 = (x2v - dv) / c0;
+        const float s = d2 * c1;
+        return xv + s;
+    }
+    if (mode == kStepExpPredict || mode == kStepExpCorrect || mode == kStepDpm2mFirst) {
+        const float a = c0 * xv, b = c1 * dv;
+        if (mode == kStepDpm2mFirst) h[0] = dv;
+        return a - b;
+    }
+    if (mode == kStepDpm2m) {
+        const float p = c2 * dv, q = c3 * h[0];
+        const float bl = p - q;
+        h[0] = dv;
+        const float a = c0 * xv, b = c1 * bl;
+        return a - b;
+    }
+    // LMS: the newest slope first, then the older ones (reversed(history)); the slabs keep the last `keep` slopes
+    const int terms = (mode_bits >> 12) & 3, keep = (mode_bits >> 14) & 3;
+    const float d = (xv - dv) / sigma;
+    float s = c0 * d;
+    float old[3];
+    for (int j = 0; j < terms; ++j) old[j] = h[(size_t)j * stride];
+    if (terms > 0) { const float p = c1 * old[0]; s = s + p; }
+    if (terms > 1) { const float p = c2 * old[1]; s = s + p; }
+    if (terms > 2) { const float p = c3 * old[2]; s = s + p; }
+    for (int j = (terms < keep - 1 ? terms : keep - 1); j > 0; --j) h[(size_t)j * stride] = old[j - 1];
+    if (keep > 0) h[0] = d;
+    return xv + s;
+}
+// The step's noise behind the update (mode_bits carries the flag; nz points at the element of the step's randn)
+__device__ __forceinline__ float step_noise(int mode_bits, float o, const float* nz, float c2, float c3) {
+#pragma clang fp contract(off)
+    if (mode_bits & kStepAddNoise) {
+        const float v = *nz * c2;
+        return o + v;
+    }
+    if (mode_bits & kStepScaledNoise) {
+        const float a = *nz * c3;
+        const float v = a * c2;
+        return o + v;
+    }
+    return o;
+}
+
 // Training-mode dropout: keep-scale of one element from a counter-based hash of (seed, site, element index) -- the
 // backward pass recomputes the mask.  p = 0 never reaches this function.  (train.hip; the attention core of the one-launch
 // training forward in fused.hip draws the same mask as attn_small_kernel.)
@@ -244,9 +324,16 @@ enum { EPI_BIAS_STORE = 0, EPI_BIAS_GELU_STORE = 1, EPI_BIAS_RESID = 2 };
 hipError_t launch_gemm(int precision, int epi, const void* A, int lda, const void* Wt, int ldw,
                        const float* bias, void* out, int ldo,
                        int n_store, int M, int Np, int Kp, hipStream_t s);
+// beso_sample_solver's part of an update launch: the numbers behind c0 / c1, the step's randn and the state slabs
+// (slab k of element i at hist[k * n + i])
+struct SolverStepArgs {
+    float c2 = 0.f, c3 = 0.f, sigma = 0.f;
+    const float* noise = nullptr;
+    float* hist = nullptr;
+};
 hipError_t launch_sampler_step(int mode, float* out, float* aux, const float* x, const float* x2, const float* den,
                                float c0, float c1, size_t n, hipStream_t s, float* sig_next = nullptr, float sigma_next = 0.f,
-                               int n_sig = 0);
+                               int n_sig = 0, const SolverStepArgs& sv = SolverStepArgs{});
 
 // small.hip: the chip-wide small-batch path (five short launches per layer)
 // token rows up to which the library takes it by itself (measured, kitchen: bf16 190 ... 228 us for 1 ... 16 samples against

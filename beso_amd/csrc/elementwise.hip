@@ -443,7 +443,7 @@ hipError_t launch_head(const Layout& lay, const char* packed, const FwdArgs& a, 
 __global__ void sampler_step_kernel(int mode, float* __restrict__ out, float* __restrict__ aux,
                                     const float* __restrict__ x, const float* __restrict__ x2,
                                     const float* __restrict__ den, float c0, float c1, size_t n, float* __restrict__ sig_next,
-                                    float sigma_next, int n_sig) {
+                                    float sigma_next, int n_sig, SolverStepArgs sv) {
     if (sig_next)
         for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_sig; i += gridDim.x * blockDim.x) sig_next[i] = sigma_next;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -455,23 +455,29 @@ __global__ void sampler_step_kernel(int mode, float* __restrict__ out, float* __
 #pragma clang fp contract(off)
             const float nz = x2[i] * c0;
             r = xv + nz;
-        } else {
+        } else if ((mode & 0xff) <= BESO_STEP_HEUN_CORRECT) {
             float a = (mode == BESO_STEP_HEUN_CORRECT) ? aux[i] : 0.f;
-            r = sampler_update(mode, xv, mode == BESO_STEP_HEUN_CORRECT ? x2[i] : 0.f, dv, a, c0, c1);
+            r = sampler_update(mode & 0xff, xv, mode == BESO_STEP_HEUN_CORRECT ? x2[i] : 0.f, dv, a, c0, c1);
             if (mode == BESO_STEP_HEUN_PREDICT) aux[i] = a;
+        } else {
+            // beso_sample_solver's modes: x is the parked x of a two-evaluation step, x2 the second evaluation's input
+            r = solver_update(mode, xv, step_unparks(mode & 0xff) ? x2[i] : 0.f, dv, sv.hist ? sv.hist + i : nullptr, n, sv.sigma,
+                              c0, c1, sv.c2, sv.c3);
         }
+        if (mode & (kStepAddNoise | kStepScaledNoise)) r = step_noise(mode, r, sv.noise + i, sv.c2, sv.c3);
         out[i] = r;
     }
 }
 
 hipError_t launch_sampler_step(int mode, float* out, float* aux, const float* x, const float* x2, const float* den,
-                               float c0, float c1, size_t n, hipStream_t s, float* sig_next, float sigma_next, int n_sig) {
+                               float c0, float c1, size_t n, hipStream_t s, float* sig_next, float sigma_next, int n_sig,
+                               const SolverStepArgs& sv) {
     (void)hipGetLastError();   // clear any stale error left by other runtime users in this thread
     int grid = (int)((n + 255) / 256);
     if (grid > 2048) grid = 2048;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(sampler_step_kernel, dim3(grid), dim3(256), 0, s, mode, out, aux, x, x2, den, c0, c1, n, sig_next, sigma_next,
-                       n_sig);
+                       n_sig, sv);
     return hipGetLastError();
 }
 

@@ -8,15 +8,19 @@ namespace beso {
 // is evaluated at (the same for every sample) and the update that follows it in the head (BESO_STEP_* with the coefficients
 // of beso_sampler_step).  Travels as a kernel argument: no table in device memory, nothing to copy, graph-capturable.
 constexpr int kMaxLoopEvals = 128;
-// mode: BESO_STEP_* | kStepAddNoise (euler_ancestral: behind the update, x += noise[evaluation] * c2 -- the caller's randn of
-// that step, gc_sampling.py:246-247)
-constexpr int kStepAddNoise = 0x100;
+// mode: BESO_STEP_* or one of beso_sample_solver's modes (common.h), | kStepAddNoise / kStepScaledNoise (ancestral samplers: behind
+// the update, x += noise[step] * c2 -- the caller's randn of that step, gc_sampling.py:246-247), | the step's index inside the
+// launch << kStepShift (the slab of EdgeArgs::noise)
 struct StepRec { float sigma, c0, c1; int mode; float c2; };
 struct SampleSteps {
     int n;                         // evaluations of this launch; 0: one plain forward (per-sample sigma, out <- denoised)
     int pad[3];
     StepRec rec[kMaxLoopEvals];          // 20 B each: 2.5 KiB of the 4 KiB kernel argument
 };
+// The fifth number of an evaluation (DPM-Solver++(2M)'s c3, the fourth LMS coefficient, s_noise of DPM-Solver++(2S) ancestral).
+// A kernel argument of its own BEHIND stamps / cap: the arguments the loop-free instances read keep their offsets (and those
+// instances their code); 0.5 KiB more of the 4 KiB (static_assert in fused.hip).
+struct SampleExtra { float c3[kMaxLoopEvals]; };
 constexpr int kLoopMaxElems = 512;   // action-window elements per workgroup the loop can carry (one per thread)
 
 size_t fused_packed_bytes(const Layout& lay, int precision);
@@ -24,7 +28,7 @@ int    fused_pack(const Layout& lay, const float* const* params, char* packed, i
 int    fused_level(const Layout& lay, const FwdArgs& a, int precision);   // 0 none, 1 MLP block, 2 whole layers
 int    fused_layer_edges(const Layout& lay);        // bit 0: fused_layers embeds, bit 1: it runs the head
 int    fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,
-                    hipStream_t s, const SampleSteps* steps = nullptr);
+                    hipStream_t s, const SampleSteps* steps = nullptr, const SampleExtra* extra = nullptr);
 bool   fused_can_loop(const Layout& lay, const FwdArgs& a, int precision);   // the whole sampler loop can run inside one launch
 int    fused_mlp_block(const Layout& lay, const char* packed, int layer, float* x, int M, hipStream_t s);
 bool   fused_has_lin_blocks(const Layout& lay, int precision);
@@ -89,7 +93,7 @@ int    fused_pack_f16(const Layout& lay, const float* const* params, char* packe
 int    fused_level_f16(const Layout& lay, const FwdArgs& a, int precision);
 int    fused_layer_edges_f16(const Layout& lay);
 int    fused_layers_f16(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,
-                        hipStream_t s, const SampleSteps* steps = nullptr);
+                        hipStream_t s, const SampleSteps* steps = nullptr, const SampleExtra* extra = nullptr);
 bool   fused_can_loop_f16(const Layout& lay, const FwdArgs& a, int precision);
 
 }  // namespace beso

@@ -1518,8 +1518,9 @@ struct LoopState {
     int mode;              // -1: a single forward (out <- denoised); else the BESO_STEP_* update of this evaluation (| kStepAddNoise)
     float c0, c1, sigma;   // the step's coefficients; sigma of this evaluation (> 0: uniform over the batch)
     bool last;             // the last evaluation of the launch: x goes out
-    float c2;              // kStepAddNoise: sigma_up
-    int ev;                // index of the evaluation inside the launch (its slab of EdgeArgs::noise)
+    float c2;              // kStepAddNoise: sigma_up (beso_sample_solver's modes: their third coefficient)
+    int ev;                // index of the evaluation's step inside the launch (its slab of EdgeArgs::noise)
+    float c3;              // beso_sample_solver's modes: SampleExtra's number of the evaluation
 };
 template <int RPW, int NT = kNTT>
 __device__ __forceinline__ void head_tile(const Tile<RPW>& T, const EdgeArgs& e, const FusedDims& d, const char* gw,
@@ -1600,20 +1601,24 @@ __device__ __forceinline__ void head_tile(const Tile<RPW>& T, const EdgeArgs& e,
         float* dst = e.out + (size_t)b0 * e.t * act + it;
         if (ls.mode < 0) *dst = r;
         else {
+            // (aux: Heun's first slope, or the state slabs of beso_sample_solver -- slab k at k * B * t * act)
             float* daux = e.aux + (size_t)b0 * e.t * act + it;
             float xv = av, x2v = 0.f, d1 = 0.f;
             const int mode = ls.mode & 0xff;
-            if (mode == BESO_STEP_HEUN_CORRECT) { xv = *dst; x2v = av; d1 = *daux; }      // (wave-uniform)
-            float o = sampler_update(mode, xv, x2v, r, d1, ls.c0, ls.c1);
-            if (ls.mode & kStepAddNoise) {
-                // sample_euler_ancestral (gc_sampling.py:246-247): x <- x + randn * sigma_up, the step's draw supplied by the
-                // caller; two rounded operations, as BESO_STEP_ADD_NOISE of the step-by-step form
-                const float nz = e.noise[((size_t)ls.ev * e.B + b0) * e.t * act + it] * ls.c2;
-                o = o + nz;
-            }
+            if (step_unparks(mode)) { xv = *dst; x2v = av; }      // (wave-uniform)
+            if (mode == BESO_STEP_HEUN_CORRECT) d1 = *daux;
+            float o = mode <= BESO_STEP_HEUN_CORRECT
+                          ? sampler_update(mode, xv, x2v, r, d1, ls.c0, ls.c1)
+                          : solver_update(ls.mode, xv, x2v, r, daux, (size_t)e.B * e.t * act, ls.sigma, ls.c0, ls.c1, ls.c2, ls.c3);
+            // ancestral samplers (gc_sampling.py:246-247 and the like): x <- x + randn * sigma_up, the step's draw supplied by
+            // the caller; rounded operation by operation, as the step-by-step form
+            if (ls.mode & (kStepAddNoise | kStepScaledNoise))
+                o = step_noise(ls.mode, o, e.noise + ((size_t)ls.ev * e.B + b0) * e.t * act + it, ls.c2, ls.c3);
             xs[it] = o;
-            if (mode == BESO_STEP_HEUN_PREDICT) { *dst = xv; *daux = d1; }
-            else if (ls.last) *dst = o;
+            if (step_parks(mode)) {
+                *dst = xv;
+                if (mode == BESO_STEP_HEUN_PREDICT) *daux = d1;
+            } else if (ls.last) *dst = o;
         }
     }
 }
@@ -3184,10 +3189,13 @@ __global__ __launch_bounds__(512, 2) void lin_block_x3_kernel(float* __restrict_
 // CORE = 1: the long-sequence instance (SPW = 1: a sample of up to 16 NTA tokens per workgroup, tokens in natural order).
 // LOOP = 1: the sampler-loop instance (S.n evaluations, each followed by its update in the head); LOOP = 0 is one forward and
 // compiles to the loop-free code (S is not read).
+static_assert(3 * sizeof(void*) + sizeof(FusedDims) + 6 * sizeof(int) + sizeof(EdgeArgs) + sizeof(SampleSteps) +
+              sizeof(SampleExtra) + 64 <= 4096, "layers_kernel's arguments stay under the 4 KiB kernel-argument limit");
 template <int RPW, int KS, int HG, int NTL, int SPW = kSPW, int NTA = kNTT, int PX = 0, int CORE = 0, int LOOP = 0>
 __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, const char* __restrict__ lw0,
                                                         FusedDims d, int l0, int l1, int n_samples_total, int Tn,
-                                                        EdgeArgs e, SampleSteps S, unsigned long long* stamps, int cap) {
+                                                        EdgeArgs e, SampleSteps S, unsigned long long* stamps, int cap,
+                                                        SampleExtra X3) {
     Stamps st{stamps, cap, 0};
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     static_assert(CORE == 0 || (SPW == 1 && PX == 0), "long-sequence instance");
@@ -3217,7 +3225,7 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
     const bool actions_first = CORE == 0;
     build_slot_tabs(tb, n_samples, Tn, e.t, d.G, actions_first, CORE == 1 ? 7 : 4);
     // the action windows of the workgroup's real samples (contiguous in `action`): x_T of the sampler loop / the noisy action
-    LoopState ls{-1, 0.f, 0.f, 0.f, true, 0.f, 0};
+    LoopState ls{-1, 0.f, 0.f, 0.f, true, 0.f, 0, 0.f};
     {
         int b0; bool un0;
         sample_of(e, s0, b0, un0);
@@ -3342,7 +3350,7 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
     stamp(st, 4);
     if constexpr (LOOP) {
         const StepRec rec = S.rec[ev];
-        ls.mode = rec.mode; ls.c0 = rec.c0; ls.c1 = rec.c1; ls.c2 = rec.c2; ls.ev = ev;
+        ls.mode = rec.mode; ls.c0 = rec.c0; ls.c1 = rec.c1; ls.c2 = rec.c2; ls.c3 = X3.c3[ev]; ls.ev = rec.mode >> kStepShift;
         ls.last = ev + 1 == n_evals;
     }
     {
@@ -4124,22 +4132,22 @@ hipError_t launch_tail_block(float* x, const char* lw, const char* lw_next, cons
 // One instance of layers_kernel: LDS attribute once, then the launch (LOOP = 1: the sampler-loop form, steps.n evaluations).
 template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int PX, int CORE, int LOOP>
 hipError_t launch_instance(size_t lds_bytes, int grid, float* x, const char* lw0, const FusedDims& d, int l0, int l1,
-                           int n_samples, int Tn, const EdgeArgs& edge, const SampleSteps& steps, hipStream_t s) {
+                           int n_samples, int Tn, const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, hipStream_t s) {
     static LdsAttr attr;
     hipError_t e = ensure_lds(layers_kernel<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, LOOP>, lds_bytes, &attr);
     if (e != hipSuccess) return e;
     (void)hipGetLastError();
     hipLaunchKernelGGL((layers_kernel<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, LOOP>), dim3(grid), dim3(512), lds_bytes, s, x, lw0, d,
-                       l0, l1, n_samples, Tn, edge, steps, g_stamps, g_stamps_cap);
+                       l0, l1, n_samples, Tn, edge, steps, g_stamps, g_stamps_cap, extra);
     return hipGetLastError();
 }
 template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int PX, int CORE>
 hipError_t launch_either(size_t lds_bytes, float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                         const EdgeArgs& edge, const SampleSteps& steps, hipStream_t s) {
+                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, hipStream_t s) {
     const int grid = (n_samples + SPW - 1) / SPW;
     if (steps.n > 0)
-        return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 1>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, s);
-    return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 0>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, s);
+        return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 1>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
+    return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 0>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
 }
 
 // samples of Tn tokens in NT token tiles: the tokens, and the last sample's 16-row attention window, must fit
@@ -4152,7 +4160,7 @@ constexpr int kSmallBatchMax = 512;    // batches up to this size take the two-s
 // it (the instances compute the same per-sample arithmetic -- equal bits --, so the hint is a performance / test knob only).
 template <int RPW, int KS, int HG, int NTL>
 hipError_t launch_layers(float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                         const EdgeArgs& edge, const SampleSteps& steps, int precision, int plan, hipStream_t s) {
+                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, int precision, int plan, hipStream_t s) {
     constexpr LdsMap L = lds_map(KS);
     constexpr int kSmallSPW = 2, kSmallNT = 2, kMidSPW = 4, kMidNT = 4;
     const int want = plan & BESO_PLAN_SPW_MASK;
@@ -4172,30 +4180,30 @@ hipError_t launch_layers(float* x, const char* lw0, const FusedDims& d, int l0, 
         if (four_ok && (want == BESO_PLAN_SPW4 || (want != BESO_PLAN_SPW2 && n_samples > kSmallBatchMax) || !small_ok)) {
             constexpr LdsMapX3 X = lds_map_x3(KS, kX3NT);
             static_assert(X.total <= 160 * 1024, "LDS of the four-sample split-bf16 instance");
-            return launch_either<RPW, KS, HG, kX3NTL, kX3SPW, kX3NT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, s);
+            return launch_either<RPW, KS, HG, kX3NTL, kX3SPW, kX3NT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
         }
         if (!small_ok) return hipErrorInvalidValue;
         constexpr LdsMapX3 X = lds_map_x3(KS, kSmallNT);
-        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, s);
+        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
     }
 #endif
     const bool mid_ok = kMidSPW * Tn <= 16 * kMidNT && (kMidSPW - 1) * Tn + 16 <= 16 * kMidNT;
     // latency instances: the samples' tokens and the last sample's 16-row attention window must fit the token tiles
     if (small_ok && (want == BESO_PLAN_SPW2 || (!want && n_samples <= kSmallBatchMax)))
-        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, s);
+        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
     // up to one workgroup of four samples per CU: two thirds of the throughput instance's work per workgroup
     if (mid_ok && (want == BESO_PLAN_SPW4 || (!want && n_samples <= 2 * kSmallBatchMax)))
-        return launch_either<RPW, KS, HG, NTL, kMidSPW, kMidNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, s);
-    return launch_either<RPW, KS, HG, NTL, kSPW, kNTT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, s);
+        return launch_either<RPW, KS, HG, NTL, kMidSPW, kMidNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
+    return launch_either<RPW, KS, HG, NTL, kSPW, kNTT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
 }
 
 // The long-sequence instance: one sample (Tn <= 16 NT tokens) per workgroup.
 template <int RPW, int KS, int NT>
 hipError_t launch_layers_long(float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                              const EdgeArgs& edge, const SampleSteps& steps, hipStream_t s) {
+                              const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, hipStream_t s) {
     constexpr LdsMap L = lds_map(KS, false, NT);
     static_assert(L.total <= 160 * 1024, "LDS of the long-sequence instance");
-    return launch_either<RPW, KS, 1, NT, 1, NT, 0, 1>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, s);
+    return launch_either<RPW, KS, 1, NT, 1, NT, 0, 1>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
 }
 
 }  // namespace
@@ -4766,11 +4774,13 @@ bool fused_can_loop(const Layout& lay, const FwdArgs& a, int precision) {
 }
 
 int fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,
-                 hipStream_t s, const SampleSteps* steps) {
+                 hipStream_t s, const SampleSteps* steps, const SampleExtra* extra) {
     FusedDims d;
     if (!fused_dims(lay, &d) || !d.attn) return BESO_ERR_UNSUPPORTED;
     static const SampleSteps no_steps{};
+    static const SampleExtra no_extra{};
     const SampleSteps& S = steps ? *steps : no_steps;
+    const SampleExtra& X3 = extra ? *extra : no_extra;
     const char* base = packed + lay.fused;
     EdgeArgs e;
     e.state = a.state; e.action = a.action; e.goal = a.goal; e.sigma = a.sigma; e.out = a.out;
@@ -4787,9 +4797,9 @@ int fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float*
     if ((size_t)(d.seq1 ? 1 : kSPW) * a.t * lay.act * sizeof(float) > (size_t)kXsBytes) return BESO_ERR_UNSUPPORTED;
     if (fused_edges) *fused_edges = 3;
     hipError_t err;
-    if (d.RPW == 3 && d.KS == 12 && d.HG == 1) err = launch_layers<3, 12, 1, 2>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, precision, a.plan, s);    // kitchen: 8 x 4 action tokens
-    else if (d.RPW == 2 && d.KS == 8 && d.HG == 3) err = launch_layers<2, 8, 3, 4>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, precision, a.plan, s);   // block-push: 8 x 5
-    else if (d.seq1 && precision == BESO_PREC_BF16) err = launch_layers_long<4, 16, kLongNT>(x, base, d, 0, lay.L, a.batch, a.T, e, S, s);   // long horizon: 1 x 67 tokens
+    if (d.RPW == 3 && d.KS == 12 && d.HG == 1) err = launch_layers<3, 12, 1, 2>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, precision, a.plan, s);    // kitchen: 8 x 4 action tokens
+    else if (d.RPW == 2 && d.KS == 8 && d.HG == 3) err = launch_layers<2, 8, 3, 4>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, precision, a.plan, s);   // block-push: 8 x 5
+    else if (d.seq1 && precision == BESO_PREC_BF16) err = launch_layers_long<4, 16, kLongNT>(x, base, d, 0, lay.L, a.batch, a.T, e, S, X3, s);   // long horizon: 1 x 67 tokens
                                                                                                              // (one workgroup per REAL sample: pairs run as two passes)
     else return BESO_ERR_UNSUPPORTED;
     return err == hipSuccess ? BESO_OK : BESO_ERR_HIP;

@@ -271,6 +271,54 @@ class ScoreNetRuntime:
         _lib.check(st, "sample[euler_ancestral]")
         return x
 
+    def sample_solver(self, packed: PackedWeights, solver: str, state, x_t, goal, sigmas, cond_lambda: float = 1.0,
+                      eta: float = 1.0, s_noise: float = 1.0, order: int = 4, noise=None, stepwise: bool = False) -> torch.Tensor:
+        """sample_dpm_2 / _dpm_2_ancestral / _dpmpp_2s / _dpmpp_2s_ancestral / _dpmpp_2m / _lms (``_lib.SOLVER_IDS``) as ONE
+        enqueue of all steps (``beso_sample_solver``) -- one launch for the whole loop where the shape has the one-launch kernel
+        (``stepwise``: evaluation by evaluation, bit-identical).  The ancestral solvers' noise is drawn here when ``noise`` is
+        None, one ``torch.randn_like`` per step that draws and in the order of the steps, as ``sample_ancestral``;
+        ``noise`` [n_steps, B, t, act] injects it instead.  The multistep state lives in a buffer of this call."""
+        if solver not in _lib.SOLVER_IDS:
+            raise ValueError("desired sampler type not found!")
+        if solver == "lms" and not 1 <= int(order) <= 4:
+            raise ValueError("beso_sample_solver runs LMS orders 1 ... 4")
+        dev, B, t, state, x, goal, _ = self._prep(state, x_t, goal, None)
+        if x.data_ptr() == x_t.data_ptr():
+            x = x.clone()
+        sig = [float(s) for s in (sigmas.detach().cpu().tolist() if torch.is_tensor(sigmas) else sigmas)]
+        n_steps = len(sig) - 1
+        if solver in ("dpm_2_ancestral", "dpmpp_2s_ancestral"):
+            if noise is None:
+                noise = torch.zeros((n_steps,) + tuple(x.shape), dtype=torch.float32, device=dev)
+                for i in range(n_steps):
+                    sf, sn = sig[i], sig[i + 1]
+                    up = min(sn, eta * (sn ** 2 * (sf ** 2 - sn ** 2) / sf ** 2) ** 0.5) if eta else 0.0
+                    # dpm_2_ancestral draws on steps with sigma_down > 0 (gc_sampling.py:405-411), dpmpp_2s_ancestral on every step
+                    if solver == "dpmpp_2s_ancestral" or sn ** 2 - up ** 2 > 0:
+                        noise[i] = torch.randn_like(x)
+            else:
+                noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+                if noise.shape != (n_steps,) + tuple(x.shape):
+                    raise ValueError("noise must be [len(sigmas) - 1, B, t, act]")
+        else:
+            noise = None
+        n_hist = {"dpmpp_2m": 1, "lms": int(order) - 1}.get(solver, 0)
+        hist = torch.empty((n_hist,) + tuple(x.shape), dtype=torch.float32, device=dev) if n_hist else None
+        two = cond_lambda not in (0.0, 1.0)
+        ws = self._workspace(B, t, two, dev)
+        arr = (C.c_float * len(sig))(*sig)
+        gp = goal.data_ptr() if goal is not None else None
+        with torch.cuda.device(dev):
+            st = self.lib.beso_sample_solver(C.byref(self.cfg), packed.buf.data_ptr(), packed.precision, _lib.SOLVER_IDS[solver],
+                                             state.data_ptr(), gp, x.data_ptr(), B, t, arr, len(sig), float(cond_lambda),
+                                             float(eta), float(s_noise), int(order),
+                                             noise.data_ptr() if noise is not None else None,
+                                             hist.data_ptr() if hist is not None else None,
+                                             (_lib.SAMPLE_STEPWISE if stepwise else 0) | forward_hints(),
+                                             ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+        _lib.check(st, f"sample[{solver}]")
+        return x
+
     # ------------------------------------------------------------------ profiling hooks (bench.py)
     def profile_enable(self, site: str) -> None:
         self.lib.beso_profile_enable(_lib.SITES[site])

@@ -14,6 +14,7 @@
  *                                                                      k_diffusion/gc_sampling.py:205-210,296-310,921-923
  *   beso_sample         <- sample_ddim / sample_euler / sample_heun    k_diffusion/gc_sampling.py:167-213,259-314,895-924
  *   beso_sample_ancestral <- sample_euler_ancestral                    k_diffusion/gc_sampling.py:216-256
+ *   beso_sample_solver  <- sample_dpm_2(_ancestral) / sample_dpmpp_2s(_ancestral) / sample_dpmpp_2m / sample_lms
  *   beso_loss_grad      <- GCDenoiser.loss + loss.backward()           k_diffusion/score_wrappers.py:45-79, beso_agent.py:228-233
  *                          (+ DiffusionGPT.mask_cond, training mode     k_diffusion/score_gpts.py:298-299, 360-371)
  *   beso_goal_mask      <- the Bernoulli mask of DiffusionGPT.mask_cond k_diffusion/score_gpts.py:365-368
@@ -207,6 +208,29 @@ int beso_sample(const beso_config* cfg, const void* packed, int precision, int s
 int beso_sample_ancestral(const beso_config* cfg, const void* packed, int precision, const float* state, const float* goal,
                           float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda, float eta,
                           const float* noise, int flags, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The other fixed-schedule samplers of gc_sampling.py as one enqueue (scaler = None, no callback, s_churn = 0):
+ *   BESO_SOLVER_DPM_2                sample_dpm_2               :317-375   2 evaluations per step, 1 on the last
+ *   BESO_SOLVER_DPM_2_ANCESTRAL      sample_dpm_2_ancestral     :378-413   to sigma_down, then x += noise_i * sigma_up
+ *   BESO_SOLVER_DPMPP_2S             sample_dpmpp_2s            :928-966   2 evaluations per step, 1 on the last
+ *   BESO_SOLVER_DPMPP_2S_ANCESTRAL   sample_dpmpp_2s_ancestral  :969-1016  to sigma_down, then x += noise_i * s_noise * sigma_up
+ *   BESO_SOLVER_DPMPP_2M             sample_dpmpp_2m            :702-736   1 evaluation per step
+ *   BESO_SOLVER_LMS                  sample_lms (order 1 ... 4) :432-468   1 evaluation per step
+ * Coefficients in fp32 on the host as the reference's scalars (the LMS integrals of its Lagrange basis in double, exactly).
+ * `noise` (the ancestral solvers only; else may be NULL): a DEVICE array of n_sigmas - 1 standard-normal tensors
+ * [batch,t,act] back to back, the draws of the reference's steps (entries of steps that draw nothing are not read).
+ * `history` (DPMPP_2M: 1 slab, LMS: order - 1 slabs of batch*t*act floats; else may be NULL): caller-owned DEVICE scratch
+ * for the state a multistep solver carries from step to step.  `eta` is the ancestral solvers', `s_noise` DPMPP_2S_ANCESTRAL's,
+ * `order` LMS's.  One launch for the whole loop where beso_sample runs one (up to 128 evaluations per launch, cut at step
+ * boundaries); otherwise, and with BESO_SAMPLE_STEPWISE, one forward + one update launch per evaluation (bit-identical).
+ * BESO_ERR_BAD_ARG: unknown solver or flags, LMS order outside 1 ... 4, a missing noise / history, eta < 0, an interior
+ * sigma <= 0.  Everything else as beso_sample; the workspace is beso_workspace_bytes'.                                   */
+enum { BESO_SOLVER_DPM_2 = 0, BESO_SOLVER_DPM_2_ANCESTRAL = 1, BESO_SOLVER_DPMPP_2S = 2, BESO_SOLVER_DPMPP_2S_ANCESTRAL = 3,
+       BESO_SOLVER_DPMPP_2M = 4, BESO_SOLVER_LMS = 5 };
+int beso_sample_solver(const beso_config* cfg, const void* packed, int precision, int solver, const float* state,
+                       const float* goal, float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda,
+                       float eta, float s_noise, int order, const float* noise, float* history, int flags,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* One Adam / AdamW step over ALL parameter tensors in one launch, optionally followed by the EMA update
  * of the shadow copy on the updated parameters.  Replaces `self.optimizer.step()` + `self.ema_helper.update`
