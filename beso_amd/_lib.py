@@ -21,6 +21,9 @@ TRAIN_LAST_ACTION_ONLY, TRAIN_PLAN_PER_OP, TRAIN_PLAN_TILES = 1, 2, 4
 SAMPLER_IDS = {"ddim": 0, "euler": 1, "heun": 2}
 # beso_sample_solver (include/beso_hip.h BESO_SOLVER_*): the gc_sampling.py function names without "sample_"
 SOLVER_IDS = {"dpm_2": 0, "dpm_2_ancestral": 1, "dpmpp_2s": 2, "dpmpp_2s_ancestral": 3, "dpmpp_2m": 4, "lms": 5}
+# every sampler loop the library runs as one enqueue: name -> (C entry point, its sampler / solver id)
+SAMPLERS = {**{k: ("beso_sample", v) for k, v in SAMPLER_IDS.items()}, "euler_ancestral": ("beso_sample_ancestral", None),
+            **{k: ("beso_sample_solver", v) for k, v in SOLVER_IDS.items()}}
 GOAL_RANDOM, GOAL_TAIL, GOAL_SEQ_END = 0, 1, 2
 STEP_DDIM, STEP_EULER, STEP_HEUN_PREDICT, STEP_HEUN_CORRECT = 0, 1, 2, 3
 SITES = {"off": 0, "gemm_qkv": 1, "gemm_proj": 2, "gemm_fc1": 3, "gemm_fc2": 4, "attention": 5,

@@ -11,9 +11,9 @@ MI355X-first differences that do not change results:
     as fp32 scalars, so the loop never branches on a device tensor (the reference syncs on every
     ``sigmas[i + 1] == 0`` / ``s_tmin <= sigmas[i]`` test: gc_sampling.py:198,289,301,360);
   * when ``model`` is a ``beso_amd`` GCDenoiser (optionally inside ClassifierFreeSampleModel) and the
-    call is the plain one (no churn, no callback, no scaler, no extra args),
-    ddim / euler / heun / euler_ancestral run as ONE enqueue of the whole loop through ``beso_sample`` / ``beso_sample_ancestral``
-    (include/beso_hip.h) -- otherwise the generic loops below call ``model`` once per evaluation.
+    call is the plain one (no churn, no callback, no scaler, no extra args), ddim / euler / heun / euler_ancestral / dpm_2 /
+    dpm_2_ancestral / dpmpp_2s / dpmpp_2s_ancestral / dpmpp_2m / lms run as ONE enqueue of the whole loop
+    (``GCDenoiser.fused_sampler``, include/beso_hip.h) -- otherwise the generic loops below call ``model`` once per evaluation.
 """
 import math
 
@@ -139,35 +139,33 @@ def _fused_target(model):
     return None, None
 
 
-def _try_fused(name, model, state, action, goal, sigmas, scaler, extra_args, callback):
-    if scaler is not None or callback is not None or extra_args:
-        return None
-    den, lam = _fused_target(model)
-    if den is None or not action.is_cuda:
-        return None
-    sig = _host_sigmas(sigmas)
-    if not _interior_positive(sig):
-        return None                    # e.g. get_sigmas_linear(sigma_min=0), the clipped cosine_beta: the stepwise loop serves them
-    return den.fused_sampler(name, state, action, goal, sig, cond_lambda=lam)
-
-
-def _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback):
-    """(GCDenoiser, cond_lambda, host sigmas) when a sampler call can run as one enqueue (``beso_sample_solver``), else None.
-    Checked before anything is drawn: the ancestral samplers pre-draw their noise only for a call that takes this path."""
+def _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback):
+    """(GCDenoiser, cond_lambda, host sigmas) when a sampler call can run as one enqueue (``GCDenoiser.fused_sampler``), else
+    None: the plain call (no scaler, callback or extra_args) on a ``beso_amd`` denoiser whose inputs it runs, with a schedule
+    that is positive up to its trailing value (get_sigmas_linear(sigma_min=0), the clipped cosine_beta: the Python loop serves
+    them).  Each sampler adds its own conditions.  Checked before anything is drawn: the ancestral samplers pre-draw their
+    noise only for a call that takes this path."""
     if scaler is not None or callback is not None or extra_args:
         return None
     den, lam = _fused_target(model)
     if den is None or not action.is_cuda or not den.can_fuse_sampler(state, action, goal):
         return None
     sig = _host_sigmas(sigmas)
-    if not _interior_positive(sig):
+    if len(sig) < 2 or not all(float(v) > 0.0 for v in sig[:-1]):
         return None
     return den, lam, sig
 
 
-def _interior_positive(sig) -> bool:
-    """beso_sample / beso_sample_ancestral take schedules whose values are positive up to the trailing one."""
-    return len(sig) >= 2 and all(float(v) > 0.0 for v in sig[:-1])
+def predraw_noise(sampler, sig, action, eta, noise_sampler=None):
+    """The draws of an ancestral sampler's loop made up front for its one enqueue, in the loop's order and number:
+    [len(sig) - 1, *action.shape], zero where a step draws nothing.  dpmpp_2s_ancestral draws on every step (through
+    ``noise_sampler``), euler_ancestral and dpm_2_ancestral on the steps whose sigma_down != 0 (``get_ancestral_step``)."""
+    noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
+    noise = torch.zeros((len(sig) - 1,) + tuple(action.shape), dtype=torch.float32, device=action.device)
+    for i in range(len(sig) - 1):
+        if sampler == 'dpmpp_2s_ancestral' or get_ancestral_step(sig[i], sig[i + 1], eta=eta)[0] != 0:
+            noise[i] = noise_sampler(sig[i], sig[i + 1])
+    return noise
 
 
 def _churn(i, n, sig, s_churn, s_tmin, s_tmax):
@@ -185,10 +183,10 @@ def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     The generic loop draws ``eps`` every step like the reference (:199), used or not; the fused
     loop draws nothing (with s_churn = 0 the draws never enter the result)."""
     extra_args = {} if extra_args is None else extra_args
-    if not s_churn:
-        fused = _try_fused('euler', model, state, action, goal, sigmas, scaler, extra_args, callback)
-        if fused is not None:
-            return fused
+    tgt = None if s_churn else _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback)
+    if tgt is not None:
+        den, lam, sig = tgt
+        return den.fused_sampler('euler', state, action, goal, sig, cond_lambda=lam)
     sig = _host_sigmas(sigmas)
     n = len(sig) - 1
     for i in range(n):
@@ -212,12 +210,11 @@ def sample_euler_ancestral(model, state, action, goal, sigmas, scaler=None, extr
     """Euler steps to sigma_down, then fresh noise of scale sigma_up (:216-256).  The plain call on a ``beso_amd``
     denoiser runs as one enqueue (``beso_sample_ancestral``) with the same sequence of ``randn_like`` draws."""
     extra_args = {} if extra_args is None else extra_args
-    if scaler is None and callback is None and not extra_args and eta >= 0:
-        den, lam = _fused_target(model)
-        if den is not None and action.is_cuda and _interior_positive(_host_sigmas(sigmas)):
-            fused = den.fused_sampler('euler_ancestral', state, action, goal, _host_sigmas(sigmas), cond_lambda=lam, eta=eta)
-            if fused is not None:
-                return fused
+    tgt = _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback) if eta >= 0 else None
+    if tgt is not None:
+        den, lam, sig = tgt
+        return den.fused_sampler('euler_ancestral', state, action, goal, sig, cond_lambda=lam, eta=eta,
+                                 noise=predraw_noise('euler_ancestral', sig, action, eta))
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)
@@ -239,10 +236,10 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
     """Algorithm 2 of Karras et al. (2022): Euler predictor + trapezoid corrector; the last step
     (sigma_next == 0) is plain Euler (:259-314)."""
     extra_args = {} if extra_args is None else extra_args
-    if not s_churn:
-        fused = _try_fused('heun', model, state, action, goal, sigmas, scaler, extra_args, callback)
-        if fused is not None:
-            return fused
+    tgt = None if s_churn else _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback)
+    if tgt is not None:
+        den, lam, sig = tgt
+        return den.fused_sampler('heun', state, action, goal, sig, cond_lambda=lam)
     sig = _host_sigmas(sigmas)
     n = len(sig) - 1
     for i in range(n):
@@ -278,7 +275,7 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     """DPM-Solver-2-like midpoint steps in log sigma (:317-375).  With s_churn = 0 the plain call on a ``beso_amd`` denoiser
     runs as one enqueue (``beso_sample_solver``; the generic loop's unused ``eps`` draws are not made)."""
     extra_args = {} if extra_args is None else extra_args
-    tgt = None if s_churn else _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback)
+    tgt = None if s_churn else _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback)
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('dpm_2', state, action, goal, sig, cond_lambda=lam)
@@ -312,14 +309,11 @@ def sample_dpm_2_ancestral(model, state, action, goal, sigmas, scaler=None, extr
     """Ancestral variant of the DPM-Solver-2-like sampler (:378-413).  The plain call on a ``beso_amd`` denoiser runs as one
     enqueue (``beso_sample_solver``) with the loop's ``randn_like`` draws made up front, in the same order and number."""
     extra_args = {} if extra_args is None else extra_args
-    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback) if eta >= 0 else None
+    tgt = _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback) if eta >= 0 else None
     if tgt is not None:
         den, lam, sig = tgt
-        noise = torch.zeros((len(sig) - 1,) + tuple(action.shape), dtype=torch.float32, device=action.device)
-        for i in range(len(sig) - 1):
-            if get_ancestral_step(sig[i], sig[i + 1], eta=eta)[0] != 0:
-                noise[i] = torch.randn_like(action)
-        return den.fused_sampler('dpm_2_ancestral', state, action, goal, sig, cond_lambda=lam, eta=eta, noise=noise)
+        return den.fused_sampler('dpm_2_ancestral', state, action, goal, sig, cond_lambda=lam, eta=eta,
+                                 noise=predraw_noise('dpm_2_ancestral', sig, action, eta))
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)
@@ -361,7 +355,7 @@ def sample_lms(model, state, action, goal, sigmas, scaler=None, extra_args=None,
     """Linear multistep sampler (:432-468).  Orders up to 4 on a ``beso_amd`` denoiser run as one enqueue
     (``beso_sample_solver``: the coefficients are the exact integrals that quad approximates)."""
     extra_args = {} if extra_args is None else extra_args
-    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback) if 1 <= order <= 4 else None
+    tgt = _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback) if 1 <= order <= 4 else None
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('lms', state, action, goal, sig, cond_lambda=lam, order=order)
@@ -395,7 +389,7 @@ def _exp_step_coeffs(s_from, s_to):
 def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None):
     """DPM-Solver++(2M) (:702-736); one enqueue (``beso_sample_solver``) on a ``beso_amd`` denoiser."""
     extra_args = {} if extra_args is None else extra_args
-    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback)
+    tgt = _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback)
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('dpmpp_2m', state, action, goal, sig, cond_lambda=lam)
@@ -421,9 +415,10 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
                 eta=1.):
     """DPM-Solver-1 / DDIM (:895-924).  The final step (sigma_next = 0) returns the denoised action."""
     extra_args = {} if extra_args is None else extra_args
-    fused = _try_fused('ddim', model, state, action, goal, sigmas, None, extra_args, callback)
-    if fused is not None:
-        return fused
+    tgt = _fused_call(model, state, action, goal, sigmas, None, extra_args, callback)       # (ddim ignores the scaler)
+    if tgt is not None:
+        den, lam, sig = tgt
+        return den.fused_sampler('ddim', state, action, goal, sig, cond_lambda=lam)
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)
@@ -439,7 +434,7 @@ def sample_dpmpp_2s(model, state, action, goal, sigmas, scaler=None, extra_args=
                     eta=1.):
     """DPM-Solver++(2S) (:928-966); one enqueue (``beso_sample_solver``) on a ``beso_amd`` denoiser."""
     extra_args = {} if extra_args is None else extra_args
-    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback)
+    tgt = _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback)
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('dpmpp_2s', state, action, goal, sig, cond_lambda=lam)
@@ -474,14 +469,11 @@ def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, e
     (``beso_sample_solver``) with the loop's ``noise_sampler`` calls made up front, in the same order and number."""
     extra_args = {} if extra_args is None else extra_args
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
-    tgt = _solver_target(model, state, action, goal, sigmas, scaler, extra_args, callback) if eta >= 0 else None
+    tgt = _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback) if eta >= 0 else None
     if tgt is not None:
         den, lam, sig = tgt
-        noise = torch.zeros((len(sig) - 1,) + tuple(action.shape), dtype=torch.float32, device=action.device)
-        for i in range(len(sig) - 1):
-            noise[i] = noise_sampler(sig[i], sig[i + 1])
         return den.fused_sampler('dpmpp_2s_ancestral', state, action, goal, sig, cond_lambda=lam, eta=eta, s_noise=s_noise,
-                                 noise=noise)
+                                 noise=predraw_noise('dpmpp_2s_ancestral', sig, action, eta, noise_sampler))
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)

@@ -11,7 +11,6 @@ from torch import nn
 from ...._instantiate import instantiate
 from .score_gpts import DiffusionGPT
 from .utils import append_dims
-from .... import _lib
 from ....training import HipTrainStep, ScoreMatchingLoss
 
 
@@ -128,18 +127,10 @@ class GCDenoiser(nn.Module):
 
     def fused_sampler(self, sampler: str, state, x_t, goal, sigmas, cond_lambda: float = 1.0, eta: float = 1.0, noise=None,
                       stepwise: bool = False, s_noise: float = 1.0, order: int = 4):
-        """Whole ddim / euler / heun / euler_ancestral loop as one enqueue (``beso_sample``, ``beso_sample_ancestral``), and
-        dpm_2 / dpm_2_ancestral / dpmpp_2s / dpmpp_2s_ancestral / dpmpp_2m / lms (``beso_sample_solver``); None if not
-        applicable."""
+        """A whole sampler loop of ``_lib.SAMPLERS`` as one enqueue (``ScoreNetRuntime.sample``); None if not applicable."""
         inner = self.inner_model
         if not self.can_fuse_sampler(state, x_t, goal):
             return None
-        if sampler in _lib.SOLVER_IDS:
-            return inner.runtime(self.sigma_data).sample_solver(inner.packed_weights(), sampler, state, x_t, goal, sigmas,
-                                                                cond_lambda=cond_lambda, eta=eta, s_noise=s_noise, order=order,
-                                                                noise=noise, stepwise=stepwise)
-        if sampler == "euler_ancestral":
-            return inner.runtime(self.sigma_data).sample_ancestral(inner.packed_weights(), state, x_t, goal, sigmas,
-                                                                   cond_lambda=cond_lambda, eta=eta, noise=noise, stepwise=stepwise)
         return inner.runtime(self.sigma_data).sample(inner.packed_weights(), sampler, state, x_t, goal, sigmas,
-                                                     cond_lambda=cond_lambda, stepwise=stepwise)
+                                                     cond_lambda=cond_lambda, eta=eta, s_noise=s_noise, order=order,
+                                                     noise=noise, stepwise=stepwise)

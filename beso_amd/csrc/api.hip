@@ -298,6 +298,246 @@ static int forward(const beso_config* cfg, const void* packed, int precision, co
     return r;
 }
 
+// ---------------------------------------------------------------------------------------------
+// sampling loops: each sampler entry point lists its network evaluations (a plan) and one driver runs the list
+// ---------------------------------------------------------------------------------------------
+// One evaluation: its record (sigma, c0, c1, mode, c2), its fifth number (SampleExtra's c3) and the sampler step it belongs to.
+// Every coefficient is an fp32 scalar computed as the reference computes it (numpy float32 / 0-d tensors).
+struct PlanEval { StepRec rec; float c3; int step; };
+struct Plan {
+    std::vector<PlanEval> ev;
+    std::vector<int> first;      // index of the first evaluation of every step, then ev.size()
+    void add(int step, float sigma, float c0, float c1, int mode, float c2 = 0.f, float c3 = 0.f) {
+        ev.push_back(PlanEval{StepRec{sigma, c0, c1, mode, c2}, c3, step});
+    }
+};
+
+// get_ancestral_step (gc_sampling.py:107-114) in fp32
+static void ancestral_step(float sf, float sn, float eta, float& down, float& up) {
+    down = sn; up = 0.f;
+    if (eta != 0.f) {
+        up = eta * sqrtf(sn * sn * (sf * sf - sn * sn) / (sf * sf));
+        if (sn < up) up = sn;
+        down = sqrtf(sn * sn - up * up);
+    }
+}
+
+// exp(lerp(log a, log b, 0.5))
+static float log_midpoint(float a, float b) {
+    const float la = logf(a), lb = logf(b);
+    const float hm = 0.5f * (lb - la);
+    return expf(la + hm);
+}
+
+// The exponential-integrator step from sigma a to sigma b (gc_sampling.py:921-923): t = -log a, h = -log b - t,
+// x <- ratio*x - em1*den with ratio = sigma_fn(t + h)/sigma_fn(t), em1 = expm1(-h).  b == 0 -> h = +inf -> x = den exactly.
+struct ExpStep { float t, h, ratio, em1; };
+static ExpStep exp_step(float a, float b) {
+    const float t = -logf(a), tn = -logf(b);
+    const float h = tn - t;
+    return ExpStep{t, h, expf(-tn) / expf(-t), expm1f(-h)};
+}
+
+// linear_multistep_coeff (gc_sampling.py:416-429): the integral over [t_i, t_{i+1}] of the Lagrange basis polynomial of node
+// t_{i-j} on t_i ... t_{i-order+1}.  The reference integrates it with scipy's quad, exact for a polynomial of degree <= 3 up to
+// rounding; so does the three-point Gauss-Legendre rule (exact to degree 5), in double.  The denominators are fp32 differences
+// of the fp32 schedule, as the reference's numpy scalars.
+static double lms_coeff(int order, const float* t, int i, int j) {
+    auto basis = [&](double tau) {
+        double prod = 1.0;
+        for (int k = 0; k < order; ++k)
+            if (k != j) prod *= (tau - (double)t[i - k]) / (double)(t[i - j] - t[i - k]);
+        return prod;
+    };
+    const double a = t[i], b = t[i + 1], mid = 0.5 * (a + b), half = 0.5 * (b - a);
+    const double xg = sqrt(0.6);
+    return half * ((5.0 / 9.0) * basis(mid - half * xg) + (8.0 / 9.0) * basis(mid) + (5.0 / 9.0) * basis(mid + half * xg));
+}
+
+// beso_sample: DDIM (gc_sampling.py:921-923), Euler (:205-210) and Heun (:296-310, plain Euler on the last step :301-303)
+static Plan plan_sample(int sampler, const float* sigmas, int n_sigmas) {
+    Plan p;
+    for (int i = 0; i + 1 < n_sigmas; ++i) {
+        const float si = sigmas[i], sn = sigmas[i + 1];
+        p.first.push_back((int)p.ev.size());
+        if (sampler == BESO_SAMPLER_DDIM) {
+            const ExpStep e = exp_step(si, sn);
+            p.add(i, si, e.ratio, e.em1, BESO_STEP_DDIM);
+        } else if (sampler == BESO_SAMPLER_EULER || sn == 0.f) {
+            // gamma = 0: sigma_hat = sigma_i; d = (x - den)/sigma_hat; x += d*(sigma_next - sigma_hat)
+            p.add(i, si, si, sn - si, BESO_STEP_EULER);
+        } else {
+            // Heun: predictor, second evaluation at sigma_{i+1}, trapezoid corrector
+            p.add(i, si, si, sn - si, BESO_STEP_HEUN_PREDICT);
+            p.add(i, sn, sn, sn - si, BESO_STEP_HEUN_CORRECT);
+        }
+    }
+    p.first.push_back((int)p.ev.size());
+    return p;
+}
+
+// beso_sample_ancestral: an Euler step to sigma_down, then the step's noise times sigma_up while sigma_down > 0 (:240-247)
+static Plan plan_ancestral(const float* sigmas, int n_sigmas, float eta) {
+    Plan p;
+    for (int i = 0; i + 1 < n_sigmas; ++i) {
+        const float sf = sigmas[i];
+        float down, up;
+        ancestral_step(sf, sigmas[i + 1], eta, down, up);
+        p.first.push_back((int)p.ev.size());
+        p.add(i, sf, sf, down - sf, BESO_STEP_EULER | (down > 0.f ? kStepAddNoise : 0), up);
+    }
+    p.first.push_back((int)p.ev.size());
+    return p;
+}
+
+// beso_sample_solver's six loops (include/beso_hip.h lists their reference lines)
+static Plan plan_solver(int solver, const float* sigmas, int n_sigmas, float eta, float s_noise, int order) {
+    Plan p;
+    for (int i = 0; i + 1 < n_sigmas; ++i) {
+        const float si = sigmas[i], sn = sigmas[i + 1];
+        p.first.push_back((int)p.ev.size());
+        if (solver == BESO_SOLVER_DPM_2 || solver == BESO_SOLVER_DPM_2_ANCESTRAL) {
+            float to = sn, up = 0.f;
+            if (solver == BESO_SOLVER_DPM_2_ANCESTRAL) ancestral_step(si, sn, eta, to, up);
+            if (to == 0.f) {
+                p.add(i, si, si, to - si, BESO_STEP_EULER);
+            } else {
+                const float mid = log_midpoint(si, to);
+                p.add(i, si, si, mid - si, kStepDpm2Predict);
+                p.add(i, mid, mid, to - si, kStepDpm2Correct | (solver == BESO_SOLVER_DPM_2_ANCESTRAL ? kStepAddNoise : 0), up);
+            }
+        } else if (solver == BESO_SOLVER_DPMPP_2S || solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL) {
+            float to = sn, up = 0.f;
+            const bool anc = solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL;
+            if (anc) ancestral_step(si, sn, eta, to, up);
+            const int nz = anc ? kStepScaledNoise : 0;       // every step of the ancestral form draws, the last one included
+            if (to == 0.f) {
+                p.add(i, si, si, to - si, BESO_STEP_EULER | nz, up, s_noise);
+            } else {
+                // _dpmpp_2s_update: r = 1/2, s = t + r h, stage 1 to sigma = exp(-s), stage 2 from x to sigma_to
+                const ExpStep e = exp_step(si, to);
+                const float rh = e.h * 0.5f;
+                const float smid = expf(-(e.t + rh));
+                p.add(i, si, smid / expf(-e.t), expm1f(-rh), kStepExpPredict);
+                p.add(i, smid, e.ratio, e.em1, kStepExpCorrect | nz, up, s_noise);
+            }
+        } else if (solver == BESO_SOLVER_DPMPP_2M) {
+            const ExpStep e = exp_step(si, sn);
+            if (i == 0 || sn == 0.f) {
+                p.add(i, si, e.ratio, e.em1, i == 0 ? kStepDpm2mFirst : BESO_STEP_DDIM);
+            } else {
+                const float tp = -logf(sigmas[i - 1]);
+                const float r = (e.t - tp) / e.h;
+                const float c3 = 1.0f / (2.0f * r);
+                p.add(i, si, e.ratio, e.em1, kStepDpm2m, 1.0f + c3, c3);
+            }
+        } else {
+            const int cur = i + 1 < order ? i + 1 : order;
+            float c[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < cur; ++j) c[j] = (float)lms_coeff(cur, sigmas, i, j);
+            p.add(i, si, c[0], c[1], lms_mode(cur - 1, order - 1), c[2], c[3]);
+        }
+    }
+    p.first.push_back((int)p.ev.size());
+    return p;
+}
+
+// The arguments the three sampler entry points share; sample_prologue fills the rest
+struct SampleCall {
+    const beso_config* cfg; const void* packed; int precision; const float* state; const float* goal; float* x;
+    int batch, t; const float* sigmas; int n_sigmas; float cond_lambda; int flags;
+    const float* noise; float* history;           // (beso_sample_ancestral / beso_sample_solver)
+    void* workspace; size_t workspace_bytes; hipStream_t s;
+    Layout lay; Workspace ws; FwdArgs a;          // the forward of the loop at x
+};
+
+// The checks every sampler entry point makes, in one order: config -> arguments and flags (`args_ok`: the entry point's own
+// checks) -> batch / t -> layout -> workspace shape and bytes -> interior sigmas -> packed / state / goal.
+static int sample_prologue(SampleCall& c, bool args_ok) {
+    int st = validate_config(c.cfg);
+    if (st != BESO_OK) return st;
+    if (!args_ok || (c.flags & ~(BESO_SAMPLE_STEPWISE | BESO_PLAN_MASK)) || !c.sigmas || c.n_sigmas < 2 || !c.x || !c.workspace)
+        return BESO_ERR_BAD_ARG;
+    if (c.batch < 1 || c.t < 1 || c.t > c.cfg->obs_seq_len) return BESO_ERR_BAD_SHAPE;
+    if (!make_layout(c.cfg, c.precision, &c.lay)) return BESO_ERR_BAD_ARG;
+    const int two = (c.cond_lambda != 0.f && c.cond_lambda != 1.f) ? 1 : 0;
+    if (!make_workspace(c.cfg, c.lay, c.batch, c.t, c.precision, two, &c.ws)) return BESO_ERR_BAD_SHAPE;
+    if (c.workspace_bytes < c.ws.total) return BESO_ERR_WORKSPACE;
+    for (int i = 0; i + 1 < c.n_sigmas; ++i) if (!(c.sigmas[i] > 0.f)) return BESO_ERR_BAD_ARG;
+    if (!c.packed || !c.state || (c.cfg->goal_seq_len > 0 && !c.goal)) return BESO_ERR_BAD_ARG;
+    FwdArgs& a = c.a;
+    a.state = c.state; a.action = c.x; a.goal = c.goal; a.sigma = (float*)((char*)c.workspace + c.ws.sig); a.out = c.x;
+    a.batch = c.batch; a.vbatch = two ? 2 * c.batch : c.batch; a.t = c.t; a.T = 1 + c.lay.G + 2 * c.t;
+    a.precondition = 1;
+    a.uncond_from = two ? c.batch : (c.cond_lambda == 0.f ? 0 : a.vbatch);
+    a.cond_lambda = c.cond_lambda; a.sigma_data = c.cfg->sigma_data;
+    a.plan = c.flags & BESO_PLAN_MASK;
+    if (c.precision == BESO_PREC_FP16) a.plan &= ~(BESO_PLAN_PER_OP | BESO_PLAN_BLOCKS);      // (fp16 has no per-op / block form)
+    return BESO_OK;
+}
+
+// Runs a plan.  Where the shape has the one-launch kernel: ONE launch for the whole loop (K8 fused into K7: the workgroup that
+// owns a sample from the embedding to the head also applies the update and feeds itself the next input), cut at step
+// boundaries past kMaxLoopEvals evaluations -- x travels through `x`, two-evaluation steps park x there between their
+// evaluations, Heun's slope lives in the workspace's d1 and the multistep state in `history`, the noise is indexed by step.
+// (Few samples: every evaluation runs on the chip-wide small-batch path, step by step -- one workgroup carrying a sample group
+// through the whole loop would stream all the weights alone, evaluation after evaluation.)
+static int run_plan(const SampleCall& c, const Plan& p) {
+    char* wsp = (char*)c.workspace;
+    float* den = (float*)(wsp + c.ws.den);
+    float* x2 = (float*)(wsp + c.ws.x2);
+    float* d1 = (float*)(wsp + c.ws.d1);
+    float* sig = (float*)(wsp + c.ws.sig);
+    const size_t n = (size_t)c.batch * c.t * c.lay.act;
+    const bool f16 = c.precision == BESO_PREC_FP16;
+    if (!(c.flags & BESO_SAMPLE_STEPWISE) && !small_wanted(c.lay, c.a, c.precision) &&
+        (f16 ? fused_can_loop_f16(c.lay, c.a, BESO_PREC_BF16) : fused_can_loop(c.lay, c.a, c.precision))) {
+        FwdArgs a = c.a;
+        a.aux = c.history ? c.history : d1;
+        const size_t n_steps = p.first.size() - 1;
+        for (size_t i0 = 0, i1; i0 < n_steps; i0 = i1) {
+            i1 = i0 + 1;
+            while (i1 < n_steps && p.first[i1 + 1] - p.first[i0] <= kMaxLoopEvals) ++i1;
+            SampleSteps S{};
+            SampleExtra X3{};
+            S.n = p.first[i1] - p.first[i0];
+            for (int k = 0; k < S.n; ++k) {
+                const PlanEval& e = p.ev[p.first[i0] + k];
+                S.rec[k] = e.rec;
+                S.rec[k].mode |= (e.step - (int)i0) << kStepShift;
+                X3.c3[k] = e.c3;
+            }
+            a.noise = c.noise ? c.noise + i0 * n : nullptr;
+            profile_begin(BESO_SITE_FUSED_LAYER, c.s);
+            const int st = f16 ? fused_layers_f16(c.lay, (const char*)c.packed, a, (float*)(wsp + c.ws.x), nullptr, BESO_PREC_BF16, c.s, &S, &X3)
+                               : fused_layers(c.lay, (const char*)c.packed, a, (float*)(wsp + c.ws.x), nullptr, c.precision, c.s, &S, &X3);
+            profile_end(BESO_SITE_FUSED_LAYER, c.s);
+            if (st != BESO_OK) return st;
+        }
+        return BESO_OK;
+    }
+    // step by step: per evaluation the forward (at x, or at x2 for the second stage of a step) and one update launch, which
+    // also writes the sigma vector of the next evaluation (the first one is a fill); x2 / den / d1 are the workspace's, x
+    // stays parked in place
+    uint32_t bits; memcpy(&bits, &p.ev[0].rec.sigma, 4);
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)sig, (int)bits, (size_t)c.batch, c.s));
+    for (size_t k = 0; k < p.ev.size(); ++k) {
+        const PlanEval& e = p.ev[k];
+        const int mode = e.rec.mode & 0xff;
+        const int st = forward(c.cfg, c.packed, c.precision, c.state, step_unparks(mode) ? x2 : c.x, c.goal, sig, den, c.batch, c.t,
+                               c.flags & BESO_PLAN_MASK, c.cond_lambda, 1, c.workspace, c.workspace_bytes, c.s);
+        if (st != BESO_OK) return st;
+        SolverStepArgs sv;
+        sv.c2 = e.rec.c2; sv.c3 = e.c3; sv.sigma = e.rec.sigma;
+        sv.noise = c.noise ? c.noise + (size_t)e.step * n : nullptr;
+        sv.hist = c.history;
+        const bool more = k + 1 < p.ev.size();
+        HIP_TRY(launch_sampler_step(e.rec.mode, step_parks(mode) ? x2 : c.x, d1, c.x, x2, den, e.rec.c0, e.rec.c1, n, c.s,
+                                    more ? sig : nullptr, more ? p.ev[k + 1].rec.sigma : 0.f, c.batch, sv));
+    }
+    return BESO_OK;
+}
+
 }  // namespace beso
 
 using namespace beso;
@@ -436,379 +676,34 @@ int beso_sampler_step(int mode, float* out, float* aux, const float* x, const fl
 int beso_sample(const beso_config* cfg, const void* packed, int precision, int sampler, const float* state,
                 const float* goal, float* x, int batch, int t, const float* sigmas, int n_sigmas,
                 float cond_lambda, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-    int st = validate_config(cfg);
-    if (st != BESO_OK) return st;
-    if (sampler < BESO_SAMPLER_DDIM || sampler > BESO_SAMPLER_HEUN || (flags & ~(BESO_SAMPLE_STEPWISE | BESO_PLAN_MASK)))
-        return BESO_ERR_BAD_ARG;
-    const int plan = flags & BESO_PLAN_MASK;
-    if (!sigmas || n_sigmas < 2 || !x || !workspace) return BESO_ERR_BAD_ARG;
-    if (batch < 1 || t < 1 || t > cfg->obs_seq_len) return BESO_ERR_BAD_SHAPE;
-    Layout lay;
-    Workspace ws;
-    if (!make_layout(cfg, precision, &lay)) return BESO_ERR_BAD_ARG;
-    const int two = (cond_lambda != 0.f && cond_lambda != 1.f) ? 1 : 0;
-    if (!make_workspace(cfg, lay, batch, t, precision, two, &ws)) return BESO_ERR_BAD_SHAPE;
-    if (workspace_bytes < ws.total) return BESO_ERR_WORKSPACE;
-    for (int i = 0; i + 1 < n_sigmas; ++i) if (!(sigmas[i] > 0.f)) return BESO_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    char* wsp = (char*)workspace;
-    float* den = (float*)(wsp + ws.den);
-    float* x2 = (float*)(wsp + ws.x2);
-    float* d1 = (float*)(wsp + ws.d1);
-    float* sig = (float*)(wsp + ws.sig);
-    const size_t n = (size_t)batch * t * lay.act;
-    // The evaluations of the loop and the update behind each (coefficients in fp32 on the host, as the reference's 0-d
-    // tensors: gc_sampling.py:921-923 DDIM, :205-210 Euler, :296-310 Heun with plain Euler on the last step :301-303).
-    std::vector<StepRec> recs;
-    std::vector<int> step_first;                  // index of the first evaluation of every sampler step
-    for (int i = 0; i + 1 < n_sigmas; ++i) {
-        const float si = sigmas[i], sn = sigmas[i + 1];
-        step_first.push_back((int)recs.size());
-        if (sampler == BESO_SAMPLER_DDIM) {
-            // t = -log(sigma); h = t_next - t; x = (sigma_fn(t_next)/sigma_fn(t))*x - expm1(-h)*den
-            const float tt = -logf(si), tn = -logf(sn);      // sn == 0 -> tn = +inf -> x = den exactly
-            const float h = tn - tt;
-            recs.push_back(StepRec{si, expf(-tn) / expf(-tt), expm1f(-h), BESO_STEP_DDIM, 0.f});
-        } else if (sampler == BESO_SAMPLER_EULER || sn == 0.f) {
-            // gamma = 0: sigma_hat = sigma_i; d = (x - den)/sigma_hat; x += d*(sigma_next - sigma_hat)
-            recs.push_back(StepRec{si, si, sn - si, BESO_STEP_EULER, 0.f});
-        } else {
-            // Heun: predictor, second evaluation at sigma_{i+1}, trapezoid corrector
-            recs.push_back(StepRec{si, si, sn - si, BESO_STEP_HEUN_PREDICT, 0.f});
-            recs.push_back(StepRec{sn, sn, sn - si, BESO_STEP_HEUN_CORRECT, 0.f});
-        }
-    }
-    step_first.push_back((int)recs.size());
-    {
-        // ONE launch for the whole loop where the shape has the one-launch kernel (K8 fused into K7: the workgroup that owns a
-        // sample from the embedding to the head also applies the update and feeds itself the next input); loops of more than
-        // kMaxLoopEvals evaluations are cut at step boundaries (x travels through `x`, the Heun state lives inside a step)
-        FwdArgs a;
-        a.state = state; a.action = x; a.goal = goal; a.sigma = sig; a.out = x; a.aux = d1;
-        a.batch = batch; a.vbatch = two ? 2 * batch : batch; a.t = t; a.T = 1 + lay.G + 2 * t;
-        a.precondition = 1;
-        a.uncond_from = two ? batch : (cond_lambda == 0.f ? 0 : a.vbatch);
-        a.cond_lambda = cond_lambda; a.sigma_data = cfg->sigma_data;
-        a.plan = precision == BESO_PREC_FP16 ? (plan & ~(BESO_PLAN_PER_OP | BESO_PLAN_BLOCKS)) : plan;      // (fp16 has no per-op / block form)
-        if (!packed || !state || (cfg->goal_seq_len > 0 && !goal)) return BESO_ERR_BAD_ARG;
-        const bool f16 = precision == BESO_PREC_FP16;
-        // (few samples: every evaluation runs on the chip-wide small-batch path, step by step -- one workgroup carrying a sample
-        //  group through the whole loop would stream all the weights alone, evaluation after evaluation)
-        if (!(flags & BESO_SAMPLE_STEPWISE) && !small_wanted(lay, a, precision) &&
-            (f16 ? fused_can_loop_f16(lay, a, BESO_PREC_BF16) : fused_can_loop(lay, a, precision))) {
-            size_t i0 = 0;
-            const size_t n_steps = step_first.size() - 1;
-            while (i0 < n_steps) {
-                size_t i1 = i0 + 1;
-                while (i1 < n_steps && step_first[i1 + 1] - step_first[i0] <= kMaxLoopEvals) ++i1;
-                SampleSteps S{};
-                S.n = step_first[i1] - step_first[i0];
-                for (int k = 0; k < S.n; ++k) S.rec[k] = recs[step_first[i0] + k];
-                profile_begin(BESO_SITE_FUSED_LAYER, s);
-                st = f16 ? fused_layers_f16(lay, (const char*)packed, a, (float*)(wsp + ws.x), nullptr, BESO_PREC_BF16, s, &S)
-                         : fused_layers(lay, (const char*)packed, a, (float*)(wsp + ws.x), nullptr, precision, s, &S);
-                profile_end(BESO_SITE_FUSED_LAYER, s);
-                if (st != BESO_OK) return st;
-                i0 = i1;
-            }
-            return BESO_OK;
-        }
-    }
-    auto fill_sigma = [&](float v) -> hipError_t {
-        uint32_t bits; memcpy(&bits, &v, 4);
-        return hipMemsetD32Async((hipDeviceptr_t)sig, (int)bits, (size_t)batch, s);
-    };
-    // the sigma vector of an evaluation is written by the update launch in front of it (the first one by a fill): two
-    // dependent launches per evaluation, not three
-    HIP_TRY(fill_sigma(sigmas[0]));
-    for (int i = 0; i + 1 < n_sigmas; ++i) {
-        const float si = sigmas[i], sn = sigmas[i + 1];
-        st = beso_denoise_fwd(cfg, packed, precision, state, x, goal, sig, den, batch, t, plan, cond_lambda, workspace,
-                              workspace_bytes, stream);
-        if (st != BESO_OK) return st;
-        if (sampler == BESO_SAMPLER_DDIM) {
-            // t = -log(sigma); h = t_next - t; x = (sigma_fn(t_next)/sigma_fn(t))*x - expm1(-h)*den  (gc_sampling.py:921-923)
-            const float tt = -logf(si), tn = -logf(sn);      // sn == 0 -> tn = +inf -> x = den exactly
-            const float h = tn - tt;
-            const float c0 = expf(-tn) / expf(-tt), c1 = expm1f(-h);
-            HIP_TRY(launch_sampler_step(BESO_STEP_DDIM, x, nullptr, x, nullptr, den, c0, c1, n, s, sig, sn, batch));
-        } else if (sampler == BESO_SAMPLER_EULER || sn == 0.f) {
-            // gamma = 0: sigma_hat = sigma_i; d = (x - den)/sigma_hat; x += d*(sigma_next - sigma_hat)  (:205-210, :301-303)
-            HIP_TRY(launch_sampler_step(BESO_STEP_EULER, x, nullptr, x, nullptr, den, si, sn - si, n, s, sig, sn, batch));
-        } else {
-            // Heun: predictor, second evaluation at sigma_{i+1}, trapezoid corrector (:304-310)
-            HIP_TRY(launch_sampler_step(BESO_STEP_HEUN_PREDICT, x2, d1, x, nullptr, den, si, sn - si, n, s, sig, sn, batch));
-            st = beso_denoise_fwd(cfg, packed, precision, state, x2, goal, sig, den, batch, t, plan, cond_lambda,
-                                  workspace, workspace_bytes, stream);
-            if (st != BESO_OK) return st;
-            HIP_TRY(launch_sampler_step(BESO_STEP_HEUN_CORRECT, x, d1, x, x2, den, sn, sn - si, n, s));     // (sig already holds sigma_{i+1})
-        }
-    }
-    return BESO_OK;
+    SampleCall c{cfg, packed, precision, state, goal, x, batch, t, sigmas, n_sigmas, cond_lambda, flags, nullptr, nullptr,
+                 workspace, workspace_bytes, (hipStream_t)stream};
+    const int st = sample_prologue(c, sampler >= BESO_SAMPLER_DDIM && sampler <= BESO_SAMPLER_HEUN);
+    return st != BESO_OK ? st : run_plan(c, plan_sample(sampler, sigmas, n_sigmas));
 }
 
 int beso_sample_ancestral(const beso_config* cfg, const void* packed, int precision, const float* state, const float* goal,
                           float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda, float eta,
                           const float* noise, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-    int st = validate_config(cfg);
-    if (st != BESO_OK) return st;
-    if (!sigmas || n_sigmas < 2 || !x || !workspace || !noise || !(eta >= 0.f) || (flags & ~(BESO_PLAN_MASK | BESO_SAMPLE_STEPWISE)))
-        return BESO_ERR_BAD_ARG;
-    const int plan = flags & BESO_PLAN_MASK;
-    if (batch < 1 || t < 1 || t > cfg->obs_seq_len) return BESO_ERR_BAD_SHAPE;
-    Layout lay;
-    Workspace ws;
-    if (!make_layout(cfg, precision, &lay)) return BESO_ERR_BAD_ARG;
-    const int two = (cond_lambda != 0.f && cond_lambda != 1.f) ? 1 : 0;
-    if (!make_workspace(cfg, lay, batch, t, precision, two, &ws)) return BESO_ERR_BAD_SHAPE;
-    if (workspace_bytes < ws.total) return BESO_ERR_WORKSPACE;
-    for (int i = 0; i + 1 < n_sigmas; ++i) if (!(sigmas[i] > 0.f)) return BESO_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    char* wsp = (char*)workspace;
-    float* den = (float*)(wsp + ws.den);
-    float* sig = (float*)(wsp + ws.sig);
-    const size_t n = (size_t)batch * t * lay.act;
-    // get_ancestral_step (:107-114) in fp32
-    auto ancestral = [&](float sf, float sn, float& down, float& up) {
-        down = sn; up = 0.f;
-        if (eta != 0.f) {
-            up = eta * sqrtf(sn * sn * (sf * sf - sn * sn) / (sf * sf));
-            if (sn < up) up = sn;
-            down = sqrtf(sn * sn - up * up);
-        }
-    };
-    {
-        // ONE launch for the whole loop (as beso_sample): every step is an Euler update to sigma_down followed by the caller's
-        // noise of that step times sigma_up, both applied in the kernel's head by the workgroup that owns the sample
-        FwdArgs a;
-        a.state = state; a.action = x; a.goal = goal; a.sigma = sig; a.out = x; a.aux = nullptr;
-        a.batch = batch; a.vbatch = two ? 2 * batch : batch; a.t = t; a.T = 1 + lay.G + 2 * t;
-        a.precondition = 1;
-        a.uncond_from = two ? batch : (cond_lambda == 0.f ? 0 : a.vbatch);
-        a.cond_lambda = cond_lambda; a.sigma_data = cfg->sigma_data;
-        a.plan = precision == BESO_PREC_FP16 ? (plan & ~(BESO_PLAN_PER_OP | BESO_PLAN_BLOCKS)) : plan;
-        if (!packed || !state || (cfg->goal_seq_len > 0 && !goal)) return BESO_ERR_BAD_ARG;
-        const bool f16 = precision == BESO_PREC_FP16;
-        // (few samples: every evaluation runs on the chip-wide small-batch path, step by step -- one workgroup carrying a sample
-        //  group through the whole loop would stream all the weights alone, evaluation after evaluation)
-        if (!(flags & BESO_SAMPLE_STEPWISE) && !small_wanted(lay, a, precision) &&
-            (f16 ? fused_can_loop_f16(lay, a, BESO_PREC_BF16) : fused_can_loop(lay, a, precision))) {
-            const int n_steps = n_sigmas - 1;
-            for (int i0 = 0; i0 < n_steps; i0 += kMaxLoopEvals) {
-                SampleSteps S{};
-                S.n = n_steps - i0 < kMaxLoopEvals ? n_steps - i0 : kMaxLoopEvals;
-                for (int k = 0; k < S.n; ++k) {
-                    const float sf = sigmas[i0 + k], sn = sigmas[i0 + k + 1];
-                    float down, up;
-                    ancestral(sf, sn, down, up);
-                    S.rec[k] = StepRec{sf, sf, down - sf, BESO_STEP_EULER | (down > 0.f ? kStepAddNoise : 0) | (k << kStepShift), up};      // :240-247
-                }
-                a.noise = noise + (size_t)i0 * n;
-                profile_begin(BESO_SITE_FUSED_LAYER, s);
-                st = f16 ? fused_layers_f16(lay, (const char*)packed, a, (float*)(wsp + ws.x), nullptr, BESO_PREC_BF16, s, &S)
-                         : fused_layers(lay, (const char*)packed, a, (float*)(wsp + ws.x), nullptr, precision, s, &S);
-                profile_end(BESO_SITE_FUSED_LAYER, s);
-                if (st != BESO_OK) return st;
-            }
-            return BESO_OK;
-        }
-    }
-    for (int i = 0; i + 1 < n_sigmas; ++i) {
-        const float sf = sigmas[i], sn = sigmas[i + 1];
-        float down, up;
-        ancestral(sf, sn, down, up);
-        if (i == 0) {        // (the sigma vector of every later step is written by the previous step's update launch)
-            uint32_t bits; memcpy(&bits, &sf, 4);
-            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)sig, (int)bits, (size_t)batch, s));
-        }
-        st = beso_denoise_fwd(cfg, packed, precision, state, x, goal, sig, den, batch, t, plan, cond_lambda, workspace,
-                              workspace_bytes, stream);
-        if (st != BESO_OK) return st;
-        HIP_TRY(launch_sampler_step(BESO_STEP_EULER, x, nullptr, x, nullptr, den, sf, down - sf, n, s, sig, sn, batch));     // :240-245
-        if (down > 0.f) HIP_TRY(launch_sampler_step(BESO_STEP_ADD_NOISE, x, nullptr, x, noise + (size_t)i * n, x, up, 0.f, n, s));
-    }
-    return BESO_OK;
-}
-
-// linear_multistep_coeff (gc_sampling.py:416-429): the integral over [t_i, t_{i+1}] of the Lagrange basis polynomial of node
-// t_{i-j} on t_i ... t_{i-order+1}.  The reference integrates it with scipy's quad, exact for a polynomial of degree <= 3 up to
-// rounding; so does the three-point Gauss-Legendre rule (exact to degree 5), in double.  The denominators are fp32 differences
-// of the fp32 schedule, as the reference's numpy scalars.
-static double lms_coeff(int order, const float* t, int i, int j) {
-    auto basis = [&](double tau) {
-        double prod = 1.0;
-        for (int k = 0; k < order; ++k)
-            if (k != j) prod *= (tau - (double)t[i - k]) / (double)(t[i - j] - t[i - k]);
-        return prod;
-    };
-    const double a = t[i], b = t[i + 1], mid = 0.5 * (a + b), half = 0.5 * (b - a);
-    const double xg = sqrt(0.6);
-    return half * ((5.0 / 9.0) * basis(mid - half * xg) + (8.0 / 9.0) * basis(mid) + (5.0 / 9.0) * basis(mid + half * xg));
+    SampleCall c{cfg, packed, precision, state, goal, x, batch, t, sigmas, n_sigmas, cond_lambda, flags, noise, nullptr,
+                 workspace, workspace_bytes, (hipStream_t)stream};
+    const int st = sample_prologue(c, noise && eta >= 0.f);
+    return st != BESO_OK ? st : run_plan(c, plan_ancestral(sigmas, n_sigmas, eta));
 }
 
 int beso_sample_solver(const beso_config* cfg, const void* packed, int precision, int solver, const float* state,
                        const float* goal, float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda,
                        float eta, float s_noise, int order, const float* noise, float* history, int flags,
                        void* workspace, size_t workspace_bytes, void* stream) {
-    int st = validate_config(cfg);
-    if (st != BESO_OK) return st;
-    if (solver < BESO_SOLVER_DPM_2 || solver > BESO_SOLVER_LMS || (flags & ~(BESO_SAMPLE_STEPWISE | BESO_PLAN_MASK)))
-        return BESO_ERR_BAD_ARG;
     const bool ancestral = solver == BESO_SOLVER_DPM_2_ANCESTRAL || solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL;
-    if (solver == BESO_SOLVER_LMS && (order < 1 || order > 4)) return BESO_ERR_BAD_ARG;
+    const bool lms_ok = solver != BESO_SOLVER_LMS || (order >= 1 && order <= 4);
     const int n_hist = solver == BESO_SOLVER_DPMPP_2M ? 1 : solver == BESO_SOLVER_LMS ? order - 1 : 0;
-    if ((ancestral && !noise) || (n_hist > 0 && !history) || !(eta >= 0.f)) return BESO_ERR_BAD_ARG;
-    const int plan = flags & BESO_PLAN_MASK;
-    if (!sigmas || n_sigmas < 2 || !x || !workspace) return BESO_ERR_BAD_ARG;
-    if (batch < 1 || t < 1 || t > cfg->obs_seq_len) return BESO_ERR_BAD_SHAPE;
-    Layout lay;
-    Workspace ws;
-    if (!make_layout(cfg, precision, &lay)) return BESO_ERR_BAD_ARG;
-    const int two = (cond_lambda != 0.f && cond_lambda != 1.f) ? 1 : 0;
-    if (!make_workspace(cfg, lay, batch, t, precision, two, &ws)) return BESO_ERR_BAD_SHAPE;
-    if (workspace_bytes < ws.total) return BESO_ERR_WORKSPACE;
-    for (int i = 0; i + 1 < n_sigmas; ++i) if (!(sigmas[i] > 0.f)) return BESO_ERR_BAD_ARG;
-    if (!packed || !state || (cfg->goal_seq_len > 0 && !goal)) return BESO_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    char* wsp = (char*)workspace;
-    float* den = (float*)(wsp + ws.den);
-    float* x2 = (float*)(wsp + ws.x2);
-    float* sig = (float*)(wsp + ws.sig);
-    const size_t n = (size_t)batch * t * lay.act;
-
-    // The evaluations of the loop: their records (sigma, c0, c1, mode, c2), the fifth number (c3) and the step of each.
-    // Every coefficient is an fp32 scalar computed as the reference computes it (numpy float32 / 0-d tensors).
-    std::vector<StepRec> recs;
-    std::vector<float> c3s;
-    std::vector<int> rec_step, step_first;
-    auto push = [&](int i, float sigma, float c0, float c1, int mode, float c2, float c3) {
-        recs.push_back(StepRec{sigma, c0, c1, mode, c2});
-        c3s.push_back(c3);
-        rec_step.push_back(i);
-    };
-    auto ancestral_step = [&](float sf, float sn, float& down, float& up) {      // get_ancestral_step (:107-114)
-        down = sn; up = 0.f;
-        if (eta != 0.f) {
-            up = eta * sqrtf(sn * sn * (sf * sf - sn * sn) / (sf * sf));
-            if (sn < up) up = sn;
-            down = sqrtf(sn * sn - up * up);
-        }
-    };
-    auto log_midpoint = [](float a, float b) {          // exp(lerp(log a, log b, 0.5))
-        const float la = logf(a), lb = logf(b);
-        const float hm = 0.5f * (lb - la);
-        return expf(la + hm);
-    };
-    for (int i = 0; i + 1 < n_sigmas; ++i) {
-        const float si = sigmas[i], sn = sigmas[i + 1];
-        step_first.push_back((int)recs.size());
-        if (solver == BESO_SOLVER_DPM_2 || solver == BESO_SOLVER_DPM_2_ANCESTRAL) {
-            float to = sn, up = 0.f;
-            if (solver == BESO_SOLVER_DPM_2_ANCESTRAL) ancestral_step(si, sn, to, up);
-            if (to == 0.f) {
-                push(i, si, si, to - si, BESO_STEP_EULER, 0.f, 0.f);
-            } else {
-                const float mid = log_midpoint(si, to);
-                push(i, si, si, mid - si, kStepDpm2Predict, 0.f, 0.f);
-                push(i, mid, mid, to - si, kStepDpm2Correct | (solver == BESO_SOLVER_DPM_2_ANCESTRAL ? kStepAddNoise : 0), up, 0.f);
-            }
-        } else if (solver == BESO_SOLVER_DPMPP_2S || solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL) {
-            float to = sn, up = 0.f;
-            const bool anc = solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL;
-            if (anc) ancestral_step(si, sn, to, up);
-            const int nz = anc ? kStepScaledNoise : 0;       // every step of the ancestral form draws, the last one included
-            if (to == 0.f) {
-                push(i, si, si, to - si, BESO_STEP_EULER | nz, up, s_noise);
-            } else {
-                // _dpmpp_2s_update: r = 1/2, s = t + r h, stage 1 to sigma = exp(-s), stage 2 from x to sigma_to
-                const float tt = -logf(si), tn = -logf(to);
-                const float h = tn - tt;
-                const float rh = h * 0.5f;
-                const float sm = tt + rh;
-                const float smid = expf(-sm);
-                push(i, si, smid / expf(-tt), expm1f(-rh), kStepExpPredict, 0.f, 0.f);
-                push(i, smid, expf(-tn) / expf(-tt), expm1f(-h), kStepExpCorrect | nz, up, s_noise);
-            }
-        } else if (solver == BESO_SOLVER_DPMPP_2M) {
-            const float tt = -logf(si), tn = -logf(sn);        // sn == 0 -> tn = +inf -> x = den exactly
-            const float h = tn - tt;
-            const float ratio = expf(-tn) / expf(-tt), em1 = expm1f(-h);
-            if (i == 0 || sn == 0.f) {
-                push(i, si, ratio, em1, i == 0 ? kStepDpm2mFirst : BESO_STEP_DDIM, 0.f, 0.f);
-            } else {
-                const float tp = -logf(sigmas[i - 1]);
-                const float r = (tt - tp) / h;
-                const float c3 = 1.0f / (2.0f * r);
-                push(i, si, ratio, em1, kStepDpm2m, 1.0f + c3, c3);
-            }
-        } else {
-            const int cur = i + 1 < order ? i + 1 : order;
-            float c[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int j = 0; j < cur; ++j) c[j] = (float)lms_coeff(cur, sigmas, i, j);
-            push(i, si, c[0], c[1], lms_mode(cur - 1, order - 1), c[2], c[3]);
-        }
-    }
-    step_first.push_back((int)recs.size());
-
-    FwdArgs a;
-    a.state = state; a.action = x; a.goal = goal; a.sigma = sig; a.out = x; a.aux = history; a.noise = noise;
-    a.batch = batch; a.vbatch = two ? 2 * batch : batch; a.t = t; a.T = 1 + lay.G + 2 * t;
-    a.precondition = 1;
-    a.uncond_from = two ? batch : (cond_lambda == 0.f ? 0 : a.vbatch);
-    a.cond_lambda = cond_lambda; a.sigma_data = cfg->sigma_data;
-    a.plan = precision == BESO_PREC_FP16 ? (plan & ~(BESO_PLAN_PER_OP | BESO_PLAN_BLOCKS)) : plan;
-    const bool f16 = precision == BESO_PREC_FP16;
-    // ONE launch for the whole loop where beso_sample runs one: two-evaluation steps park x in `x` between their evaluations,
-    // the multistep state lives in `history`, the noise is indexed by step; cut at step boundaries past kMaxLoopEvals
-    if (!(flags & BESO_SAMPLE_STEPWISE) && !small_wanted(lay, a, precision) &&
-        (f16 ? fused_can_loop_f16(lay, a, BESO_PREC_BF16) : fused_can_loop(lay, a, precision))) {
-        const size_t n_steps = step_first.size() - 1;
-        size_t i0 = 0;
-        while (i0 < n_steps) {
-            size_t i1 = i0 + 1;
-            while (i1 < n_steps && step_first[i1 + 1] - step_first[i0] <= kMaxLoopEvals) ++i1;
-            SampleSteps S{};
-            SampleExtra X3{};
-            S.n = step_first[i1] - step_first[i0];
-            for (int k = 0; k < S.n; ++k) {
-                const int r = step_first[i0] + k;
-                S.rec[k] = recs[r];
-                S.rec[k].mode |= (rec_step[r] - (int)i0) << kStepShift;
-                X3.c3[k] = c3s[r];
-            }
-            a.noise = noise ? noise + i0 * n : nullptr;
-            profile_begin(BESO_SITE_FUSED_LAYER, s);
-            st = f16 ? fused_layers_f16(lay, (const char*)packed, a, (float*)(wsp + ws.x), nullptr, BESO_PREC_BF16, s, &S, &X3)
-                     : fused_layers(lay, (const char*)packed, a, (float*)(wsp + ws.x), nullptr, precision, s, &S, &X3);
-            profile_end(BESO_SITE_FUSED_LAYER, s);
-            if (st != BESO_OK) return st;
-            i0 = i1;
-        }
-        return BESO_OK;
-    }
-    // step by step: per evaluation the forward (at x, or at x2 for the second stage of a step) and one update launch, which
-    // also writes the sigma vector of the next evaluation; x2 / den are the workspace's, x stays parked in place
-    {
-        uint32_t bits; memcpy(&bits, &recs[0].sigma, 4);
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)sig, (int)bits, (size_t)batch, s));
-    }
-    for (size_t k = 0; k < recs.size(); ++k) {
-        const StepRec& r = recs[k];
-        const int mode = r.mode & 0xff;
-        const bool second = mode == kStepDpm2Correct || mode == kStepExpCorrect;
-        const bool first = mode == kStepDpm2Predict || mode == kStepExpPredict;
-        st = beso_denoise_fwd(cfg, packed, precision, state, second ? x2 : x, goal, sig, den, batch, t, plan, cond_lambda,
-                              workspace, workspace_bytes, stream);
-        if (st != BESO_OK) return st;
-        SolverStepArgs sv;
-        sv.c2 = r.c2; sv.c3 = c3s[k]; sv.sigma = r.sigma;
-        sv.noise = noise ? noise + (size_t)rec_step[k] * n : nullptr;
-        sv.hist = history;
-        const bool more = k + 1 < recs.size();
-        HIP_TRY(launch_sampler_step(r.mode, first ? x2 : x, nullptr, x, x2, den, r.c0, r.c1, n, s, more ? sig : nullptr,
-                                    more ? recs[k + 1].sigma : 0.f, batch, sv));
-    }
-    return BESO_OK;
+    const bool args_ok = solver >= BESO_SOLVER_DPM_2 && solver <= BESO_SOLVER_LMS && lms_ok && (!ancestral || noise) &&
+                         (n_hist <= 0 || history) && eta >= 0.f;
+    SampleCall c{cfg, packed, precision, state, goal, x, batch, t, sigmas, n_sigmas, cond_lambda, flags, noise, history,
+                 workspace, workspace_bytes, (hipStream_t)stream};
+    const int st = sample_prologue(c, args_ok);
+    return st != BESO_OK ? st : run_plan(c, plan_solver(solver, sigmas, n_sigmas, eta, s_noise, order));
 }
 
 #if BESO_DEV_API

@@ -152,10 +152,10 @@ enum { kStepDpm2Predict = 5, kStepDpm2Correct = 6, kStepExpPredict = 7, kStepExp
 constexpr int kStepAddNoise = 0x100, kStepScaledNoise = 0x200;
 constexpr int kStepShift = 16;
 __host__ __device__ constexpr int lms_mode(int terms, int keep) { return kStepLms | (terms << 12) | (keep << 14); }
-__device__ __forceinline__ bool step_parks(int mode) {
+__host__ __device__ __forceinline__ bool step_parks(int mode) {
     return mode == BESO_STEP_HEUN_PREDICT || mode == kStepDpm2Predict || mode == kStepExpPredict;
 }
-__device__ __forceinline__ bool step_unparks(int mode) {
+__host__ __device__ __forceinline__ bool step_unparks(int mode) {
     return mode == BESO_STEP_HEUN_CORRECT || mode == kStepDpm2Correct || mode == kStepExpCorrect;
 }
 // xv: x (the parked x for the second stage of a step), x2v: the second stage's input, dv: the evaluation's denoised value

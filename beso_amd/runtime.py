@@ -214,109 +214,53 @@ class ScoreNetRuntime:
         return out
 
     def sample(self, packed: PackedWeights, sampler: str, state, x_t, goal, sigmas, cond_lambda: float = 1.0,
-               inplace: bool = False, stepwise: bool = False) -> torch.Tensor:
-        """sample_ddim / sample_euler / sample_heun (s_churn = 0) as ONE enqueue of all steps -- one launch for the whole
-        loop where the shape has the one-launch kernel; ``stepwise`` enqueues evaluation by evaluation instead (same
-        arithmetic, bit-identical results)."""
-        if sampler not in _lib.SAMPLER_IDS:
+               eta: float = 1.0, s_noise: float = 1.0, order: int = 4, noise=None, stepwise: bool = False) -> torch.Tensor:
+        """One of the sampler loops of ``_lib.SAMPLERS`` (ddim / euler / heun with s_churn = 0, euler_ancestral, dpm_2,
+        dpm_2_ancestral, dpmpp_2s, dpmpp_2s_ancestral, dpmpp_2m, lms of order 1 ... 4) as ONE enqueue of all steps -- one
+        launch for the whole loop where the shape has the one-launch kernel; ``stepwise`` enqueues evaluation by evaluation
+        instead (same arithmetic, bit-identical results).  ``eta`` is the ancestral samplers', ``s_noise``
+        dpmpp_2s_ancestral's, ``order`` LMS's.  The ancestral samplers' noise [n_steps, B, t, act] is ``noise``, or drawn
+        here by ``gc_sampling.predraw_noise`` (the draws of the Python loop, in its order).  The multistep state lives in a
+        buffer of this call."""
+        if sampler not in _lib.SAMPLERS:
             raise ValueError("desired sampler type not found!")
-        dev, B, t, state, x, goal, _ = self._prep(state, x_t, goal, None)
-        if not inplace and x.data_ptr() == x_t.data_ptr():
-            x = x.clone()          # the loop updates x in place; keep the caller's x_T intact
-        sig = [float(s) for s in (sigmas.detach().cpu().tolist() if torch.is_tensor(sigmas) else sigmas)]
-        two = cond_lambda not in (0.0, 1.0)
-        ws = self._workspace(B, t, two, dev)
-        arr = (C.c_float * len(sig))(*sig)
-        gp = goal.data_ptr() if goal is not None else None
-        with torch.cuda.device(dev):
-            st = self.lib.beso_sample(C.byref(self.cfg), packed.buf.data_ptr(), packed.precision,
-                                      _lib.SAMPLER_IDS[sampler], state.data_ptr(), gp, x.data_ptr(), B, t, arr,
-                                      len(sig), float(cond_lambda), (_lib.SAMPLE_STEPWISE if stepwise else 0) | forward_hints(),
-                                      ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, f"sample[{sampler}]")
-        return x
-
-    def sample_ancestral(self, packed: PackedWeights, state, x_t, goal, sigmas, cond_lambda: float = 1.0, eta: float = 1.0,
-                         noise=None, stepwise: bool = False) -> torch.Tensor:
-        """sample_euler_ancestral as ONE enqueue of all steps (``beso_sample_ancestral``) -- one LAUNCH for the whole loop
-        where the shape has the one-launch kernel (``stepwise``: evaluation by evaluation, bit-identical).  The per-step noise is drawn
-        here, one ``torch.randn_like`` per step that adds noise and in the order of the steps -- the calls the reference's
-        loop makes, so a seeded generator gives the same draws as the step-by-step loop; ``noise`` [n_steps, B, t, act]
-        injects them instead."""
-        dev, B, t, state, x, goal, _ = self._prep(state, x_t, goal, None)
-        if x.data_ptr() == x_t.data_ptr():
-            x = x.clone()
-        sig = [float(s) for s in (sigmas.detach().cpu().tolist() if torch.is_tensor(sigmas) else sigmas)]
-        n_steps = len(sig) - 1
-        if noise is None:
-            noise = torch.zeros((n_steps,) + tuple(x.shape), dtype=torch.float32, device=dev)
-            for i in range(n_steps):
-                sf, sn = sig[i], sig[i + 1]
-                up = min(sn, eta * (sn ** 2 * (sf ** 2 - sn ** 2) / sf ** 2) ** 0.5) if eta else 0.0
-                if sn ** 2 - up ** 2 > 0:                # sigma_down > 0: the step draws (gc_sampling.py:246-247)
-                    noise[i] = torch.randn_like(x)
-        else:
-            noise = noise.to(device=dev, dtype=torch.float32).contiguous()
-            if noise.shape != (n_steps,) + tuple(x.shape):
-                raise ValueError("noise must be [len(sigmas) - 1, B, t, act]")
-        two = cond_lambda not in (0.0, 1.0)
-        ws = self._workspace(B, t, two, dev)
-        arr = (C.c_float * len(sig))(*sig)
-        gp = goal.data_ptr() if goal is not None else None
-        with torch.cuda.device(dev):
-            st = self.lib.beso_sample_ancestral(C.byref(self.cfg), packed.buf.data_ptr(), packed.precision, state.data_ptr(), gp,
-                                                x.data_ptr(), B, t, arr, len(sig), float(cond_lambda), float(eta),
-                                                noise.data_ptr(), (_lib.SAMPLE_STEPWISE if stepwise else 0) | forward_hints(),
-                                                ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, "sample[euler_ancestral]")
-        return x
-
-    def sample_solver(self, packed: PackedWeights, solver: str, state, x_t, goal, sigmas, cond_lambda: float = 1.0,
-                      eta: float = 1.0, s_noise: float = 1.0, order: int = 4, noise=None, stepwise: bool = False) -> torch.Tensor:
-        """sample_dpm_2 / _dpm_2_ancestral / _dpmpp_2s / _dpmpp_2s_ancestral / _dpmpp_2m / _lms (``_lib.SOLVER_IDS``) as ONE
-        enqueue of all steps (``beso_sample_solver``) -- one launch for the whole loop where the shape has the one-launch kernel
-        (``stepwise``: evaluation by evaluation, bit-identical).  The ancestral solvers' noise is drawn here when ``noise`` is
-        None, one ``torch.randn_like`` per step that draws and in the order of the steps, as ``sample_ancestral``;
-        ``noise`` [n_steps, B, t, act] injects it instead.  The multistep state lives in a buffer of this call."""
-        if solver not in _lib.SOLVER_IDS:
-            raise ValueError("desired sampler type not found!")
-        if solver == "lms" and not 1 <= int(order) <= 4:
+        entry, sid = _lib.SAMPLERS[sampler]
+        if sampler == "lms" and not 1 <= int(order) <= 4:
             raise ValueError("beso_sample_solver runs LMS orders 1 ... 4")
         dev, B, t, state, x, goal, _ = self._prep(state, x_t, goal, None)
         if x.data_ptr() == x_t.data_ptr():
-            x = x.clone()
+            x = x.clone()          # the loop updates x in place; keep the caller's x_T intact
         sig = [float(s) for s in (sigmas.detach().cpu().tolist() if torch.is_tensor(sigmas) else sigmas)]
-        n_steps = len(sig) - 1
-        if solver in ("dpm_2_ancestral", "dpmpp_2s_ancestral"):
-            if noise is None:
-                noise = torch.zeros((n_steps,) + tuple(x.shape), dtype=torch.float32, device=dev)
-                for i in range(n_steps):
-                    sf, sn = sig[i], sig[i + 1]
-                    up = min(sn, eta * (sn ** 2 * (sf ** 2 - sn ** 2) / sf ** 2) ** 0.5) if eta else 0.0
-                    # dpm_2_ancestral draws on steps with sigma_down > 0 (gc_sampling.py:405-411), dpmpp_2s_ancestral on every step
-                    if solver == "dpmpp_2s_ancestral" or sn ** 2 - up ** 2 > 0:
-                        noise[i] = torch.randn_like(x)
-            else:
-                noise = noise.to(device=dev, dtype=torch.float32).contiguous()
-                if noise.shape != (n_steps,) + tuple(x.shape):
-                    raise ValueError("noise must be [len(sigmas) - 1, B, t, act]")
-        else:
+        if not sampler.endswith("_ancestral"):
             noise = None
-        n_hist = {"dpmpp_2m": 1, "lms": int(order) - 1}.get(solver, 0)
+        elif noise is None:
+            # (the draw rule is the sampler module's: imported here, where it is needed, as that module imports this one)
+            from .agents.diffusion_agents.k_diffusion.gc_sampling import predraw_noise
+            noise = predraw_noise(sampler, sig, x, eta)
+        else:
+            noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+            if noise.shape != (len(sig) - 1,) + tuple(x.shape):
+                raise ValueError("noise must be [len(sigmas) - 1, B, t, act]")
+        n_hist = {"dpmpp_2m": 1, "lms": int(order) - 1}.get(sampler, 0)
         hist = torch.empty((n_hist,) + tuple(x.shape), dtype=torch.float32, device=dev) if n_hist else None
-        two = cond_lambda not in (0.0, 1.0)
-        ws = self._workspace(B, t, two, dev)
+        ws = self._workspace(B, t, cond_lambda not in (0.0, 1.0), dev)
         arr = (C.c_float * len(sig))(*sig)
-        gp = goal.data_ptr() if goal is not None else None
+        head = (C.byref(self.cfg), packed.buf.data_ptr(), packed.precision)
+        loop = (state.data_ptr(), goal.data_ptr() if goal is not None else None, x.data_ptr(), B, t, arr, len(sig),
+                float(cond_lambda))
+        nz = noise.data_ptr() if noise is not None else None
+        flags = (_lib.SAMPLE_STEPWISE if stepwise else 0) | forward_hints()
+        tail = (ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+        if entry == "beso_sample":
+            args = head + (sid,) + loop + (flags,) + tail
+        elif entry == "beso_sample_ancestral":
+            args = head + loop + (float(eta), nz, flags) + tail
+        else:
+            args = head + (sid,) + loop + (float(eta), float(s_noise), int(order), nz,
+                                           hist.data_ptr() if hist is not None else None, flags) + tail
         with torch.cuda.device(dev):
-            st = self.lib.beso_sample_solver(C.byref(self.cfg), packed.buf.data_ptr(), packed.precision, _lib.SOLVER_IDS[solver],
-                                             state.data_ptr(), gp, x.data_ptr(), B, t, arr, len(sig), float(cond_lambda),
-                                             float(eta), float(s_noise), int(order),
-                                             noise.data_ptr() if noise is not None else None,
-                                             hist.data_ptr() if hist is not None else None,
-                                             (_lib.SAMPLE_STEPWISE if stepwise else 0) | forward_hints(),
-                                             ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-        _lib.check(st, f"sample[{solver}]")
+            st = getattr(self.lib, entry)(*args)
+        _lib.check(st, f"sample[{sampler}]")
         return x
 
     # ------------------------------------------------------------------ profiling hooks (bench.py)

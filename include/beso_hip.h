@@ -203,7 +203,7 @@ int beso_sample(const beso_config* cfg, const void* packed, int precision, int s
  * step, drawn by the caller (the library has no random number generator); entries of steps with sigma_down = 0 are not
  * read.  Where the shape has the one-launch kernel the WHOLE loop is ONE launch, as in beso_sample: the workgroup that owns
  * a sample applies the Euler update and adds its slice of the step's noise in the kernel's head.  Otherwise, and with
- * BESO_SAMPLE_STEPWISE, one forward launch + one or two update launches per step (bit-identical results).
+ * BESO_SAMPLE_STEPWISE, one forward + one update launch per step (bit-identical results).
  * `flags`: BESO_PLAN_* hints | BESO_SAMPLE_STEPWISE.  Everything else as beso_sample.                                  */
 int beso_sample_ancestral(const beso_config* cfg, const void* packed, int precision, const float* state, const float* goal,
                           float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda, float eta,

@@ -256,14 +256,15 @@ class _IdentityScaler:
 
 
 @pytest.mark.gpu
-def test_fallbacks_keep_the_python_loop(monkeypatch):
+def test_fallbacks_keep_the_python_loop_off_the_runtime_sampler(monkeypatch):
     """s_churn > 0, a scaler, a callback, LMS of order 5 and non-empty extra_args keep today's Python loop: no call reaches
-    beso_sample_solver, the fused kernel runs one plain forward per evaluation, and the result equals the loop bit for bit."""
+    the fused sampler (ScoreNetRuntime.sample), the fused kernel runs one plain forward per evaluation, and the result equals
+    the loop bit for bit."""
     from beso_amd.agents.diffusion_agents.k_diffusion import gc_sampling as ks
     from beso_amd.runtime import ScoreNetRuntime as Runtime
     calls = []
-    real = Runtime.sample_solver
-    monkeypatch.setattr(Runtime, "sample_solver", lambda self, *a, **k: calls.append(a[1]) or real(self, *a, **k))
+    real = Runtime.sample
+    monkeypatch.setattr(Runtime, "sample", lambda self, *a, **k: calls.append(a[1]) or real(self, *a, **k))
     cfg = O.KITCHEN
     m = make_module(cfg, "bf16")
     s_np, g_np, x_np = O.make_inputs(cfg, 64, seed=51)
