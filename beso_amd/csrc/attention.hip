@@ -296,8 +296,8 @@ __global__ __launch_bounds__(256) void attention_mfma_x3_kernel(const float* __r
     const int vb = pair / H, h = pair % H;
     const size_t ldq = (size_t)3 * D;
     const float* base = qkv + (size_t)vb * T * ldq + (size_t)h * hd;
-    // ---- HBM -> LDS: units of 8 head dims of one token, split into the two planes; dims >= hd and tokens >= T are zero.  Four
-    // units (24 loads) in flight per lane: one unit at a time the loop was ten dependent memory round trips per pair -- most of
+    // ---- HBM -> LDS: units of 8 head dims of one token, split into the two planes; dims >= hd and tokens >= T are zero.  Three
+    // units (kU: 18 loads) in flight per lane: one unit at a time the loop was ten dependent memory round trips per pair -- most of
     // the kernel's time (clamped addresses, values selected afterwards: no load under a branch)
     constexpr int kU = 3;
     for (int u0 = threadIdx.x; u0 < Tp * 8; u0 += 256 * kU) {
@@ -500,13 +500,10 @@ hipError_t launch_attention(const void* qkv, void* y, int vbatch, int T, int D, 
         const int Tp = ((T + 15) / 16) * 16;
         const size_t pair_bytes = (size_t)3 * Tp * kAttRow * 4;
         if (hd <= 64 && hd % 8 == 0 && D % 8 == 0 && ld_y % 4 == 0 && T > 16 && T <= 16 * kAttMaxTiles && pair_bytes <= 160 * 1024) {
-            if (hipFuncSetAttribute((const void*)attention_mfma_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024) != hipSuccess) return hipErrorInvalidValue;
-            (void)hipGetLastError();
             const int n_pairs = vbatch * H;
-            hipLaunchKernelGGL(attention_mfma_x3_kernel, dim3(n_pairs), dim3(256), pair_bytes, s, (const float*)qkv, (float*)y, n_pairs,
-                               T, D, H, hd, ld_y, 1.4426950408889634f / sqrtf((float)hd));
-            return hipGetLastError();
+            return launch_lds_attr<attention_mfma_x3_kernel>(160 * 1024, dim3(n_pairs), dim3(256), pair_bytes, s, (const float*)qkv,
+                                                             (float*)y, n_pairs, T, D, H, hd, ld_y,
+                                                             1.4426950408889634f / sqrtf((float)hd));
         }
         return launch_t<float>(qkv, y, vbatch, T, D, H, ld_y, s);
     }
@@ -517,14 +514,10 @@ hipError_t launch_attention(const void* qkv, void* y, int vbatch, int T, int D, 
         int ppw = (int)((size_t)(160 * 1024) / pair_bytes);          // pairs (= waves) per workgroup
         ppw = ppw >= 4 ? 4 : (ppw >= 2 ? 2 : 1);
         const size_t lds = (size_t)ppw * pair_bytes;
-        // (every call: the attribute belongs to the kernel on the CURRENT device, and this is not a hot launch site)
-        if (hipFuncSetAttribute((const void*)attention_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess) return hipErrorInvalidValue;
-        (void)hipGetLastError();
         const int n_pairs = vbatch * H;
-        hipLaunchKernelGGL(attention_mfma_kernel, dim3((n_pairs + ppw - 1) / ppw), dim3(64 * ppw), lds, s, (const uint16_t*)qkv,
-                           (uint16_t*)y, n_pairs, T, D, H, hd, ld_y, 1.4426950408889634f / sqrtf((float)hd));
-        return hipGetLastError();
+        return launch_lds_attr<attention_mfma_kernel>(160 * 1024, dim3((n_pairs + ppw - 1) / ppw), dim3(64 * ppw), lds, s,
+                                                      (const uint16_t*)qkv, (uint16_t*)y, n_pairs, T, D, H, hd, ld_y,
+                                                      1.4426950408889634f / sqrtf((float)hd));
     }
     return launch_t<uint16_t>(qkv, y, vbatch, T, D, H, ld_y, s);
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <atomic>
 #include <type_traits>
 #include "../../include/beso_hip.h"
 #ifndef BESO_DEV_API
@@ -291,6 +292,38 @@ int  validate_config(const beso_config* cfg);
 bool make_layout(const beso_config* cfg, int precision, Layout* out);
 bool make_workspace(const beso_config* cfg, const Layout& lay, int batch, int t, int precision,
                     int cfg_guidance, Workspace* out);
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is a property of the kernel ON A DEVICE: the "already set" flag of a launch site
+// is a bit per device (a process may drive several GPUs), written with a relaxed atomic (launch sites are reached from any
+// thread; setting the attribute twice is harmless).  Setting it is a driver call: once, not per launch.
+struct LdsAttr { std::atomic<unsigned long long> devices{0}; };
+template <typename K>
+hipError_t ensure_lds(K kernel, size_t bytes, LdsAttr* done) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (dev < 64 && (done->devices.load(std::memory_order_relaxed) & bit)) return hipSuccess;
+    e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess && dev < 64) done->devices.fetch_or(bit, std::memory_order_relaxed);
+    return e;
+}
+// One launch of a kernel with dynamic LDS: attribute (once per kernel instance and device) -> clear the last error -> launch ->
+// the launch's error.  attr_bytes: the attribute's size where it differs from the launch's lds_bytes (a fixed ceiling above a
+// size computed per call).
+template <auto Kernel, typename... Args>
+hipError_t launch_lds_attr(size_t attr_bytes, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
+    static LdsAttr attr;
+    const hipError_t e = ensure_lds(Kernel, attr_bytes, &attr);
+    if (e != hipSuccess) return e;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s, args...);
+    return hipGetLastError();
+}
+template <auto Kernel, typename... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
+    return launch_lds_attr<Kernel>(lds_bytes, grid, block, lds_bytes, s, args...);
+}
 
 // ---- kernel launchers (each enqueues on `s`, returns hipError_t) -------------------------------
 struct FwdArgs {

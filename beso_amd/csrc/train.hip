@@ -1825,19 +1825,6 @@ __global__ __launch_bounds__(256) void vjp_input_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// "the dynamic-LDS attribute of this kernel is set" per device (hipFuncSetAttribute is a driver call: once, not per step)
-struct LdsAttrT { std::atomic<unsigned long long> devices{0}; };
-static hipError_t ensure_lds_t(const void* kernel, size_t bytes, LdsAttrT* done) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (dev < 64 && (done->devices.load(std::memory_order_relaxed) & bit)) return hipSuccess;
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess && dev < 64) done->devices.fetch_or(bit, std::memory_order_relaxed);
-    return e;
-}
-
 // compute units of the current device (cached per device; 256 on the MI355X): the row-range heuristics of the grouped
 // weight-gradient launches fill THIS part's workgroup slots
 static int device_cus() {
@@ -2261,12 +2248,11 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
     auto gs_grid = [&](size_t n4) { const size_t g = (n4 + 255) / 256; return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g)); };
     const size_t lds_f = attn_lds_bytes(T, hd, false), lds_b = attn_lds_bytes(T, hd, true);
     const bool attn_small = T <= kTP && hd <= 64 && hd % 4 == 0;
-    if (lds_f > 64 * 1024) {
-        TRY(hipFuncSetAttribute((const void*)attn_fwd_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-    }
-    if (lds_b > 64 * 1024) {
-        TRY(hipFuncSetAttribute((const void*)attn_bwd_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-    }
+    // (once per device, at the ceiling train_validate admits: lds_f / lds_b change with the window, the attribute need not)
+    constexpr size_t kAttnLdsAttr = 150 * 1024;
+    static LdsAttr attr_f, attr_b;
+    if (lds_f > 64 * 1024) TRY(ensure_lds(attn_fwd_kernel<E>, kAttnLdsAttr, &attr_f));
+    if (lds_b > 64 * 1024) TRY(ensure_lds(attn_bwd_kernel<E>, kAttnLdsAttr, &attr_b));
     if (fork) TRY(hipStreamWaitEvent(s, ev_join, 0));             // the forward's weight image is in place
     if (fork && !use_whole) TRY(hipStreamWaitEvent(s, ev_copies, 0));      // (per-op / tile forward: the plain copies too)
     if (use_whole) {
@@ -2466,15 +2452,15 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
         arrange_group();
         if (panel_w) {
             const int psp = (w.w_splits_panel > 1 && g_floats <= w.wslab_floats) ? w.w_splits_panel : 1;
-            static LdsAttrT attr2, attr3;
+            static LdsAttr attr2, attr3;
             hipError_t e = hipSuccess;
             if (panel_w == 2) {
-                e = ensure_lds_t((const void*)wgrad_panel_group_kernel<2>, wgrad_panel_lds(2), &attr2);
+                e = ensure_lds(wgrad_panel_group_kernel<2>, wgrad_panel_lds(2), &attr2);
                 if (e == hipSuccess)
                     hipLaunchKernelGGL(wgrad_panel_group_kernel<2>, dim3(g_tiles * psp), dim3(kGT), wgrad_panel_lds(2), s, gt, g_tiles, psp,
                                        F(w.wslab), w.wslab_floats);
             } else {
-                e = ensure_lds_t((const void*)wgrad_panel_group_kernel<3>, wgrad_panel_lds(3), &attr3);
+                e = ensure_lds(wgrad_panel_group_kernel<3>, wgrad_panel_lds(3), &attr3);
                 if (e == hipSuccess)
                     hipLaunchKernelGGL(wgrad_panel_group_kernel<3>, dim3(g_tiles * psp), dim3(kGT), wgrad_panel_lds(3), s, gt, g_tiles, psp,
                                        F(w.wslab), w.wslab_floats);
@@ -2773,11 +2759,13 @@ int train_debug_gemm(int precision, int a_kslow, int b_kslow, const void* A, int
         float* slab = C + (size_t)round_up(M * N, 4);
         (void)hipGetLastError();
         if (W == 2) {
-            TRY(hipFuncSetAttribute((const void*)wgrad_panel_group_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wgrad_panel_lds(2)));
+            static LdsAttr attr;
+            TRY(ensure_lds(wgrad_panel_group_kernel<2>, wgrad_panel_lds(2), &attr));
             hipLaunchKernelGGL(wgrad_panel_group_kernel<2>, dim3(tiles * splits), dim3(kGT), wgrad_panel_lds(2), s, t, tiles, splits, slab,
                                (size_t)round_up(M * N, 4));
         } else {
-            TRY(hipFuncSetAttribute((const void*)wgrad_panel_group_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wgrad_panel_lds(3)));
+            static LdsAttr attr;
+            TRY(ensure_lds(wgrad_panel_group_kernel<3>, wgrad_panel_lds(3), &attr));
             hipLaunchKernelGGL(wgrad_panel_group_kernel<3>, dim3(tiles * splits), dim3(kGT), wgrad_panel_lds(3), s, t, tiles, splits, slab,
                                (size_t)round_up(M * N, 4));
         }
