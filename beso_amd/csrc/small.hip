@@ -524,16 +524,26 @@ __global__ __launch_bounds__(768) void sb_qkv_attn_wide_kernel(const float* __re
         }
     }
     // PROJ: this wave's fragments of Wp[:, h hd ..] -- feature tiles `wave` and `wave + 12`, two k-steps of 32 dims (the head's
-    // columns start at a multiple of hd = 4 n elements: 8-byte pieces; dims past hd meet zeros of the attention output) --
-    // requested here, where the q | k | v fragments are dead: they arrive under the attention
+    // columns start at a multiple of hd = 4 n elements: 8-byte pieces) -- requested here, where the q | k | v fragments are
+    // dead: they arrive under the attention.  A piece whose k index 32 ks + 8 lg (+ 4) lies past hd belongs to the next head, the
+    // next row or whatever is carved behind Wp: it is fetched from the head's first columns instead and set to zero (selects,
+    // not branches), so the product never depends on bytes outside the head's columns -- the attention output is zero there,
+    // but 0 x Inf / NaN is not
     uint2 pw[2][2][2];
     if constexpr (PROJ) {
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
             const int ft = wave + 12 * f;
-            const uint16_t* wp = Wp + (size_t)(16 * min(ft, (D + 15) / 16 - 1) + li) * Kd + h * hd + KPL * lg;
+            const uint16_t* wp = Wp + (size_t)(16 * min(ft, (D + 15) / 16 - 1) + li) * Kd + h * hd;
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) { pw[f][ks][0] = *(const uint2*)(wp + 32 * ks); pw[f][ks][1] = *(const uint2*)(wp + 32 * ks + 4); }
+            for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int k = 32 * ks + KPL * lg + 4 * q;
+                    const uint2 v = *(const uint2*)(wp + (k < hd ? k : 0));
+                    pw[f][ks][q] = k < hd ? v : make_uint2(0u, 0u);
+                }
+            }
         }
     }
 #pragma unroll

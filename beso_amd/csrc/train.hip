@@ -1536,7 +1536,8 @@ constexpr int kAmLd = 72;                          // halfwords per LDS row: 64 
 __device__ __forceinline__ u32x4 row_chunk16(const uint16_t* __restrict__ base, size_t ld, int x, int c0, int T, int hd) {
     // ONE 16-byte request per chunk (a head's rows are 8-byte aligned when hd is not a multiple of 8: global memory takes the
     // unaligned dwordx4).  A chunk that straddles the end of the head (hd = 60: columns 56 .. 63) is fetched as the head's last
-    // eight columns and shifted down, so nothing behind the head -- or the tensor -- is read.  hd >= 8, a multiple of 4.
+    // eight columns and shifted down, so nothing behind the head -- or the tensor -- is read.  hd >= 8 (the launch site sends
+    // hd = 4 to attn_small_kernel: min(c0, hd - 8) would start in front of the row), a multiple of 4.
     typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
     const uint16_t* p = base + (size_t)min(x, T - 1) * ld;
     const int cl = min(c0, hd - 8);
@@ -2584,7 +2585,9 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
                                (const float*)F(w.dxa), F(w.dx), M, t, T, G, D);
             TRY(hipGetLastError());
         }
-        if (attn_small && sizeof(E) == 2 && !(flags & BESO_TRAIN_PLAN_PER_OP)) {
+        // (hd >= 8: row_chunk16 fetches a head's row in 16-byte chunks clamped to its last eight columns; a head of four dims
+        //  has no such chunk inside its row and takes the VALU kernel)
+        if (attn_small && hd >= 8 && sizeof(E) == 2 && !(flags & BESO_TRAIN_PLAN_PER_OP)) {
             const int n_pairs = batch * H;
             hipLaunchKernelGGL(attn_mfma_bwd_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, s, (const uint16_t*)P(y.qkv),
                                (const uint16_t*)P(w.dy), (uint16_t*)P(y.dqkv), n_pairs, T, D, H, hd, scale, attn_p, attn_ik, seed,

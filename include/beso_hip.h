@@ -31,6 +31,11 @@
  *   - every tensor is device memory, contiguous, fp32, owned by the caller.  The library never
  *     allocates or frees device memory and never synchronises the stream; work is enqueued on
  *     `stream` and the call returns.
+ *   - buffers the library writes are handed over UNINITIALISED: the workspace, every output (`out`, `denoised`, `x_grad`,
+ *     `dot`, `loss_out`), the solver `history`, `grads_flat` and the `packed` image may hold anything on entry -- NaN bit
+ *     patterns and what an earlier, larger call left behind included.  No result depends on a byte the call did not write,
+ *     every element of a result is written, and nothing outside [ptr, ptr + size) of a buffer is written
+ *     (tests/test_buffer_independence.py).  Inputs are read inside their extents only.
  *   - return value: 0 = ok, negative = error (see beso_status_string).  Bad shapes and unsupported
  *     configurations are rejected before anything is enqueued.
  *   - thread-safety: the library keeps no mutable process-wide state; calls on distinct workspaces/streams are
@@ -356,7 +361,9 @@ int beso_loss_grad_overlap(const beso_config* cfg, const float* const* params, i
  * are still running on `stream`, and prepare the next step under them.  The call also uses loss_stream at its start, for the
  * step's copies of the weights (they depend on the parameters only and run beside the embedding of the batch on `stream`;
  * both streams are joined before the first layer): loss_stream must not carry unrelated work of the caller's that the step
- * should not wait for.                                                                                                   */
+ * should not wait for.  beso_loss_grad_streams zeroes `grads_flat` on `loss_stream` (with the weight copies: on `stream` when
+ * loss_stream is NULL); the forward on `stream` is ordered behind it, so the caller need not -- and must not rely on an
+ * earlier fill of its own surviving.                                          */
 int beso_loss_grad_streams(const beso_config* cfg, const float* const* params, int n_params, float* grads_flat, int precision,
                            const float* state, const float* action, const float* goal, const float* noise, const float* sigma,
                            float* loss_out, int batch, int t, int flags, float embed_pdrop, float attn_pdrop, float resid_pdrop,
