@@ -21,6 +21,7 @@
 // Dropout masks come from a counter-based hash of (seed, site, element index): the backward recomputes them.
 #include <string.h>
 #include <atomic>
+#include <type_traits>
 #include "common.h"
 #include "fused.h"
 #include "train.h"
@@ -1877,6 +1878,11 @@ static hipError_t step_side_stream(hipStream_t* out) {
     return hipSuccess;
 }
 
+// records the calling thread's event `which` on stream st
+static hipError_t record_event(int which, hipStream_t st, hipEvent_t* ev) {
+    const hipError_t e = step_event(which, ev);
+    return e != hipSuccess ? e : hipEventRecord(*ev, st);
+}
 static size_t carve_t(size_t& cur, size_t bytes) {
     const size_t off = cur;
     cur = round_up_sz(cur + bytes, 256);
@@ -2056,6 +2062,28 @@ static bool tail_forward_enabled(int rows, int flags) {
 }
 
 #define TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { *err = _e; *err_line = __LINE__; return BESO_ERR_HIP; } } while (0)
+// ... for a BESO_* status (a fused.hip launch): BESO_OK, or the status the caller reports with the HIP error behind it
+#define TRY_ST(call) do { const int st_ = (call); if (st_ != BESO_OK) { *err = hipGetLastError(); *err_line = __LINE__; return st_; } } while (0)
+// ... and for a phase of the step, which has reported its error already
+#define PHASE(call) do { const int st_ = (call); if (st_ != BESO_OK) return st_; } while (0)
+
+// workgroups of a grid-stride kernel of 256 threads over n elements: at least one, at most `cap`
+static int capped_grid(size_t n, size_t cap) { const size_t g = (n + 255) / 256; return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
+// nv: float4s per lane of a LayerNorm row (TrainPlan::nv); f(Int<nv>) launches that kernel instance
+template <int N> using Int = std::integral_constant<int, N>;
+template <typename F>
+static void with_ln_vec(int nv, F&& f) { if (nv == 1) f(Int<1>{}); else if (nv == 2) f(Int<2>{}); else f(Int<4>{}); }
+template <typename E>
+static hipError_t colsum(const E* a, int ld, int cols, int rows, float* out, hipStream_t s) {
+    constexpr int EPC = 16 / (int)sizeof(E), rpb = 128;        // rpb: rows per block of the column sums
+    hipLaunchKernelGGL(colsum_kernel<E>, dim3((cols + 64 * EPC - 1) / (64 * EPC), (rows + rpb - 1) / rpb), dim3(256), 0, s, a, ld, rows, cols,
+                       out, out, out, 1 << 30, rpb);
+    return hipGetLastError();
+}
+template <int W>
+static hipError_t launch_panel_group(const GTable& gt, int tiles, int splits, float* slab, size_t slab_floats, hipStream_t s) {
+    return launch_lds<wgrad_panel_group_kernel<W>>(dim3(tiles * splits), dim3(kGT), wgrad_panel_lds(W), s, gt, tiles, splits, slab, slab_floats);
+}
 
 // The input-VJP mode of the step (beso_denoise_vjp): the same forward and chain of data gradients, seeded with the caller's
 // cotangent instead of the loss, ending in the projection onto the action input.  No weight gradient, no reduction of partial
@@ -2063,129 +2091,312 @@ static bool tail_forward_enabled(int rows, int flags) {
 // in this mode) -- the kernels that write bias sums as side outputs write there.
 struct VjpIo { const float* cot; float* denoised; float* x_grad; float* dot; };
 
-template <typename E>
-static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat, int precision, const float* state,
-                       const float* action, const float* goal, const float* noise, const float* sigma, float* loss_out,
-                       int batch, int t, int flags, float embed_p, float attn_p, float resid_p, float goal_p, uint32_t seed,
-                       float grad_scale, char* ws,
-                       const TrainWs& w, hipStream_t s, hipStream_t early_stream, hipStream_t loss_stream, hipError_t* err, int* err_line,
-                       const VjpIo* vjp = nullptr) {
-    const int D = c->embed_dim, H = c->n_heads, hd = D / H, L = c->n_layers, G = c->goal_seq_len;
-    const int obs = c->obs_dim, act = c->act_dim, seq = G + c->obs_seq_len + 1;
-    const int M = w.M, T = w.T, Ke = w.Ke, ap = w.ap, D3 = 3 * D, D4 = 4 * D;
-    const int last_only = flags & BESO_TRAIN_LAST_ACTION_ONLY;
-    const float scale = 1.0f / sqrtf((float)hd);
-    const float attn_ik = attn_p > 0.f ? 1.0f / (1.0f - attn_p) : 1.f, resid_ik = resid_p > 0.f ? 1.0f / (1.0f - resid_p) : 1.f;
-    auto F = [&](size_t off) { return (float*)(ws + off); };
-    auto P = [&](size_t off) { return (E*)(ws + off); };
+// The arguments of one call of the step (train_loss_grad's; gflat: the scratch slab when vjp is set)
+struct TrainCall {
+    const beso_config* c; const float* const* p; float* gflat; int precision;
+    const float *state, *action, *goal, *noise, *sigma; float* loss_out;
+    int batch, t, flags; float embed_p, attn_p, resid_p, goal_p; uint32_t seed; float grad_scale;
+    char* ws; hipStream_t s, early_stream, loss_stream; hipError_t* err; int* err_line; const VjpIo* vjp;
+};
 
-    // parameter / gradient pointers, order of beso_pack_weights
-    const float* const* q = p;
-    float* g = gflat;
-    struct PG { const float* p; float* g; };
-    auto take = [&](size_t n) { PG r{*q, g}; ++q; if (!vjp) g += n; return r; };      // (VJP: all on the scratch slab)
-    const PG pos = take((size_t)seq * D), tokw = take((size_t)D * obs), tokb = take(D);
-    struct LayerPG { PG ln1w, ln1b, ln2w, ln2b, kw, kb, qw, qb, vw, vb, pw, pb, f1w, f1b, f2w, f2b; };
+// ---- parameters: the parameter / gradient pointers, order of beso_pack_weights
+struct PG { const float* p; float* g; };
+struct LayerPG { PG ln1w, ln1b, ln2w, ln2b, kw, kb, qw, qb, vw, vb, pw, pb, f1w, f1b, f2w, f2b; };
+struct TrainParams {
+    PG pos, tokw, tokb;
     LayerPG lp[kMaxLayers];
-    for (int l = 0; l < L; ++l) {
-        LayerPG& y = lp[l];
+    PG lnfw, lnfb, sigw, sigb, actw, actb, h0w, h0b, hw, hb;
+    size_t n_grad;                                        // floats of the flat gradient buffer
+};
+// advance = false (input VJP): every gradient pointer stays on `gflat`, the scratch slab
+static TrainParams walk_params(const beso_config* c, const float* const* q, float* gflat, bool advance) {
+    const size_t D = c->embed_dim, D4 = 4 * D, act = c->act_dim, seq = c->goal_seq_len + c->obs_seq_len + 1;
+    TrainParams r;
+    float* g = gflat;
+    auto take = [&](size_t n) { PG x{*q, g}; ++q; if (advance) g += n; return x; };
+    r.pos = take(seq * D); r.tokw = take(D * c->obs_dim); r.tokb = take(D);
+    for (int l = 0; l < c->n_layers; ++l) {
+        LayerPG& y = r.lp[l];
         y.ln1w = take(D); y.ln1b = take(D); y.ln2w = take(D); y.ln2b = take(D);
-        y.kw = take((size_t)D * D); y.kb = take(D); y.qw = take((size_t)D * D); y.qb = take(D);
-        y.vw = take((size_t)D * D); y.vb = take(D); y.pw = take((size_t)D * D); y.pb = take(D);
-        y.f1w = take((size_t)D4 * D); y.f1b = take(D4); y.f2w = take((size_t)D * D4); y.f2b = take(D);
+        y.kw = take(D * D); y.kb = take(D); y.qw = take(D * D); y.qb = take(D);
+        y.vw = take(D * D); y.vb = take(D); y.pw = take(D * D); y.pb = take(D);
+        y.f1w = take(D4 * D); y.f1b = take(D4); y.f2w = take(D * D4); y.f2b = take(D);
     }
-    const PG lnfw = take(D), lnfb = take(D), sigw = take(D), sigb = take(D), actw = take((size_t)D * act), actb = take(D);
+    r.lnfw = take(D); r.lnfb = take(D); r.sigw = take(D); r.sigb = take(D); r.actw = take(D * act); r.actb = take(D);
     // action head: Linear(D, act), or Linear(D, 100) - SiLU - Linear(100, act)   (score_gpts.py:184-191)
-    const int Hh = kHeadHidden, Hp = w.Hp;
     const bool mlp_head = !c->linear_output;
-    const PG h0w = mlp_head ? take((size_t)Hh * D) : PG{nullptr, nullptr}, h0b = mlp_head ? take(Hh) : PG{nullptr, nullptr};
-    const PG hw = take((size_t)act * (mlp_head ? Hh : D)), hb = take(act);
-    const size_t n_grad = (size_t)(g - gflat);
+    r.h0w = mlp_head ? take((size_t)kHeadHidden * D) : PG{nullptr, nullptr}; r.h0b = mlp_head ? take(kHeadHidden) : PG{nullptr, nullptr};
+    r.hw = take(act * (mlp_head ? (size_t)kHeadHidden : D)); r.hb = take(act);
+    r.n_grad = (size_t)(g - gflat);
+    return r;
+}
 
+// ---- plan: which form every part of the step takes.  A pure host function of the call's shape and flags.
+struct TrainPlan {
+    Layout lay;                                           // bf16 layout of the fused kernels (valid when one of their forms is taken)
+    bool use_whole, use_tail;                             // forward: one launch / tail blocks / (neither) per-op
+    bool use_dgrad, use_mlp_bwd;                          // backward: transposed-formulation data gradients, ... as one launch per MLP
+    int x16, panel_w;                                     // TrainWholeBufs::x_bf16; W of the panel weight-gradient tiles (0: 128 x 128 tiles)
+    int nv;                                               // float4s per lane of a LayerNorm row
+    bool attn_small, attn_mfma_bwd, wcat_side;
+};
+static TrainPlan make_train_plan(const beso_config* c, int flags, int M, int T, int t, float embed_p, float resid_p, size_t elem, bool fork) {
+    TrainPlan pl;
+    const int D = c->embed_dim, L = c->n_layers, hd = D / c->n_heads;
+    const bool per_op = flags & BESO_TRAIN_PLAN_PER_OP;
+    const bool lay = elem == 2 && make_layout(c, BESO_PREC_BF16, &pl.lay);
     // Which form the forward takes (decided here: its weight image is packed with the other per-step weight copies).
     // bf16, no dropout on the proj / MLP outputs, a shape with a fused tile kernel: everything of a layer behind its
     // attention and the LN1 + q/k/v of the next layer run as ONE launch (fused.hip: train_tail_kernel) on 96-token tiles
     // with the residual in registers -- six launches of the per-op forward below -- writing the same kept activations in
     // the same formats.  The last layer stays per-op (it continues on the compact action rows).
-    Layout flay;
-    const bool use_tail = sizeof(E) == 2 && resid_p == 0.f && L >= 2 && L * 13 <= 96 && make_layout(c, BESO_PREC_BF16, &flay) &&
-                          fused_train_supported(flay) && fused_train_image_bytes(flay) > 0 && tail_forward_enabled(M, flags);
+    pl.use_tail = lay && resid_p == 0.f && L >= 2 && L * 13 <= 96 && fused_train_supported(pl.lay) &&
+                  fused_train_image_bytes(pl.lay) > 0 && tail_forward_enabled(M, flags);
     // ... and where the shape has the one-launch kernel (kitchen, block-push; bf16; round 5: with or without dropout on the
-    // proj / MLP outputs), ALL
-    // layers run as ONE launch (fused.hip: train_fwd_kernel) -- 44 launches of the per-op forward at six layers; the call's plan
-    // hints keep the other two forms reachable (BESO_TRAIN_PLAN_PER_OP, BESO_TRAIN_PLAN_TILES)
-    const bool use_whole = sizeof(E) == 2 && !(flags & (BESO_TRAIN_PLAN_PER_OP | BESO_TRAIN_PLAN_TILES)) &&
-                           make_layout(c, BESO_PREC_BF16, &flay) && fused_train_whole_supported(flay, T, t);
-
+    // proj / MLP outputs), ALL layers run as ONE launch (fused.hip: train_fwd_kernel) -- 44 launches of the per-op forward at six
+    // layers; the call's plan hints keep the other two forms reachable (BESO_TRAIN_PLAN_PER_OP, BESO_TRAIN_PLAN_TILES)
+    pl.use_whole = lay && !(flags & (BESO_TRAIN_PLAN_PER_OP | BESO_TRAIN_PLAN_TILES)) && fused_train_whole_supported(pl.lay, T, t);
     // The data-gradient GEMMs of the backward pass in the transposed formulation (fused.hip: train_dgrad_kernel; bf16, the shapes
     // with the fused kernels); BESO_TRAIN_PLAN_PER_OP keeps the 128 x 128 tile kernel for them too
     // (they address the [M][D] ... [M][4 D] tensors with 32-bit byte offsets through buffer resources: M 4 D < 2^30 elements)
-    const bool use_dgrad = sizeof(E) == 2 && !(flags & BESO_TRAIN_PLAN_PER_OP) && make_layout(c, BESO_PREC_BF16, &flay) &&
-                           fused_train_dgrad_supported(flay) && (size_t)M * D < ((size_t)1 << 28);
+    pl.use_dgrad = lay && !per_op && fused_train_dgrad_supported(pl.lay) && (size_t)M * D < ((size_t)1 << 28);
+    pl.use_mlp_bwd = pl.use_dgrad && fused_train_mlp_bwd_supported(pl.lay);
+    // the one-launch forward keeps x_mid / x_out as bf16 when nothing but the fused LayerNorm-backward epilogues read them
+    // (no residual dropout: with it the forward itself adds the residual back from the kept fp32 rows)
+    pl.x16 = (pl.use_whole && pl.use_dgrad && pl.use_mlp_bwd && resid_p == 0.f) ? 1 : 0;
+    // bf16, 128 < D <= 384: the grouped launch runs on panel-owning tiles (wgrad_panel_group_kernel); the per-op plan keeps the
+    // 128 x 128 tiles
+    pl.panel_w = per_op ? 0 : wgrad_panel_w(D, elem);
+    pl.nv = D <= 256 ? 1 : (D <= 512 ? 2 : 4);
+    pl.attn_small = T <= kTP && hd <= 64 && hd % 4 == 0;
+    // (hd >= 8: row_chunk16 fetches a head's row in 16-byte chunks clamped to its last eight columns; a head of four dims
+    //  has no such chunk inside its row and takes the VALU kernel)
+    pl.attn_mfma_bwd = pl.attn_small && hd >= 8 && elem == 2 && !per_op;
+    // (the embedding's concatenated weight -- parameters only -- is packed on the side stream too, first: the compute stream
+    //  waits for it in front of the embedding GEMM, three small launches later)
+    pl.wcat_side = fork && embed_p == 0.f;
+    return pl;
+}
 
+// ---- LayerNorm backward partial sums: a slab [grid][3][D] per call (LayerNorm backward kernel, or the epilogue of a data
+// gradient), reduced into the gradient tensors of the table by ln_reduce_kernel
+struct LnPartials {
+    LnRedTable tab;
+    int calls = 0, reduced = 0, grid, D; float* base;     // grid: blocks of ln_bwd_kernel = the slab stride in block partials
+    // the slab of the next call, which writes `blocks` block partials of (dgamma, dbeta, dbias)
+    float* next(int blocks, float* dgam, float* dbet, float* dbias) {
+        tab.nb[calls] = blocks; tab.c[calls] = LnRedCall{dgam, dbet, dbias};
+        return base + (size_t)calls++ * grid * 3 * D;
+    }
+    hipError_t reduce(hipStream_t st) {                   // the calls since the last reduction, on stream st
+        hipLaunchKernelGGL(ln_reduce_kernel, dim3((D + 63) / 64, 3, calls - reduced), dim3(256), 0, st, (const float*)base, tab, grid, D, reduced);
+        reduced = calls;
+        return hipGetLastError();
+    }
+};
+
+// ---- The weight gradients are collected and run as one grouped launch after the chain of data gradients: every
+// output gradient they need stays in its own buffer until then.
+template <typename E>
+struct WgradGroup {
+    GTable gt;
+    int tiles = 0; uint32_t floats = 0;                   // floats: of the collected problems in a range's slab
+    bool off;                                             // input VJP: no weight gradient
+    int panel_w, per_op, M, splits, splits_panel; float* slab; size_t slab_floats; hipStream_t s;
+    int tiles_of(const GProb& q) const {
+        if (panel_w) { int o; return wgrad_panel_tiles(q.Mo, q.No, panel_w, &o); }
+        return q.nt_n * ((q.Mo + kTileMN - 1) / kTileMN);
+    }
+    static uint32_t floats_of(int Mo, int No, const float* bias) { return (uint32_t)round_up(Mo * No + (bias ? Mo : 0), 4); }
+    // out[Mo][No] = A^T B over `rows` token rows.
+    // bias: the gradient of the bias that goes with this weight = the column sums of A.  It rides along as a column of ones
+    // behind B's last real column (free whenever No is not a multiple of the 128-column tile: every shipped shape -- on the
+    // panel tiles too, whose n-wide tile holds column No unless No == 128 W); otherwise a colsum launch of its own.
+    hipError_t add(const E* A, int lda, int Mo, const E* B, int ldb, int No, int rows, float* out, float* bias = nullptr) {
+        if (off) return hipSuccess;
+        if (gt.n == kMaxGroup) { hipError_t e = flush(); if (e != hipSuccess) return e; }
+        if (bias && No % kTileMN == 0) {
+            hipError_t e = colsum(A, lda, Mo, rows, bias, s);
+            if (e != hipSuccess) return e;
+            bias = nullptr;
+        }
+        int orient = (No + kTileMN - 1) / kTileMN;        // (GProb::nt_n: tiles along n, or the panel tiles' orientation)
+        const int nt = panel_w ? wgrad_panel_tiles(Mo, No, panel_w, &orient) : orient * ((Mo + kTileMN - 1) / kTileMN);
+        gt.p[gt.n++] = GProb{A, B, out, bias, lda, ldb, Mo, No, tiles, orient, rows, floats};
+        tiles += nt; floats += floats_of(Mo, No, bias);
+        return hipSuccess;
+    }
+    // Order of the problems inside a launch: each XCD takes a contiguous run of the launch's tiles (xcd_tile), and a problem
+    // whose tiles straddle two runs has its operand panels fetched into two L2s.  Units (problems sharing their B operand:
+    // q | k | v of a layer) are packed into eight bins of ceil(tiles / 8), largest first, and emitted bin by bin -- kitchen:
+    // six bins {FC2, FC1, out-projection} of 81 tiles and two of three q|k|v triples, against runs of 81 / 82.
+    void arrange() {
+        const int n = gt.n;
+        if (n < 3 || per_op) return;
+        int ufirst[kMaxGroup], ucnt[kMaxGroup], utiles[kMaxGroup], order[kMaxGroup], bin_of[kMaxGroup], nu = 0;
+        for (int i = 0; i < n; ++i) {
+            if (i > 0 && gt.p[i].B == gt.p[i - 1].B) { ++ucnt[nu - 1]; utiles[nu - 1] += tiles_of(gt.p[i]); }
+            else { ufirst[nu] = i; ucnt[nu] = 1; utiles[nu] = tiles_of(gt.p[i]); ++nu; }
+        }
+        for (int u = 0; u < nu; ++u) {                    // (stable insertion sort, largest first)
+            int j = u;
+            while (j > 0 && utiles[order[j - 1]] < utiles[u]) { order[j] = order[j - 1]; --j; }
+            order[j] = u;
+        }
+        const int cap = (tiles + 7) / 8;
+        int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int k = 0; k < nu; ++k) {
+            const int u = order[k];
+            int b = -1;
+            for (int x = 0; x < 8 && b < 0; ++x) if (load[x] + utiles[u] <= cap) b = x;
+            if (b < 0) { b = 0; for (int x = 1; x < 8; ++x) if (load[x] < load[b]) b = x; }
+            bin_of[u] = b; load[b] += utiles[u];
+        }
+        GTable out;
+        out.n = 0; int tile0 = 0; uint32_t float0 = 0;
+        for (int b = 0; b < 8; ++b)
+            for (int k = 0; k < nu; ++k) {
+                const int u = order[k];
+                if (bin_of[u] != b) continue;
+                for (int i = ufirst[u]; i < ufirst[u] + ucnt[u]; ++i) {
+                    GProb q = gt.p[i];
+                    q.tile_begin = tile0; q.slab_off = float0;
+                    tile0 += tiles_of(q);
+                    float0 += floats_of(q.Mo, q.No, q.bias);
+                    out.p[out.n++] = q;
+                }
+            }
+        gt = out;
+    }
+    // launches the collected weight gradients behind everything issued on `s` so far.  (Measured and rejected, round 2: the
+    // grouped launch of a layer on a side stream under the data gradients of the layers in front of it -- 3.63 vs 3.39 ms per
+    // 1024-sample kitchen step, the two streams evict each other's operands from L2 / MALL.)
+    hipError_t flush() {
+        if (gt.n == 0) return hipSuccess;
+        arrange();
+        // row ranges into slabs of their own (make_train_ws), added up by wgrad_reduce_kernel
+        const int want = panel_w ? splits_panel : splits, sp = (want > 1 && floats <= slab_floats) ? want : 1;
+        if (panel_w) {
+            const hipError_t e = panel_w == 2 ? launch_panel_group<2>(gt, tiles, sp, slab, slab_floats, s)
+                                              : launch_panel_group<3>(gt, tiles, sp, slab, slab_floats, s);
+            if (e != hipSuccess) return e;
+        } else {
+            // Long contractions (M >= ~18 k token rows) run as one launch per ROW WINDOW of ~12 k rows, window w > 0 adding to the
+            // outputs of the windows before it (stream order: deterministic).  The tiles of a weight gradient share operand panels
+            // through an XCD's L2, but the sharers drift apart over a long contraction -- FETCH_SIZE 24 GB for 6.2 GB of operands at
+            // 8192 kitchen samples (90 k rows) against 1.9 GB for 0.78 GB at 1024 -- and a launch boundary lines them up again:
+            // 14.6 -> 14.2 ms per 8192-sample step with 8 windows (4: 14.3, 16: 14.25, 32: 14.6); nothing to gain at 11 k rows.
+            int n_win = (sp > 1 || per_op) ? 1 : (M + 6144) / 12288;
+            n_win = n_win < 1 ? 1 : (n_win > 16 ? 16 : n_win);
+            for (int win = 0; win < n_win; ++win)
+                hipLaunchKernelGGL(tgemm_wgrad_group_kernel<E>, dim3(tiles * sp), dim3(kGT), 0, s, gt, tiles, sp, slab, slab_floats, win, n_win);
+        }
+        if (sp > 1)
+            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((floats + 1023) / 1024), dim3(256), 0, s, gt, (const float*)slab, slab_floats, sp, floats);
+        gt.n = 0; tiles = 0; floats = 0;
+        return hipGetLastError();
+    }
+};
+
+// ---- the step: its phases in the order run() calls them.  A phase returns BESO_OK or a status it has reported in *err / *err_line.
+template <typename E>
+struct TrainStep : TrainCall {
+    const TrainWs& w;
+    const int D = c->embed_dim, H = c->n_heads, hd = D / H, L = c->n_layers, G = c->goal_seq_len, obs = c->obs_dim, act = c->act_dim;
+    const int seq = G + c->obs_seq_len + 1, M = w.M, T = w.T, Ke = w.Ke, ap = w.ap, D3 = 3 * D, D4 = 4 * D;
+    const int Ma = batch * t;                             // compact action rows (last layer's projection, MLP, ln_f, head)
+    const int Hh = kHeadHidden, Hp = w.Hp, mlp_head = !c->linear_output;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const float attn_ik = attn_p > 0.f ? 1.0f / (1.0f - attn_p) : 1.f, resid_ik = resid_p > 0.f ? 1.0f / (1.0f - resid_p) : 1.f;
+    const bool fork = loss_stream != nullptr;             // the weight copies run on the caller's second stream: ps
+    const hipStream_t ps = fork ? loss_stream : s;
+    const TrainParams par = walk_params(c, p, gflat, !vjp);
+    const TrainPlan plan = make_train_plan(c, flags, M, T, t, embed_p, resid_p, sizeof(E), fork);
+    const LayerPG* const lp = par.lp;
+    hipEvent_t ev_join = nullptr, ev_copies = nullptr, ev_wcat = nullptr;      // recorded by copy_weights(), waited for by the forward
+    static constexpr int kRpw = 4;                        // rows per wave of the LayerNorm backward
+    LnPartials ln; WgradGroup<E> wg;
+    // FC1 bias gradients of the transposed-formulation data-gradient kernel: per-workgroup sums in a slab per layer, added up
+    // (assigned, not accumulated) where the LayerNorm partial sums are
+    const float* b1_slabs[kMaxLayers]; float* b1_outs[kMaxLayers]; int b1_blocks[kMaxLayers]; int b1_n = 0;
+    TrainStep(const TrainCall& call, const TrainWs& ws_) : TrainCall(call), w(ws_) {
+        ln.base = F(w.ln_part); ln.grid = (M + 4 * kRpw - 1) / (4 * kRpw); ln.D = D;
+        wg.gt.n = 0; wg.off = vjp != nullptr; wg.panel_w = plan.panel_w; wg.per_op = flags & BESO_TRAIN_PLAN_PER_OP; wg.M = M; wg.s = s;
+        wg.splits = w.w_splits; wg.splits_panel = w.w_splits_panel; wg.slab = F(w.wslab); wg.slab_floats = w.wslab_floats;
+    }
+    float* F(size_t off) const { return (float*)(ws + off); }
+    E* P(size_t off) const { return (E*)(ws + off); }
+    const float* layer_in(int l) const { return l == 0 ? F(w.x0) : F(w.layer[l - 1].x_out); }
+    int run() {
+        PHASE(copy_weights());
+        PHASE(embed());
+        if (plan.use_whole) PHASE(forward_whole());
+        else for (int l = 0; l < L; ++l) PHASE(forward_layer(l));
+        PHASE(head_and_seed());
+        PHASE(backward_head());
+        for (int l = L - 1; l >= 0; --l) {
+            PHASE(backward_layer(l));
+            if (early_stream && l == train_early_layer(c) && l > 0) PHASE(early_flush());
+        }
+        return finish();
+    }
+    // ---- weight copies
     // The per-step weight copies depend on the parameters only, the embedding on the batch only: when the caller handed over a
     // second stream (loss_stream: idle at this point), the copies run THERE beside the gradient buffer's memset, the
     // preconditioning and the embedding on `s` -- two short chains of small kernels side by side instead of one after the
     // other (round 4: -50 us of a 2.5 ms step).  The forward waits for both.
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_copies = nullptr;
-    const bool fork = loss_stream != nullptr;
-    hipStream_t ps = fork ? loss_stream : s;
-    if (fork) {
-        TRY(step_event(kEvFork, &ev_fork));
-        TRY(step_event(kEvJoin, &ev_join));
-        TRY(step_event(kEvCopies, &ev_copies));
-        TRY(hipEventRecord(ev_fork, s));                 // (behind the optimizer step that wrote the parameters)
-        TRY(hipStreamWaitEvent(ps, ev_fork, 0));
+    int copy_weights() {
+        if (fork) {
+            hipEvent_t ev_fork = nullptr;
+            TRY(record_event(kEvFork, s, &ev_fork));         // (behind the optimizer step that wrote the parameters)
+            TRY(hipStreamWaitEvent(ps, ev_fork, 0));
+        }
+        // (loss_out and the padded head bias: prep_kernel.  Beside the store-bound forward the 37.5 MB memset measured slower; round 6:
+        //  in FRONT of the forward image's pack on the side stream -- the forward waits for that stream anyway (ev_join), and the
+        //  compute stream's chain of small launches in front of the forward is 9 us shorter)
+        if (plan.wcat_side) {
+            TRY(pack_wcat(ps));
+            TRY(record_event(kEvWcat, ps, &ev_wcat));
+        }
+        if (!vjp) TRY(hipMemsetAsync(gflat, 0, sizeof(float) * par.n_grad, ps));
+        // (first what the forward launch needs -- its fragment image --, then the plain copies the backward pass reads)
+        if (plan.use_whole) TRY_ST(fused_train_whole_pack(plan.lay, p, ws + w.fimg, ps));
+        else if (plan.use_tail) TRY_ST(fused_train_pack(plan.lay, p, ws + w.fimg, ps));
+        if (fork) TRY(record_event(kEvJoin, ps, &ev_join));
+        if (plan.use_dgrad) TRY_ST(fused_train_dgrad_pack(plan.lay, p, ws + w.bimg, ps));
+        // (nobody reads the operand-typed copies when the forward is the one-launch kernel and the data gradients take the transposed weights)
+        if (!(plan.use_whole && plan.use_dgrad)) TRY(pack_layer_weights());
+        if (mlp_head) {
+            TRY(launch_pack_matrix(par.h0w.p, Hh, D, ws + w.w_hid, Hp, D, precision, ps));          // zero rows Hh..Hp
+            TRY(hipMemsetAsync(ws + w.b_hid, 0, sizeof(float) * Hp, ps));
+            TRY(hipMemcpyAsync(ws + w.b_hid, par.h0b.p, sizeof(float) * Hh, hipMemcpyDeviceToDevice, ps));
+            TRY(hipMemsetAsync(ws + w.db_hid, 0, sizeof(float) * Hp, ps));
+            TRY(launch_pack_matrix(par.hw.p, act, Hh, ws + w.w_head, ap, Hp, precision, ps));       // zero columns Hh..Hp, rows act..ap
+        } else TRY(launch_pack_matrix(par.hw.p, act, D, ws + w.w_head, ap, D, precision, ps));
+        if (fork) TRY(record_event(kEvCopies, ps, &ev_copies));
+        return BESO_OK;
     }
-    // (loss_out and the padded head bias: prep_kernel.  Beside the store-bound forward the 37.5 MB memset measured slower; round 6:
-    //  in FRONT of the forward image's pack on the side stream -- the forward waits for that stream anyway (ev_join), and the
-    //  compute stream's chain of small launches in front of the forward is 9 us shorter)
-    // (the embedding's concatenated weight -- parameters only -- is packed there too, first: the compute stream waits for it
-    //  in front of the embedding GEMM, three small launches later)
-    hipEvent_t ev_wcat = nullptr;
-    const bool wcat_side = fork && embed_p == 0.f;
-    if (wcat_side) {
-        hipLaunchKernelGGL(wcat_pack_kernel, dim3((D * Ke + 255) / 256), dim3(256), 0, ps, pos.p, tokw.p, tokb.p, sigw.p, sigb.p,
-                           actw.p, actb.p, F(w.wcat), D, obs, act, seq, Ke);
-        TRY(hipGetLastError());
-        TRY(step_event(kEvWcat, &ev_wcat));
-        TRY(hipEventRecord(ev_wcat, ps));
+    hipError_t pack_wcat(hipStream_t st) {
+        hipLaunchKernelGGL(wcat_pack_kernel, dim3((D * Ke + 255) / 256), dim3(256), 0, st, par.pos.p, par.tokw.p, par.tokb.p, par.sigw.p,
+                           par.sigb.p, par.actw.p, par.actb.p, F(w.wcat), D, obs, act, seq, Ke);
+        return hipGetLastError();
     }
-    if (!vjp) TRY(hipMemsetAsync(gflat, 0, sizeof(float) * n_grad, ps));
-
-    // (first what the forward launch needs -- its fragment image --, then the plain copies the backward pass reads)
-    if (use_whole || use_tail) {
-        const int pst = use_whole ? fused_train_whole_pack(flay, p, ws + w.fimg, ps) : fused_train_pack(flay, p, ws + w.fimg, ps);
-        if (pst != BESO_OK) { *err = hipGetLastError(); *err_line = __LINE__; return pst; }
-    }
-    if (fork) TRY(hipEventRecord(ev_join, ps));
-    const bool use_mlp_bwd = use_dgrad && fused_train_mlp_bwd_supported(flay);
-    // the one-launch forward keeps x_mid / x_out as bf16 when nothing but the fused LayerNorm-backward epilogues read them
-    // (no residual dropout: with it the forward itself adds the residual back from the kept fp32 rows)
-    const int x16 = (use_whole && use_dgrad && use_mlp_bwd && resid_p == 0.f) ? 1 : 0;
-    if (use_dgrad) {
-        const int pst = fused_train_dgrad_pack(flay, p, ws + w.bimg, ps);
-        if (pst != BESO_OK) { *err = hipGetLastError(); *err_line = __LINE__; return pst; }
-    }
-    // ---- operand-typed weight copies (fused q|k|v rows as in the inference image): one launch for up to seven layers
-    // (nobody reads them when the forward is the one-launch kernel and the data gradients take the transposed weights)
-    if (!(use_whole && use_dgrad)) {
-        PackTable t;
-        t.n = 0;
-        uint32_t total4 = 0;
+    // operand-typed weight copies (fused q|k|v rows as in the inference image): one launch for up to seven layers
+    hipError_t pack_layer_weights() {
+        PackTable tab;
+        tab.n = 0; uint32_t total4 = 0;
         auto flush = [&]() -> hipError_t {
-            if (t.n == 0) return hipSuccess;
-            hipLaunchKernelGGL(pack_table_kernel<E>, dim3((total4 + 255) / 256 > 4096 ? 4096 : (total4 + 255) / 256), dim3(256), 0,
-                               ps, t, total4);
-            t.n = 0; total4 = 0;
+            if (tab.n == 0) return hipSuccess;
+            hipLaunchKernelGGL(pack_table_kernel<E>, dim3(capped_grid(total4, 4096)), dim3(256), 0, ps, tab, total4);
+            tab.n = 0; total4 = 0;
             return hipGetLastError();
         };
+        auto seg = [&](const float* src, void* dst, uint32_t n4, uint32_t f32) { tab.seg[tab.n++] = PackSeg{src, dst, total4, f32}; total4 += n4; };
         for (int l = 0; l < L; ++l) {
             const TrainLayerWs& y = w.layer[l];
             const size_t e = sizeof(E);
             const uint32_t dd4 = (uint32_t)((size_t)D * D / 4), d4 = (uint32_t)(D / 4);
-            if (t.n + 9 > kPackSegs) TRY(flush());
-            auto seg = [&](const float* src, void* dst, uint32_t n4, uint32_t f32) { t.seg[t.n++] = PackSeg{src, dst, total4, f32}; total4 += n4; };
+            if (tab.n + 9 > kPackSegs) { const hipError_t st = flush(); if (st != hipSuccess) return st; }
             seg(lp[l].qw.p, ws + y.w_qkv, dd4, 0);
             seg(lp[l].kw.p, ws + y.w_qkv + e * (size_t)D * D, dd4, 0);
             seg(lp[l].vw.p, ws + y.w_qkv + e * (size_t)2 * D * D, dd4, 0);
@@ -2196,484 +2407,321 @@ static int loss_grad_e(const beso_config* c, const float* const* p, float* gflat
             seg(lp[l].kb.p, ws + y.b_qkv + sizeof(float) * D, d4, 1);
             seg(lp[l].vb.p, ws + y.b_qkv + sizeof(float) * 2 * D, d4, 1);
         }
-        TRY(flush());
+        return flush();
     }
-    if (mlp_head) {
-        TRY(launch_pack_matrix(h0w.p, Hh, D, ws + w.w_hid, Hp, D, precision, ps));          // zero rows Hh..Hp
-        TRY(hipMemsetAsync(ws + w.b_hid, 0, sizeof(float) * Hp, ps));
-        TRY(hipMemcpyAsync(ws + w.b_hid, h0b.p, sizeof(float) * Hh, hipMemcpyDeviceToDevice, ps));
-        TRY(hipMemsetAsync(ws + w.db_hid, 0, sizeof(float) * Hp, ps));
-        TRY(launch_pack_matrix(hw.p, act, Hh, ws + w.w_head, ap, Hp, precision, ps));       // zero columns Hh..Hp, rows act..ap
-    } else {
-        TRY(launch_pack_matrix(hw.p, act, D, ws + w.w_head, ap, D, precision, ps));
-    }
-    if (fork) TRY(hipEventRecord(ev_copies, ps));
-
     // ---- forward
-    {
+    int embed() {
         // (VJP: the caller's x IS the noised action -- no elements to prepare, only the loss slot and the padded head bias)
         const size_t n = vjp ? 0 : (size_t)batch * t * act;
-        int grid = (int)((n + 255) / 256); if (grid > 2048) grid = 2048; if (grid < 1) grid = 1;
-        hipLaunchKernelGGL(prep_kernel, dim3(grid), dim3(256), 0, s, action, noise, sigma, F(w.noised), F(w.target),
-                           t * act, n, c->sigma_data, loss_out, F(w.b_head), hb.p, act, ap);
+        hipLaunchKernelGGL(prep_kernel, dim3(capped_grid(n, 2048)), dim3(256), 0, s, action, noise, sigma, F(w.noised), F(w.target),
+                           t * act, n, c->sigma_data, loss_out, F(w.b_head), par.hb.p, act, ap);
         TRY(hipGetLastError());
         if (embed_p == 0.f) {
             // the embedding as one exact-fp32 GEMM over the feature matrix (train_feat_kernel)
-            if (!wcat_side)
-                hipLaunchKernelGGL(wcat_pack_kernel, dim3((D * Ke + 255) / 256), dim3(256), 0, s, pos.p, tokw.p, tokb.p, sigw.p, sigb.p,
-                                   actw.p, actb.p, F(w.wcat), D, obs, act, seq, Ke);
-            const size_t nf = (size_t)M * Ke;
-            hipLaunchKernelGGL(train_feat_kernel<E>, dim3((unsigned)((nf + 255) / 256 > 4096 ? 4096 : (nf + 255) / 256)), dim3(256), 0, s,
-                               state, vjp ? action : (const float*)F(w.noised), goal, sigma, P(w.xemb), F(w.xemb32), M, t, T, G, obs, act, Ke,
-                               c->sigma_data, goal_p, seed);
+            if (!plan.wcat_side) TRY(pack_wcat(s));
+            hipLaunchKernelGGL(train_feat_kernel<E>, dim3(capped_grid((size_t)M * Ke, 4096)), dim3(256), 0, s, state, vjp ? action : (const float*)F(w.noised),
+                               goal, sigma, P(w.xemb), F(w.xemb32), M, t, T, G, obs, act, Ke, c->sigma_data, goal_p, seed);
             TRY(hipGetLastError());
-            if (wcat_side) TRY(hipStreamWaitEvent(s, ev_wcat, 0));
+            if (plan.wcat_side) TRY(hipStreamWaitEvent(s, ev_wcat, 0));
             TRY((tgemm<float, false, false>(F(w.xemb32), Ke, F(w.wcat), Ke, M, D, Ke, 1, EpiStore<float>{F(w.x0), nullptr, nullptr, D}, s)));
         } else {
-        const int threads = D >= 256 ? 256 : round_up(D, 64);
-        hipLaunchKernelGGL(train_embed_kernel<E>, dim3(M), dim3(threads), sizeof(float) * (size_t)(obs > act ? obs : act), s,
-                           state, (const float*)F(w.noised), goal, sigma, pos.p, tokw.p, tokb.p, sigw.p, sigb.p, actw.p,
-                           actb.p, F(w.x0), P(w.xemb), t, T, G, D, obs, act, Ke, c->sigma_data, embed_p, goal_p, seed);
-        TRY(hipGetLastError());
+            const int threads = D >= 256 ? 256 : round_up(D, 64);
+            hipLaunchKernelGGL(train_embed_kernel<E>, dim3(M), dim3(threads), sizeof(float) * (size_t)(obs > act ? obs : act), s,
+                               state, (const float*)F(w.noised), goal, sigma, par.pos.p, par.tokw.p, par.tokb.p, par.sigw.p, par.sigb.p,
+                               par.actw.p, par.actb.p, F(w.x0), P(w.xemb), t, T, G, D, obs, act, Ke, c->sigma_data, embed_p, goal_p, seed);
+            TRY(hipGetLastError());
         }
+        return BESO_OK;
     }
-    const int nv = D <= 256 ? 1 : (D <= 512 ? 2 : 4);
-    const int Ma = batch * t;                             // compact action rows (last layer's projection, MLP, ln_f, head)
-    auto ln_fwd = [&](const float* x, const float* gw, const float* gb, E* out, float* st, int rows) -> hipError_t {
-        const int grid = (rows + 3) / 4;
-        if (nv == 1) hipLaunchKernelGGL((ln_fwd_kernel<E, 1>), dim3(grid), dim3(256), 0, s, x, gw, gb, out, st, rows, D);
-        else if (nv == 2) hipLaunchKernelGGL((ln_fwd_kernel<E, 2>), dim3(grid), dim3(256), 0, s, x, gw, gb, out, st, rows, D);
-        else hipLaunchKernelGGL((ln_fwd_kernel<E, 4>), dim3(grid), dim3(256), 0, s, x, gw, gb, out, st, rows, D);
+    hipError_t ln_fwd(const float* x, PG gamma, PG beta, E* out, float* st, int rows) {
+        with_ln_vec(plan.nv, [&](auto nv) {
+            hipLaunchKernelGGL((ln_fwd_kernel<E, decltype(nv)::value>), dim3((rows + 3) / 4), dim3(256), 0, s, x, gamma.p, beta.p, out, st, rows, D);
+        });
         return hipGetLastError();
-    };
-    auto gs_grid = [&](size_t n4) { const size_t g = (n4 + 255) / 256; return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g)); };
-    const size_t lds_f = attn_lds_bytes(T, hd, false), lds_b = attn_lds_bytes(T, hd, true);
-    const bool attn_small = T <= kTP && hd <= 64 && hd % 4 == 0;
-    // (once per device, at the ceiling train_validate admits: lds_f / lds_b change with the window, the attribute need not)
-    constexpr size_t kAttnLdsAttr = 150 * 1024;
-    static LdsAttr attr_f, attr_b;
-    if (lds_f > 64 * 1024) TRY(ensure_lds(attn_fwd_kernel<E>, kAttnLdsAttr, &attr_f));
-    if (lds_b > 64 * 1024) TRY(ensure_lds(attn_bwd_kernel<E>, kAttnLdsAttr, &attr_b));
-    if (fork) TRY(hipStreamWaitEvent(s, ev_join, 0));             // the forward's weight image is in place
-    if (fork && !use_whole) TRY(hipStreamWaitEvent(s, ev_copies, 0));      // (per-op / tile forward: the plain copies too)
-    if (use_whole) {
+    }
+    // attention of layer l, forward (qkv -> y) or backward (qkv, dy -> dqkv)
+    template <bool BWD>
+    hipError_t launch_attention(int l) {
+        const TrainLayerWs& y = w.layer[l];
+        constexpr size_t kAttnLdsAttr = 150 * 1024;  // (the ceiling train_validate admits: the size changes with the window, the attribute need not)
+        const uint32_t site = (uint32_t)(4 * l);
+        if (BWD && plan.attn_mfma_bwd) {
+            const int n_pairs = batch * H;
+            hipLaunchKernelGGL(attn_mfma_bwd_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, s, (const uint16_t*)P(y.qkv),
+                               (const uint16_t*)P(w.dy), (uint16_t*)P(y.dqkv), n_pairs, T, D, H, hd, scale, attn_p, attn_ik, seed, site);
+        } else if (plan.attn_small) {
+            auto small = [&](auto tt) {
+                hipLaunchKernelGGL((attn_small_kernel<E, BWD, decltype(tt)::value>), dim3(batch * H), dim3(64), 0, s, (const E*)P(y.qkv),
+                                   BWD ? (const E*)P(w.dy) : (const E*)nullptr, BWD ? P(y.dqkv) : P(y.y), T, D, H, hd, scale, attn_p, attn_ik, seed, site);
+            };
+            if (T <= 8) small(Int<8>{}); else if (T <= 12) small(Int<12>{}); else small(Int<16>{});
+        } else if (BWD)
+            return launch_lds_attr<attn_bwd_kernel<E>>(kAttnLdsAttr, dim3(batch * H), dim3(64), attn_lds_bytes(T, hd, true), s, (const E*)P(y.qkv),
+                                                       (const E*)P(w.dy), P(y.dqkv), T, D, H, hd, scale, attn_p, attn_ik, seed, site);
+        else
+            return launch_lds_attr<attn_fwd_kernel<E>>(kAttnLdsAttr, dim3(batch * H), dim3(64), attn_lds_bytes(T, hd, false), s, (const E*)P(y.qkv),
+                                                       P(y.y), T, D, H, hd, scale, attn_p, attn_ik, seed, site);
+        return hipGetLastError();
+    }
+    int forward_whole() {
+        if (fork) TRY(hipStreamWaitEvent(s, ev_join, 0));             // the forward's weight image is in place
         const TrainLayerWs& y0 = w.layer[0];
         const size_t stride = L > 1 ? w.layer[1].x_mid - y0.x_mid : 0;
         const TrainWholeBufs b{F(w.x0), ws, y0.x_mid, y0.x_out, y0.st1, y0.st2, y0.xn1, y0.qkv, y0.y, y0.xn2, y0.h, y0.g,
-                               stride, w.ya, t, attn_p, seed, resid_p, x16};
+                               stride, w.ya, t, attn_p, seed, resid_p, plan.x16};
         profile_begin(BESO_SITE_FUSED_LAYER, s);
-        const int st = fused_train_whole(flay, ws + w.fimg, batch, T, b, s);
+        const int st = fused_train_whole(plan.lay, ws + w.fimg, batch, T, b, s);
         profile_end(BESO_SITE_FUSED_LAYER, s);
-        if (st != BESO_OK) { *err = hipGetLastError(); *err_line = __LINE__; return st; }
-        if (fork) TRY(hipStreamWaitEvent(s, ev_copies, 0));       // head weights and the backward's copies: ready long since
+        TRY_ST(st);
+        if (fork) TRY(hipStreamWaitEvent(s, ev_copies, 0));           // head weights and the backward's copies: ready long since
+        return BESO_OK;
     }
-    for (int l = 0; l < (use_whole ? 0 : L); ++l) {
-        const TrainLayerWs& y = w.layer[l];
-        const float* x_in = l == 0 ? F(w.x0) : F(w.layer[l - 1].x_out);
-        const bool last = l == L - 1;
-        if (!(use_tail && l > 0)) {           // (behind a tail block these arrive from the previous layer's launch)
-            TRY(ln_fwd(x_in, lp[l].ln1w.p, lp[l].ln1b.p, P(y.xn1), F(y.st1), M));
-            TRY((tgemm<E, false, false>(P(y.xn1), D, P(y.w_qkv), D, M, D3, D, 1,
-                                        EpiStore<E>{nullptr, P(y.qkv), F(y.b_qkv), D3}, s)));
+    // layer l through the per-op kernels, or (use_tail) everything behind its attention as one tail-block launch
+    int forward_layer(int l) {
+        if (fork && l == 0) {
+            TRY(hipStreamWaitEvent(s, ev_join, 0));                   // the forward's weight image is in place
+            TRY(hipStreamWaitEvent(s, ev_copies, 0));                 // (per-op / tile forward: the plain copies too)
         }
-        if (attn_small) {
-#define ATT(TT) hipLaunchKernelGGL((attn_small_kernel<E, false, TT>), dim3(batch * H), dim3(64), 0, s, (const E*)P(y.qkv), \
-                                   (const E*)nullptr, P(y.y), T, D, H, hd, scale, attn_p, attn_ik, seed, (uint32_t)(4 * l))
-            if (T <= 8) ATT(8); else if (T <= 12) ATT(12); else ATT(16);
-#undef ATT
-        } else
-            hipLaunchKernelGGL(attn_fwd_kernel<E>, dim3(batch * H), dim3(64), lds_f, s, (const E*)P(y.qkv), P(y.y), T, D, H,
-                               hd, scale, attn_p, attn_ik, seed, (uint32_t)(4 * l));
-        TRY(hipGetLastError());
-        if (use_tail && !last) {
+        const TrainLayerWs& y = w.layer[l];
+        const float* x_in = layer_in(l);
+        const bool last = l == L - 1;
+        if (!(plan.use_tail && l > 0)) {      // (behind a tail block these arrive from the previous layer's launch)
+            TRY(ln_fwd(x_in, lp[l].ln1w, lp[l].ln1b, P(y.xn1), F(y.st1), M));
+            TRY((tgemm<E, false, false>(P(y.xn1), D, P(y.w_qkv), D, M, D3, D, 1, EpiStore<E>{nullptr, P(y.qkv), F(y.b_qkv), D3}, s)));
+        }
+        TRY(launch_attention<false>(l));
+        if (plan.use_tail && !last) {
             const TrainLayerWs& nx = w.layer[l + 1];
-            const int tst = fused_train_tail(flay, ws + w.fimg, l, M, x_in, P(y.y), D, F(y.x_mid), F(y.x_out), F(y.st2), P(y.xn2),
-                                             P(y.h), P(y.g), F(nx.st1), P(nx.xn1), P(nx.qkv), s);
-            if (tst != BESO_OK) { *err = hipGetLastError(); *err_line = __LINE__; return tst; }
-            continue;
+            TRY_ST(fused_train_tail(plan.lay, ws + w.fimg, l, M, x_in, P(y.y), D, F(y.x_mid), F(y.x_out), F(y.st2), P(y.xn2),
+                                    P(y.h), P(y.g), F(nx.st1), P(nx.xn1), P(nx.qkv), s));
+            return BESO_OK;
         }
         // the last layer continues on the compact action rows only (its buffers hold Ma rows from here on)
         const int rows = last ? Ma : M;
         const E* y_in = P(y.y);
         const float* res_in = x_in;
         if (last) {
-            const size_t n4 = (size_t)Ma * (D / 4);
-            hipLaunchKernelGGL(gather_rows_kernel<E>, dim3(gs_grid(n4)), dim3(256), 0, s, (const E*)P(y.y), P(w.ya), Ma, t, T, G, D);
-            hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(gs_grid(n4)), dim3(256), 0, s, x_in, F(w.xa), Ma, t, T, G, D);
+            const int grid = capped_grid((size_t)Ma * (D / 4), 4096);
+            hipLaunchKernelGGL(gather_rows_kernel<E>, dim3(grid), dim3(256), 0, s, (const E*)P(y.y), P(w.ya), Ma, t, T, G, D);
+            hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(grid), dim3(256), 0, s, x_in, F(w.xa), Ma, t, T, G, D);
             TRY(hipGetLastError());
             y_in = P(w.ya); res_in = F(w.xa);
         }
         TRY((tgemm<E, false, false>(y_in, D, P(y.w_proj), D, rows, D, D, 1,
                                     EpiResid{res_in, F(y.x_mid), lp[l].pb.p, D, resid_p, resid_ik, seed, (uint32_t)(4 * l + 1)}, s)));
-        TRY(ln_fwd(F(y.x_mid), lp[l].ln2w.p, lp[l].ln2b.p, P(y.xn2), F(y.st2), rows));
+        TRY(ln_fwd(F(y.x_mid), lp[l].ln2w, lp[l].ln2b, P(y.xn2), F(y.st2), rows));
         TRY((tgemm<E, false, false>(P(y.xn2), D, P(y.w_fc1), D, rows, D4, D, 1, EpiFc1<E>{P(y.h), P(y.g), lp[l].f1b.p, D4}, s)));
         TRY((tgemm<E, false, false>(P(y.g), D4, P(y.w_fc2), D4, rows, D, D4, 1,
-                                    EpiResid{(const float*)F(y.x_mid), F(y.x_out), lp[l].f2b.p, D, resid_p, resid_ik, seed,
-                                             (uint32_t)(4 * l + 2)}, s)));
+                                    EpiResid{(const float*)F(y.x_mid), F(y.x_out), lp[l].f2b.p, D, resid_p, resid_ik, seed, (uint32_t)(4 * l + 2)}, s)));
+        return BESO_OK;
     }
-    const float* x_last = F(w.layer[L - 1].x_out);       // [Ma][D]
-    TRY(ln_fwd(x_last, lnfw.p, lnfb.p, P(w.xf), F(w.stf), Ma));
-    if (mlp_head) {
-        TRY((tgemm<E, false, false>(P(w.xf), D, P(w.w_hid), D, Ma, Hp, D, 1, EpiSilu<E>{P(w.hz), P(w.ha), F(w.b_hid), Hp}, s)));
-        TRY((tgemm<E, false, false>(P(w.ha), Hp, P(w.w_head), Hp, Ma, ap, Hp, 1, EpiStore<E>{F(w.pred), nullptr, F(w.b_head), ap}, s)));
-    } else {
-        TRY((tgemm<E, false, false>(P(w.xf), D, P(w.w_head), D, Ma, ap, D, 1, EpiStore<E>{F(w.pred), nullptr, F(w.b_head), ap}, s)));
-    }
-    if (vjp) {
-        const size_t n = (size_t)Ma * ap;
-        int grid = (int)((n + 255) / 256); if (grid > 1024) grid = 1024;
-        hipLaunchKernelGGL(vjp_seed_kernel<E>, dim3(grid), dim3(256), 0, s, (const float*)F(w.pred), action, sigma, vjp->cot,
-                           P(w.dpred), vjp->denoised, Ma, act, ap, t, c->sigma_data);
-        TRY(hipGetLastError());
-    } else {
-        const size_t n = (size_t)Ma * ap;
-        int grid = (int)((n + 255) / 256); if (grid > 1024) grid = 1024;
-        hipLaunchKernelGGL(loss_kernel<E>, dim3(grid), dim3(256), 0, s, (const float*)F(w.pred), (const float*)F(w.target),
-                           P(w.dpred), loss_out, Ma, act, ap,
-                           1.0f / (float)((size_t)batch * (last_only ? 1 : t) * act), grad_scale, t, last_only);
+    // ln_f and the action head on the compact rows, then the loss and its gradient dpred -- or the VJP's seed
+    int head_and_seed() {
+        TRY(ln_fwd(F(w.layer[L - 1].x_out), par.lnfw, par.lnfb, P(w.xf), F(w.stf), Ma));
+        if (mlp_head) {
+            TRY((tgemm<E, false, false>(P(w.xf), D, P(w.w_hid), D, Ma, Hp, D, 1, EpiSilu<E>{P(w.hz), P(w.ha), F(w.b_hid), Hp}, s)));
+            TRY((tgemm<E, false, false>(P(w.ha), Hp, P(w.w_head), Hp, Ma, ap, Hp, 1, EpiStore<E>{F(w.pred), nullptr, F(w.b_head), ap}, s)));
+        } else TRY((tgemm<E, false, false>(P(w.xf), D, P(w.w_head), D, Ma, ap, D, 1, EpiStore<E>{F(w.pred), nullptr, F(w.b_head), ap}, s)));
+        const int grid = capped_grid((size_t)Ma * ap, 1024);
+        if (vjp) {
+            hipLaunchKernelGGL(vjp_seed_kernel<E>, dim3(grid), dim3(256), 0, s, (const float*)F(w.pred), action, sigma, vjp->cot,
+                               P(w.dpred), vjp->denoised, Ma, act, ap, t, c->sigma_data);
+            TRY(hipGetLastError());
+            return BESO_OK;
+        }
+        const int last_only = flags & BESO_TRAIN_LAST_ACTION_ONLY;
+        hipLaunchKernelGGL(loss_kernel<E>, dim3(grid), dim3(256), 0, s, (const float*)F(w.pred), (const float*)F(w.target), P(w.dpred),
+                           loss_out, Ma, act, ap, 1.0f / (float)((size_t)batch * (last_only ? 1 : t) * act), grad_scale, t, last_only);
         TRY(hipGetLastError());
         if (loss_stream) {
             // the loss is final here, long before the step is: a stream of the caller's is ordered behind this point, so that
             // reading the loss there (beso_agent.py:248 `loss.item()`) does not wait for the backward pass
             hipEvent_t ev_loss = nullptr;
-            TRY(step_event(kEvLoss, &ev_loss));
-            TRY(hipEventRecord(ev_loss, s));
+            TRY(record_event(kEvLoss, s, &ev_loss));
             TRY(hipStreamWaitEvent(loss_stream, ev_loss, 0));
         }
+        return BESO_OK;
     }
-
     // ---- backward
-    const int rpb = 128;                                  // rows per block of the column sums
-    constexpr int EPC = 16 / (int)sizeof(E);
-    auto colsum = [&](const E* a, int ld, int cols, int rows, float* o0, float* o1 = nullptr, float* o2 = nullptr,
-                      int seg = 1 << 30) -> hipError_t {
-        hipLaunchKernelGGL(colsum_kernel<E>, dim3((cols + 64 * EPC - 1) / (64 * EPC), (rows + rpb - 1) / rpb), dim3(256), 0, s, a,
-                           ld, rows, cols, o0, o1 ? o1 : o0, o2 ? o2 : o0, seg, rpb);
+    // (every call launches ln.grid blocks so that the partial slabs have one shape; blocks past `rows` write zeros)
+    hipError_t ln_bwd(const float* x, size_t st, const float* gamma, const float* dres_in, float* dres_out, E* dxb, int rows,
+                      float* dgam, float* dbet, float* dbias, float p_site, uint32_t site, int skip_mod = 0) {
+        float* part = ln.next(ln.grid, dgam, dbet, dbias);
+        with_ln_vec(plan.nv, [&](auto nv) {
+            hipLaunchKernelGGL((ln_bwd_kernel<E, decltype(nv)::value>), dim3(ln.grid), dim3(256), 0, s, (const float*)F(w.dxn), x, (const float*)F(st),
+                               gamma, dres_in, dres_out, dxb, part, rows, D, kRpw, p_site, p_site > 0.f ? 1.0f / (1.0f - p_site) : 1.f, seed, site, skip_mod);
+        });
         return hipGetLastError();
-    };
-    const int rpw = 4;                                    // rows per wave of the LayerNorm backward
-    const int lnb_grid = (M + 4 * rpw - 1) / (4 * rpw);
-    LnRedTable lrt;
-    int ln_calls = 0, ln_reduced = 0;
-    // (every call launches lnb_grid blocks so that the partial slabs have one shape; blocks past `rows` write zeros)
-    auto ln_bwd = [&](const float* x, size_t st, const float* gamma, const float* dres_in, float* dres_out, E* dxb, int rows,
-                      float* dgam, float* dbet, float* dbias, float p_site, uint32_t site, int skip_mod = 0) -> hipError_t {
-        float* part = F(w.ln_part) + (size_t)ln_calls * lnb_grid * 3 * D;
-        lrt.nb[ln_calls] = lnb_grid;
-        lrt.c[ln_calls++] = LnRedCall{dgam, dbet, dbias};
-#define LNB(NV)                                                                                                     \
-        hipLaunchKernelGGL((ln_bwd_kernel<E, NV>), dim3(lnb_grid), dim3(256), 0, s, (const float*)F(w.dxn), x,                \
-                           (const float*)F(st), gamma, dres_in, dres_out, dxb, part, rows, D,                               \
-                           rpw, p_site, p_site > 0.f ? 1.0f / (1.0f - p_site) : 1.f, seed, site, skip_mod)
-        if (nv == 1) LNB(1); else if (nv == 2) LNB(2); else LNB(4);
-#undef LNB
-        return hipGetLastError();
-    };
-    // the same LayerNorm backward as the epilogue of the data gradient in front of it (which = 0: q|k|v, 2: FC1); dxn is never
-    // written (dropout at the site: the same (row, feature) hash, evaluated in the epilogue).
-    auto dgrad_ln = [&](int l, int which, int rows, const E* in, const float* x, size_t st, const float* gamma, float* dres,
-                        E* dxb, float* dgam, float* dbet, float* dbias, float p_site, uint32_t site, int skip_mod = 0,
-                        int x_is_bf16 = 0) -> int {
-        float* part = F(w.ln_part) + (size_t)ln_calls * lnb_grid * 3 * D;
-        lrt.nb[ln_calls] = fused_train_dgrad_blocks(rows);
-        lrt.c[ln_calls++] = LnRedCall{dgam, dbet, dbias};
-        const TrainLnBwd ln{x, (const float*)F(st), gamma, dres, dres, dxb, part, p_site, seed, site, skip_mod, x_is_bf16};
-        return fused_train_dgrad(flay, ws + w.bimg, l, which, rows, in, nullptr, nullptr, nullptr, nullptr, nullptr, s, &ln);
-    };
-    // The weight gradients are collected and run as one grouped launch after the chain of data gradients: every
-    // output gradient they need stays in its own buffer until then.
-    GTable gt;
-    gt.n = 0;
-    int g_tiles = 0;
-    // bf16, 128 < D <= 384: the grouped launch runs on panel-owning tiles (wgrad_panel_group_kernel); the per-op plan keeps the
-    // 128 x 128 tiles
-    const int panel_w = (flags & BESO_TRAIN_PLAN_PER_OP) ? 0 : wgrad_panel_w(D, sizeof(E));
-    // FC1 bias gradients of the transposed-formulation data-gradient kernel: per-workgroup sums in a slab per layer, added up
-    // (assigned, not accumulated) where the LayerNorm partial sums are
-    const float* b1_slabs[kMaxLayers]; float* b1_outs[kMaxLayers]; int b1_blocks[kMaxLayers]; int b1_n = 0;
-    hipStream_t rs = s;                                   // stream of the partial-sum reductions (the side stream at the step's end)
-    auto flush_b1 = [&]() -> int {
-        const int st = fused_train_bias_reduce(b1_slabs, b1_outs, b1_blocks, b1_n, D4, rs);
-        b1_n = 0;
-        return st;
-    };
-    // launches the collected weight gradients behind everything issued on `s` so far.  (Measured and rejected, round 2: the
-    // grouped launch of a layer on a side stream under the data gradients of the layers in front of it -- 3.63 vs 3.39 ms per
-    // 1024-sample kitchen step, the two streams evict each other's operands from L2 / MALL.)
-    uint32_t g_floats = 0;                                // floats of the collected problems in a range's slab
-    // Order of the problems inside a launch: each XCD takes a contiguous run of the launch's tiles (xcd_tile), and a problem
-    // whose tiles straddle two runs has its operand panels fetched into two L2s.  Units (problems sharing their B operand:
-    // q | k | v of a layer) are packed into eight bins of ceil(tiles / 8), largest first, and emitted bin by bin -- kitchen:
-    // six bins {FC2, FC1, out-projection} of 81 tiles and two of three q|k|v triples, against runs of 81 / 82.
-    auto arrange_group = [&]() {
-        const int n = gt.n;
-        if (n < 3 || (flags & BESO_TRAIN_PLAN_PER_OP)) return;
-        int ufirst[kMaxGroup], ucnt[kMaxGroup], utiles[kMaxGroup], order[kMaxGroup], bin_of[kMaxGroup], nu = 0;
-        auto tiles_of = [&](const GProb& q) {
-            if (panel_w) { int o; return wgrad_panel_tiles(q.Mo, q.No, panel_w, &o); }
-            return q.nt_n * ((q.Mo + kTileMN - 1) / kTileMN);
-        };
-        for (int i = 0; i < n; ++i) {
-            if (i > 0 && gt.p[i].B == gt.p[i - 1].B) { ++ucnt[nu - 1]; utiles[nu - 1] += tiles_of(gt.p[i]); }
-            else { ufirst[nu] = i; ucnt[nu] = 1; utiles[nu] = tiles_of(gt.p[i]); ++nu; }
-        }
-        for (int u = 0; u < nu; ++u) {                    // (stable insertion sort, largest first)
-            int j = u;
-            while (j > 0 && utiles[order[j - 1]] < utiles[u]) { order[j] = order[j - 1]; --j; }
-            order[j] = u;
-        }
-        const int cap = (g_tiles + 7) / 8;
-        int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k = 0; k < nu; ++k) {
-            const int u = order[k];
-            int b = -1;
-            for (int x = 0; x < 8 && b < 0; ++x) if (load[x] + utiles[u] <= cap) b = x;
-            if (b < 0) { b = 0; for (int x = 1; x < 8; ++x) if (load[x] < load[b]) b = x; }
-            bin_of[u] = b; load[b] += utiles[u];
-        }
-        GTable out;
-        out.n = 0;
-        int tiles = 0; uint32_t floats = 0;
-        for (int b = 0; b < 8; ++b)
-            for (int k = 0; k < nu; ++k) {
-                const int u = order[k];
-                if (bin_of[u] != b) continue;
-                for (int i = ufirst[u]; i < ufirst[u] + ucnt[u]; ++i) {
-                    GProb q = gt.p[i];
-                    q.tile_begin = tiles; q.slab_off = floats;
-                    tiles += tiles_of(q);
-                    floats += (uint32_t)round_up(q.Mo * q.No + (q.bias ? q.Mo : 0), 4);
-                    out.p[out.n++] = q;
-                }
-            }
-        gt = out;
-    };
-    auto flush_group = [&]() -> hipError_t {
-        if (gt.n == 0) return hipSuccess;
-        arrange_group();
-        if (panel_w) {
-            const int psp = (w.w_splits_panel > 1 && g_floats <= w.wslab_floats) ? w.w_splits_panel : 1;
-            static LdsAttr attr2, attr3;
-            hipError_t e = hipSuccess;
-            if (panel_w == 2) {
-                e = ensure_lds(wgrad_panel_group_kernel<2>, wgrad_panel_lds(2), &attr2);
-                if (e == hipSuccess)
-                    hipLaunchKernelGGL(wgrad_panel_group_kernel<2>, dim3(g_tiles * psp), dim3(kGT), wgrad_panel_lds(2), s, gt, g_tiles, psp,
-                                       F(w.wslab), w.wslab_floats);
-            } else {
-                e = ensure_lds(wgrad_panel_group_kernel<3>, wgrad_panel_lds(3), &attr3);
-                if (e == hipSuccess)
-                    hipLaunchKernelGGL(wgrad_panel_group_kernel<3>, dim3(g_tiles * psp), dim3(kGT), wgrad_panel_lds(3), s, gt, g_tiles, psp,
-                                       F(w.wslab), w.wslab_floats);
-            }
-            if (e != hipSuccess) return e;
-            if (psp > 1)
-                hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((g_floats + 1023) / 1024), dim3(256), 0, s, gt, (const float*)F(w.wslab),
-                                   w.wslab_floats, psp, g_floats);
-            gt.n = 0; g_tiles = 0; g_floats = 0;
-            return hipGetLastError();
-        }
-        const int sp = (w.w_splits > 1 && g_floats <= w.wslab_floats) ? w.w_splits : 1;
-        // Long contractions (M >= ~18 k token rows) run as one launch per ROW WINDOW of ~12 k rows, window w > 0 adding to the
-        // outputs of the windows before it (stream order: deterministic).  The tiles of a weight gradient share operand panels
-        // through an XCD's L2, but the sharers drift apart over a long contraction -- FETCH_SIZE 24 GB for 6.2 GB of operands at
-        // 8192 kitchen samples (90 k rows) against 1.9 GB for 0.78 GB at 1024 -- and a launch boundary lines them up again:
-        // 14.6 -> 14.2 ms per 8192-sample step with 8 windows (4: 14.3, 16: 14.25, 32: 14.6); nothing to gain at 11 k rows.
-        int n_win = (sp > 1 || (flags & BESO_TRAIN_PLAN_PER_OP)) ? 1 : (M + 6144) / 12288;
-        n_win = n_win < 1 ? 1 : (n_win > 16 ? 16 : n_win);
-        for (int win = 0; win < n_win; ++win)
-        hipLaunchKernelGGL(tgemm_wgrad_group_kernel<E>, dim3(g_tiles * sp), dim3(kGT), 0, s, gt, g_tiles, sp, F(w.wslab),
-                           w.wslab_floats, win, n_win);
-        if (sp > 1)
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((g_floats + 1023) / 1024), dim3(256), 0, s, gt, (const float*)F(w.wslab),
-                               w.wslab_floats, sp, g_floats);
-        gt.n = 0; g_tiles = 0; g_floats = 0;
-        return hipGetLastError();
-    };
-    // bias: the gradient of the bias that goes with this weight = the column sums of A.  It rides along as a column of ones
-    // behind B's last real column (free whenever No is not a multiple of the 128-column tile: every shipped shape); otherwise
-    // a colsum launch of its own.
-    auto wgrad = [&](const E* A, int lda, int Mo, const E* B, int ldb, int No, int rows, float* out, float* bias = nullptr) -> hipError_t {
-        if (vjp) return hipSuccess;                       // (input VJP: no weight gradient)
-        if (gt.n == kMaxGroup) { hipError_t e = flush_group(); if (e != hipSuccess) return e; }
-        if (bias && No % kTileMN == 0) {
-            hipError_t e = colsum(A, lda, Mo, rows, bias);
-            if (e != hipSuccess) return e;
-            bias = nullptr;
-        }
-        if (panel_w) {
-            // (the ones column rides in the tile that covers column No: n-wide tiles always hold it unless No == 128 W)
-            if (bias && (No <= 128 * panel_w ? No == 128 * panel_w : No % kTileMN == 0)) {
-                hipError_t e = colsum(A, lda, Mo, rows, bias);
-                if (e != hipSuccess) return e;
-                bias = nullptr;
-            }
-            int orient = 0;
-            const int nt = wgrad_panel_tiles(Mo, No, panel_w, &orient);
-            gt.p[gt.n++] = GProb{A, B, out, bias, lda, ldb, Mo, No, g_tiles, orient, rows, g_floats};
-            g_tiles += nt;
-            g_floats += (uint32_t)round_up(Mo * No + (bias ? Mo : 0), 4);
-            return hipSuccess;
-        }
-        const int nt_n = (No + kTileMN - 1) / kTileMN, nt_m = (Mo + kTileMN - 1) / kTileMN;
-        gt.p[gt.n++] = GProb{A, B, out, bias, lda, ldb, Mo, No, g_tiles, nt_n, rows, g_floats};
-        g_tiles += nt_n * nt_m;
-        g_floats += (uint32_t)round_up(Mo * No + (bias ? Mo : 0), 4);
-        return hipSuccess;
-    };
-    // head (compact rows): dW = dpred^T xf (the act real rows of dpred's ap columns, straight into the gradient tensor),
-    // db = its column sums, dxf = dpred W
-    if (mlp_head) {
-        if (!vjp) TRY(colsum(P(w.dpred), ap, act, Ma, hb.g));
-        // second layer: dW1 = dpred^T a, da = dpred W1 -> dz = da * SiLU'(z) (+ its column sums = db0); first layer:
-        // dW0 = dz^T xf, dxf = dz W0.  Padded rows / columns are zeros all the way.
-        TRY(wgrad(P(w.dpred), ap, ap, P(w.ha), Hp, Hp, Ma, F(w.dw_head)));
-        TRY((tgemm<E, false, true>(P(w.dpred), ap, P(w.w_head), Hp, Ma, Hp, ap, 1, EpiSiluBwd<E>{P(w.hz), P(w.hdz), F(w.db_hid), Hp}, s)));
-        TRY(wgrad(P(w.hdz), Hp, Hp, P(w.xf), D, D, Ma, F(w.dw_hid)));
-        TRY((tgemm<E, false, true>(P(w.hdz), Hp, P(w.w_hid), D, Ma, D, Hp, 1, EpiStore<E>{F(w.dxn), nullptr, nullptr, D}, s)));
-    } else {
-        TRY(wgrad(P(w.dpred), ap, act, P(w.xf), D, D, Ma, hw.g, hb.g));
-        TRY((tgemm<E, false, true>(P(w.dpred), ap, P(w.w_head), D, Ma, D, ap, 1, EpiStore<E>{F(w.dxn), nullptr, nullptr, D}, s)));
     }
-    TRY(ln_bwd(x_last, w.stf, lnfw.p, nullptr, F(w.dxa), P(w.layer[L - 1].dyo), Ma, lnfw.g, lnfb.g, lp[L - 1].f2b.g, resid_p,
-               (uint32_t)(4 * (L - 1) + 2)));
+    // the arguments of the same LayerNorm backward as the epilogue of the data gradient in front of it (fused_train_dgrad's which = 0:
+    // q|k|v, 2: FC1); dxn is never written (dropout at the site: the same (row, feature) hash, evaluated in the epilogue).
+    TrainLnBwd ln_epilogue(int rows, const float* x, size_t st, const float* gamma, float* dres, E* dxb, float* dgam, float* dbet,
+                           float* dbias, float p_site, uint32_t site, int skip_mod, int x_is_bf16) {
+        float* part = ln.next(fused_train_dgrad_blocks(rows), dgam, dbet, dbias);
+        return TrainLnBwd{x, (const float*)F(st), gamma, dres, dres, dxb, part, p_site, seed, site, skip_mod, x_is_bf16};
+    }
+    // head (compact rows): dW = dpred^T xf (the act real rows of dpred's ap columns, straight into the gradient tensor),
+    // db = its column sums, dxf = dpred W; then ln_f
+    int backward_head() {
+        if (mlp_head) {
+            if (!vjp) TRY(colsum(P(w.dpred), ap, act, Ma, par.hb.g, s));
+            // second layer: dW1 = dpred^T a, da = dpred W1 -> dz = da * SiLU'(z) (+ its column sums = db0); first layer:
+            // dW0 = dz^T xf, dxf = dz W0.  Padded rows / columns are zeros all the way.
+            TRY(wg.add(P(w.dpred), ap, ap, P(w.ha), Hp, Hp, Ma, F(w.dw_head)));
+            TRY((tgemm<E, false, true>(P(w.dpred), ap, P(w.w_head), Hp, Ma, Hp, ap, 1, EpiSiluBwd<E>{P(w.hz), P(w.hdz), F(w.db_hid), Hp}, s)));
+            TRY(wg.add(P(w.hdz), Hp, Hp, P(w.xf), D, D, Ma, F(w.dw_hid)));
+            TRY((tgemm<E, false, true>(P(w.hdz), Hp, P(w.w_hid), D, Ma, D, Hp, 1, EpiStore<E>{F(w.dxn), nullptr, nullptr, D}, s)));
+        } else {
+            TRY(wg.add(P(w.dpred), ap, act, P(w.xf), D, D, Ma, par.hw.g, par.hb.g));
+            TRY((tgemm<E, false, true>(P(w.dpred), ap, P(w.w_head), D, Ma, D, ap, 1, EpiStore<E>{F(w.dxn), nullptr, nullptr, D}, s)));
+        }
+        TRY(ln_bwd(F(w.layer[L - 1].x_out), w.stf, par.lnfw.p, nullptr, F(w.dxa), P(w.layer[L - 1].dyo), Ma, par.lnfw.g, par.lnfb.g,
+                   lp[L - 1].f2b.g, resid_p, (uint32_t)(4 * (L - 1) + 2)));
+        return BESO_OK;
+    }
     // (Measured and rejected, round 2: the chain of data gradients between two attention backwards as ONE tile kernel, the mirror
     // image of the tail-block forward -- parity-green, 209 us per launch against 164 us + gaps for the eight per-op launches it
     // replaces: 3.60 vs 3.43 ms per 1024-sample step.  DESIGN.md section 7.)
-    // (status of a fused.hip launch: BESO_OK or the error the caller reports)
-#define FUSED(call) do { const int st_ = (call); if (st_ != BESO_OK) { *err = hipGetLastError(); *err_line = __LINE__; return st_; } } while (0)
-    for (int l = L - 1; l >= 0; --l) {
+    int backward_layer(int l) {
         const TrainLayerWs& y = w.layer[l];
-        const float* x_in = l == 0 ? F(w.x0) : F(w.layer[l - 1].x_out);
-        const bool last = l == L - 1;
+        const float* x_in = layer_in(l);
+        const bool last = l == L - 1, first = l == 0;
         const int rows = last ? Ma : M;
         float* dres = last ? F(w.dxa) : F(w.dx);          // residual gradient of this layer's second half
         // FC2: dW2 = dyo^T g, dh = (dyo W2) * GELU'(h)
-        TRY(wgrad(P(y.dyo), D, D, P(y.g), D4, D4, rows, lp[l].f2w.g));
+        TRY(wg.add(P(y.dyo), D, D, P(y.g), D4, D4, rows, lp[l].f2w.g));
         E* dy_out = last ? P(w.dya) : P(w.dy);
+        const uint32_t site2 = (uint32_t)(4 * l + 1);     // dropout site behind LayerNorm-2's branch (the out-projection)
         float* slab = F(w.b1slab) + (size_t)l * fused_train_dgrad_blocks(M) * D4;       // FC1 bias sums per workgroup (use_dgrad)
-        if (use_dgrad) { b1_slabs[b1_n] = slab; b1_outs[b1_n] = lp[l].f1b.g; b1_blocks[b1_n] = fused_train_dgrad_blocks(rows); ++b1_n; }
-        if (use_mlp_bwd) {
-            // FC2 + GELU' -> FC1 -> LayerNorm-2 backward -> out-projection: one launch, dh and dym stay in LDS between the GEMMs
-            float* part = F(w.ln_part) + (size_t)ln_calls * lnb_grid * 3 * D;
-            lrt.nb[ln_calls] = fused_train_dgrad_blocks(rows);
-            lrt.c[ln_calls++] = LnRedCall{lp[l].ln2w.g, lp[l].ln2b.g, lp[l].pb.g};
-            const TrainLnBwd ln{F(y.x_mid), (const float*)F(y.st2), lp[l].ln2w.p, dres, dres, P(y.dym), part, resid_p, seed,
-                                (uint32_t)(4 * l + 1), 0, x16};
-            FUSED(fused_train_mlp_bwd(flay, ws + w.bimg, l, rows, P(y.dyo), P(y.h), P(y.dh), slab, dy_out, ln, s));
-        } else if (use_dgrad) {
-            // the same chain as three launches (shapes without the one-kernel form)
-            FUSED(fused_train_dgrad(flay, ws + w.bimg, l, 3, rows, P(y.dyo), nullptr, nullptr, P(y.h), P(y.dh), slab, s));
-            FUSED(dgrad_ln(l, 2, rows, P(y.dh), F(y.x_mid), y.st2, lp[l].ln2w.p, dres, P(y.dym), lp[l].ln2w.g, lp[l].ln2b.g, lp[l].pb.g,
-                           resid_p, (uint32_t)(4 * l + 1), 0, x16));
-            FUSED(fused_train_dgrad(flay, ws + w.bimg, l, 1, rows, P(y.dym), nullptr, dy_out, nullptr, nullptr, nullptr, s));
+        if (plan.use_dgrad) {
+            b1_slabs[b1_n] = slab; b1_outs[b1_n] = lp[l].f1b.g; b1_blocks[b1_n] = fused_train_dgrad_blocks(rows); ++b1_n;
+            const TrainLnBwd e = ln_epilogue(rows, F(y.x_mid), y.st2, lp[l].ln2w.p, dres, P(y.dym), lp[l].ln2w.g, lp[l].ln2b.g,
+                                             lp[l].pb.g, resid_p, site2, 0, plan.x16);
+            if (plan.use_mlp_bwd) {
+                // FC2 + GELU' -> FC1 -> LayerNorm-2 backward -> out-projection: one launch, dh and dym stay in LDS between the GEMMs
+                TRY_ST(fused_train_mlp_bwd(plan.lay, ws + w.bimg, l, rows, P(y.dyo), P(y.h), P(y.dh), slab, dy_out, e, s));
+            } else {
+                // the same chain as three launches (shapes without the one-kernel form)
+                TRY_ST(fused_train_dgrad(plan.lay, ws + w.bimg, l, 3, rows, P(y.dyo), nullptr, nullptr, P(y.h), P(y.dh), slab, s));
+                TRY_ST(fused_train_dgrad(plan.lay, ws + w.bimg, l, 2, rows, P(y.dh), nullptr, nullptr, nullptr, nullptr, nullptr, s, &e));
+                TRY_ST(fused_train_dgrad(plan.lay, ws + w.bimg, l, 1, rows, P(y.dym), nullptr, dy_out, nullptr, nullptr, nullptr, s));
+            }
         } else {
             // per-op: dh = (dyo W2) * GELU'(h) (+ db1), dxn2 = dh W1, LayerNorm-2 backward, dy = dym Wp
             TRY((tgemm<E, false, true>(P(y.dyo), D, P(y.w_fc2), D4, rows, D4, D, 1, EpiGeluBwd<E>{P(y.h), P(y.dh), lp[l].f1b.g, D4}, s)));
             TRY((tgemm<E, false, true>(P(y.dh), D4, P(y.w_fc1), D, rows, D, D4, 1, EpiStore<E>{F(w.dxn), nullptr, nullptr, D}, s)));
-            TRY(ln_bwd(F(y.x_mid), y.st2, lp[l].ln2w.p, dres, dres, P(y.dym), rows, lp[l].ln2w.g, lp[l].ln2b.g, lp[l].pb.g, resid_p,
-                       (uint32_t)(4 * l + 1)));
+            TRY(ln_bwd(F(y.x_mid), y.st2, lp[l].ln2w.p, dres, dres, P(y.dym), rows, lp[l].ln2w.g, lp[l].ln2b.g, lp[l].pb.g, resid_p, site2));
             TRY((tgemm<E, false, true>(P(y.dym), D, P(y.w_proj), D, rows, D, D, 1, EpiStore<E>{nullptr, dy_out, nullptr, D}, s)));
         }
         // FC1: dW1 = dh^T xn2; proj: dWp = dym^T y
-        TRY(wgrad(P(y.dh), D4, D4, P(y.xn2), D, D, rows, lp[l].f1w.g));
-        TRY(wgrad(P(y.dym), D, D, last ? P(w.ya) : P(y.y), D, D, rows, lp[l].pw.g));
+        TRY(wg.add(P(y.dh), D4, D4, P(y.xn2), D, D, rows, lp[l].f1w.g));
+        TRY(wg.add(P(y.dym), D, D, last ? P(w.ya) : P(y.y), D, D, rows, lp[l].pw.g));
         if (last) {
             // back to all token rows: dy and the residual gradient are zero off the action rows
-            const size_t n4 = (size_t)M * (D / 4);
-            hipLaunchKernelGGL(scatter_rows2_kernel<E>, dim3(gs_grid(n4)), dim3(256), 0, s, (const E*)P(w.dya), P(w.dy),
-                               (const float*)F(w.dxa), F(w.dx), M, t, T, G, D);
+            hipLaunchKernelGGL(scatter_rows2_kernel<E>, dim3(capped_grid((size_t)M * (D / 4), 4096)), dim3(256), 0, s, (const E*)P(w.dya),
+                               P(w.dy), (const float*)F(w.dxa), F(w.dx), M, t, T, G, D);
             TRY(hipGetLastError());
         }
-        // (hd >= 8: row_chunk16 fetches a head's row in 16-byte chunks clamped to its last eight columns; a head of four dims
-        //  has no such chunk inside its row and takes the VALU kernel)
-        if (attn_small && hd >= 8 && sizeof(E) == 2 && !(flags & BESO_TRAIN_PLAN_PER_OP)) {
-            const int n_pairs = batch * H;
-            hipLaunchKernelGGL(attn_mfma_bwd_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, s, (const uint16_t*)P(y.qkv),
-                               (const uint16_t*)P(w.dy), (uint16_t*)P(y.dqkv), n_pairs, T, D, H, hd, scale, attn_p, attn_ik, seed,
-                               (uint32_t)(4 * l));
-        } else if (attn_small) {
-#define ATT(TT) hipLaunchKernelGGL((attn_small_kernel<E, true, TT>), dim3(batch * H), dim3(64), 0, s, (const E*)P(y.qkv), \
-                                   (const E*)P(w.dy), P(y.dqkv), T, D, H, hd, scale, attn_p, attn_ik, seed, (uint32_t)(4 * l))
-            if (T <= 8) ATT(8); else if (T <= 12) ATT(12); else ATT(16);
-#undef ATT
-        } else
-            hipLaunchKernelGGL(attn_bwd_kernel<E>, dim3(batch * H), dim3(64), lds_b, s, (const E*)P(y.qkv), (const E*)P(w.dy),
-                               P(y.dqkv), T, D, H, hd, scale, attn_p, attn_ik, seed, (uint32_t)(4 * l));
-        TRY(hipGetLastError());
+        TRY(launch_attention<true>(l));
         // q/k/v: three weight gradients from the column blocks of dqkv, bias gradients, dxn1 = dqkv Wqkv
-        TRY(wgrad(P(y.dqkv), D3, D, P(y.xn1), D, D, M, lp[l].qw.g, lp[l].qb.g));
-        TRY(wgrad(P(y.dqkv) + D, D3, D, P(y.xn1), D, D, M, lp[l].kw.g, lp[l].kb.g));
-        TRY(wgrad(P(y.dqkv) + 2 * D, D3, D, P(y.xn1), D, D, M, lp[l].vw.g, lp[l].vb.g));
-        const bool first = l == 0;
-        if (use_dgrad) {
-            FUSED(dgrad_ln(l, 0, M, P(y.dqkv), x_in, y.st1, lp[l].ln1w.p, F(w.dx), first ? P(w.dx0b) : P(w.layer[l - 1].dyo),
-                           lp[l].ln1w.g, lp[l].ln1b.g, first ? nullptr : lp[l - 1].f2b.g, first ? embed_p : resid_p,
-                           first ? kEmbedSite : (uint32_t)(4 * (l - 1) + 2), first ? T : 0, first ? 0 : x16));
+        TRY(wg.add(P(y.dqkv), D3, D, P(y.xn1), D, D, M, lp[l].qw.g, lp[l].qb.g));
+        TRY(wg.add(P(y.dqkv) + D, D3, D, P(y.xn1), D, D, M, lp[l].kw.g, lp[l].kb.g));
+        TRY(wg.add(P(y.dqkv) + 2 * D, D3, D, P(y.xn1), D, D, M, lp[l].vw.g, lp[l].vb.g));
+        // LayerNorm-1 backward: into the previous layer's dyo with its FC2 dropout -- first layer: into dx0b with the embedding's
+        E* dxb = first ? P(w.dx0b) : P(w.layer[l - 1].dyo);
+        float* dbias = first ? nullptr : lp[l - 1].f2b.g;
+        const uint32_t site = first ? kEmbedSite : (uint32_t)(4 * (l - 1) + 2);
+        const float p_site = first ? embed_p : resid_p; const int skip_mod = first ? T : 0;
+        if (plan.use_dgrad) {
+            const TrainLnBwd e = ln_epilogue(M, x_in, y.st1, lp[l].ln1w.p, F(w.dx), dxb, lp[l].ln1w.g, lp[l].ln1b.g, dbias, p_site, site, skip_mod,
+                                             first ? 0 : plan.x16);
+            TRY_ST(fused_train_dgrad(plan.lay, ws + w.bimg, l, 0, M, P(y.dqkv), nullptr, nullptr, nullptr, nullptr, nullptr, s, &e));
         } else {
             TRY((tgemm<E, false, true>(P(y.dqkv), D3, P(y.w_qkv), D, M, D, D3, 1, EpiStore<E>{F(w.dxn), nullptr, nullptr, D}, s)));
-            TRY(ln_bwd(x_in, y.st1, lp[l].ln1w.p, F(w.dx), F(w.dx), first ? P(w.dx0b) : P(w.layer[l - 1].dyo), M, lp[l].ln1w.g,
-                       lp[l].ln1b.g, first ? nullptr : lp[l - 1].f2b.g, first ? embed_p : resid_p,
-                       first ? kEmbedSite : (uint32_t)(4 * (l - 1) + 2), first ? T : 0));
+            TRY(ln_bwd(x_in, y.st1, lp[l].ln1w.p, F(w.dx), F(w.dx), dxb, M, lp[l].ln1w.g, lp[l].ln1b.g, dbias, p_site, site, skip_mod));
         }
-        if (early_stream && l == train_early_layer(c) && l > 0) {
-            // the gradients of layers l .. L-1 and ln_f are complete once their weight gradients and LayerNorm sums
-            // have run: do those now and order `early_stream` behind this point (the C1 exchange of that range can
-            // start under the backward of layers l-1 .. 0)
-            TRY(flush_group());
-            if (flush_b1() != BESO_OK) { *err = hipGetLastError(); *err_line = __LINE__; return BESO_ERR_HIP; }
-            hipLaunchKernelGGL(ln_reduce_kernel, dim3((D + 63) / 64, 3, ln_calls), dim3(256), 0, s, (const float*)F(w.ln_part),
-                               lrt, lnb_grid, D, 0);
-            TRY(hipGetLastError());
-            ln_reduced = ln_calls;
-            hipEvent_t ev = nullptr;
-            TRY(step_event(kEvEarly, &ev));
-            TRY(hipEventRecord(ev, s));
-            TRY(hipStreamWaitEvent(early_stream, ev, 0));
-        }
+        return BESO_OK;
     }
-#undef FUSED
-    if (vjp) {
-        // F(w.dx) holds the fp32 gradient of x0 (layer 0's LayerNorm-1 backward): onto the action input
-        hipLaunchKernelGGL(vjp_input_kernel, dim3(batch), dim3(256), 0, s, (const float*)F(w.dx), actw.p, sigma, vjp->cot,
-                           vjp->x_grad, vjp->dot, t, T, G, D, act, c->sigma_data);
+    // the gradients of layers l .. L-1 and ln_f are complete once their weight gradients and LayerNorm sums have run: do those now and
+    // order `early_stream` behind this point (the C1 exchange of that range can start under the backward of layers l-1 .. 0)
+    int early_flush() {
+        TRY(wg.flush());
+        TRY_ST(fused_train_bias_reduce(b1_slabs, b1_outs, b1_blocks, b1_n, D4, s));
+        b1_n = 0;
+        TRY(ln.reduce(s));
+        hipEvent_t ev = nullptr;
+        TRY(record_event(kEvEarly, s, &ev));
+        TRY(hipStreamWaitEvent(early_stream, ev, 0));
+        return BESO_OK;
+    }
+    int finish() {
+        if (vjp) {
+            // F(w.dx) holds the fp32 gradient of x0 (layer 0's LayerNorm-1 backward): onto the action input
+            hipLaunchKernelGGL(vjp_input_kernel, dim3(batch), dim3(256), 0, s, (const float*)F(w.dx), par.actw.p, sigma, vjp->cot,
+                               vjp->x_grad, vjp->dot, t, T, G, D, act, c->sigma_data);
+            TRY(hipGetLastError());
+            return BESO_OK;
+        }
+        // embeddings: dWcat[Ke][D] = Xemb^T dx0, routed to pos_emb / tok_emb / action_emb / sigma_emb after the launch
+        TRY(wg.add(P(w.xemb), Ke, Ke, P(w.dx0b), D, D, M, F(w.dw_cat)));
+        // The reductions of the FC1-bias slabs and of the LayerNorm / bias partial sums read what the data-gradient kernels wrote
+        // and write gradient tensors of their own: nothing ties them to the grouped weight-gradient launch, which leaves 38 of the
+        // 256 CUs idle (218 panel tiles) -- they run BESIDE it on the library's side stream (three launches of 12 + 12 + 24 us off the
+        // step's chain; a dependent launch costs ~5 us whatever it does: tools/microbench/launch_chain).
+        hipEvent_t ev_sf = nullptr, ev_sj = nullptr;
+        hipStream_t rs = s;                               // stream of the partial-sum reductions
+        if (plan.panel_w) {
+            TRY(step_side_stream(&rs));
+            TRY(record_event(kEvSideFork, s, &ev_sf));
+            TRY(hipStreamWaitEvent(rs, ev_sf, 0));
+        } else TRY(wg.flush());
+        TRY_ST(fused_train_bias_reduce(b1_slabs, b1_outs, b1_blocks, b1_n, D4, rs));
+        b1_n = 0;
+        TRY(ln.reduce(rs));
+        if (plan.panel_w) {
+            TRY(record_event(kEvSideJoin, rs, &ev_sj));
+            TRY(wg.flush());
+            TRY(hipStreamWaitEvent(s, ev_sj, 0));
+        }
+        if (mlp_head) {
+            TRY(hipMemcpy2DAsync(par.hw.g, sizeof(float) * Hh, ws + w.dw_head, sizeof(float) * Hp, sizeof(float) * Hh, act,
+                                 hipMemcpyDeviceToDevice, s));                                    // [act][Hp] -> [act][100]
+            TRY(hipMemcpyAsync(par.h0w.g, ws + w.dw_hid, sizeof(float) * (size_t)Hh * D, hipMemcpyDeviceToDevice, s));
+            TRY(hipMemcpyAsync(par.h0b.g, ws + w.db_hid, sizeof(float) * Hh, hipMemcpyDeviceToDevice, s));
+        }
+        hipLaunchKernelGGL(scatter_emb_kernel, dim3(64), dim3(256), 0, s, (const float*)F(w.dw_cat), par.pos.g, par.tokw.g, par.tokb.g,
+                           par.sigw.g, par.sigb.g, par.actw.g, par.actb.g, D, obs, act, seq);
         TRY(hipGetLastError());
         return BESO_OK;
     }
-    // embeddings: dWcat[Ke][D] = Xemb^T dx0, routed to pos_emb / tok_emb / action_emb / sigma_emb after the launch
-    TRY(wgrad(P(w.xemb), Ke, Ke, P(w.dx0b), D, D, M, F(w.dw_cat)));
-    // The reductions of the FC1-bias slabs and of the LayerNorm / bias partial sums read what the data-gradient kernels wrote
-    // and write gradient tensors of their own: nothing ties them to the grouped weight-gradient launch, which leaves 38 of the
-    // 256 CUs idle (218 panel tiles) -- they run BESIDE it on the library's side stream (three launches of 12 + 12 + 24 us off the
-    // step's chain; a dependent launch costs ~5 us whatever it does: tools/microbench/launch_chain).
-    hipEvent_t ev_sf = nullptr, ev_sj = nullptr;
-    if (panel_w) {
-        TRY(step_side_stream(&rs));
-        TRY(step_event(kEvSideFork, &ev_sf));
-        TRY(step_event(kEvSideJoin, &ev_sj));
-        TRY(hipEventRecord(ev_sf, s));
-        TRY(hipStreamWaitEvent(rs, ev_sf, 0));
-    } else TRY(flush_group());
-    if (flush_b1() != BESO_OK) { *err = hipGetLastError(); *err_line = __LINE__; return BESO_ERR_HIP; }
-    hipLaunchKernelGGL(ln_reduce_kernel, dim3((D + 63) / 64, 3, ln_calls - ln_reduced), dim3(256), 0, rs,
-                       (const float*)F(w.ln_part), lrt, lnb_grid, D, ln_reduced);
-    TRY(hipGetLastError());
-    if (panel_w) {
-        TRY(hipEventRecord(ev_sj, rs));
-        TRY(flush_group());
-        TRY(hipStreamWaitEvent(s, ev_sj, 0));
-        rs = s;
+};
+
+// checks the call (train_validate's status first, then BESO_ERR_BAD_ARG, then the workspace) and runs it in its precision
+static int run_train_step(TrainCall a, int n_params, size_t workspace_bytes) {
+    const beso_config* c = a.c;
+    int st = train_validate(c, a.batch, a.t);
+    if (st != BESO_OK) return st;
+    if (a.precision != BESO_PREC_BF16 && a.precision != BESO_PREC_FP32) return BESO_ERR_BAD_ARG;
+    if (!a.p || !a.state || !a.action || !a.sigma || !a.ws) return BESO_ERR_BAD_ARG;
+    if (a.vjp ? (!a.vjp->cot || !a.vjp->denoised || !a.vjp->x_grad) : (!a.gflat || !a.noise || !a.loss_out)) return BESO_ERR_BAD_ARG;
+    if (c->goal_seq_len > 0 && !a.goal) return BESO_ERR_BAD_ARG;
+    if (n_params != 3 + 16 * c->n_layers + 6 + (c->linear_output ? 2 : 4)) return BESO_ERR_BAD_ARG;
+    for (int i = 0; i < n_params; ++i) if (!a.p[i]) return BESO_ERR_BAD_ARG;
+    if (a.flags & ~((a.vjp ? 0 : BESO_TRAIN_LAST_ACTION_ONLY) | BESO_TRAIN_PLAN_PER_OP | BESO_TRAIN_PLAN_TILES)) return BESO_ERR_BAD_ARG;
+    if (!(a.attn_p >= 0.f && a.attn_p < 1.f && a.resid_p >= 0.f && a.resid_p < 1.f && a.embed_p >= 0.f && a.embed_p < 1.f &&
+          a.goal_p >= 0.f && a.goal_p <= 1.f))
+        return BESO_ERR_BAD_ARG;
+    TrainWs w;
+    make_train_ws(c, a.batch, a.t, a.precision, &w);
+    if (workspace_bytes < w.total) return BESO_ERR_WORKSPACE;
+    if (a.vjp) {
+        // (the step's loss slot: the target buffer, unused in this mode; the gradient pointers: the dw_cat slab, see VjpIo)
+        a.loss_out = (float*)(a.ws + w.target);
+        a.gflat = (float*)(a.ws + w.dw_cat);
+        (void)hipGetLastError();
     }
-    if (mlp_head) {
-        TRY(hipMemcpy2DAsync(hw.g, sizeof(float) * Hh, ws + w.dw_head, sizeof(float) * Hp, sizeof(float) * Hh, act,
-                             hipMemcpyDeviceToDevice, s));                                    // [act][Hp] -> [act][100]
-        TRY(hipMemcpyAsync(h0w.g, ws + w.dw_hid, sizeof(float) * (size_t)Hh * D, hipMemcpyDeviceToDevice, s));
-        TRY(hipMemcpyAsync(h0b.g, ws + w.db_hid, sizeof(float) * Hh, hipMemcpyDeviceToDevice, s));
-    }
-    hipLaunchKernelGGL(scatter_emb_kernel, dim3(64), dim3(256), 0, s, (const float*)F(w.dw_cat), pos.g, tokw.g, tokb.g, sigw.g,
-                       sigb.g, actw.g, actb.g, D, obs, act, seq);
-    TRY(hipGetLastError());
-    return BESO_OK;
+    if (a.precision == BESO_PREC_FP32) return TrainStep<float>(a, w).run();
+    return TrainStep<uint16_t>(a, w).run();
 }
 
 int train_loss_grad(const beso_config* c, const float* const* params, int n_params, float* grads_flat, int precision,
@@ -2682,63 +2730,25 @@ int train_loss_grad(const beso_config* c, const float* const* params, int n_para
                     float goal_drop, uint32_t seed, float grad_scale,
                     void* workspace, size_t workspace_bytes, hipStream_t s, hipStream_t early_stream, hipStream_t loss_stream,
                     hipError_t* err, int* err_line) {
-    int st = train_validate(c, batch, t);
-    if (st != BESO_OK) return st;
-    if (precision != BESO_PREC_BF16 && precision != BESO_PREC_FP32) return BESO_ERR_BAD_ARG;
-    if (!params || !grads_flat || !state || !action || !noise || !sigma || !loss_out || !workspace) return BESO_ERR_BAD_ARG;
-    if (c->goal_seq_len > 0 && !goal) return BESO_ERR_BAD_ARG;
-    if (n_params != 3 + 16 * c->n_layers + 6 + (c->linear_output ? 2 : 4)) return BESO_ERR_BAD_ARG;
-    for (int i = 0; i < n_params; ++i) if (!params[i]) return BESO_ERR_BAD_ARG;
-    if (flags & ~(BESO_TRAIN_LAST_ACTION_ONLY | BESO_TRAIN_PLAN_PER_OP | BESO_TRAIN_PLAN_TILES)) return BESO_ERR_BAD_ARG;
-    if (!(attn_pdrop >= 0.f && attn_pdrop < 1.f && resid_pdrop >= 0.f && resid_pdrop < 1.f && embed_pdrop >= 0.f &&
-          embed_pdrop < 1.f && goal_drop >= 0.f && goal_drop <= 1.f))
-        return BESO_ERR_BAD_ARG;
-    TrainWs w;
-    make_train_ws(c, batch, t, precision, &w);
-    if (workspace_bytes < w.total) return BESO_ERR_WORKSPACE;
-    if (precision == BESO_PREC_FP32)
-        return loss_grad_e<float>(c, params, grads_flat, precision, state, action, goal, noise, sigma, loss_out, batch, t,
-                                  flags, embed_pdrop, attn_pdrop, resid_pdrop, goal_drop, seed, grad_scale,
-                                  (char*)workspace, w, s, early_stream, loss_stream, err, err_line);
-    return loss_grad_e<uint16_t>(c, params, grads_flat, precision, state, action, goal, noise, sigma, loss_out, batch, t,
-                                 flags, embed_pdrop, attn_pdrop, resid_pdrop, goal_drop, seed, grad_scale,
-                                 (char*)workspace, w, s, early_stream, loss_stream, err, err_line);
+    return run_train_step(TrainCall{c, params, grads_flat, precision, state, action, goal, noise, sigma, loss_out, batch, t, flags,
+                                    embed_pdrop, attn_pdrop, resid_pdrop, goal_drop, seed, grad_scale, (char*)workspace, s, early_stream,
+                                    loss_stream, err, err_line, nullptr}, n_params, workspace_bytes);
 }
 
 int train_denoise_vjp(const beso_config* c, const float* const* params, int n_params, int precision, const float* state,
                       const float* x, const float* goal, const float* sigma, const float* cot, float* denoised, float* x_grad,
                       float* dot, int batch, int t, int flags, void* workspace, size_t workspace_bytes, hipStream_t s,
                       hipError_t* err, int* err_line) {
-    int st = train_validate(c, batch, t);
-    if (st != BESO_OK) return st;
-    if (precision != BESO_PREC_BF16 && precision != BESO_PREC_FP32) return BESO_ERR_BAD_ARG;
-    if (!params || !state || !x || !sigma || !cot || !denoised || !x_grad || !workspace) return BESO_ERR_BAD_ARG;
-    if (c->goal_seq_len > 0 && !goal) return BESO_ERR_BAD_ARG;
-    if (n_params != 3 + 16 * c->n_layers + 6 + (c->linear_output ? 2 : 4)) return BESO_ERR_BAD_ARG;
-    for (int i = 0; i < n_params; ++i) if (!params[i]) return BESO_ERR_BAD_ARG;
-    if (flags & ~(BESO_TRAIN_PLAN_PER_OP | BESO_TRAIN_PLAN_TILES)) return BESO_ERR_BAD_ARG;
-    TrainWs w;
-    make_train_ws(c, batch, t, precision, &w);
-    if (workspace_bytes < w.total) return BESO_ERR_WORKSPACE;
-    char* ws = (char*)workspace;
-    // (the step's loss slot: the target buffer, unused in this mode; the gradient pointers: the dw_cat slab, see VjpIo)
-    float* loss_slot = (float*)(ws + w.target);
-    float* scratch = (float*)(ws + w.dw_cat);
     const VjpIo io{cot, denoised, x_grad, dot};
-    (void)hipGetLastError();
-    if (precision == BESO_PREC_FP32)
-        return loss_grad_e<float>(c, params, scratch, precision, state, x, goal, nullptr, sigma, loss_slot, batch, t, flags,
-                                  0.f, 0.f, 0.f, 0.f, 0u, 1.f, ws, w, s, nullptr, nullptr, err, err_line, &io);
-    return loss_grad_e<uint16_t>(c, params, scratch, precision, state, x, goal, nullptr, sigma, loss_slot, batch, t, flags,
-                                 0.f, 0.f, 0.f, 0.f, 0u, 1.f, ws, w, s, nullptr, nullptr, err, err_line, &io);
+    return run_train_step(TrainCall{c, params, nullptr, precision, state, x, goal, nullptr, sigma, nullptr, batch, t, flags, 0.f, 0.f,
+                                    0.f, 0.f, 0u, 1.f, (char*)workspace, s, nullptr, nullptr, err, err_line, &io}, n_params, workspace_bytes);
 }
 
 int train_goal_mask(float* mask, size_t n, float goal_drop, uint32_t seed, hipStream_t s, hipError_t* err, int* err_line) {
     if (!mask || !(goal_drop >= 0.f && goal_drop <= 1.f)) return BESO_ERR_BAD_ARG;
     if (n == 0) return BESO_OK;
-    int grid = (int)((n + 255) / 256); if (grid > 2048) grid = 2048;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(goal_mask_kernel, dim3(grid), dim3(256), 0, s, mask, n, goal_drop, seed);
+    hipLaunchKernelGGL(goal_mask_kernel, dim3(capped_grid(n, 2048)), dim3(256), 0, s, mask, n, goal_drop, seed);
     TRY(hipGetLastError());
     return BESO_OK;
 }
@@ -2760,19 +2770,8 @@ int train_debug_gemm(int precision, int a_kslow, int b_kslow, const void* A, int
         t.p[0] = GProb{A, B, C, nullptr, lda, ldb, M, N, 0, orient, K, 0u};
         if (splits < 1) splits = 1;
         float* slab = C + (size_t)round_up(M * N, 4);
-        (void)hipGetLastError();
-        if (W == 2) {
-            static LdsAttr attr;
-            TRY(ensure_lds(wgrad_panel_group_kernel<2>, wgrad_panel_lds(2), &attr));
-            hipLaunchKernelGGL(wgrad_panel_group_kernel<2>, dim3(tiles * splits), dim3(kGT), wgrad_panel_lds(2), s, t, tiles, splits, slab,
-                               (size_t)round_up(M * N, 4));
-        } else {
-            static LdsAttr attr;
-            TRY(ensure_lds(wgrad_panel_group_kernel<3>, wgrad_panel_lds(3), &attr));
-            hipLaunchKernelGGL(wgrad_panel_group_kernel<3>, dim3(tiles * splits), dim3(kGT), wgrad_panel_lds(3), s, t, tiles, splits, slab,
-                               (size_t)round_up(M * N, 4));
-        }
-        TRY(hipGetLastError());
+        const size_t stride = (size_t)round_up(M * N, 4);
+        TRY(W == 2 ? launch_panel_group<2>(t, tiles, splits, slab, stride, s) : launch_panel_group<3>(t, tiles, splits, slab, stride, s));
         if (splits > 1) {
             hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((M * N + 1023) / 1024), dim3(256), 0, s, t, (const float*)slab,
                                (size_t)round_up(M * N, 4), splits, (uint32_t)(M * N));
