@@ -25,6 +25,9 @@ SOLVER_IDS = {"dpm_2": 0, "dpm_2_ancestral": 1, "dpmpp_2s": 2, "dpmpp_2s_ancestr
 SAMPLERS = {**{k: ("beso_sample", v) for k, v in SAMPLER_IDS.items()}, "euler_ancestral": ("beso_sample_ancestral", None),
             **{k: ("beso_sample_solver", v) for k, v in SOLVER_IDS.items()}}
 GOAL_RANDOM, GOAL_TAIL, GOAL_SEQ_END = 0, 1, 2
+# beso_dropout_mask (include/beso_hip.h BESO_DROP_*): which nn.Dropout of the network
+DROP_EMBED, DROP_ATTN, DROP_PROJ, DROP_MLP = 0, 1, 2, 3
+DROP_KINDS = {"embed": DROP_EMBED, "attn": DROP_ATTN, "proj": DROP_PROJ, "mlp": DROP_MLP}
 STEP_DDIM, STEP_EULER, STEP_HEUN_PREDICT, STEP_HEUN_CORRECT = 0, 1, 2, 3
 SITES = {"off": 0, "gemm_qkv": 1, "gemm_proj": 2, "gemm_fc1": 3, "gemm_fc2": 4, "attention": 5,
          "layernorm": 6, "embed": 7, "head": 8, "forward": 9, "fused_layer": 10, "small": 11}
@@ -35,7 +38,8 @@ EXPORTS = ["beso_version", "beso_status_string", "beso_last_error", "beso_num_pa
            "beso_profile_enable", "beso_profile_read", "beso_adam_step",
            "beso_train_workspace_bytes", "beso_grad_floats", "beso_loss_grad", "beso_gather_windows",
            "beso_loss_grad_overlap", "beso_grad_early_range", "beso_sample_ancestral", "beso_goal_mask",
-           "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp", "beso_sample_solver"]
+           "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp", "beso_sample_solver",
+           "beso_dropout_mask"]
 # include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
 DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm"]
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
@@ -122,6 +126,9 @@ def load() -> C.CDLL:
                                            f32, f32, C.c_uint, f32, vp, sz, vp]
             lib.beso_goal_mask.restype = i32
             lib.beso_goal_mask.argtypes = [vp, i32, i32, i32, f32, C.c_uint, vp]
+            if hasattr(lib, "beso_dropout_mask") or not os.environ.get("BESO_HIP_LIB"):
+                lib.beso_dropout_mask.restype = i32
+                lib.beso_dropout_mask.argtypes = [cfgp, vp, i32, i32, i32, i32, f32, C.c_uint, vp]
             if hasattr(lib, "beso_loss_grad_overlap") or not os.environ.get("BESO_HIP_LIB"):
                 lib.beso_loss_grad_overlap.restype = i32
                 lib.beso_loss_grad_overlap.argtypes = lib.beso_loss_grad.argtypes + [vp]

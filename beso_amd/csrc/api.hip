@@ -825,6 +825,15 @@ int beso_goal_mask(float* mask, int batch, int goal_seq_len, int obs_dim, float 
     return st;
 }
 
+int beso_dropout_mask(const beso_config* cfg, float* scale, int kind, int layer, int batch, int t, float p, unsigned int seed,
+                      void* stream) {
+    hipError_t e = hipSuccess;
+    int line = 0;
+    int st = train_dropout_mask(cfg, scale, kind, layer, batch, t, p, seed, (hipStream_t)stream, &e, &line);
+    if (st == BESO_ERR_HIP) snprintf(g_last_error, sizeof(g_last_error), "%s (%d) at train.hip:%d", hipGetErrorName(e), (int)e, line);
+    return st;
+}
+
 int beso_grad_early_range(const beso_config* cfg, size_t* begin, size_t* end) {
     if (!cfg || !begin || !end) return BESO_ERR_BAD_ARG;
     int st = train_validate(cfg, 1, 1);

@@ -223,6 +223,28 @@ __device__ __forceinline__ float drop_scale(uint32_t seed, uint32_t site, size_t
     return ((float)(h >> 8) * (1.0f / 16777216.0f)) >= p ? inv_keep : 0.f;
 }
 
+// Sites and element counters of the training dropouts, in one place for the kernels that apply a mask (train.hip, the one-launch
+// training forward of fused.hip), the backward kernels that recompute it and the exporter (dropout_mask_kernel):
+//   attention probabilities of layer l   site 4 l       counter ((b H + h) T + i) T + j   (query i, key j: the causally masked
+//                                                       pairs own counters too, nothing consumes them)
+//   out-projection output of layer l     site 4 l + 1   counter row D + f
+//   MLP output of layer l                site 4 l + 2   counter row D + f
+//   embeddings                           kEmbedSite     counter row D + f, the sigma token's row (row % T == 0) has no dropout
+// row = b T + token, the natural token row -- except behind the LAST layer's attention, where only the action tokens are
+// evaluated and row = b t + i counts those compact rows (drop_action_row).
+constexpr uint32_t kEmbedSite = 4 * 32 + 16;             // (4 kMaxLayers + 16: past every layer site)
+constexpr uint32_t kGoalSite = 4 * 32 + 17;              // DiffusionGPT.mask_cond: elementwise Bernoulli over goals [B,G,obs]
+__host__ __device__ constexpr uint32_t drop_site_attn(int l) { return (uint32_t)(4 * l); }
+__host__ __device__ constexpr uint32_t drop_site_proj(int l) { return (uint32_t)(4 * l + 1); }
+__host__ __device__ constexpr uint32_t drop_site_mlp(int l) { return (uint32_t)(4 * l + 2); }
+__host__ __device__ constexpr size_t drop_idx_attn(size_t pair, int T, int i, int j) { return (pair * T + i) * T + j; }
+__host__ __device__ constexpr size_t drop_idx_row(size_t row, int D, int f) { return row * D + f; }
+// compact action row b t + i of token `tok` of sample b (tokens: sigma, G goals, then state / action alternating), -1 for the others
+__host__ __device__ constexpr long long drop_action_row(long long b, int tok, int t, int G) {
+    const int k = tok - (G + 2);
+    return k >= 0 && (k & 1) == 0 ? b * t + (k >> 1) : -1;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -259,6 +281,7 @@ struct LayerOff {
 };
 
 constexpr int kMaxLayers = 32;
+static_assert(kEmbedSite == 4 * kMaxLayers + 16 && kGoalSite == kEmbedSite + 1, "the embedding / goal sites lie past every layer site");
 
 struct Layout {
     int D, H, hd, L, G, W, obs, act, seq_size, linear_output;

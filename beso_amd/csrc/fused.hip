@@ -970,7 +970,7 @@ __device__ __forceinline__ void resid_dropout_add(Tile<RPW>& T, const float* __r
             if (rx >= 0) xv = *(const f32x4*)(x + (size_t)rx * D + f0);
             if (rm >= 0) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) T.acc[i][t][j] *= drop_scale(seed, site, (size_t)rm * D + f0 + j, p, inv_keep);
+                for (int j = 0; j < 4; ++j) T.acc[i][t][j] *= drop_scale(seed, site, drop_idx_row((size_t)rm, D, f0) + j, p, inv_keep);
             }
             T.acc[i][t] += xv;
         }
@@ -2038,7 +2038,7 @@ __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsig
     auto drop4 = [&](float (&e)[4], int rh, int n, int g) {
         if constexpr (AX::on) {
             if (ax.p > 0.f) {
-                const size_t base = (((size_t)(ax.s0 + w) * ax.H + rh) * Tn + n) * Tn + 4 * g;
+                const size_t base = drop_idx_attn((size_t)(ax.s0 + w) * ax.H + rh, Tn, n, 4 * g);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) e[r] *= drop_scale(ax.seed, ax.site, base + r, ax.p, ax.inv_keep);
             }
@@ -3451,13 +3451,13 @@ __global__ __launch_bounds__(512, 2) void train_fwd_kernel(const char* __restric
         layernorm_to_lds<RPW, KS, kWaves, !RD, NTA, 0, LnTrain>(T, xnT, red, d.D, w, lane, (const float*)(lw + d.o_bproj), st, 0, lx1);
         if constexpr (RD) set_bias_rows<RPW, NTP>(T, (const float*)(lw + d.o_bproj), w, lane);
         const AttnTrain ax{(uint16_t*)(wl + a.qkv), ybuf, rows_all, rows_tail, d.D, s0, d.H, a.p_attn, inv_keep, a.seed,
-                           (uint32_t)(4 * l)};
+                           drop_site_attn(l)};
         attn_phase<RPW, KS, HG, NTP, NTA, 0, AttnTrain>(T, xnT, lds + L.u, (const u32x4*)(lw + d.o_wqkv),
                                                         (const float*)(lw + d.o_bqkv), (const u32x4*)(lw + d.o_wproj), d.Hv, d.hd,
                                                         Tn, n_samples, w, lane, tb, qE, qO, st, ax);
         if constexpr (RD)
             resid_dropout_add<RPW, NTP>(T, l == 0 ? a.x0 : (const float*)(wl - a.stride + a.x_out), d.D, rows_all, rows_tail,
-                                        a.p_resid, inv_keep_r, a.seed, (uint32_t)(4 * l + 1), w, lane);
+                                        a.p_resid, inv_keep_r, a.seed, drop_site_proj(l), w, lane);
         // (the first FC1 weight fragments are requested BEFORE the kept x_mid leaves: loads issued behind a burst of stores wait
         //  for the stores' acknowledgements)
         u32x4 a1r[PF1][kChunkTiles / kWaves];
@@ -3473,7 +3473,7 @@ __global__ __launch_bounds__(512, 2) void train_fwd_kernel(const char* __restric
                                                        (const u32x4*)(lw + d.o_w2), d.HT, d.KS2p, w, lane, a1r, st, mx);
         if constexpr (RD)
             resid_dropout_add<RPW, NTP>(T, (const float*)(wl + a.x_mid), d.D, rows_tail, rows_tail, a.p_resid, inv_keep_r, a.seed,
-                                        (uint32_t)(4 * l + 2), w, lane);
+                                        drop_site_mlp(l), w, lane);
         // (the last layer's x_out -- the compact action rows -- stays fp32: the final LayerNorm and the head continue on it)
         if (!RD && a.x_bf16 && l + 1 < d.L) store_x_rows_bf16<RPW, NTP>(T, (uint16_t*)(wl + a.x_out), d.D, rows_tail, w, lane);
         else store_x_rows<RPW, NTP>(T, (float*)(wl + a.x_out), d.D, rows_tail, w, lane);

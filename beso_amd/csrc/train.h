@@ -17,6 +17,8 @@ int    train_denoise_vjp(const beso_config* c, const float* const* params, int n
                          float* dot, int batch, int t, int flags, void* workspace, size_t workspace_bytes, hipStream_t s,
                          hipError_t* err, int* err_line);
 int    train_goal_mask(float* mask, size_t n, float goal_drop, uint32_t seed, hipStream_t s, hipError_t* err, int* err_line);
+int    train_dropout_mask(const beso_config* c, float* scale, int kind, int layer, int batch, int t, float p, uint32_t seed,
+                          hipStream_t s, hipError_t* err, int* err_line);
 int    train_early_layer(const beso_config* c);
 void   train_early_range(const beso_config* c, size_t* begin, size_t* end);
 #if BESO_DEV_API

@@ -31,8 +31,7 @@ namespace {
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-constexpr uint32_t kEmbedSite = 4 * kMaxLayers + 16;     // dropout site of the embeddings (layer sites are 4 l + {0, 1, 2})
-constexpr uint32_t kGoalSite = 4 * kMaxLayers + 17;      // DiffusionGPT.mask_cond: elementwise Bernoulli over goals [B,G,obs]
+// (the dropout sites and element counters: common.h, drop_site_* / drop_idx_*)
 
 // mask_cond (score_gpts.py:360-371): cond * (1 - bernoulli(p)), elementwise over [B, G, obs], NO rescaling of the kept
 // elements.  keep(b, g, c) = 1 iff the hash-uniform of element ((b*G + g)*obs + c) is >= p.
@@ -41,6 +40,37 @@ __device__ __forceinline__ float goal_keep(uint32_t seed, size_t idx, float p) {
 __global__ void goal_mask_kernel(float* __restrict__ mask, size_t n, float p, uint32_t seed) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         mask[i] = p > 0.f ? goal_keep(seed, i, p) : 1.f;
+}
+
+// The keep-scales of one dropout site as the step applies them (beso_dropout_mask), in the reference's layout: n elements of
+// [B, H, T, T] (rows_D = 0: attention, the counter IS the linear index) or of [B T, D] (rows_D = D, D % 4 == 0: a chunk of
+// four lies in one token row).  skip_sigma: the embedding site, whose sigma-token rows carry no dropout; compact: the last
+// layer's proj / MLP sites, whose counters run over the compact action rows -- the rows that layer does not evaluate get 1.
+// Grid-stride over 16-byte chunks; the last chunk of an attention mask may be partial (n % 4 != 0) and is stored by element.
+__global__ __launch_bounds__(256) void dropout_mask_kernel(float* __restrict__ scale, size_t n, int rows_D, int T, int t, int G,
+                                                           int skip_sigma, int compact, float p, float inv_keep, uint32_t seed,
+                                                           uint32_t site) {
+    const size_t chunks = (n + 3) / 4;
+    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = 4 * c;
+        size_t idx = i;
+        bool drawn = p > 0.f;
+        if (rows_D > 0) {
+            const size_t row = i / (size_t)rows_D;
+            const int f = (int)(i - row * (size_t)rows_D), tok = (int)(row % (size_t)T);
+            if (skip_sigma && tok == 0) drawn = false;
+            if (compact) {
+                const long long ar = drop_action_row((long long)(row / (size_t)T), tok, t, G);
+                if (ar < 0) drawn = false;
+                idx = drop_idx_row((size_t)(ar < 0 ? 0 : ar), rows_D, f);
+            } else idx = drop_idx_row(row, rows_D, f);
+        }
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = drawn ? drop_scale(seed, site, idx + j, p, inv_keep) : 1.f;
+        if (i + 4 <= n) *(f32x4*)(scale + i) = v;
+        else for (int j = 0; i + j < n; ++j) scale[i + j] = v[j];
+    }
 }
 
 // GELU and its derivative (nn.GELU(), score_gpts.py:107): exact erf / exp in the fp32 mode, the fitted polynomial of
@@ -891,7 +921,7 @@ __global__ void train_embed_kernel(const float* __restrict__ state, const float*
             for (int c = 0; c < len; ++c) acc = fmaf(in_vec[c], w[c], acc);
             v = acc + (kind == 1 ? tok_b[d] : act_b[d]) + pos[(size_t)posrow * D + d];
             // self.drop(tok_emb(..) + pos) / self.drop(action_emb(..) + pos): score_gpts.py:321-325 (the sigma token has none)
-            if (p_drop > 0.f) v *= drop_scale(seed, kEmbedSite, (size_t)row * D + d, p_drop, 1.0f / (1.0f - p_drop));
+            if (p_drop > 0.f) v *= drop_scale(seed, kEmbedSite, drop_idx_row((size_t)row, D, d), p_drop, 1.0f / (1.0f - p_drop));
         }
         x[(size_t)row * D + d] = v;
     }
@@ -1621,7 +1651,7 @@ __global__ __launch_bounds__(256) void attn_mfma_bwd_kernel(const uint16_t* __re
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = 4 * g + r;
-            ks[r] = (p > 0.f && x < T && j <= x) ? drop_scale(seed, site, ((size_t)pair * T + x) * T + j, p, inv_keep) : 1.f;
+            ks[r] = (p > 0.f && x < T && j <= x) ? drop_scale(seed, site, drop_idx_attn((size_t)pair, T, x, j), p, inv_keep) : 1.f;
             e[r] *= inv;
             dot = fmaf(pT[r] * ks[r], e[r], dot);
         }
@@ -1638,7 +1668,7 @@ __global__ __launch_bounds__(256) void attn_mfma_bwd_kernel(const uint16_t* __re
         const float mx = row16_allreduce<true>(ev);
         const float ex = expf(ev - mx);
         const float pr = ex * (1.0f / row16_allreduce<false>(ex));
-        const float ks = (p > 0.f && i < T && in) ? drop_scale(seed, site, ((size_t)pair * T + i) * T + x, p, inv_keep) : 1.f;
+        const float ks = (p > 0.f && i < T && in) ? drop_scale(seed, site, drop_idx_attn((size_t)pair, T, i, x), p, inv_keep) : 1.f;
         const float dot = row16_allreduce<false>(pN[r] * ks * pr);
         dsN[r] = pr * (pN[r] * ks - dot) * scale;
         pdN[r] = pr * ks;
@@ -2444,7 +2474,7 @@ struct TrainStep : TrainCall {
     hipError_t launch_attention(int l) {
         const TrainLayerWs& y = w.layer[l];
         constexpr size_t kAttnLdsAttr = 150 * 1024;  // (the ceiling train_validate admits: the size changes with the window, the attribute need not)
-        const uint32_t site = (uint32_t)(4 * l);
+        const uint32_t site = drop_site_attn(l);
         if (BWD && plan.attn_mfma_bwd) {
             const int n_pairs = batch * H;
             hipLaunchKernelGGL(attn_mfma_bwd_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, s, (const uint16_t*)P(y.qkv),
@@ -2508,11 +2538,11 @@ struct TrainStep : TrainCall {
             y_in = P(w.ya); res_in = F(w.xa);
         }
         TRY((tgemm<E, false, false>(y_in, D, P(y.w_proj), D, rows, D, D, 1,
-                                    EpiResid{res_in, F(y.x_mid), lp[l].pb.p, D, resid_p, resid_ik, seed, (uint32_t)(4 * l + 1)}, s)));
+                                    EpiResid{res_in, F(y.x_mid), lp[l].pb.p, D, resid_p, resid_ik, seed, drop_site_proj(l)}, s)));
         TRY(ln_fwd(F(y.x_mid), lp[l].ln2w, lp[l].ln2b, P(y.xn2), F(y.st2), rows));
         TRY((tgemm<E, false, false>(P(y.xn2), D, P(y.w_fc1), D, rows, D4, D, 1, EpiFc1<E>{P(y.h), P(y.g), lp[l].f1b.p, D4}, s)));
         TRY((tgemm<E, false, false>(P(y.g), D4, P(y.w_fc2), D4, rows, D, D4, 1,
-                                    EpiResid{(const float*)F(y.x_mid), F(y.x_out), lp[l].f2b.p, D, resid_p, resid_ik, seed, (uint32_t)(4 * l + 2)}, s)));
+                                    EpiResid{(const float*)F(y.x_mid), F(y.x_out), lp[l].f2b.p, D, resid_p, resid_ik, seed, drop_site_mlp(l)}, s)));
         return BESO_OK;
     }
     // ln_f and the action head on the compact rows, then the loss and its gradient dpred -- or the VJP's seed
@@ -2576,7 +2606,7 @@ struct TrainStep : TrainCall {
             TRY((tgemm<E, false, true>(P(w.dpred), ap, P(w.w_head), D, Ma, D, ap, 1, EpiStore<E>{F(w.dxn), nullptr, nullptr, D}, s)));
         }
         TRY(ln_bwd(F(w.layer[L - 1].x_out), w.stf, par.lnfw.p, nullptr, F(w.dxa), P(w.layer[L - 1].dyo), Ma, par.lnfw.g, par.lnfb.g,
-                   lp[L - 1].f2b.g, resid_p, (uint32_t)(4 * (L - 1) + 2)));
+                   lp[L - 1].f2b.g, resid_p, drop_site_mlp(L - 1)));
         return BESO_OK;
     }
     // (Measured and rejected, round 2: the chain of data gradients between two attention backwards as ONE tile kernel, the mirror
@@ -2591,7 +2621,7 @@ struct TrainStep : TrainCall {
         // FC2: dW2 = dyo^T g, dh = (dyo W2) * GELU'(h)
         TRY(wg.add(P(y.dyo), D, D, P(y.g), D4, D4, rows, lp[l].f2w.g));
         E* dy_out = last ? P(w.dya) : P(w.dy);
-        const uint32_t site2 = (uint32_t)(4 * l + 1);     // dropout site behind LayerNorm-2's branch (the out-projection)
+        const uint32_t site2 = drop_site_proj(l);        // dropout site behind LayerNorm-2's branch (the out-projection)
         float* slab = F(w.b1slab) + (size_t)l * fused_train_dgrad_blocks(M) * D4;       // FC1 bias sums per workgroup (use_dgrad)
         if (plan.use_dgrad) {
             b1_slabs[b1_n] = slab; b1_outs[b1_n] = lp[l].f1b.g; b1_blocks[b1_n] = fused_train_dgrad_blocks(rows); ++b1_n;
@@ -2630,7 +2660,7 @@ struct TrainStep : TrainCall {
         // LayerNorm-1 backward: into the previous layer's dyo with its FC2 dropout -- first layer: into dx0b with the embedding's
         E* dxb = first ? P(w.dx0b) : P(w.layer[l - 1].dyo);
         float* dbias = first ? nullptr : lp[l - 1].f2b.g;
-        const uint32_t site = first ? kEmbedSite : (uint32_t)(4 * (l - 1) + 2);
+        const uint32_t site = first ? kEmbedSite : drop_site_mlp(l - 1);
         const float p_site = first ? embed_p : resid_p; const int skip_mod = first ? T : 0;
         if (plan.use_dgrad) {
             const TrainLnBwd e = ln_epilogue(M, x_in, y.st1, lp[l].ln1w.p, F(w.dx), dxb, lp[l].ln1w.g, lp[l].ln1b.g, dbias, p_site, site, skip_mod,
@@ -2749,6 +2779,28 @@ int train_goal_mask(float* mask, size_t n, float goal_drop, uint32_t seed, hipSt
     if (n == 0) return BESO_OK;
     (void)hipGetLastError();
     hipLaunchKernelGGL(goal_mask_kernel, dim3(capped_grid(n, 2048)), dim3(256), 0, s, mask, n, goal_drop, seed);
+    TRY(hipGetLastError());
+    return BESO_OK;
+}
+
+// the shapes are the step's (train_validate: the same statuses as beso_loss_grad for the same cfg, batch, t)
+int train_dropout_mask(const beso_config* c, float* scale, int kind, int layer, int batch, int t, float p, uint32_t seed,
+                       hipStream_t s, hipError_t* err, int* err_line) {
+    if (!c || !scale) return BESO_ERR_BAD_ARG;
+    const int st = train_validate(c, batch, t);
+    if (st != BESO_OK) return st;
+    if (kind < BESO_DROP_EMBED || kind > BESO_DROP_MLP || !(p >= 0.f && p < 1.f) || ((uintptr_t)scale & 15)) return BESO_ERR_BAD_ARG;
+    if (kind != BESO_DROP_EMBED && (layer < 0 || layer >= c->n_layers)) return BESO_ERR_BAD_ARG;
+    const int T = 1 + c->goal_seq_len + 2 * t, D = c->embed_dim, H = c->n_heads;
+    const bool attn = kind == BESO_DROP_ATTN;
+    const size_t n = attn ? (size_t)batch * H * T * T : (size_t)batch * T * D;
+    const uint32_t site = kind == BESO_DROP_EMBED ? kEmbedSite : attn ? drop_site_attn(layer)
+                        : kind == BESO_DROP_PROJ ? drop_site_proj(layer) : drop_site_mlp(layer);
+    // the last layer continues on the compact action rows behind its attention (forward_layer, train_fwd_kernel's rows_act)
+    const int compact = (kind == BESO_DROP_PROJ || kind == BESO_DROP_MLP) && layer == c->n_layers - 1;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(capped_grid((n + 3) / 4, 2048)), dim3(256), 0, s, scale, n, attn ? 0 : D, T, t,
+                       c->goal_seq_len, kind == BESO_DROP_EMBED ? 1 : 0, compact, p, p > 0.f ? 1.0f / (1.0f - p) : 1.f, seed, site);
     TRY(hipGetLastError());
     return BESO_OK;
 }

@@ -255,6 +255,40 @@ class HipTrainStep:
                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "goal_mask")
         return mask
 
+    def dropout_mask(self, kind, layer: int, batch: int, t: int, seed: int, p: Optional[float] = None, device=None) -> torch.Tensor:
+        """The keep-scale (0 or 1/(1-p) per element) of one training dropout as ``run(..., seed=seed)`` applies it to a
+        batch of ``batch`` windows of ``t`` steps (``beso_dropout_mask``): what the module's ``nn.Dropout`` would have
+        multiplied by, drawn with the library's counter hash instead of torch's generator.
+
+        ``kind``: ``"embed"`` (``inner.drop``), ``"attn"`` (``blocks[layer].attn.attn_drop``), ``"proj"``
+        (``blocks[layer].attn.resid_drop``), ``"mlp"`` (``blocks[layer].mlp[3]``), or the ``_lib.DROP_*`` integer; ``layer``
+        is ignored for ``"embed"``.  ``p=None`` takes the module's own probability for that kind.  Returns
+        ``[batch, H, T, T]`` for ``"attn"`` (every query / key pair, the causally masked ones too) and ``[batch, T, D]`` for
+        the others, ``T = 1 + G + 2 t`` in the network's token order (sigma, goals, then state / action alternating).
+        Elements the step draws no mask for are 1: the sigma-token row of ``"embed"``, and every row but the action
+        tokens' of ``"proj"`` / ``"mlp"`` in the last layer (the loss reads the action tokens only; the step does not
+        evaluate the others there).
+
+        Caveat for comparisons against the reference network: the kernel draws the embedding mask per sample row, while
+        the reference, given a goal with batch dimension 1, draws ONE goal-embedding mask and expands it over the batch.
+        Pass goals as ``[B, G, obs]`` when a torch evaluation is to reproduce the step with these masks."""
+        inner = self.inner
+        k = _lib.DROP_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if p is None:
+            embed_p, attn_p, resid_p = inner._pdrops
+            p = {_lib.DROP_EMBED: embed_p, _lib.DROP_ATTN: attn_p}.get(k, resid_p)
+        dev = torch.device(device) if device is not None else next(inner.parameters()).device
+        T = 1 + inner.goal_seq_len + 2 * int(t)
+        shape = (batch, inner.n_heads, T, T) if k == _lib.DROP_ATTN else (batch, T, inner.embed_dim)
+        if batch < 1 or t < 1:
+            raise ValueError(f"beso_amd: dropout_mask needs batch >= 1 and t >= 1 (batch={batch}, t={t})")
+        scale = torch.empty(shape, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self.lib.beso_dropout_mask(C.byref(self.cfg), scale.data_ptr(), k, int(layer), int(batch), int(t), float(p),
+                                                  C.c_uint(seed & 0xFFFFFFFF),
+                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "dropout_mask")
+        return scale
+
     def loss_backward(self, state, action, goal, noise, sigma, grad_scale: float = 1.0, seed: Optional[int] = None,
                       early_stream=None, loss_stream=None):
         """The training step's ``loss = model.loss(...); loss.backward()``: returns the loss and leaves the

@@ -18,6 +18,7 @@
  *   beso_loss_grad      <- GCDenoiser.loss + loss.backward()           k_diffusion/score_wrappers.py:45-79, beso_agent.py:228-233
  *                          (+ DiffusionGPT.mask_cond, training mode     k_diffusion/score_gpts.py:298-299, 360-371)
  *   beso_goal_mask      <- the Bernoulli mask of DiffusionGPT.mask_cond k_diffusion/score_gpts.py:365-368
+ *   beso_dropout_mask   <- the masks of nn.Dropout in training mode      k_diffusion/score_gpts.py:72,79,109,321-325
  *   beso_log_logistic   <- rand_log_logistic (behind the uniform draw)   k_diffusion/utils.py:178-185 (beso_agent.py:227)
  *   beso_scale_rows     <- Scaler.scale_input / scale_output              networks/scaler/scaler_class.py:95-117 (base_agent.py:111-142)
  *   beso_loss_grad_overlap  (same, with the early gradient range for the overlapped all-reduce: SURVEY 8(e) C1)
@@ -306,6 +307,31 @@ int beso_denoise_vjp(const beso_config* cfg, const float* const* params, int n_p
 /* The keep-mask (1.0 / 0.0 per element of goal [batch,G,obs]) that beso_loss_grad applies for (goal_drop, seed):
  * `1 - torch.bernoulli(...)` of DiffusionGPT.mask_cond (score_gpts.py:365-368) with this library's generator.       */
 int beso_goal_mask(float* mask, int batch, int goal_seq_len, int obs_dim, float goal_drop, unsigned int seed, void* stream);
+/* The keep-scale (0 or 1/(1-p) per element) of one training dropout, exactly as beso_loss_grad applies it for the same
+ * (cfg, batch, t, p, seed): the mask torch's nn.Dropout would have drawn, with this library's generator (a counter-based
+ * hash of (seed, site, element): nothing is recorded during the step, the same function is evaluated here).  With these
+ * masks and beso_goal_mask's a training step can be reproduced or audited elsewhere.
+ *   kind / layer  which dropout: BESO_DROP_* of transformer layer `layer` in [0, n_layers) (ignored for BESO_DROP_EMBED)
+ *   scale         out, fp32, contiguous, 16-byte aligned, reference layout with T = 1 + goal_seq_len + 2 t:
+ *                 BESO_DROP_ATTN [batch, n_heads, T, T] -- every (query, key) pair is written, the causally masked ones too
+ *                 (their probabilities are zero); the other kinds [batch, T, embed_dim] in natural token order
+ *                 (sigma, goals, then state / action alternating).
+ *   p             the probability the step is called with for that kind (embed_pdrop / attn_pdrop / resid_pdrop), in
+ *                 [0, 1); 0 writes ones.
+ * Elements the step draws no mask for are 1: the sigma-token row of every sample for BESO_DROP_EMBED (score_gpts.py:321-325
+ * has no dropout there), and for BESO_DROP_PROJ / BESO_DROP_MLP of the LAST layer every row but the action tokens' -- the
+ * loss reads the action tokens only (score_gpts.py:353), the step does not evaluate the other rows behind that layer's
+ * attention, and no value there changes the loss or a gradient.
+ * One difference to the reference: the embedding mask is drawn per sample row, while the reference, handed a goal with
+ * batch dimension 1, draws one goal-embedding mask and expands it; pass goals as [batch, G, obs] when comparing.
+ * Status as beso_loss_grad for (cfg, batch, t); BESO_ERR_BAD_ARG for a NULL cfg / scale, a misaligned scale, an unknown
+ * kind, a layer outside [0, n_layers) or p outside [0, 1) -- before anything is enqueued.                              */
+#define BESO_DROP_EMBED 0   /* self.drop on the token / action / goal embeddings   score_gpts.py:321-325 */
+#define BESO_DROP_ATTN  1   /* attn_drop on the softmax output, before @ v         score_gpts.py:72      */
+#define BESO_DROP_PROJ  2   /* resid_drop on the out-projection                    score_gpts.py:79      */
+#define BESO_DROP_MLP   3   /* Dropout at the end of the MLP                       score_gpts.py:109     */
+int beso_dropout_mask(const beso_config* cfg, float* scale, int kind, int layer, int batch, int t, float p,
+                      unsigned int seed, void* stream);
 /* The training feed on trajectories resident in HBM: one batch of TrajectorySlicerDataset.__getitem__
  * (envs/dataloaders/trajectory_loader.py:160-197; the collate of torch's DataLoader included) as one launch.
  *   observations [n_traj,t_max,obs_dim], actions [n_traj,t_max,act_dim]  padded trajectories (TensorDataset.tensors)
