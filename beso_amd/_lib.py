@@ -24,6 +24,8 @@ SOLVER_IDS = {"dpm_2": 0, "dpm_2_ancestral": 1, "dpmpp_2s": 2, "dpmpp_2s_ancestr
 # every sampler loop the library runs as one enqueue: name -> (C entry point, its sampler / solver id)
 SAMPLERS = {**{k: ("beso_sample", v) for k, v in SAMPLER_IDS.items()}, "euler_ancestral": ("beso_sample_ancestral", None),
             **{k: ("beso_sample_solver", v) for k, v in SOLVER_IDS.items()}}
+# beso_sample_traced (include/beso_hip.h BESO_ENTRY_*): which of the three sampler calls it runs
+ENTRY_IDS = {"beso_sample": 0, "beso_sample_ancestral": 1, "beso_sample_solver": 2}
 GOAL_RANDOM, GOAL_TAIL, GOAL_SEQ_END = 0, 1, 2
 # beso_dropout_mask (include/beso_hip.h BESO_DROP_*): which nn.Dropout of the network
 DROP_EMBED, DROP_ATTN, DROP_PROJ, DROP_MLP = 0, 1, 2, 3
@@ -39,7 +41,7 @@ EXPORTS = ["beso_version", "beso_status_string", "beso_last_error", "beso_num_pa
            "beso_train_workspace_bytes", "beso_grad_floats", "beso_loss_grad", "beso_gather_windows",
            "beso_loss_grad_overlap", "beso_grad_early_range", "beso_sample_ancestral", "beso_goal_mask",
            "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp", "beso_sample_solver",
-           "beso_dropout_mask"]
+           "beso_dropout_mask", "beso_sample_traced"]
 # include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
 DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm"]
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
@@ -111,6 +113,10 @@ def load() -> C.CDLL:
             lib.beso_sample_solver.restype = i32
             lib.beso_sample_solver.argtypes = [cfgp, vp, i32, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_float), i32, f32, f32, f32,
                                                i32, vp, vp, i32, vp, sz, vp]
+        if hasattr(lib, "beso_sample_traced") or not os.environ.get("BESO_HIP_LIB"):
+            lib.beso_sample_traced.restype = i32
+            lib.beso_sample_traced.argtypes = [cfgp, vp, i32, i32, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_float), i32, f32, f32,
+                                               f32, i32, vp, vp, vp, sz, vp, sz, i32, vp, sz, vp]
         lib.beso_profile_enable.restype = None
         lib.beso_profile_enable.argtypes = [i32]
         if hasattr(lib, "beso_adam_step") or not os.environ.get("BESO_HIP_LIB"):   # (A/B builds of older revisions)

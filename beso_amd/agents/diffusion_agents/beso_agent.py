@@ -498,6 +498,47 @@ class BesoAgent(BaseAgent):
         self.action_context.append(x_0)
         return model_pred
 
+    @torch.no_grad()
+    def visualize_ode(self, state: torch.Tensor, goal, get_mean=1000, new_sampling_steps=None, noise_scheduler=None):
+        """The denoising trajectory of ``get_mean`` DDIM samples per observation (beso_agent.py:478-538): the list of
+        ``n_sampling_steps + 1`` action tensors ``[x_T, x after step 0, ..., x_0]``, each [N * get_mean, t, act].
+
+        The reference calls ``sample_ddim`` once per step on a two-entry schedule; here the whole loop is ONE
+        ``gc_sampling.sample_trajectory('ddim', ...)`` call whose launch records x behind every step (equal bits: a loop and
+        its steps run one after the other agree).  Scaling, the observation window, the EMA weights, the schedule and the
+        ``repeat_interleave`` of state and goal are the reference's; ``get_mean=None`` means 100 with ``use_kde``;
+        ``noise_scheduler=None`` takes the agent's, and a 2-D goal is one goal sequence for every observation, as in ``predict``.
+        Deviation: the reference draws a 2-D x [N * get_mean, act], which only fits a window of one; x is drawn here as
+        [N * get_mean, t, act] with t the length of the observation context, the shape ``evaluate`` and ``predict`` feed the
+        network.  Needs the HIP denoiser on the GPU (``sample_trajectory`` raises NotImplementedError otherwise)."""
+        if self.use_kde:
+            get_mean = 100 if get_mean is None else get_mean
+        if get_mean is None:
+            raise ValueError("visualize_ode: get_mean must be a number of samples per observation")
+        n_steps = self.num_sampling_steps if new_sampling_steps is None else new_sampling_steps
+        noise_scheduler = self.noise_scheduler if noise_scheduler is None else noise_scheduler
+        state = self.scaler.scale_input(state)
+        goal = self.scaler.scale_input(goal)
+        if self.window_size > 1 and state.dim() == 2:
+            self.obs_context.append(state)
+            input_state = torch.stack(tuple(self.obs_context), dim=1)
+        else:
+            input_state = state.unsqueeze(1) if state.dim() == 2 else state
+        if goal.dim() == 2:
+            goal = goal.unsqueeze(0)                                       # 'b d -> 1 b d', as predict
+        if goal.shape[0] == 1 and len(input_state) > 1:
+            goal = goal.expand(len(input_state), -1, -1)
+        act_dim = self.scaler.y_bounds.shape[1]
+        with self._ema_scope():
+            if self.model.training:
+                self.model.eval()
+            sigmas = self.get_noise_schedule(n_steps, noise_scheduler)
+            x = torch.randn((len(input_state) * get_mean, input_state.shape[1], act_dim), device=self.device) * self.sigma_max
+            state_rpt = torch.repeat_interleave(input_state, repeats=get_mean, dim=0)
+            goal_rpt = torch.repeat_interleave(goal, repeats=get_mean, dim=0)
+            _, xs, _ = ks.sample_trajectory('ddim', self.model, state_rpt, x, goal_rpt, sigmas, trace=('x',))
+        return list(xs.unbind(0))
+
     def sample_loop(self, sigmas, x_t: torch.Tensor, state: torch.Tensor, goal: torch.Tensor, sampler_type: str,
                     extra_args={}):
         """Dispatch on ``sampler_type`` (beso_agent.py:390-456).  Only 'heun' receives s_churn / s_min;

@@ -758,6 +758,63 @@ def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callba
     return action
 
 
+# ------------------------------------------------------------------------------------------------
+# the denoising trajectory of a one-launch sampler loop
+# ------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def sample_trajectory(sampler, model, state, action, goal, sigmas, eta=1., s_noise=1., order=4, noise=None,
+                      trace=('x', 'denoised')):
+    """The sampler loop ``sampler`` (a key of ``_lib.SAMPLERS``: 'ddim', 'euler', 'heun', 'euler_ancestral', 'dpm_2', ...) from
+    ``action`` = x_T as ONE enqueue that also records its trajectory (``beso_sample_traced``: the launches of the plain call
+    write it, nothing is evaluated twice) -> ``(x_0, xs, denoised)``:
+
+      * ``xs`` [n + 1, B, t, act]: ``xs[0]`` is x_T, ``xs[i + 1]`` is x after step i is complete (behind the second evaluation of
+        a two-evaluation step and behind the noise of an ancestral step), so ``xs[n]`` equals ``x_0`` bit for bit -- the list
+        the reference's ``visualize_ode`` builds from repeated two-entry schedules (beso_agent.py:525-531);
+      * ``denoised`` [n, B, t, act]: the model's output at the first evaluation of step i, what the reference's loops hand
+        their callback as 'denoised' (classifier-free combination included).
+
+    An entry not named in ``trace`` is returned as None.  ``model`` is a ``beso_amd`` GCDenoiser, or a
+    ClassifierFreeSampleModel around one.  The ancestral samplers draw through ``predraw_noise`` when ``noise`` is None, as the
+    samplers do.  Fused-only by design: where ``_fused_call`` would decline (a foreign model, CPU tensors, a non-positive
+    interior sigma) this raises NotImplementedError -- there is no second evaluation path behind it.
+
+    The samplers' own ``callback=`` argument is NOT routed here: those calls keep the Python loop and the bits it returns
+    today.  ``replay_callback`` feeds an existing callback from a recorded launch instead."""
+    from .... import _lib
+    if sampler not in _lib.SAMPLERS:
+        raise ValueError('desired sampler type not found!')
+    den, lam = _fused_target(model)
+    if den is None:
+        raise NotImplementedError('sample_trajectory records inside the HIP sampler loop: the model must be a beso_amd '
+                                  'GCDenoiser (optionally inside ClassifierFreeSampleModel)')
+    if not (torch.is_tensor(action) and action.is_cuda):
+        raise NotImplementedError('sample_trajectory runs on the GPU only (the inputs are CPU tensors)')
+    if not den.can_fuse_sampler(state, action, goal):
+        raise NotImplementedError('sample_trajectory: the denoiser does not run these inputs as one enqueue (eval mode, '
+                                  'fp32 HIP tensors [B, t, .] and a beso_amd DiffusionGPT inside are required)')
+    trace = {trace} if isinstance(trace, str) else set(trace)
+    if not trace or trace - {'x', 'denoised'}:
+        raise ValueError("trace must be a non-empty subset of {'x', 'denoised'} (the plain samplers record nothing)")
+    sig = _host_sigmas(sigmas)
+    if len(sig) < 2 or not all(float(v) > 0.0 for v in sig[:-1]):
+        raise NotImplementedError('sample_trajectory: the schedule must be positive up to its trailing value')
+    if sampler.endswith('_ancestral') and noise is None:
+        noise = predraw_noise(sampler, sig, action, eta)
+    x_0, rec = den.fused_sampler(sampler, state, action, goal, sig, cond_lambda=lam, eta=eta, s_noise=s_noise, order=order,
+                                 noise=noise, trace=trace)
+    return x_0, rec.get('x'), rec.get('denoised')
+
+
+def replay_callback(callback, sigmas, xs, denoised):
+    """Hands ``callback`` the dict the sampler loops hand it, once per step of a trajectory recorded by
+    ``sample_trajectory``: {'x': xs[i], 'i': i, 'sigma': sigmas[i], 'sigma_hat': sigmas[i], 'denoised': denoised[i]} for
+    i = 0 .. n - 1 (no churn in the one-launch loops: sigma_hat is sigma)."""
+    sig = _host_sigmas(sigmas)
+    for i in range(len(sig) - 1):
+        callback({'x': xs[i], 'i': i, 'sigma': sig[i], 'sigma_hat': sig[i], 'denoised': denoised[i]})
+
+
 def _out_of_scope(name, why):
     def fn(*a, **k):
         raise NotImplementedError(f"{name} is outside the MI355X hot-path scope ({why}); see DESIGN.md")

@@ -126,11 +126,12 @@ class GCDenoiser(nn.Module):
         return self._fused(self.inner_model, {}, state, x_t, goal) and x_t.dim() == 3 and state.dim() == 3
 
     def fused_sampler(self, sampler: str, state, x_t, goal, sigmas, cond_lambda: float = 1.0, eta: float = 1.0, noise=None,
-                      stepwise: bool = False, s_noise: float = 1.0, order: int = 4):
-        """A whole sampler loop of ``_lib.SAMPLERS`` as one enqueue (``ScoreNetRuntime.sample``); None if not applicable."""
+                      stepwise: bool = False, s_noise: float = 1.0, order: int = 4, trace=None):
+        """A whole sampler loop of ``_lib.SAMPLERS`` as one enqueue (``ScoreNetRuntime.sample``); None if not applicable.
+        ``trace`` (a subset of {'x', 'denoised'}): also record the trajectory; the result is then ``(x_0, {...})``."""
         inner = self.inner_model
         if not self.can_fuse_sampler(state, x_t, goal):
             return None
         return inner.runtime(self.sigma_data).sample(inner.packed_weights(), sampler, state, x_t, goal, sigmas,
                                                      cond_lambda=cond_lambda, eta=eta, s_noise=s_noise, order=order,
-                                                     noise=noise, stepwise=stepwise)
+                                                     noise=noise, stepwise=stepwise, trace=trace)

@@ -448,6 +448,8 @@ struct SampleCall {
     int batch, t; const float* sigmas; int n_sigmas; float cond_lambda; int flags;
     const float* noise; float* history;           // (beso_sample_ancestral / beso_sample_solver)
     void* workspace; size_t workspace_bytes; hipStream_t s;
+    float* trace_x = nullptr; size_t trace_x_floats = 0;         // (beso_sample_traced: the trajectory outputs and their
+    float* trace_den = nullptr; size_t trace_den_floats = 0;     //  capacities in floats; null: not recorded)
     Layout lay; Workspace ws; FwdArgs a;          // the forward of the loop at x
 };
 
@@ -473,6 +475,20 @@ static int sample_prologue(SampleCall& c, bool args_ok) {
     a.cond_lambda = c.cond_lambda; a.sigma_data = c.cfg->sigma_data;
     a.plan = c.flags & BESO_PLAN_MASK;
     if (c.precision == BESO_PREC_FP16) a.plan &= ~(BESO_PLAN_PER_OP | BESO_PLAN_BLOCKS);      // (fp16 has no per-op / block form)
+    // the trajectory outputs: n_sigmas slabs of x, n_sigmas - 1 of the denoised values; the loop updates x in place while the
+    // slabs are written, so neither may overlap it
+    const size_t n = (size_t)c.batch * c.t * c.lay.act;
+    const size_t need_x = (size_t)c.n_sigmas * n, need_den = (size_t)(c.n_sigmas - 1) * n;
+    if ((c.trace_x && c.trace_x_floats < need_x) || (c.trace_den && c.trace_den_floats < need_den)) return BESO_ERR_WORKSPACE;
+    // ... nor each other, the workspace or the steps' noise (all written or read while the slabs are written)
+    auto overlap = [](const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+        return a && b && (uintptr_t)a < (uintptr_t)b + b_bytes && (uintptr_t)b < (uintptr_t)a + a_bytes;
+    };
+    const size_t f = sizeof(float);
+    const struct { const void* p; size_t bytes; } others[] = {{c.x, n * f}, {c.workspace, c.ws.total}, {c.noise, need_den * f}};
+    for (const auto& o : others)
+        if (overlap(c.trace_x, need_x * f, o.p, o.bytes) || overlap(c.trace_den, need_den * f, o.p, o.bytes)) return BESO_ERR_BAD_ARG;
+    if (overlap(c.trace_x, need_x * f, c.trace_den, need_den * f)) return BESO_ERR_BAD_ARG;
     return BESO_OK;
 }
 
@@ -480,6 +496,8 @@ static int sample_prologue(SampleCall& c, bool args_ok) {
 // owns a sample from the embedding to the head also applies the update and feeds itself the next input), cut at step
 // boundaries past kMaxLoopEvals evaluations -- x travels through `x`, two-evaluation steps park x there between their
 // evaluations, Heun's slope lives in the workspace's d1 and the multistep state in `history`, the noise is indexed by step.
+// The trajectory outputs (SampleCall::trace_x / trace_den) are written by the launches that run anyway -- the loop's head, or
+// the update kernel of the step-by-step form; slab 0 of trace_x, the caller's x_T, is one copy in front of them.
 // (Few samples: every evaluation runs on the chip-wide small-batch path, step by step -- one workgroup carrying a sample group
 // through the whole loop would stream all the weights alone, evaluation after evaluation.)
 static int run_plan(const SampleCall& c, const Plan& p) {
@@ -490,6 +508,7 @@ static int run_plan(const SampleCall& c, const Plan& p) {
     float* sig = (float*)(wsp + c.ws.sig);
     const size_t n = (size_t)c.batch * c.t * c.lay.act;
     const bool f16 = c.precision == BESO_PREC_FP16;
+    if (c.trace_x) HIP_TRY(hipMemcpyAsync(c.trace_x, c.x, n * sizeof(float), hipMemcpyDeviceToDevice, c.s));
     if (!(c.flags & BESO_SAMPLE_STEPWISE) && !small_wanted(c.lay, c.a, c.precision) &&
         (f16 ? fused_can_loop_f16(c.lay, c.a, BESO_PREC_BF16) : fused_can_loop(c.lay, c.a, c.precision))) {
         FwdArgs a = c.a;
@@ -508,9 +527,11 @@ static int run_plan(const SampleCall& c, const Plan& p) {
                 X3.c3[k] = e.c3;
             }
             a.noise = c.noise ? c.noise + i0 * n : nullptr;
+            // (slab i0 + 1 of trace_x is x behind the launch's first step, slab i0 of trace_den that step's denoised value)
+            const SampleTrace TR{c.trace_x ? c.trace_x + (i0 + 1) * n : nullptr, c.trace_den ? c.trace_den + i0 * n : nullptr};
             profile_begin(BESO_SITE_FUSED_LAYER, c.s);
-            const int st = f16 ? fused_layers_f16(c.lay, (const char*)c.packed, a, (float*)(wsp + c.ws.x), nullptr, BESO_PREC_BF16, c.s, &S, &X3)
-                               : fused_layers(c.lay, (const char*)c.packed, a, (float*)(wsp + c.ws.x), nullptr, c.precision, c.s, &S, &X3);
+            const int st = f16 ? fused_layers_f16(c.lay, (const char*)c.packed, a, (float*)(wsp + c.ws.x), nullptr, BESO_PREC_BF16, c.s, &S, &X3, &TR)
+                               : fused_layers(c.lay, (const char*)c.packed, a, (float*)(wsp + c.ws.x), nullptr, c.precision, c.s, &S, &X3, &TR);
             profile_end(BESO_SITE_FUSED_LAYER, c.s);
             if (st != BESO_OK) return st;
         }
@@ -531,11 +552,34 @@ static int run_plan(const SampleCall& c, const Plan& p) {
         sv.c2 = e.rec.c2; sv.c3 = e.c3; sv.sigma = e.rec.sigma;
         sv.noise = c.noise ? c.noise + (size_t)e.step * n : nullptr;
         sv.hist = c.history;
+        sv.trace_x = c.trace_x ? c.trace_x + (size_t)(e.step + 1) * n : nullptr;
+        sv.trace_den = c.trace_den ? c.trace_den + (size_t)e.step * n : nullptr;
         const bool more = k + 1 < p.ev.size();
         HIP_TRY(launch_sampler_step(e.rec.mode, step_parks(mode) ? x2 : c.x, d1, c.x, x2, den, e.rec.c0, e.rec.c1, n, c.s,
                                     more ? sig : nullptr, more ? p.ev[k + 1].rec.sigma : 0.f, c.batch, sv));
     }
     return BESO_OK;
+}
+
+// The three sampler entry points (beso_sample_traced runs the same three with the trajectory outputs set in `c`)
+static int sample_basic(SampleCall& c, int sampler) {
+    const int st = sample_prologue(c, sampler >= BESO_SAMPLER_DDIM && sampler <= BESO_SAMPLER_HEUN);
+    return st != BESO_OK ? st : run_plan(c, plan_sample(sampler, c.sigmas, c.n_sigmas));
+}
+
+static int sample_ancestral(SampleCall& c, float eta) {
+    const int st = sample_prologue(c, c.noise && eta >= 0.f);
+    return st != BESO_OK ? st : run_plan(c, plan_ancestral(c.sigmas, c.n_sigmas, eta));
+}
+
+static int sample_solver(SampleCall& c, int solver, float eta, float s_noise, int order) {
+    const bool ancestral = solver == BESO_SOLVER_DPM_2_ANCESTRAL || solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL;
+    const bool lms_ok = solver != BESO_SOLVER_LMS || (order >= 1 && order <= 4);
+    const int n_hist = solver == BESO_SOLVER_DPMPP_2M ? 1 : solver == BESO_SOLVER_LMS ? order - 1 : 0;
+    const bool args_ok = solver >= BESO_SOLVER_DPM_2 && solver <= BESO_SOLVER_LMS && lms_ok && (!ancestral || c.noise) &&
+                         (n_hist <= 0 || c.history) && eta >= 0.f;
+    const int st = sample_prologue(c, args_ok);
+    return st != BESO_OK ? st : run_plan(c, plan_solver(solver, c.sigmas, c.n_sigmas, eta, s_noise, order));
 }
 
 }  // namespace beso
@@ -678,8 +722,7 @@ int beso_sample(const beso_config* cfg, const void* packed, int precision, int s
                 float cond_lambda, int flags, void* workspace, size_t workspace_bytes, void* stream) {
     SampleCall c{cfg, packed, precision, state, goal, x, batch, t, sigmas, n_sigmas, cond_lambda, flags, nullptr, nullptr,
                  workspace, workspace_bytes, (hipStream_t)stream};
-    const int st = sample_prologue(c, sampler >= BESO_SAMPLER_DDIM && sampler <= BESO_SAMPLER_HEUN);
-    return st != BESO_OK ? st : run_plan(c, plan_sample(sampler, sigmas, n_sigmas));
+    return sample_basic(c, sampler);
 }
 
 int beso_sample_ancestral(const beso_config* cfg, const void* packed, int precision, const float* state, const float* goal,
@@ -687,23 +730,32 @@ int beso_sample_ancestral(const beso_config* cfg, const void* packed, int precis
                           const float* noise, int flags, void* workspace, size_t workspace_bytes, void* stream) {
     SampleCall c{cfg, packed, precision, state, goal, x, batch, t, sigmas, n_sigmas, cond_lambda, flags, noise, nullptr,
                  workspace, workspace_bytes, (hipStream_t)stream};
-    const int st = sample_prologue(c, noise && eta >= 0.f);
-    return st != BESO_OK ? st : run_plan(c, plan_ancestral(sigmas, n_sigmas, eta));
+    return sample_ancestral(c, eta);
 }
 
 int beso_sample_solver(const beso_config* cfg, const void* packed, int precision, int solver, const float* state,
                        const float* goal, float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda,
                        float eta, float s_noise, int order, const float* noise, float* history, int flags,
                        void* workspace, size_t workspace_bytes, void* stream) {
-    const bool ancestral = solver == BESO_SOLVER_DPM_2_ANCESTRAL || solver == BESO_SOLVER_DPMPP_2S_ANCESTRAL;
-    const bool lms_ok = solver != BESO_SOLVER_LMS || (order >= 1 && order <= 4);
-    const int n_hist = solver == BESO_SOLVER_DPMPP_2M ? 1 : solver == BESO_SOLVER_LMS ? order - 1 : 0;
-    const bool args_ok = solver >= BESO_SOLVER_DPM_2 && solver <= BESO_SOLVER_LMS && lms_ok && (!ancestral || noise) &&
-                         (n_hist <= 0 || history) && eta >= 0.f;
     SampleCall c{cfg, packed, precision, state, goal, x, batch, t, sigmas, n_sigmas, cond_lambda, flags, noise, history,
                  workspace, workspace_bytes, (hipStream_t)stream};
-    const int st = sample_prologue(c, args_ok);
-    return st != BESO_OK ? st : run_plan(c, plan_solver(solver, sigmas, n_sigmas, eta, s_noise, order));
+    return sample_solver(c, solver, eta, s_noise, order);
+}
+
+int beso_sample_traced(const beso_config* cfg, const void* packed, int precision, int entry, int sampler, const float* state,
+                       const float* goal, float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda,
+                       float eta, float s_noise, int order, const float* noise, float* history, float* trace_x,
+                       size_t trace_x_floats, float* trace_den, size_t trace_den_floats, int flags, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    SampleCall c{cfg, packed, precision, state, goal, x, batch, t, sigmas, n_sigmas, cond_lambda, flags,
+                 entry == BESO_ENTRY_SAMPLE ? nullptr : noise, entry == BESO_ENTRY_SOLVER ? history : nullptr,
+                 workspace, workspace_bytes, (hipStream_t)stream};
+    c.trace_x = trace_x; c.trace_x_floats = trace_x_floats;
+    c.trace_den = trace_den; c.trace_den_floats = trace_den_floats;
+    if (entry == BESO_ENTRY_SAMPLE) return sample_basic(c, sampler);
+    if (entry == BESO_ENTRY_ANCESTRAL) return sample_ancestral(c, eta);
+    if (entry == BESO_ENTRY_SOLVER) return sample_solver(c, sampler, eta, s_noise, order);
+    return BESO_ERR_BAD_ARG;
 }
 
 #if BESO_DEV_API

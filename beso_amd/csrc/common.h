@@ -386,6 +386,10 @@ struct SolverStepArgs {
     float c2 = 0.f, c3 = 0.f, sigma = 0.f;
     const float* noise = nullptr;
     float* hist = nullptr;
+    // beso_sample_traced: the slabs of the evaluation's step (n floats each, or null) -- trace_den takes `den` on the first
+    // evaluation of a step, trace_x the update's result on the evaluation that completes it
+    float* trace_x = nullptr;
+    float* trace_den = nullptr;
 };
 hipError_t launch_sampler_step(int mode, float* out, float* aux, const float* x, const float* x2, const float* den,
                                float c0, float c1, size_t n, hipStream_t s, float* sig_next = nullptr, float sigma_next = 0.f,

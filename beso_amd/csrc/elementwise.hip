@@ -466,6 +466,9 @@ __global__ void sampler_step_kernel(int mode, float* __restrict__ out, float* __
         }
         if (mode & (kStepAddNoise | kStepScaledNoise)) r = step_noise(mode, r, sv.noise + i, sv.c2, sv.c3);
         out[i] = r;
+        // the trajectory of beso_sample_traced, under the conditions of the one-launch loop's head (fused.hip head_tile)
+        if (sv.trace_den && !step_unparks(mode & 0xff)) sv.trace_den[i] = dv;
+        if (sv.trace_x && !step_parks(mode & 0xff)) sv.trace_x[i] = r;
     }
 }
 

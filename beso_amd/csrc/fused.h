@@ -21,6 +21,10 @@ struct SampleSteps {
 // A kernel argument of its own BEHIND stamps / cap: the arguments the loop-free instances read keep their offsets (and those
 // instances their code); 0.5 KiB more of the 4 KiB (static_assert in fused.hip).
 struct SampleExtra { float c3[kMaxLoopEvals]; };
+// The optional trajectory outputs of a sampler loop (beso_sample_traced), fp32 [steps of the launch][B][t][act] each, already
+// offset to the launch's first step: `x` takes x after every completed step (behind the step's noise), `den` the denoised value
+// of every step's FIRST evaluation.  Either may be null.  A kernel argument of its own behind SampleExtra, for the same reason.
+struct SampleTrace { float* x; float* den; };
 constexpr int kLoopMaxElems = 512;   // action-window elements per workgroup the loop can carry (one per thread)
 
 size_t fused_packed_bytes(const Layout& lay, int precision);
@@ -28,7 +32,8 @@ int    fused_pack(const Layout& lay, const float* const* params, char* packed, i
 int    fused_level(const Layout& lay, const FwdArgs& a, int precision);   // 0 none, 1 MLP block, 2 whole layers
 int    fused_layer_edges(const Layout& lay);        // bit 0: fused_layers embeds, bit 1: it runs the head
 int    fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,
-                    hipStream_t s, const SampleSteps* steps = nullptr, const SampleExtra* extra = nullptr);
+                    hipStream_t s, const SampleSteps* steps = nullptr, const SampleExtra* extra = nullptr,
+                    const SampleTrace* trace = nullptr);
 bool   fused_can_loop(const Layout& lay, const FwdArgs& a, int precision);   // the whole sampler loop can run inside one launch
 int    fused_mlp_block(const Layout& lay, const char* packed, int layer, float* x, int M, hipStream_t s);
 bool   fused_has_lin_blocks(const Layout& lay, int precision);
@@ -93,7 +98,8 @@ int    fused_pack_f16(const Layout& lay, const float* const* params, char* packe
 int    fused_level_f16(const Layout& lay, const FwdArgs& a, int precision);
 int    fused_layer_edges_f16(const Layout& lay);
 int    fused_layers_f16(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,
-                        hipStream_t s, const SampleSteps* steps = nullptr, const SampleExtra* extra = nullptr);
+                        hipStream_t s, const SampleSteps* steps = nullptr, const SampleExtra* extra = nullptr,
+                        const SampleTrace* trace = nullptr);
 bool   fused_can_loop_f16(const Layout& lay, const FwdArgs& a, int precision);
 
 }  // namespace beso

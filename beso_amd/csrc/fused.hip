@@ -1520,8 +1520,10 @@ struct LoopState {
     float c2;              // kStepAddNoise: sigma_up (beso_sample_solver's modes: their third coefficient)
     int ev;                // index of the evaluation's step inside the launch (its slab of EdgeArgs::noise)
     float c3;              // beso_sample_solver's modes: SampleExtra's number of the evaluation
+    float* tx = nullptr;   // SampleTrace of the launch (uniform; null: nothing is recorded): slab ev of x behind a completed step,
+    float* tden = nullptr; // slab ev of the denoised value of a step's first evaluation
 };
-template <int RPW, int NT = kNTT>
+template <int RPW, int NT = kNTT, bool LOOP = false>
 __device__ __forceinline__ void head_tile(const Tile<RPW>& T, const EdgeArgs& e, const FusedDims& d, const char* gw,
                                           float* red, float* part, int s0, int n_samples, int Tn, int w, int lane,
                                           const SlotTabs* tb, float* xs, LoopState& ls, Stamps& st, int cfg_pass = -1,
@@ -1563,6 +1565,11 @@ __device__ __forceinline__ void head_tile(const Tile<RPW>& T, const EdgeArgs& e,
     sample_of(e, s0, b0, un0);
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));            // (the sampler loop: nothing of this block may be hoisted out of it and kept live)
+    // trajectory (beso_sample_traced): the workgroup's part of the step's two slabs, at the offset of the step's noise -- uniform
+    // bases (scalar registers), so that a store below costs the element's index and nothing else
+    const size_t slab = ((size_t)ls.ev * e.B + b0) * e.t * act;
+    float* const tden = ls.tden ? ls.tden + slab : nullptr;
+    float* const tx = ls.tx ? ls.tx + slab : nullptr;
     for (int it = tid; it < n_real * e.t * act; it += kBlock) {
         const int a = it % act, i = (it / act) % e.t, sr = it / (act * e.t);
         const int sl = sr * per;
@@ -1574,7 +1581,14 @@ __device__ __forceinline__ void head_tile(const Tile<RPW>& T, const EdgeArgs& e,
 #pragma unroll
         for (int ww = 0; ww < kWaves; ++ww) fc += part[((size_t)ww * kMT + tok_c) * 16 + a];
         if (cfg_pass >= 0) {
-            if (cfg_pass == 0) { cfgc[it] = fc; continue; }
+            if (cfg_pass == 0) {
+                // (loop instances: the slot's address is formed here, from an index the compiler cannot tie to pass 1's read of
+                // the same slot -- shared, it was kept across the element loop in scratch once the trajectory pointers were live)
+                int iw = it;
+                if constexpr (LOOP) asm volatile("" : "+v"(iw));
+                cfgc[iw] = fc;
+                continue;
+            }
             fu = fc;
             fc = cfgc[it];
         } else if (e.two) {
@@ -1605,6 +1619,7 @@ __device__ __forceinline__ void head_tile(const Tile<RPW>& T, const EdgeArgs& e,
             float xv = av, x2v = 0.f, d1 = 0.f;
             const int mode = ls.mode & 0xff;
             if (step_unparks(mode)) { xv = *dst; x2v = av; }      // (wave-uniform)
+            else if (tden) tden[it] = r;             // the denoised value of the step's first evaluation
             if (mode == BESO_STEP_HEUN_CORRECT) d1 = *daux;
             float o = mode <= BESO_STEP_HEUN_CORRECT
                           ? sampler_update(mode, xv, x2v, r, d1, ls.c0, ls.c1)
@@ -1617,7 +1632,10 @@ __device__ __forceinline__ void head_tile(const Tile<RPW>& T, const EdgeArgs& e,
             if (step_parks(mode)) {
                 *dst = xv;
                 if (mode == BESO_STEP_HEUN_PREDICT) *daux = d1;
-            } else if (ls.last) *dst = o;
+            } else {
+                if (ls.last) *dst = o;
+                if (tx) tx[it] = o;                   // ... and x behind the completed step
+            }
         }
     }
 }
@@ -3204,12 +3222,12 @@ __global__ __launch_bounds__(512, 2) void lin_block_x3_kernel(float* __restrict_
 // LOOP = 1: the sampler-loop instance (S.n evaluations, each followed by its update in the head); LOOP = 0 is one forward and
 // compiles to the loop-free code (S is not read).
 static_assert(3 * sizeof(void*) + sizeof(FusedDims) + 6 * sizeof(int) + sizeof(EdgeArgs) + sizeof(SampleSteps) +
-              sizeof(SampleExtra) + 64 <= 4096, "layers_kernel's arguments stay under the 4 KiB kernel-argument limit");
+              sizeof(SampleExtra) + sizeof(SampleTrace) + 64 <= 4096, "layers_kernel's arguments stay under the 4 KiB kernel-argument limit");
 template <int RPW, int KS, int HG, int NTL, int SPW = kSPW, int NTA = kNTT, int PX = 0, int CORE = 0, int LOOP = 0>
 __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, const char* __restrict__ lw0,
                                                         FusedDims d, int l0, int l1, int n_samples_total, int Tn,
                                                         EdgeArgs e, SampleSteps S, unsigned long long* stamps, int cap,
-                                                        SampleExtra X3) {
+                                                        SampleExtra X3, SampleTrace TR) {
     Stamps st{stamps, cap, 0};
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     static_assert(CORE == 0 || (SPW == 1 && PX == 0), "long-sequence instance");
@@ -3240,6 +3258,7 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
     build_slot_tabs(tb, n_samples, Tn, e.t, d.G, actions_first, CORE == 1 ? 7 : 4);
     // the action windows of the workgroup's real samples (contiguous in `action`): x_T of the sampler loop / the noisy action
     LoopState ls{-1, 0.f, 0.f, 0.f, true, 0.f, 0, 0.f};
+    if constexpr (LOOP) { ls.tx = TR.x; ls.tden = TR.den; }
     {
         int b0; bool un0;
         sample_of(e, s0, b0, un0);
@@ -3369,10 +3388,10 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
     }
     {
         // (peel: the action tokens are the first n_samples * t slots, i.e. inside the first NTLa token tiles)
-        if constexpr (CORE == 1) head_tile<RPW, NTA>(T, e, d, gw, (float*)(lds + L.red), (float*)(lds + L.u), s0p, n_samples, Tn, w, lane, tb, xs, ls, st,
+        if constexpr (CORE == 1) head_tile<RPW, NTA, LOOP != 0>(T, e, d, gw, (float*)(lds + L.red), (float*)(lds + L.u), s0p, n_samples, Tn, w, lane, tb, xs, ls, st,
                                                      two_pass ? pass : -1, (float*)(lds + L.cfgc));
-        else if (peel && NTLa < kNTT) head_tile<RPW, NTLa>(T, e, d, gw, (float*)(lds + L.red), (float*)(lds + L.u), s0, n_samples, Tn, w, lane, tb, xs, ls, st);
-        else head_tile<RPW>(T, e, d, gw, (float*)(lds + L.red), (float*)(lds + L.u), s0, n_samples, Tn, w, lane, tb, xs, ls, st);
+        else if (peel && NTLa < kNTT) head_tile<RPW, NTLa, LOOP != 0>(T, e, d, gw, (float*)(lds + L.red), (float*)(lds + L.u), s0, n_samples, Tn, w, lane, tb, xs, ls, st);
+        else head_tile<RPW, kNTT, LOOP != 0>(T, e, d, gw, (float*)(lds + L.red), (float*)(lds + L.u), s0, n_samples, Tn, w, lane, tb, xs, ls, st);
     }
     stamp(st, 5);
     if (CORE == 1 && pass + 1 < n_pass) __syncthreads();      // the conditional pass's outputs are in cfgc, its partial sums read
@@ -4114,17 +4133,17 @@ hipError_t launch_tail_block(float* x, const char* lw, const char* lw_next, cons
 // One instance of layers_kernel (LOOP = 1: the sampler-loop form, steps.n evaluations).
 template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int PX, int CORE, int LOOP>
 hipError_t launch_instance(size_t lds_bytes, int grid, float* x, const char* lw0, const FusedDims& d, int l0, int l1,
-                           int n_samples, int Tn, const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, hipStream_t s) {
+                           int n_samples, int Tn, const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, hipStream_t s) {
     return launch_lds<layers_kernel<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, LOOP>>(dim3(grid), dim3(512), lds_bytes, s, x, lw0, d, l0, l1,
-                                                                                 n_samples, Tn, edge, steps, g_stamps, g_stamps_cap, extra);
+                                                                                 n_samples, Tn, edge, steps, g_stamps, g_stamps_cap, extra, trace);
 }
 template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int PX, int CORE>
 hipError_t launch_either(size_t lds_bytes, float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, hipStream_t s) {
+                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, hipStream_t s) {
     const int grid = (n_samples + SPW - 1) / SPW;
     if (steps.n > 0)
-        return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 1>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
-    return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 0>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
+        return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 1>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
+    return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 0>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
 }
 
 // samples of Tn tokens in NT token tiles: the tokens, and the last sample's 16-row attention window, must fit
@@ -4140,7 +4159,7 @@ constexpr int kSmallBatchMax = 512;    // batches up to this size take the two-s
 // it (the instances compute the same per-sample arithmetic -- equal bits --, so the hint is a performance / test knob only).
 template <int RPW, int KS, int HG, int NTL>
 hipError_t launch_layers(float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, int precision, int plan, hipStream_t s) {
+                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, int precision, int plan, hipStream_t s) {
     constexpr LdsMap L = lds_map(KS);
     constexpr int kSmallSPW = 2, kSmallNT = 2, kMidSPW = 4, kMidNT = 4;
     const int want = plan & BESO_PLAN_SPW_MASK;
@@ -4160,30 +4179,30 @@ hipError_t launch_layers(float* x, const char* lw0, const FusedDims& d, int l0, 
         if (four_ok && (want == BESO_PLAN_SPW4 || (want != BESO_PLAN_SPW2 && n_samples > kSmallBatchMax) || !small_ok)) {
             constexpr LdsMapX3 X = lds_map_x3(KS, kX3NT);
             static_assert(X.total <= 160 * 1024, "LDS of the four-sample split-bf16 instance");
-            return launch_either<RPW, KS, HG, kX3NTL, kX3SPW, kX3NT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
+            return launch_either<RPW, KS, HG, kX3NTL, kX3SPW, kX3NT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
         }
         if (!small_ok) return hipErrorInvalidValue;
         constexpr LdsMapX3 X = lds_map_x3(KS, kSmallNT);
-        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
+        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
     }
 #endif
     const bool mid_ok = tiles_hold_exact(kMidSPW, Tn, kMidNT);
     // latency instances: the samples' tokens and the last sample's 16-row attention window must fit the token tiles
     if (small_ok && (want == BESO_PLAN_SPW2 || (!want && n_samples <= kSmallBatchMax)))
-        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
+        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
     // up to one workgroup of four samples per CU: two thirds of the throughput instance's work per workgroup
     if (mid_ok && (want == BESO_PLAN_SPW4 || (!want && n_samples <= 2 * kSmallBatchMax)))
-        return launch_either<RPW, KS, HG, NTL, kMidSPW, kMidNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
-    return launch_either<RPW, KS, HG, NTL, kSPW, kNTT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
+        return launch_either<RPW, KS, HG, NTL, kMidSPW, kMidNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
+    return launch_either<RPW, KS, HG, NTL, kSPW, kNTT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
 }
 
 // The long-sequence instance: one sample (Tn <= 16 NT tokens) per workgroup.
 template <int RPW, int KS, int NT>
 hipError_t launch_layers_long(float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                              const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, hipStream_t s) {
+                              const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, hipStream_t s) {
     constexpr LdsMap L = lds_map(KS, false, NT);
     static_assert(L.total <= 160 * 1024, "LDS of the long-sequence instance");
-    return launch_either<RPW, KS, 1, NT, 1, NT, 0, 1>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, s);
+    return launch_either<RPW, KS, 1, NT, 1, NT, 0, 1>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
 }
 
 }  // namespace
@@ -4700,11 +4719,12 @@ bool fused_can_loop(const Layout& lay, const FwdArgs& a, int precision) {
 }
 
 int fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,
-                 hipStream_t s, const SampleSteps* steps, const SampleExtra* extra) {
+                 hipStream_t s, const SampleSteps* steps, const SampleExtra* extra, const SampleTrace* trace) {
     FusedDims d;
     if (!fused_dims(lay, &d) || !d.attn) return BESO_ERR_UNSUPPORTED;
     static const SampleSteps no_steps{};
     static const SampleExtra no_extra{};
+    const SampleTrace TR = trace ? *trace : SampleTrace{nullptr, nullptr};
     const SampleSteps& S = steps ? *steps : no_steps;
     const SampleExtra& X3 = extra ? *extra : no_extra;
     const char* base = packed + lay.fused;
@@ -4723,9 +4743,9 @@ int fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float*
     if ((size_t)(d.seq1 ? 1 : kSPW) * a.t * lay.act * sizeof(float) > (size_t)kXsBytes) return BESO_ERR_UNSUPPORTED;
     if (fused_edges) *fused_edges = 3;
     hipError_t err;
-    if (d.RPW == 3 && d.KS == 12 && d.HG == 1) err = launch_layers<3, 12, 1, 2>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, precision, a.plan, s);    // kitchen: 8 x 4 action tokens
-    else if (d.RPW == 2 && d.KS == 8 && d.HG == 3) err = launch_layers<2, 8, 3, 4>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, precision, a.plan, s);   // block-push: 8 x 5
-    else if (d.seq1 && precision == BESO_PREC_BF16) err = launch_layers_long<4, 16, kLongNT>(x, base, d, 0, lay.L, a.batch, a.T, e, S, X3, s);   // long horizon: 1 x 67 tokens
+    if (d.RPW == 3 && d.KS == 12 && d.HG == 1) err = launch_layers<3, 12, 1, 2>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, TR, precision, a.plan, s);    // kitchen: 8 x 4 action tokens
+    else if (d.RPW == 2 && d.KS == 8 && d.HG == 3) err = launch_layers<2, 8, 3, 4>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, TR, precision, a.plan, s);   // block-push: 8 x 5
+    else if (d.seq1 && precision == BESO_PREC_BF16) err = launch_layers_long<4, 16, kLongNT>(x, base, d, 0, lay.L, a.batch, a.T, e, S, X3, TR, s);   // long horizon: 1 x 67 tokens
                                                                                                              // (one workgroup per REAL sample: pairs run as two passes)
     else return BESO_ERR_UNSUPPORTED;
     return err == hipSuccess ? BESO_OK : BESO_ERR_HIP;

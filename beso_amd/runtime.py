@@ -214,17 +214,25 @@ class ScoreNetRuntime:
         return out
 
     def sample(self, packed: PackedWeights, sampler: str, state, x_t, goal, sigmas, cond_lambda: float = 1.0,
-               eta: float = 1.0, s_noise: float = 1.0, order: int = 4, noise=None, stepwise: bool = False) -> torch.Tensor:
+               eta: float = 1.0, s_noise: float = 1.0, order: int = 4, noise=None, stepwise: bool = False, trace=None):
         """One of the sampler loops of ``_lib.SAMPLERS`` (ddim / euler / heun with s_churn = 0, euler_ancestral, dpm_2,
         dpm_2_ancestral, dpmpp_2s, dpmpp_2s_ancestral, dpmpp_2m, lms of order 1 ... 4) as ONE enqueue of all steps -- one
         launch for the whole loop where the shape has the one-launch kernel; ``stepwise`` enqueues evaluation by evaluation
         instead (same arithmetic, bit-identical results).  ``eta`` is the ancestral samplers', ``s_noise``
         dpmpp_2s_ancestral's, ``order`` LMS's.  The ancestral samplers' noise [n_steps, B, t, act] is ``noise``, or drawn
         here by ``gc_sampling.predraw_noise`` (the draws of the Python loop, in its order).  The multistep state lives in a
-        buffer of this call."""
+        buffer of this call.
+
+        ``trace``: a subset of {'x', 'denoised'}.  Non-empty, the same launches also record the trajectory
+        (``beso_sample_traced``) and the return value is ``(x_0, {...})`` with the requested fp32 tensors: 'x'
+        [n_steps + 1, B, t, act] -- x_T, then x after every completed step, the last one equal to x_0 -- and 'denoised'
+        [n_steps, B, t, act], the denoised value of every step's first evaluation."""
         if sampler not in _lib.SAMPLERS:
             raise ValueError("desired sampler type not found!")
         entry, sid = _lib.SAMPLERS[sampler]
+        trace = set(() if trace is None else ([trace] if isinstance(trace, str) else trace))
+        if trace - {"x", "denoised"}:
+            raise ValueError("trace must be a subset of {'x', 'denoised'}")
         if sampler == "lms" and not 1 <= int(order) <= 4:
             raise ValueError("beso_sample_solver runs LMS orders 1 ... 4")
         dev, B, t, state, x, goal, _ = self._prep(state, x_t, goal, None)
@@ -251,6 +259,22 @@ class ScoreNetRuntime:
         nz = noise.data_ptr() if noise is not None else None
         flags = (_lib.SAMPLE_STEPWISE if stepwise else 0) | forward_hints()
         tail = (ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+        if trace:
+            n = len(sig) - 1
+            out = {}
+            if "x" in trace:
+                out["x"] = torch.empty((n + 1,) + tuple(x.shape), dtype=torch.float32, device=dev)
+            if "denoised" in trace:
+                out["denoised"] = torch.empty((n,) + tuple(x.shape), dtype=torch.float32, device=dev)
+            tx, td = out.get("x"), out.get("denoised")
+            args = head + (_lib.ENTRY_IDS[entry], sid or 0) + loop + (
+                float(eta), float(s_noise), int(order), nz, hist.data_ptr() if hist is not None else None,
+                tx.data_ptr() if tx is not None else None, tx.numel() if tx is not None else 0,
+                td.data_ptr() if td is not None else None, td.numel() if td is not None else 0, flags) + tail
+            with torch.cuda.device(dev):
+                st = self.lib.beso_sample_traced(*args)
+            _lib.check(st, f"sample_traced[{sampler}]")
+            return x, out
         if entry == "beso_sample":
             args = head + (sid,) + loop + (flags,) + tail
         elif entry == "beso_sample_ancestral":

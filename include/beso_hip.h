@@ -14,6 +14,8 @@
  *                                                                      k_diffusion/gc_sampling.py:205-210,296-310,921-923
  *   beso_sample         <- sample_ddim / sample_euler / sample_heun    k_diffusion/gc_sampling.py:167-213,259-314,895-924
  *   beso_sample_ancestral <- sample_euler_ancestral                    k_diffusion/gc_sampling.py:216-256
+ *   beso_sample_traced  <- any of the three with the trajectory recorded (what BesoAgent.visualize_ode and the samplers'
+ *                          callbacks look at)                          agents/diffusion_agents/beso_agent.py:478-538
  *   beso_sample_solver  <- sample_dpm_2(_ancestral) / sample_dpmpp_2s(_ancestral) / sample_dpmpp_2m / sample_lms
  *   beso_loss_grad      <- GCDenoiser.loss + loss.backward()           k_diffusion/score_wrappers.py:45-79, beso_agent.py:228-233
  *                          (+ DiffusionGPT.mask_cond, training mode     k_diffusion/score_gpts.py:298-299, 360-371)
@@ -237,6 +239,31 @@ int beso_sample_solver(const beso_config* cfg, const void* packed, int precision
                        const float* goal, float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda,
                        float eta, float s_noise, int order, const float* noise, float* history, int flags,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* Any of the three sampler calls above with its denoising trajectory recorded by the launches the call makes anyway (the head
+ * of the one-launch loop, or the update launch of the step-by-step form: recording adds no launch but one copy of x_T).
+ * `entry` picks the call -- BESO_ENTRY_SAMPLE: beso_sample with `sampler` a BESO_SAMPLER_*; BESO_ENTRY_ANCESTRAL:
+ * beso_sample_ancestral (`sampler` unused); BESO_ENTRY_SOLVER: beso_sample_solver with `sampler` a BESO_SOLVER_* -- and the
+ * arguments are the union of theirs, checked as that call checks them (those it does not take are ignored).  With n =
+ * n_sigmas - 1 steps and N = batch*t*act, two optional DEVICE outputs in fp32:
+ *   trace_x    [n + 1][batch,t,act]  slab 0 is x_T as passed in; slab i + 1 is x after step i is COMPLETE -- behind the second
+ *                                    evaluation of a two-evaluation step and behind the step's noise of the ancestral samplers
+ *                                    -- so slab n equals the returned x bit for bit.  What a step parks between its two
+ *                                    evaluations (Heun's x2, DPM-2's midpoint) is not recorded.
+ *   trace_den  [n][batch,t,act]      slab i is the denoised value of the FIRST evaluation of step i, what the reference's loops
+ *                                    hand their callback as 'denoised': the preconditioned output, the classifier-free
+ *                                    combination when cond_lambda is neither 0 nor 1, the unconditional output when it is 0.
+ * Either may be NULL (not recorded); with both NULL the call is the plain entry point.  `trace_x_floats` / `trace_den_floats`
+ * are the buffers' capacities in floats: below (n + 1) N / n N the call returns BESO_ERR_WORKSPACE before anything is
+ * enqueued.  The two buffers must be disjoint from each other and from every other buffer of the call; an overlap with x,
+ * the workspace, `noise` or each other is refused (BESO_ERR_BAD_ARG), one with `history`, the inputs or the weights is the
+ * caller's to avoid.  The result in x, the launches and their kernels are those of the plain call.                        */
+enum { BESO_ENTRY_SAMPLE = 0, BESO_ENTRY_ANCESTRAL = 1, BESO_ENTRY_SOLVER = 2 };
+int beso_sample_traced(const beso_config* cfg, const void* packed, int precision, int entry, int sampler, const float* state,
+                       const float* goal, float* x, int batch, int t, const float* sigmas, int n_sigmas, float cond_lambda,
+                       float eta, float s_noise, int order, const float* noise, float* history, float* trace_x,
+                       size_t trace_x_floats, float* trace_den, size_t trace_den_floats, int flags, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* One Adam / AdamW step over ALL parameter tensors in one launch, optionally followed by the EMA update
  * of the shadow copy on the updated parameters.  Replaces `self.optimizer.step()` + `self.ema_helper.update`
