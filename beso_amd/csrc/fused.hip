@@ -421,16 +421,10 @@ __device__ __forceinline__ f32x4 mfma_op_half(const u32x4& a, const u32x4& b, co
 // long-horizon Euler-100 -1 ... -2 %.  Only the instances that run at the power cap AND have such slots carry the two
 // compare-and-select instructions: the block-push shape fills its tiles (8 x 12 = 96), the latency instances are bound
 // by a lone workgroup's weight stream (+0.3 % with the mask).
-#ifndef BESO_ZERO_PAD
-#define BESO_ZERO_PAD 1              // 0: A/B builds
-#endif
-#ifndef BESO_KEEP_HYBRID
-#define BESO_KEEP_HYBRID 1           // odd token-tile counts: h and GELU(h) leave as 16-byte pieces for the tile pairs, 8-byte ones for the last (0: all 8-byte)
-#endif
 #ifndef BESO_TRAIN_FWD_ABL
 #define BESO_TRAIN_FWD_ABL 0         // timing experiments on train_fwd_kernel (results wrong): stores left out -- 1 x_mid / x_out,
 #endif                               // 2 LayerNorm outputs + statistics, 4 q|k|v and y, 8 h, 16 GELU(h); 128 / 256: rows folded (Rows::row)
-__host__ __device__ constexpr bool zero_pad_instance(int RPW, int NT) { return BESO_ZERO_PAD && RPW != 2 && NT >= 5; }
+__host__ __device__ constexpr bool zero_pad_instance(int RPW, int NT) { return RPW != 2 && NT >= 5; }
 __device__ __forceinline__ void mixed_chain_pad() {
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_nop 4\n\ts_nop 4");
@@ -458,17 +452,6 @@ __device__ __forceinline__ void mixed_chain_pad() {
 #define ABL_KS(x) (x)
 #define ABL_PTR(base, off) ((base).adv(off))
 #endif
-
-#ifndef BESO_FUSED_WLOAD
-#define BESO_FUSED_WLOAD 0           // 0: plain loads, 1: non-temporal (measured 11 % SLOWER: 1.39 vs 1.26 ms)
-#endif
-__device__ __forceinline__ u32x4 wload(const u32x4* p) {
-#if BESO_FUSED_WLOAD == 1
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
 
 // Address of a wave's weight fragments: a buffer resource over a wave-uniform base (SGPRs: kernel
 // arguments, wave index), a uniform byte offset (SGPR: k-step / chunk / head stepping is scalar arithmetic)
@@ -753,12 +736,9 @@ __device__ __forceinline__ void gemm_x3(f32x4 (&acc)[R][NTA], WPtr a, int a_ks, 
 // shared pieces of the kernels
 // ---------------------------------------------------------------------------------------------
 constexpr int kKCc = kChunkTiles / 2;      // FC2 k-steps per hidden chunk (= kKC below)
-#ifndef BESO_RED_PAD
-#define BESO_RED_PAD 4               // floats of padding per token in the LayerNorm statistics exchange (0: A/B)
-#endif
 // LayerNorm statistics exchange: per token kWaves (sum, sum of squares) pairs + padding -- with 16 floats per token the 16
 // lanes of a row hit 4 banks groups four times over (reads of 16 B at a 64-B stride); 20 floats spread them over all 64 banks
-constexpr int kRedTok = 2 * kWaves + BESO_RED_PAD;
+constexpr int kRedTok = 2 * kWaves + 4;
 constexpr int kXsBytes = 2048;        // the workgroup's action windows (n_real x t x act <= 512 floats): input of every evaluation
 // (every instance stages them: the bound is what fused_level admits -- kSPW samples x (kMT / kSPW tokens >= 2 t) x 4 kEmbActK
 //  action dims, or one long-sequence sample of 16 kLongNT / 2 steps)
@@ -1665,9 +1645,6 @@ __device__ __forceinline__ void gelu_pair(const f32x4 (&h)[RC][NT], float (&gq)[
 // VALU instruction directly behind its own MFMA issues in that MFMA's shadow, a run of them does not
 // (measured, tools/microbench/issue_rate.hip), and alternating two independent chains keeps the packed-fp32
 // pipe (8 cycles dependent, 5.5 independent) from waiting on itself.
-#ifndef BESO_GELU_SCALAR
-#define BESO_GELU_SCALAR 0           // 1: GELU chain as v_fma_f32 pairs instead of v_pk_fma_f32 (A/B experiment)
-#endif
 struct GeluChain { f32x2 v, vc, s, p; };
 template <int RC, int NT, int SIGMA>
 __device__ __forceinline__ void gelu_slot(const f32x4 (&h)[RC][NT], GeluChain& c0, GeluChain& c1, float (&gq)[8],
@@ -1682,20 +1659,6 @@ __device__ __forceinline__ void gelu_slot(const f32x4 (&h)[RC][NT], GeluChain& c
             g.v = f32x2{h[2 * j2 + (j >> 2)][t][j & 3], h[2 * j2 + (j >> 2)][t][(j & 3) + 1]};
             g.vc.x = __builtin_amdgcn_fmed3f(g.v.x, -4.0f, 4.0f);
         } else if constexpr (step == 1) g.vc.y = __builtin_amdgcn_fmed3f(g.v.y, -4.0f, 4.0f);
-#if BESO_GELU_SCALAR
-        // experiment: the same chain as single-lane-width ops (two per slot), kept apart so that they are not re-packed
-#define BESO_G2(dst, ex, ey) do { dst.x = (ex); asm volatile("" : "+v"(dst.x)); dst.y = (ey); asm volatile("" : "+v"(dst.y)); } while (0)
-        else if constexpr (step == 2) BESO_G2(g.s, g.vc.x * g.vc.x, g.vc.y * g.vc.y);
-        else if constexpr (step == 3) BESO_G2(g.p, __builtin_fmaf(g.s.x, 2.277972093e-08f, -1.598515742e-06f), __builtin_fmaf(g.s.y, 2.277972093e-08f, -1.598515742e-06f));
-        else if constexpr (step == 4) BESO_G2(g.p, __builtin_fmaf(g.p.x, g.s.x, 4.795382804e-05f), __builtin_fmaf(g.p.y, g.s.y, 4.795382804e-05f));
-        else if constexpr (step == 5) BESO_G2(g.p, __builtin_fmaf(g.p.x, g.s.x, -0.0008139993719f), __builtin_fmaf(g.p.y, g.s.y, -0.0008139993719f));
-        else if constexpr (step == 6) BESO_G2(g.p, __builtin_fmaf(g.p.x, g.s.x, 0.00877231165f), __builtin_fmaf(g.p.y, g.s.y, 0.00877231165f));
-        else if constexpr (step == 7) BESO_G2(g.p, __builtin_fmaf(g.p.x, g.s.x, -0.06457294506f), __builtin_fmaf(g.p.y, g.s.y, -0.06457294506f));
-        else if constexpr (step == 8) BESO_G2(g.p, __builtin_fmaf(g.p.x, g.s.x, 0.3978832308f), __builtin_fmaf(g.p.y, g.s.y, 0.3978832308f));
-        else if constexpr (step == 9) BESO_G2(g.p, __builtin_fmaf(g.vc.x, g.p.x, 0.5f), __builtin_fmaf(g.vc.y, g.p.y, 0.5f));
-        else if constexpr (step == 10) { gq[j] = g.v.x * g.p.x; asm volatile("" : "+v"(gq[j])); gq[j + 1] = g.v.y * g.p.y; }
-#undef BESO_G2
-#else
         else if constexpr (step == 2) g.s = g.vc * g.vc;
         else if constexpr (step == 3) g.p = __builtin_elementwise_fma(g.s, (f32x2)(2.277972093e-08f), (f32x2)(-1.598515742e-06f));
         else if constexpr (step == 4) g.p = __builtin_elementwise_fma(g.p, g.s, (f32x2)(4.795382804e-05f));
@@ -1705,7 +1668,6 @@ __device__ __forceinline__ void gelu_slot(const f32x4 (&h)[RC][NT], GeluChain& c
         else if constexpr (step == 8) g.p = __builtin_elementwise_fma(g.p, g.s, (f32x2)(0.3978832308f));
         else if constexpr (step == 9) g.p = __builtin_elementwise_fma(g.vc, g.p, (f32x2)(0.5f));
         else if constexpr (step == 10) { const f32x2 r = g.v * g.p; gq[j] = r.x; gq[j + 1] = r.y; }
-#endif
         // every slot is pinned where it is issued (otherwise the whole chain sinks to its use)
         if constexpr (step <= 1) asm volatile("" : "+v"(g.vc));
         else if constexpr (step == 2) asm volatile("" : "+v"(g.s));
@@ -1729,13 +1691,8 @@ __device__ __forceinline__ void gelu_slot(const f32x4 (&h)[RC][NT], GeluChain& c
 //     FC1(0)
 //     for c:  [FC2(c-1) || GELU(c)]  barrier  hT <- GELU(c)  FC1(c+1)  barrier
 //     FC2(n-1)
-#ifndef BESO_FC1_PF
-#define BESO_FC1_PF 2
-#endif
-constexpr int kFc1PF = BESO_FC1_PF;      // k-steps of FC1 weight fragments in flight per wave
-#ifndef BESO_LAT_PF1
-#define BESO_LAT_PF1 4                   // ... in the latency instances (KS % BESO_LAT_PF1 == 0)
-#endif
+constexpr int kFc1PF = 2;                // k-steps of FC1 weight fragments in flight per wave
+constexpr int kFc1PFLat = 4;             // ... in the latency instances (KS % kFc1PFLat == 0)
 constexpr int kKC = kChunkTiles / 2;     // FC2 k-steps per hidden chunk
 // First k-steps of chunk 0's FC1 weights of a layer (issued before the LayerNorm that precedes the phase).
 template <int KS, int NW, int PF1 = kFc1PF>
@@ -1803,7 +1760,7 @@ __device__ __forceinline__ void mlp_phase(Tile<RPW>& T, const u32x4* xnT, u32x4*
             for (int r = 0; r < RC; ++r) {
                 const int f0 = 16 * (c * kChunkTiles + RC * w + r) + 4 * g;
                 // (an odd tile count: the pairs as 16-byte pieces, the last tile as 8-byte ones)
-                constexpr int NTE = BESO_KEEP_HYBRID ? (NT & ~1) : (NT % 2 == 0 ? NT : 0);
+                constexpr int NTE = NT & ~1;
                 {
 #pragma unroll
                     for (int t = 0; t < NTE; t += 2)
@@ -1832,7 +1789,7 @@ __device__ __forceinline__ void mlp_phase(Tile<RPW>& T, const u32x4* xnT, u32x4*
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int f0 = 16 * (c * kChunkTiles + RC * w + 2 * j2 + q) + 4 * g;
-                    constexpr int NTE = BESO_KEEP_HYBRID ? (NT & ~1) : (NT % 2 == 0 ? NT : 0);
+                    constexpr int NTE = NT & ~1;
                     {
 #pragma unroll
                         for (int t = 0; t < NTE; t += 2)
@@ -1961,21 +1918,10 @@ __device__ __forceinline__ void mlp_phase(Tile<RPW>& T, const u32x4* xnT, u32x4*
 // with gfx950's transpose read: the 16 lanes of a group address the [4 keys][16 dims] block row by row (lane i: key
 // 4g + i/4, dims 4(i%4)..+3, 8 bytes) and each receives column i of it -- four ds_read_b64_tr_b16 per sample and head
 // instead of sixteen 16-bit reads and their shifts (V stays row-major in LDS: 144-byte rows).
-#ifndef BESO_V_TR
-#define BESO_V_TR 1                  // 0: the 16-bit gather (A/B)
-#endif
 __device__ __forceinline__ uint2 v_frag(const uint16_t* qkv, int row0, int dt, int n, int g) {
-#if BESO_V_TR
     typedef s16x4 __attribute__((address_space(3))) * lds_s16x4;
     const uint16_t* p = qkv + ((size_t)2 * kQKVRows + row0 + 4 * g + (n >> 2)) * kQKVRow + 16 * dt + 4 * (n & 3);
     return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p)));
-#else
-    const uint16_t* vb = qkv + ((size_t)2 * kQKVRows + row0 + 4 * g) * kQKVRow + n + 16 * dt;
-    uint2 va;
-    va.x = (uint32_t)vb[0] | ((uint32_t)vb[kQKVRow] << 16);
-    va.y = (uint32_t)vb[2 * kQKVRow] | ((uint32_t)vb[3 * kQKVRow] << 16);
-    return va;
-#endif
 }
 
 // First two k-steps of the first head pair's QKV weights of a layer (issued before the LayerNorm that precedes
@@ -1999,9 +1945,7 @@ __device__ __forceinline__ void attn_prefetch(u32x4 (&qE)[3], u32x4 (&qO)[3], co
 // the next pair before core(B); each head's projection weights (two k-steps: all of them) are requested
 // before the barrier that precedes its core.
 // HG > 1: a virtual head is HG real heads of `hd` dims side by side (FusedDims); H counts virtual heads.
-// CORE = 1 (one sample of up to 16 NTQ tokens per workgroup): the core of a head runs on waves 0 .. NTQ-1, wave qt owning
-// query tile qt against key tiles 0 .. qt (causal), softmax over all of its keys in registers.
-template <int RPW, int KS, int HG, int NTP = kNTT, int NTQ = kNTT, int CORE = 0, class AX = AttnPlain>   // NTP: token tiles that receive the out-projection (last layer:
+template <int RPW, int KS, int HG, int NTP = kNTT, int NTQ = kNTT, class AX = AttnPlain>   // NTP: token tiles that receive the out-projection (last layer:
                                                                      // action tokens only); NTQ: token tiles that hold tokens at all
 __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsigned char* u,
                                            const u32x4* __restrict__ wqkv, const float* __restrict__ bqkv,
@@ -2046,7 +1990,7 @@ __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsig
     //   D layout: lane (i = lane&15, g) holds keys j = 4g + r  ->  causal mask, softmax over j =
     //   in-lane over r + two xor-shuffles over g; the unnormalised probabilities are already the B
     //   operand (k = 4g..4g+3) of v_mfma_f32_16x16x16_bf16 for
-    //   Y^T[d][i] = sum_j V[j][d] P[i][j]          4 x (A = V^T gathered with 16-bit LDS reads)
+    //   Y^T[d][i] = sum_j V[j][d] P[i][j]          4 x (A = V^T, v_frag)
     //   whose D layout is the B fragment of the out-projection (same k permutation as the weights).
     // token slot of (sample w, position lane & 15): looked up ONCE (it was an LDS round trip at the tail of every core's
     // serial chain); clamped index, used only where position < Tn
@@ -2075,69 +2019,7 @@ __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsig
     };
     auto core = [&](int vh) {
     const int n = ln & 15, g = ln >> 4;
-    if constexpr (CORE == 1) {
-        // ---- long sequence, one sample: S^T tiles [key tile kt][query tile w] for kt <= w, same operand roles and D
-        // layout as below (lane (i, g) holds keys 16 kt + 4 g + r of query 16 w + i), one softmax over the wave's
-        // 4 (w + 1) scores per lane, Y^T accumulated over the key tiles
-        static_assert(HG == 1, "grouped heads are a short-sequence layout");
-        if (w < NTQ && !(BESO_ABL_MASK & 16)) {
-            const uint16_t* qb = qkv + ((size_t)0 * kQKVRows + 16 * w + n) * kQKVRow + 8 * g;
-            const u32x4 q0 = *(const u32x4*)qb, q1 = *(const u32x4*)(qb + 32);
-            float e[NTQ][4];
-            float m = -INFINITY;
-            const int query = 16 * w + n;
-#pragma unroll
-            for (int kt = 0; kt < NTQ; ++kt) {
-                if (kt <= w) {                                             // wave-uniform
-                    const uint16_t* kb = qkv + ((size_t)1 * kQKVRows + 16 * kt + n) * kQKVRow + 8 * g;
-                    f32x4 sT = {0.f, 0.f, 0.f, 0.f};
-                    sT = mfma_op(*(const u32x4*)kb, q0, sT);
-                    sT = mfma_op(*(const u32x4*)(kb + 32), q1, sT);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = 16 * kt + 4 * g + r;
-                        e[kt][r] = (key <= query && key < Tn) ? sT[r] * scale_log2e : -INFINITY;
-                        m = fmaxf(m, e[kt][r]);
-                    }
-                }
-            }
-            m = rows_allreduce<true>(m);
-            float sum = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < NTQ; ++kt) {
-                if (kt <= w) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { e[kt][r] = __builtin_amdgcn_exp2f(e[kt][r] - m); sum += e[kt][r]; }
-                }
-            }
-            sum = rows_allreduce<false>(sum);
-            const float inv = __builtin_amdgcn_rcpf(sum);
-            f32x4 y[4];
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) y[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kt = 0; kt < NTQ; ++kt) {
-                if (kt <= w) {
-                    const uint2 pb = make_uint2(pack_op2(e[kt][0], e[kt][1]), pack_op2(e[kt][2], e[kt][3]));
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) {
-                        const uint2 va = v_frag(qkv, 16 * kt, dt, n, g);
-                        y[dt] = mfma_op16(va, pb, y[dt]);
-                    }
-                }
-            }
-            // (tokens in natural order: query 16 w + n sits in slot 16 w + n)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                u32x4 yb;
-                yb[0] = pack_op2(y[2 * kk][0] * inv, y[2 * kk][1] * inv);
-                yb[1] = pack_op2(y[2 * kk][2] * inv, y[2 * kk][3] * inv);
-                yb[2] = pack_op2(y[2 * kk + 1][0] * inv, y[2 * kk + 1][1] * inv);
-                yb[3] = pack_op2(y[2 * kk + 1][2] * inv, y[2 * kk + 1][3] * inv);
-                yT[((size_t)w * 2 + kk) * 64 + ln] = yb;
-            }
-        }
-    } else if constexpr (HG > 1) {
+    if constexpr (HG > 1) {
         // Grouped heads: the same fragments, but head h only sees its own dims.  S_h: the Q fragment with the
         // other heads' dims zeroed (dword granular: hd is a multiple of 4); Y rows are taken from the head they
         // belong to (lane-group granular for the same reason), already normalised by that head's 1/sum.
@@ -3239,13 +3121,8 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
     const int n = lane & 15, g = lane >> 4;
     constexpr int NTLa = NTL < NTA ? NTL : NTA;
     // the latency instances are bound by the L2 -> CU weight stream: more FC1 weight fragments in flight per wave
-#ifndef BESO_LONG_PAIRED
-#define BESO_LONG_PAIRED 1               // long-sequence instance: both heads of a pair in LDS, their cores at once (0: A/B)
-#endif
-#ifndef BESO_LONG_PF1
-#define BESO_LONG_PF1 BESO_FC1_PF        // ... in the long-sequence instance
-#endif
-    constexpr int PF1 = CORE == 1 ? BESO_LONG_PF1 : (NTA < kNTT ? BESO_LAT_PF1 : kFc1PF);
+    // (the long-sequence instance keeps kFc1PF)
+    constexpr int PF1 = CORE == 0 && NTA < kNTT ? kFc1PFLat : kFc1PF;
     // (CORE = 1 with a classifier-free pair: the workgroup's one REAL sample runs as two passes -- virtual samples 2 b, 2 b + 1)
     const bool two_pass = CORE == 1 && e.two;
     const int s0 = two_pass ? 2 * (int)blockIdx.x : (int)blockIdx.x * SPW;
@@ -3342,12 +3219,12 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
         layernorm_to_lds<RPW, KS, kWaves, true, NTA>(T, (u32x4*)(lds + L.xnT), (float*)(lds + L.red), d.D, w, lane,
                                           (const float*)(lw + d.o_bproj), st, 0, LnPlain{}, n_valid);
         stamp(st, 7);
-        if constexpr (CORE == 1 && BESO_LONG_PAIRED)
+        if constexpr (CORE == 1)
             attn_phase_long<RPW, KS, NTA>(T, (const u32x4*)(lds + L.xnT), lds + L.u, (const u32x4*)(lw + d.o_wqkv),
                                           (const float*)(lw + d.o_bqkv), (const u32x4*)(lw + d.o_wproj), d.Hv, d.hd, Tn, w, lane,
                                           qE, qO, st);
         else
-        attn_phase<RPW, KS, HG, NTA, NTA, CORE>(T, (const u32x4*)(lds + L.xnT), lds + L.u, (const u32x4*)(lw + d.o_wqkv),
+        attn_phase<RPW, KS, HG, NTA, NTA>(T, (const u32x4*)(lds + L.xnT), lds + L.u, (const u32x4*)(lw + d.o_wqkv),
                                 (const float*)(lw + d.o_bqkv), (const u32x4*)(lw + d.o_wproj), d.Hv, d.hd, Tn, n_samples, w,
                                 lane, tb, qE, qO, st);
         stamp(st, 3);
@@ -3367,7 +3244,7 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
         layernorm_to_lds<RPW, KS, kWaves, true, NTA>(T, (u32x4*)(lds + L.xnT), (float*)(lds + L.red), d.D, w, lane,
                                           (const float*)(lw + d.o_bproj), st, 0, LnPlain{}, n_valid);
         stamp(st, 7);
-        attn_phase<RPW, KS, HG, NTLa, NTA, CORE>(T, (const u32x4*)(lds + L.xnT), lds + L.u, (const u32x4*)(lw + d.o_wqkv),
+        attn_phase<RPW, KS, HG, NTLa, NTA>(T, (const u32x4*)(lds + L.xnT), lds + L.u, (const u32x4*)(lw + d.o_wqkv),
                                      (const float*)(lw + d.o_bqkv), (const u32x4*)(lw + d.o_wproj), d.Hv, d.hd, Tn, n_samples, w,
                                      lane, tb, qE, qO, st);
         stamp(st, 3);
@@ -3429,7 +3306,7 @@ __global__ __launch_bounds__(512, 2) void train_fwd_kernel(const char* __restric
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr LdsMap L = lds_map(KS);
     constexpr int NTLa = NTL < NTA ? NTL : NTA;
-    constexpr int PF1 = NTA < kNTT ? BESO_LAT_PF1 : kFc1PF;
+    constexpr int PF1 = NTA < kNTT ? kFc1PFLat : kFc1PF;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int s0 = blockIdx.x * SPW;
@@ -3471,7 +3348,7 @@ __global__ __launch_bounds__(512, 2) void train_fwd_kernel(const char* __restric
         if constexpr (RD) set_bias_rows<RPW, NTP>(T, (const float*)(lw + d.o_bproj), w, lane);
         const AttnTrain ax{(uint16_t*)(wl + a.qkv), ybuf, rows_all, rows_tail, d.D, s0, d.H, a.p_attn, inv_keep, a.seed,
                            drop_site_attn(l)};
-        attn_phase<RPW, KS, HG, NTP, NTA, 0, AttnTrain>(T, xnT, lds + L.u, (const u32x4*)(lw + d.o_wqkv),
+        attn_phase<RPW, KS, HG, NTP, NTA, AttnTrain>(T, xnT, lds + L.u, (const u32x4*)(lw + d.o_wqkv),
                                                         (const float*)(lw + d.o_bqkv), (const u32x4*)(lw + d.o_wproj), d.Hv, d.hd,
                                                         Tn, n_samples, w, lane, tb, qE, qO, st, ax);
         if constexpr (RD)

@@ -102,14 +102,11 @@ constexpr int kRowBytes32 = 528;       // fp32 k-slow image: one k-row = 128 col
 // k advance in the scalar offset.  Nothing relies on the descriptor's range check: rows / columns outside the
 // operand are read at offset 0 (their products land in outputs that are never stored), lanes past k_end are read
 // at a valid address and replaced by zeros.
-#ifndef BESO_TGEMM_WAVES
-#define BESO_TGEMM_WAVES 8                 // 8: waves as 2 x 4, 64 x 32 each; 4: 2 x 2, 64 x 64 each (A/B builds)
-#endif
-constexpr int kNW = BESO_TGEMM_WAVES;
+constexpr int kNW = 8;                     // waves of a tgemm workgroup: 2 x 4, 64 x 32 each
 constexpr int kGT = 64 * kNW;              // threads of a tgemm workgroup
 constexpr int kGL = 1024 / kGT;            // 16-byte chunks per thread, operand and stage
-constexpr int kWN = kNW == 8 ? 4 : 2;      // waves along n
-constexpr int kOcc = kNW == 8 ? 4 : 2;     // waves per SIMD asked of the compiler (two workgroups per CU)
+constexpr int kWN = 4;                     // waves along n
+constexpr int kOcc = 4;                    // waves per SIMD asked of the compiler (two workgroups per CU)
 template <int NCH> struct GOp { uint32_t voff[NCH]; };          // (the descriptor is rebuilt from the kernel argument at every use: a
                                            //  descriptor carried in VGPRs makes every load a waterfall loop)
 
@@ -600,11 +597,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(GTable t, const float
 // only the D-wide panel (dyo, xn2, y, xn1) is shared, by all tiles of its problem at the same stage.  Kitchen: 36 tiles per
 // layer, 218 per step = ONE round of one workgroup per CU (no second round to start out of step), a wave tile of 64 x 96
 // (or 96 x 64): 10 fragment reads per 24 MFMAs instead of 6 per 8.  Same operand images in LDS as tgemm_tile (k-slow
-// 16-column subtiles, ds_read_b64_tr_b16), same two-register-set pipeline, same epilogue and ones column.
+// 16-column subtiles, ds_read_b64_tr_b16), same epilogue and ones column; ONE register set in the pipeline (see the loop).
 // ---------------------------------------------------------------------------------------------
-#ifndef BESO_WG_SETS
-#define BESO_WG_SETS 1                     // register sets of the global -> LDS pipeline (A/B builds: 2)
-#endif
 template <int MT, int NT>
 __device__ __forceinline__ void wgrad_panel_tile(unsigned char* lds, const uint16_t* __restrict__ A, int lda,
                                                  const uint16_t* __restrict__ B, int ldb, int M, int N, int m0, int n0,
@@ -715,30 +709,6 @@ __device__ __forceinline__ void wgrad_panel_tile(unsigned char* lds, const uint1
 #pragma unroll
             for (int j = 0; j < NT; ++j) op_lstore<E, true, kGL>(st + A_BYTES + 8 * j * kSubBytes, tid, rb[j], b_ones[j]);
         };
-#if BESO_WG_SETS == 2
-        // two register sets, ping-pong (tgemm_tile's pipeline): two stages in flight
-        u32x4 a0[MT][kGL], b0[NT][kGL], a1[MT][kGL], b1[NT][kGL];
-        load(0, a0, b0);
-        load(1, a1, b1);
-        store(lds, a0, b0);
-        __syncthreads();
-        for (int kt = 0; kt < nk; kt += 2) {
-            load(kt + 2, a0, b0);
-            __builtin_amdgcn_sched_barrier(0);          // the loads are issued HERE (the scheduler sinks them below the MFMAs)
-            head(lds);
-            store(lds + STAGE, a1, b1);
-            body(lds);
-            __syncthreads();
-            // (no exit here when nk is odd: the stage past the end is zeros -- one wasted stage, but an exit in the middle of the
-            //  loop makes the compiler keep TWO copies of the accumulators, 64 ... 96 VGPRs)
-            load(kt + 3, a1, b1);
-            __builtin_amdgcn_sched_barrier(0);
-            head(lds + STAGE);
-            store(lds, a0, b0);
-            body(lds + STAGE);
-            __syncthreads();
-        }
-#else
         // ONE register set (a stage is 128 B per thread): the stage that landed during the previous iteration's MFMAs is written
         // to the other LDS buffer, the stage after it requested, then the MFMAs of the current one run -- every load has a whole
         // compute phase to land
@@ -756,7 +726,6 @@ __device__ __forceinline__ void wgrad_panel_tile(unsigned char* lds, const uint1
             body(lds + (kt & 1) * STAGE);
             __syncthreads();
         }
-#endif
     }
     int te = tid;
     asm volatile("" : "+v"(te));          // epilogue addresses are formed HERE, not hoisted above the k loop (spills)

@@ -29,7 +29,15 @@ for lib in "" $V/libbeso_hip_r5.so; do
 done; done > $O/${TAG}_train_ab.txt 2>&1
 # small batches: latency tables, same-box A/B, kernel stats
 ( python tools/latency_small.py kitchen; python tools/latency_small.py block_push; python tools/latency_predict.py; python tools/r05_graph_small.py 1; python tools/r05_graph_small.py 16; python tools/r05_fp32_cross.py | grep "^fp32" ) 2>&1 | grep -v amdgpu.ids > $O/${TAG}_latency.txt
-bash tools/r06_job7.sh > /dev/null 2>&1; cp $O/r06_small_ab.txt $O/${TAG}_small_ab.txt
+# ... same-box A/B of the small-batch path against round 5's library
+for rep in 1 2; do
+for lib in "" $V/libbeso_hip_r5.so; do
+  name=$(basename "${lib:-product}" .so)
+  for B in 1 4 8 16; do
+    BESO_HIP_LIB=$lib timeout 200 python tools/r05_graph_small.py $B 2>&1 | grep -v amdgpu.ids | sed "s/^/$name /"
+  done
+  BESO_HIP_LIB=$lib timeout 300 python tools/latency_predict.py 2>&1 | grep "B=" | sed "s/^/$name /"
+done; done > $O/${TAG}_small_ab.txt 2>&1
 ( bash tools/r05_small_stats.sh 1 bf16; bash tools/r05_small_stats.sh 16 bf16; bash tools/r05_small_stats.sh 1 fp32; echo '== a 3-step DDIM call at one sample'; bash tools/r05_sampler_stats.sh ) 2>&1 | grep -v amdgpu.ids > $O/${TAG}_small_batch_kernels.txt
 # the 1e-4 mode
 bash tools/r06_x3_stats.sh > $O/${TAG}_x3_stats.txt 2>&1

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Development aid: build and time compile-time variants of the fused kernel in one GPU call.
 
-    python tools/variants.py build  name1=-DFLAG=1,-DX=2  name2=@<git-rev>,...   (CPU box: hipcc cross-compile;
-                                                                       "@rev" = all of csrc/ as of that commit)
+    python tools/variants.py build  probe=-DBESO_ABL_MASK=1  r5=@7162316  old=@133ba77,-D<SWITCH>=1
+                                        (CPU box: hipcc cross-compile; "@rev" = all of csrc/ as of that commit, which is how
+                                         an A/B switch that has since left the sources is built again)
     python tools/variants.py time   [--batch 4096] [--stamps]           (GPU box: times every built variant)
 
 Variants are libbeso_hip_<name>.so under beso_amd/lib/variants/ (only fused.hip is recompiled; the other
@@ -42,15 +43,14 @@ def build(specs):
             csrc = os.path.join(tree, "beso_amd", "csrc")
             units = sorted(f[:-4] for f in os.listdir(csrc) if f.endswith(".hip"))
         else:
-            every = "-DBESO_DEV_API=1" in flags or any(f.startswith("-DBESO_TGEMM") for f in flags)     # flags of train.hip too
-            train_only = not every and any(f.startswith("-DBESO_WG_") for f in flags)                 # ... of train.hip alone
-            every = every or train_only
-            csrc, units = B.CSRC, (["train"] if train_only else list(B.UNITS) if every else ["fused", "fused_f16"])
+            every = "-DBESO_DEV_API=1" in flags or any(f.startswith("-DBESO_TGEMM_NOSTORE") for f in flags)      # flags of train.hip too
+            csrc, units = B.CSRC, (list(B.UNITS) if every else ["fused", "fused_f16"])
         procs = []
         for u in units:
             obj = os.path.join(B.OBJDIR, f"{u}_{name}.o")
-            # (-DBESO_DEV_API=1 changes the entry points of api.hip / train.hip too: such a variant rebuilds every unit)
-            extra = flags if (u in ("fused", "fused_f16") or not rev and every) else []
+            # (-DBESO_DEV_API=1 changes the entry points of api.hip / train.hip too: such a variant rebuilds every unit;
+            #  a historical tree is compiled whole, so its flags reach whichever unit reads them)
+            extra = flags if (u in ("fused", "fused_f16") or rev or every) else []
             cmd = [B._hipcc(), *B.FLAGS, *extra, "-c", os.path.join(csrc, u + ".hip"), "-o", obj]
             procs.append((u, obj, subprocess.Popen(cmd, stderr=subprocess.PIPE, text=True)))
         jobs.append((name, bool(rev), procs))
