@@ -41,7 +41,7 @@ EXPORTS = ["beso_version", "beso_status_string", "beso_last_error", "beso_num_pa
            "beso_train_workspace_bytes", "beso_grad_floats", "beso_loss_grad", "beso_gather_windows",
            "beso_loss_grad_overlap", "beso_grad_early_range", "beso_sample_ancestral", "beso_goal_mask",
            "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp", "beso_sample_solver",
-           "beso_dropout_mask", "beso_sample_traced"]
+           "beso_dropout_mask", "beso_sample_traced", "beso_rollout_begin", "beso_rollout_end"]
 # include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
 DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm"]
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
@@ -152,6 +152,11 @@ def load() -> C.CDLL:
         if hasattr(lib, "beso_log_logistic") or not os.environ.get("BESO_HIP_LIB"):
             lib.beso_log_logistic.restype = i32
             lib.beso_log_logistic.argtypes = [vp, vp, sz, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+        if hasattr(lib, "beso_rollout_begin") or not os.environ.get("BESO_HIP_LIB"):
+            lib.beso_rollout_begin.restype = i32
+            lib.beso_rollout_begin.argtypes = [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+            lib.beso_rollout_end.restype = i32
+            lib.beso_rollout_end.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
         if hasattr(lib, "beso_gather_windows") or not os.environ.get("BESO_HIP_LIB"):
             lib.beso_gather_windows.restype = i32
             lib.beso_gather_windows.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, C.c_longlong, vp, vp, i32, i32, i32,

@@ -498,6 +498,13 @@ class BesoAgent(BaseAgent):
         self.action_context.append(x_0)
         return model_pred
 
+    def vector_rollout(self, n_envs: int):
+        """A ``VectorRollout`` over ``n_envs`` environments that finish and reset independently: one sampler call per
+        environment step for all of them, the windows kept per environment on the device (beso_amd/rollout.py).  ``predict``
+        and ``reset`` keep serving the reference's single set of environments; the two share nothing but the agent."""
+        from ...rollout import VectorRollout
+        return VectorRollout(self, n_envs)
+
     @torch.no_grad()
     def visualize_ode(self, state: torch.Tensor, goal, get_mean=1000, new_sampling_steps=None, noise_scheduler=None):
         """The denoising trajectory of ``get_mean`` DDIM samples per observation (beso_agent.py:478-538): the list of

@@ -796,6 +796,31 @@ int beso_gather_windows(const float* observations, const float* actions, const i
     return BESO_OK;
 }
 
+int beso_rollout_begin(const float* obs, const uint8_t* reset, const float* noise, const float* mean, const float* den,
+                       float sigma_max, int32_t* lengths, float* obs_ctx, float* act_ctx, float* state_out, float* x_out,
+                       int n_envs, int window, int obs_dim, int act_dim, void* stream) {
+    if (!obs || !noise || !lengths || !obs_ctx || !act_ctx || !state_out || !x_out || (!mean) != (!den)) return BESO_ERR_BAD_ARG;
+    if (n_envs < 0 || window < 1 || obs_dim < 1 || act_dim < 1) return BESO_ERR_BAD_ARG;
+    if ((long long)window * ((long long)obs_dim + act_dim) * (n_envs > 1 ? n_envs : 1) > 0x7fffffffLL) return BESO_ERR_BAD_ARG;
+    if (n_envs == 0) return BESO_OK;
+    hipError_t e = launch_rollout_begin(obs, reset, noise, mean, den, sigma_max, lengths, obs_ctx, act_ctx, state_out, x_out,
+                                        n_envs, window, obs_dim, act_dim, (hipStream_t)stream);
+    if (e != hipSuccess) return record_hip_error(e, "rollout_begin_kernel", __LINE__);
+    return BESO_OK;
+}
+
+int beso_rollout_end(const float* x0, const int32_t* lengths, const double* lo, const double* hi, const float* den_y,
+                     const float* mean_y, float* act_ctx, float* pred, int n_envs, int window, int act_dim, void* stream) {
+    if (!x0 || !lengths || !lo || !hi || !act_ctx || !pred || (!den_y) != (!mean_y)) return BESO_ERR_BAD_ARG;
+    if (n_envs < 0 || window < 1 || act_dim < 1) return BESO_ERR_BAD_ARG;
+    if ((long long)window * act_dim * (n_envs > 1 ? n_envs : 1) > 0x7fffffffLL) return BESO_ERR_BAD_ARG;
+    if (n_envs == 0) return BESO_OK;
+    hipError_t e = launch_rollout_end(x0, lengths, lo, hi, den_y, mean_y, act_ctx, pred, n_envs, window, act_dim,
+                                      (hipStream_t)stream);
+    if (e != hipSuccess) return record_hip_error(e, "rollout_end_kernel", __LINE__);
+    return BESO_OK;
+}
+
 size_t beso_train_workspace_bytes(const beso_config* cfg, int batch, int t, int precision) {
     return train_workspace_bytes(cfg, batch, t, precision);
 }

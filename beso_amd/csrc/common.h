@@ -414,6 +414,12 @@ hipError_t launch_gather_windows(const float* observations, const float* actions
                                  int window, int goal_len, int goal_mode, int min_future_sep, float* obs_out,
                                  float* act_out, float* goal_out, hipStream_t s);
 hipError_t launch_log_logistic(const double* u, float* out, size_t n, double loc, double scale, double lo, double hi, hipStream_t s);
+// vectorised rollout (rollout.hip)
+hipError_t launch_rollout_begin(const float* obs_in, const unsigned char* reset, const float* noise, const float* mean,
+                                const float* den, float sigma_max, int* lengths, float* obs_ctx, float* act_ctx,
+                                float* state_out, float* x_out, int n_envs, int W, int obs, int act, hipStream_t s);
+hipError_t launch_rollout_end(const float* x0, const int* lengths, const double* lo, const double* hi, const float* den_y,
+                              const float* mean_y, float* act_ctx, float* pred, int n_envs, int W, int act, hipStream_t s);
 hipError_t launch_adam_ema(const void* chunks, int n_chunks, float* m, float* v, float* ema, float lr, float beta1,
                            float beta2, float eps, float wd, int decoupled, int step, float ema_decay, hipStream_t s);
 

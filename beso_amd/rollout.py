@@ -1,0 +1,193 @@
+"""Vectorised rollout inference: ONE sampler call per environment step for N environments whose episodes start and end
+independently (``gym.vector``, a pool of simulator processes) -- what ``BesoAgent.predict`` (reference beso_agent.py:296-388)
+does for one set of environments that are reset together.
+
+The observation / action windows live on the device as ``[N, W, .]`` contexts with a length per environment.  Every step runs
+``beso_rollout_begin`` (append the observation, write the sampler's inputs), the agent's ``sample_loop`` and
+``beso_rollout_end`` (take the newest action, clip, remember, un-scale): three launches beside the sampler's.  An environment
+with ``t < W`` observations is run as a full ``W``-slot window whose unused slots are zero: attention is causal and positions
+belong to slots, so the tokens of the ``t`` valid slots never see the padding, and the padded action slots evolve on their own
+through a sampler loop without anything reading them.  No denoiser or sampler kernel knows about ragged windows.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+
+
+class VectorRollout:
+    """``agent.vector_rollout(n_envs)``.  ``step(obs)`` returns the actions ``[N, act]`` of one environment step; ``reset`` /
+    ``set_goal`` act on all environments or on the listed ones.  The rollout reads the agent's scaler, sampler settings and
+    EMA weights at every step, so whatever ``predict`` would pick up it picks up.  GPU only: there is no CPU path.
+
+    ``lengths`` [N] int32, ``obs_ctx`` [N, W, obs] and ``act_ctx`` [N, W, act] are the device-resident state (slots at or
+    behind an environment's length are dead); ``last`` holds the latest step's ``state`` / ``x`` (the sampler's inputs),
+    ``x0`` (its result) and ``lengths`` (the live tensor), for audit."""
+
+    def __init__(self, agent, n_envs: int):
+        n_envs = int(n_envs)
+        if n_envs < 1:
+            raise ValueError("n_envs must be at least 1")
+        den = agent._hip_denoiser()
+        if den is None:
+            raise RuntimeError("beso_amd: the vectorised rollout needs the HIP denoiser (GCDenoiser around DiffusionGPT)")
+        first = next(iter(agent.model.parameters()), None)
+        if first is None or not first.is_cuda:
+            raise RuntimeError("beso_amd: the vectorised rollout runs on the GPU only (no CPU path); move the model to the MI355X")
+        shape = den.inner_model.shape(den.sigma_data)
+        self.agent = agent
+        self.lib = _lib.load()
+        self.device = first.device
+        self.n_envs = n_envs
+        self.window = max(1, int(agent.window_size))
+        if self.window > shape.obs_seq_len:
+            raise ValueError(f"window_size {self.window} exceeds the model's obs_seq_len {shape.obs_seq_len}")
+        self.obs_dim, self.act_dim, self.goal_len = shape.obs_dim, shape.act_dim, shape.goal_seq_len
+        dev, N, W = self.device, n_envs, self.window
+        self.lengths = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.obs_ctx = torch.zeros((N, W, self.obs_dim), dtype=torch.float32, device=dev)
+        self.act_ctx = torch.zeros((N, W, self.act_dim), dtype=torch.float32, device=dev)
+        self.goal = None
+        self.last = {}
+        self._reset = torch.ones(N, dtype=torch.uint8, device=dev)
+        self._reset_pending = True
+        self._rows = torch.arange(N, device=dev)
+        self._plan_key = None
+        self._plan = None
+
+    # ------------------------------------------------------------------ episode control
+    def _ids(self, env_ids):
+        ids = torch.as_tensor(env_ids, dtype=torch.long).reshape(-1)
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.n_envs):
+            raise IndexError(f"environment ids must be in [0, {self.n_envs})")
+        return ids.to(self.device)
+
+    def reset(self, env_ids=None) -> None:
+        """Mark environments (default: all) for reset: their windows start empty at their next step."""
+        if env_ids is None:
+            self._reset.fill_(1)
+        else:
+            self._reset.index_fill_(0, self._ids(env_ids), 1)
+        self._reset_pending = True
+
+    @torch.no_grad()
+    def set_goal(self, goal, env_ids=None) -> None:
+        """Raw goals: ``[G, obs]`` for the listed environments (default: all of them), or one per environment as
+        ``[N, G, obs]`` (``[len(env_ids), G, obs]``).  Scaled once, as ``predict`` scales its goal, and kept on the device."""
+        agent = self.agent
+        goal = agent.scaler.scale_input(torch.as_tensor(goal)).to(device=self.device, dtype=torch.float32)
+        if goal.shape[-1] == 10:                                           # base_agent.py:119-120, as process_batch
+            keep = torch.ones(10, dtype=torch.bool, device=self.device)
+            keep[[2, 5, 6, 7, 8, 9]] = False
+            goal = torch.where(keep, goal, 0.0)
+        if goal.dim() not in (2, 3) or goal.shape[-1] != self.obs_dim or (self.goal_len and goal.shape[-2] != self.goal_len):
+            raise ValueError(f"goal must be [{self.goal_len}, {self.obs_dim}] or [n, {self.goal_len}, {self.obs_dim}], "
+                             f"got {tuple(goal.shape)}")
+        if self.goal is None:
+            self.goal = torch.zeros((self.n_envs,) + tuple(goal.shape[-2:]), dtype=torch.float32, device=self.device)
+        if env_ids is None:
+            if goal.dim() == 3 and goal.shape[0] != self.n_envs:
+                raise ValueError(f"expected {self.n_envs} goals, got {goal.shape[0]}")
+            self.goal.copy_(goal if goal.dim() == 3 else goal.unsqueeze(0).expand_as(self.goal))
+        else:
+            ids = self._ids(env_ids)
+            if goal.dim() == 3 and goal.shape[0] != ids.numel():
+                raise ValueError(f"expected {ids.numel()} goals, got {goal.shape[0]}")
+            self.goal[ids] = goal
+
+    # ------------------------------------------------------------------ what of the scaler the two launches can take over
+    def _scaler_plan(self):
+        """(x statistics for beso_rollout_begin or None, (lo, hi, den_y, mean_y) for beso_rollout_end or None), rebuilt when
+        the scaler, one of its tensors or a tensor's version changes.  The launches take fp32 statistics and float64 bounds
+        of the package's Scaler; anything else is served by the scaler's own methods."""
+        from .networks.scaler.scaler_class import Scaler
+        sc = self.agent.scaler
+        parts = tuple(getattr(sc, k, None) for k in ("x_mean", "x_std", "y_mean", "y_std", "y_bounds_tensor"))
+        key = (sc, getattr(sc, "scale_data", None)) + tuple((p, getattr(p, "_version", None)) for p in parts)
+        old = self._plan_key
+        if old is not None and len(old) == len(key) and all(
+                (a[0] is b[0] and a[1] == b[1]) if isinstance(a, tuple) else (a is b) for a, b in zip(old, key)):
+            return self._plan
+        dev = self.device
+        f32 = lambda v, n: (isinstance(v, torch.Tensor) and v.device == dev and v.dtype == torch.float32     # noqa: E731
+                            and v.dim() == 1 and v.numel() == n and v.is_contiguous())
+        ours = isinstance(sc, Scaler) and all(getattr(type(sc), m) is getattr(Scaler, m)
+                                              for m in ("scale_input", "clip_action", "inverse_scale_output", "_den"))
+        xs = ys = None
+        if ours and sc.scale_data and not (self.obs_dim == 7 and len(sc.x_mean) == 30):
+            mean, den = sc.x_mean, sc._den("x")
+            if f32(mean, self.obs_dim) and f32(den, self.obs_dim):
+                xs = (mean, den)
+        b = parts[4]
+        if ours and isinstance(b, torch.Tensor) and b.device == dev and b.dtype == torch.float64 and tuple(b.shape) == (2, self.act_dim):
+            lo, hi = (b[0] * 1.1).contiguous(), (b[1] * 1.1).contiguous()        # clip_action's bounds, in float64
+            if not sc.scale_data:
+                ys = (lo, hi, None, None)
+            elif f32(sc.y_mean, self.act_dim) and f32(sc._den("y"), self.act_dim):
+                ys = (lo, hi, sc._den("y"), sc.y_mean)
+        self._plan_key, self._plan = key, (xs, ys)
+        return self._plan
+
+    # ------------------------------------------------------------------ one environment step
+    @torch.no_grad()
+    def step(self, obs, new_sampler_type=None, new_sampling_steps=None, noise_scheduler=None, noise=None) -> torch.Tensor:
+        """Raw observations ``[N, obs]`` (device or host) -> actions ``[N, act]``.  ``noise`` ``[N, 1, act]`` is the x_T draw
+        of the newest action; None draws ``torch.randn((N, 1, act), device=...)``, the draw ``predict`` makes."""
+        agent, dev, N, W = self.agent, self.device, self.n_envs, self.window
+        xs, ys = self._scaler_plan()
+        obs = torch.as_tensor(obs)
+        if xs is None:
+            obs = agent.scaler.scale_input(obs)
+        obs = obs.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(obs.shape) != (N, self.obs_dim):
+            raise ValueError(f"obs must be [{N}, {self.obs_dim}], got {tuple(obs.shape)}")
+        if noise is None:
+            noise = torch.randn((N, 1, self.act_dim), device=dev)
+        else:
+            noise = torch.as_tensor(noise).to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(noise.shape) != (N, 1, self.act_dim):
+                raise ValueError(f"noise must be [{N}, 1, {self.act_dim}], got {tuple(noise.shape)}")
+        if self.goal_len and self.goal is None:
+            raise ValueError("set_goal() must be called before the first step of a goal-conditioned model")
+        sampler_type = agent.sampler_type if new_sampler_type is None else new_sampler_type
+        n_steps = agent.num_sampling_steps if new_sampling_steps is None else new_sampling_steps
+        noise_scheduler = agent.noise_scheduler if noise_scheduler is None else noise_scheduler
+        state = torch.empty((N, W, self.obs_dim), dtype=torch.float32, device=dev)
+        x = torch.empty((N, W, self.act_dim), dtype=torch.float32, device=dev)
+        ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(self.lib.beso_rollout_begin(
+                obs.data_ptr(), self._reset.data_ptr() if self._reset_pending else None, noise.data_ptr(),
+                ptr(xs and xs[0]), ptr(xs and xs[1]), float(agent.sigma_max), self.lengths.data_ptr(), self.obs_ctx.data_ptr(),
+                self.act_ctx.data_ptr(), state.data_ptr(), x.data_ptr(), N, W, self.obs_dim, self.act_dim, stream), "rollout_begin")
+        if self._reset_pending:
+            self._reset.zero_()
+            self._reset_pending = False
+        with agent._ema_scope():
+            if agent.model.training:
+                agent.model.eval()
+            sigmas = agent.get_noise_schedule(n_steps, noise_scheduler)
+            x0 = agent.sample_loop(sigmas, x, state, self.goal, sampler_type)
+        if x0.dtype != torch.float32 or not x0.is_contiguous():
+            x0 = x0.to(torch.float32).contiguous()
+        if tuple(x0.shape) != (N, W, self.act_dim):
+            raise RuntimeError(f"the sampler returned {tuple(x0.shape)}, expected {(N, W, self.act_dim)}")
+        if ys is not None:
+            pred = torch.empty((N, self.act_dim), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                _lib.check(self.lib.beso_rollout_end(
+                    x0.data_ptr(), self.lengths.data_ptr(), ys[0].data_ptr(), ys[1].data_ptr(), ptr(ys[2]), ptr(ys[3]),
+                    self.act_ctx.data_ptr(), pred.data_ptr(), N, W, self.act_dim, stream), "rollout_end")
+        else:
+            # a scaler the launch cannot serve (other dtypes, another class): its own methods on the gathered rows
+            slot = (self.lengths - 1).long()
+            clipped = agent.scaler.clip_action(x0[self._rows, slot])
+            self.act_ctx[self._rows, slot] = clipped
+            pred = agent.scaler.inverse_scale_output(clipped)
+        self.last = {"state": state, "x": x, "lengths": self.lengths, "x0": x0}
+        return pred

@@ -28,6 +28,8 @@
  *   beso_denoise_vjp    <- GCDenoiser.forward + torch.autograd.grad w.r.t. the action   k_diffusion/gc_sampling.py:480-485
  *   beso_adam_step      <- optimizer.step() + ema_helper.update()      beso_agent.py:236-244
  *   beso_gather_windows <- TrajectorySlicerDataset.__getitem__ x batch envs/dataloaders/trajectory_loader.py:160-197
+ *   beso_rollout_begin / beso_rollout_end <- the window bookkeeping around the sampler call of BesoAgent.predict, for N
+ *                          environments with independent resets            agents/diffusion_agents/beso_agent.py:296-388
  *
  * Conventions
  *   - plain C, plain pointers and sizes.  No torch types.  `stream` is a hipStream_t passed as void*.
@@ -378,6 +380,45 @@ int beso_gather_windows(const float* observations, const float* actions, const i
                         int obs_dim, int act_dim, const int* slice_traj, const int* slice_start, long long n_slices,
                         const long long* batch_slices, const long long* draws, int batch, int window, int goal_len,
                         int goal_mode, int min_future_sep, float* obs_out, float* act_out, float* goal_out, void* stream);
+
+/* The vectorised rollout: BesoAgent.predict's window bookkeeping (beso_agent.py:296-388) for n_envs environments whose episodes
+ * start and end independently, one launch in front of the sampler call and one behind it.  The rollout's state is caller-owned
+ * DEVICE memory that lives from step to step:
+ *   lengths [n_envs] int32            observations in each environment's window, 0 ... window
+ *   obs_ctx [n_envs, window, obs_dim] the scaled observations (the reference's deque(maxlen = window))
+ *   act_ctx [n_envs, window, act_dim] the clipped actions in the scaled domain, slot j beside observation slot j (the
+ *                                     reference's deque(maxlen = window - 1): the slot of the newest observation is filled by
+ *                                     beso_rollout_end)
+ * Slots at or behind an environment's length are never read; the buffers may start uninitialised once every environment's
+ * first step carries its reset flag (or `lengths` starts at zero).
+ *
+ * beso_rollout_begin -- one environment step's inputs:
+ *   reset [n_envs] uint8, may be NULL: where set, lengths[n] = 0 first (the reference's reset()).
+ *   obs [n_envs, obs_dim] raw observations, scaled as (x - mean[c]) / den[c] -- beso_scale_rows' subtraction and correctly
+ *   rounded division, the same bits; mean / den [obs_dim] both NULL: passed through.
+ *   The scaled row is appended: with lengths[n] < window into slot lengths[n], and the length grows by one; otherwise both
+ *   contexts move down one slot (the oldest leaves) and the row goes into slot window - 1.  The move happens in place and reads
+ *   nothing the launch has overwritten.  With t = lengths[n] after the append, the sampler's inputs are written as FULL windows:
+ *   state_out [n_envs, window, obs_dim]  the context, slots >= t zero
+ *   x_out     [n_envs, window, act_dim]  slots 0 .. t-2 the previous actions, slot t-1 = noise[n] * sigma_max (one fp32 multiply:
+ *                                        `torch.randn(...) * self.sigma_max`, noise [n_envs, act_dim]), slots >= t zero
+ *   Attention is causal and positions belong to slots, so the tokens of slots < t never see the padding: rows < t of a
+ *   denoiser or sampler call on these windows equal the t-slot call to fp32 rounding.  Every element of both outputs is written.
+ *
+ * beso_rollout_end -- behind the sampler call, with x0 [n_envs, window, act_dim] its result and t = lengths[n]:
+ *   a = x0[n, t-1, :] is clipped to [lo, hi] (float64 [act_dim], as Scaler.clip_action's torch.clamp against float64 bounds:
+ *   compared in double, rounded to fp32), stored into act_ctx[n, t-1] and written un-scaled to pred [n_envs, act_dim] as
+ *   clipped * den_y + mean_y -- a separately rounded multiply and add, Scaler.inverse_scale_output's bits; den_y / mean_y
+ *   [act_dim] both NULL: pred is the clipped row.
+ *
+ * No workspace.  BESO_ERR_BAD_ARG before anything is enqueued: a NULL required pointer, only one of a statistics pair, window,
+ * obs_dim or act_dim < 1, n_envs < 0, more than 2^31 - 1 context elements.  n_envs == 0 returns BESO_OK and enqueues nothing.
+ * A length outside [0, window] found on the device is clamped into it.                                                    */
+int beso_rollout_begin(const float* obs, const uint8_t* reset, const float* noise, const float* mean, const float* den,
+                       float sigma_max, int32_t* lengths, float* obs_ctx, float* act_ctx, float* state_out, float* x_out,
+                       int n_envs, int window, int obs_dim, int act_dim, void* stream);
+int beso_rollout_end(const float* x0, const int32_t* lengths, const double* lo, const double* hi, const float* den_y,
+                     const float* mean_y, float* act_ctx, float* pred, int n_envs, int window, int act_dim, void* stream);
 
 /* rand_log_logistic (k_diffusion/utils.py:178-185), the sigma density of the shipped training configs, behind the caller's
  * uniform draw: out[i] = (float) exp(logit(u[i] * (cdf_hi - cdf_lo) + cdf_lo) * scale + loc), every operation in float64 as the

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Rollout inference per environment step: ``VectorRollout.step`` for N environments in one sampler call against N sequential
+``BesoAgent.predict`` calls at B = 1 (the reference's rollout), in the same process.  Kitchen shape, bf16, DDIM-3, EMA image.
+
+    python tools/bench_rollout.py [--envs 1,16,100,256] [--steps 200] [--reps 7] [--out profiles/rollout_bench.jsonl]
+
+Per N, every repetition times `steps` consecutive environment steps of each form, alternating the forms:
+  wall_ms    host clock around the steps, a device synchronise on both sides -- what a rollout loop pays per step
+  event_ms   device events on the stream around the same steps: from the first launch to the end of the last kernel, the
+             idle time between launches of a host-bound loop included (not a sum of kernel times)
+Both are divided by `steps`; the record holds the median over the repetitions and the extremes.  Observations come from the
+host, as a simulator hands them over; windows are full and no environment resets inside the timed steps, except in the
+`reset_every_step` figure, where one environment is reset in front of every step (two small fill launches more).
+``predict`` runs one set of environments per agent, so N sequential calls are timed as `steps` calls of one B = 1 agent and
+multiplied by N (`predict_n_ms`).  One JSON line per N is appended to --out."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from bench import build_model  # noqa: E402
+from beso_amd import synthetic as O  # noqa: E402
+from _agent import build_agent  # noqa: E402
+from beso_amd.networks.scaler.scaler_class import Scaler  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def timed(fn, steps):
+    """(wall ms, event ms) per step of `steps` calls of fn(i)."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    a.record()
+    for i in range(steps):
+        fn(i)
+    b.record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) * 1e3
+    return wall / steps, a.elapsed_time(b) / steps
+
+
+def stats(v):
+    return {"median": round(float(np.median(v)), 4), "min": round(float(np.min(v)), 4), "max": round(float(np.max(v)), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", default="1,16,100,256")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rollout_bench.jsonl"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_rollout.py measures on the GPU; none found")
+    cfg = O.SHAPES["kitchen"]
+    w = O.make_weights(cfg, seed=0, std=0.02)
+    agent = build_agent(cfg, lambda: build_model(cfg, w, "bf16", DEV), device=DEV, sampler="ddim")
+    rng = np.random.default_rng(0)
+    agent.get_scaler(Scaler(rng.standard_normal((256, cfg.obs_dim)).astype(np.float32),
+                            rng.standard_normal((256, cfg.act_dim)).astype(np.float32), True, DEV))
+    agent.set_bounds(agent.scaler)
+    box = {"device": torch.cuda.get_device_name(0), "hip": torch.version.hip, "torch": torch.__version__}
+    goal = torch.randn(cfg.goal_seq_len, cfg.obs_dim)
+    warm = max(20, 3 * cfg.obs_seq_len)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    for N in [int(v) for v in a.envs.split(",")]:
+        obs = [torch.randn(N, cfg.obs_dim) for _ in range(a.steps)]
+        one = [o[:1].clone() for o in obs]
+        roll = agent.vector_rollout(N)
+        roll.set_goal(goal)
+        agent.reset()
+        batch = lambda i: {"observation": one[i], "goal_observation": goal}      # noqa: E731
+        step = lambda i: roll.step(obs[i])                                       # noqa: E731
+
+        def step_reset(i):
+            roll.reset([i % N])
+            roll.step(obs[i])
+
+        for i in range(warm):
+            step(i % a.steps)
+            agent.predict(batch(i % a.steps))
+        t = {"step": [], "step_reset": [], "predict": []}
+        for _ in range(a.reps):
+            t["step"].append(timed(step, a.steps))
+            t["predict"].append(timed(lambda i: agent.predict(batch(i)), a.steps))
+            t["step_reset"].append(timed(step_reset, a.steps))
+            for i in range(cfg.obs_seq_len):                                     # (full windows again)
+                step(i)
+        wall = lambda k: stats([v[0] for v in t[k]])                             # noqa: E731
+        event = lambda k: stats([v[1] for v in t[k]])                            # noqa: E731
+        r = {"bench": "rollout", "config": "kitchen", "precision": "bf16", "sampler": "ddim", "sampling_steps": 3,
+             "n_envs": N, "steps_per_rep": a.steps, "reps": a.reps,
+             "step_wall_ms": wall("step"), "step_event_ms": event("step"),
+             "reset_every_step_wall_ms": wall("step_reset"), "reset_every_step_event_ms": event("step_reset"),
+             "predict_wall_ms": wall("predict"), "predict_event_ms": event("predict")}
+        r["predict_n_ms"] = round(N * r["predict_wall_ms"]["median"], 4)
+        r["step_over_predict"] = round(r["step_wall_ms"]["median"] / r["predict_wall_ms"]["median"], 3)
+        r["speedup_over_n_predicts"] = round(r["predict_n_ms"] / r["step_wall_ms"]["median"], 2)
+        r.update(box)
+        line = json.dumps(r)
+        print(line, flush=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
