@@ -17,6 +17,7 @@ FLAG_UNCOND = 1
 PLAN_PER_OP, PLAN_BLOCKS, PLAN_SMALL, PLAN_FUSED = 0x10, 0x20, 0x40, 0x80
 PLAN_SPW2, PLAN_SPW4, PLAN_SPW8 = 0x100, 0x200, 0x300
 SAMPLE_STEPWISE = 0x1000
+FLAG_LAST_ACTION_ONLY = 0x2000     # beso_loss_fwd: only the last step of every window is scored
 TRAIN_LAST_ACTION_ONLY, TRAIN_PLAN_PER_OP, TRAIN_PLAN_TILES = 1, 2, 4
 SAMPLER_IDS = {"ddim": 0, "euler": 1, "heun": 2}
 # beso_sample_solver (include/beso_hip.h BESO_SOLVER_*): the gc_sampling.py function names without "sample_"
@@ -41,7 +42,8 @@ EXPORTS = ["beso_version", "beso_status_string", "beso_last_error", "beso_num_pa
            "beso_train_workspace_bytes", "beso_grad_floats", "beso_loss_grad", "beso_gather_windows",
            "beso_loss_grad_overlap", "beso_grad_early_range", "beso_sample_ancestral", "beso_goal_mask",
            "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp", "beso_sample_solver",
-           "beso_dropout_mask", "beso_sample_traced", "beso_rollout_begin", "beso_rollout_end"]
+           "beso_dropout_mask", "beso_sample_traced", "beso_rollout_begin", "beso_rollout_end",
+           "beso_loss_fwd_workspace_bytes", "beso_loss_fwd"]
 # include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
 DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm"]
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
@@ -146,6 +148,11 @@ def load() -> C.CDLL:
         if hasattr(lib, "beso_denoise_vjp") or not os.environ.get("BESO_HIP_LIB"):
             lib.beso_denoise_vjp.restype = i32
             lib.beso_denoise_vjp.argtypes = [cfgp, C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
+        if hasattr(lib, "beso_loss_fwd") or not os.environ.get("BESO_HIP_LIB"):
+            lib.beso_loss_fwd_workspace_bytes.restype = sz
+            lib.beso_loss_fwd_workspace_bytes.argtypes = [cfgp, i32, i32, i32]
+            lib.beso_loss_fwd.restype = i32
+            lib.beso_loss_fwd.argtypes = [cfgp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
         if hasattr(lib, "beso_scale_rows") or not os.environ.get("BESO_HIP_LIB"):
             lib.beso_scale_rows.restype = i32
             lib.beso_scale_rows.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp]

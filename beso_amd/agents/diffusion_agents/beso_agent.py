@@ -454,6 +454,89 @@ class BesoAgent(BaseAgent):
             mse = nn.functional.mse_loss(x_0, action, reduction="none").mean().item()
         return mse
 
+    # ------------------------------------------------------------------ held-out denoising loss
+    def _held_out_draws(self, action, n_sigma, sigma, noise, generator):
+        """(sigma or None, noise) of a held-out loss call: what the caller passed, else a draw from the training density /
+        N(0, I) -- from ``generator`` when given (the density functions take none: they draw from the global generator inside a
+        forked RNG scope seeded from it, and the global stream is left where it was)."""
+        dev = action.device
+        if noise is None:
+            noise = (torch.randn_like(action) if generator is None else
+                     torch.randn(action.shape, generator=generator, device=generator.device, dtype=action.dtype).to(dev))
+        else:
+            noise = torch.as_tensor(noise, dtype=action.dtype, device=dev)
+        if sigma is not None or n_sigma == 0:
+            return (None if sigma is None else torch.as_tensor(sigma, dtype=torch.float32, device=dev).reshape(-1)), noise
+        density = self.make_sample_density()
+        if generator is None:
+            return density(shape=(n_sigma,), device=self.device), noise
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=generator.device).item())
+        with torch.random.fork_rng(devices=[dev] if dev.type == "cuda" else []):
+            torch.manual_seed(seed)
+            return density(shape=(n_sigma,), device=self.device), noise
+
+    def _held_out_model(self):
+        den = self._hip_denoiser()
+        if den is None:
+            raise NotImplementedError("the held-out denoising loss needs the beso_amd GCDenoiser / DiffusionGPT (the HIP kernels)")
+        return den
+
+    @torch.no_grad()
+    def validation_loss(self, batch: dict, sigma=None, noise=None, generator=None) -> float:
+        """The denoising (score-matching) loss on a held-out batch: ``GCDenoiser.loss`` of the eval-mode network on the EMA
+        weights (with ``use_ema``), gradient-free, as ONE ``beso_loss_fwd`` call -- the model's own error, without the sampler
+        error and the x_T draw that ``evaluate`` mixes in.  ``batch`` is a training-style batch (``process_batch(batch,
+        predict=False)``); ``sigma`` [B] defaults to a draw from the training density (``make_sample_density``), ``noise``
+        to ``randn_like(action)``, both from ``generator`` when given.  An agent built with ``pred_last_action_only`` scores the last step of
+        every window only (``GCDenoiser.loss(..., pred_last_action_only=True)``), the step ``evaluate`` compares and ``predict`` keeps --
+        NOT what ``train_step`` optimises: like the reference's, it calls ``model.loss`` without the keyword and scores the
+        whole window; ``GCDenoiser.loss`` under ``torch.no_grad()`` gives that full-window value.
+        ``steps``, the parameters, the optimizer and the EMA are left alone; the module is left in eval mode, as ``evaluate``
+        leaves it (``train_step`` switches back to ``train()`` itself).  Fixed-order
+        reductions: the same inputs give the same bits."""
+        den = self._held_out_model()
+        state, action, goal = self.process_batch(batch, predict=False)
+        sigma, noise = self._held_out_draws(action, len(action), sigma, noise, generator)
+        with self._ema_scope():
+            if self.model.training:
+                self.model.eval()
+            return den.loss(state, action, goal, noise.clone(), sigma, pred_last_action_only=self.pred_last_action_only).item()
+
+    @torch.no_grad()
+    def loss_by_sigma(self, batch: dict, sigmas, noise=None, generator=None):
+        """The held-out denoising loss as a function of the noise level: every one of the B windows of ``batch`` at every one
+        of the K values of ``sigmas`` -> ``(curve [K], table [K, B])``, ``table[k, b]`` the loss of window b at ``sigmas[k]``
+        and ``curve[k]`` its mean over the batch.  ONE ``beso_loss_fwd`` call over K * B virtual samples (state, goal and
+        action repeated K times, sigma ``repeat_interleave``d).  ``noise`` is [B, t, act] (the same draw at every level: the
+        curve then varies with sigma alone) or [K, B, t, act]; default N(0, I) of the first form, from ``generator`` when
+        given.  EMA weights with ``use_ema``; ``pred_last_action_only``, the module's mode and the training state as in
+        ``validation_loss``."""
+        den = self._held_out_model()
+        state, action, goal = self.process_batch(batch, predict=False)
+        B = len(action)
+        sigmas = torch.as_tensor(sigmas, dtype=torch.float32, device=action.device).reshape(-1)
+        K = sigmas.numel()
+        if K < 1:
+            raise ValueError("loss_by_sigma: at least one sigma")
+        if noise is not None and tuple(noise.shape) == (K,) + tuple(action.shape):
+            noise = torch.as_tensor(noise, dtype=action.dtype, device=action.device).reshape((K * B,) + tuple(action.shape[1:])).clone()
+        else:
+            _, noise = self._held_out_draws(action, 0, None, noise, generator)
+            if noise.shape != action.shape:
+                raise ValueError(f"loss_by_sigma: noise must be {tuple(action.shape)} or {(K,) + tuple(action.shape)}")
+            noise = noise.repeat(K, 1, 1)
+        if goal is not None and goal.dim() == 2:
+            goal = goal.unsqueeze(0)
+        if goal is not None and goal.shape[0] == 1 and B > 1:
+            goal = goal.expand(B, -1, -1)
+        with self._ema_scope():
+            if self.model.training:
+                self.model.eval()
+            rows = den.loss_per_sample(state.repeat(K, 1, 1), action.repeat(K, 1, 1), None if goal is None else goal.repeat(K, 1, 1),
+                                       noise, sigmas.repeat_interleave(B), pred_last_action_only=self.pred_last_action_only)
+        table = rows.view(K, B)
+        return table.mean(dim=1), table
+
     # ------------------------------------------------------------------ rollout inference
     def reset(self):
         self.obs_context.clear()

@@ -45,7 +45,10 @@ class GCDenoiser(nn.Module):
 
     def loss(self, state, action, goal, noise, sigma, **kwargs):
         """Score-matching objective (score_wrappers.py:45-79).  Mutates ``noise`` in place when
-        ``pred_last_action_only`` is set, like the reference (:63)."""
+        ``pred_last_action_only`` is set, like the reference (:63).  Under autograd: the HIP training step.  With autograd
+        disabled and the module in eval mode: the held-out objective on the inference path (``beso_loss_fwd``), a plain
+        tensor without ``grad_fn``, in the module's precision and on the weights ``packed_weights()`` returns (the EMA image
+        inside ``use_weights``); in training mode that call raises -- the masked, dropped-out loss is a training-step quantity."""
         last_only = bool(kwargs.pop("pred_last_action_only", False))
         if last_only:
             noise[:, :-1, :] = 0                                   # in place, like the reference (:63)
@@ -55,6 +58,9 @@ class GCDenoiser(nn.Module):
             # torch-op evaluation behind it: what the kernels cannot serve raises
             if kwargs:
                 raise ValueError(f"GCDenoiser.loss: unsupported keyword arguments {sorted(kwargs)} for the HIP training step")
+            if not torch.is_grad_enabled():
+                # the held-out objective: the eval-mode network on the inference path (beso_loss_fwd), no gradient anywhere
+                return self._loss_forward(state, action, goal, noise, sigma, last_only=last_only)
             step = self.hip_train_step(state, action, goal, noise, sigma)
             if step is None:
                 raise ValueError("GCDenoiser.loss: " + self._why_no_hip_step(state, action, goal, noise, sigma))
@@ -68,6 +74,29 @@ class GCDenoiser(nn.Module):
         if last_only:
             return (out[:, -1, :] - target[:, -1, :]).pow(2).mean()
         return (out - target).pow(2).flatten(1).mean()
+
+    def loss_per_sample(self, state, action, goal, noise, sigma, uncond: bool = False, pred_last_action_only: bool = False):
+        """[B]: every sample's score-matching loss on the eval-mode network (``beso_loss_fwd``) -- the mean of
+        (F(c_in * noised) - target)^2 over the sample's window, or over its last step with ``pred_last_action_only`` (which
+        zeroes ``noise[:, :-1]`` in place, as ``loss`` does).  Their mean is the scalar ``loss`` returns under
+        ``torch.no_grad()``.  No gradient is computed; the module must be in eval mode."""
+        if pred_last_action_only:
+            noise[:, :-1, :] = 0
+        return self._loss_forward(state, action, goal, noise, sigma, uncond=uncond, last_only=bool(pred_last_action_only),
+                                  per_sample=True)[1]
+
+    def _loss_forward(self, state, action, goal, noise, sigma, uncond=False, last_only=False, per_sample=False):
+        inner = self.inner_model
+        if not isinstance(inner, DiffusionGPT):
+            raise NotImplementedError("GCDenoiser: the gradient-free loss needs a beso_amd DiffusionGPT inside (the HIP kernels)")
+        if inner.training:
+            raise ValueError("GCDenoiser.loss: called with autograd disabled on a module in training mode (the masked, "
+                             "dropped-out loss is a training-step quantity); call eval() for the held-out loss")
+        if not (torch.is_tensor(action) and action.is_cuda):
+            raise ValueError("GCDenoiser.loss: the inputs are not on the GPU (beso_amd has no CPU path)")
+        with torch.no_grad():
+            return inner.runtime(self.sigma_data).loss(inner.packed_weights(), state, action, goal, noise, sigma,
+                                                       uncond=bool(uncond), last_only=bool(last_only), per_sample=per_sample)
 
     # -- HIP training step ---------------------------------------------------------------------
     def hip_train_step(self, state, action, goal, noise, sigma):
@@ -101,8 +130,6 @@ class GCDenoiser(nn.Module):
 
     def _why_no_hip_step(self, state, action, goal, noise, sigma) -> str:
         inner = self.inner_model
-        if not torch.is_grad_enabled():
-            return "called with autograd disabled (the loss is a training-step quantity)"
         if not HipTrainStep.supported(inner):
             return f"embed_dim={inner.embed_dim} is not a multiple of 8 (the HIP training kernels need that)"
         if not (torch.is_tensor(action) and action.is_cuda):

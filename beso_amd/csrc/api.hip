@@ -298,6 +298,42 @@ static int forward(const beso_config* cfg, const void* packed, int precision, co
     return r;
 }
 
+// Whether forward() has kernels for a raw-network (no preconditioning, no classifier-free pair) call of this shape, precision
+// and plan: its BESO_ERR_UNSUPPORTED decision alone, for an entry point that enqueues work of its own in front of the forward
+// and has made the other checks itself.  Nothing is enqueued.
+static int forward_supported(const beso_config* cfg, int precision, int batch, int t, int flags) {
+    Layout lay;
+    if (!make_layout(cfg, precision, &lay)) return BESO_ERR_BAD_CONFIG;
+    FwdArgs a{};
+    a.batch = a.vbatch = batch; a.t = t; a.T = 1 + lay.G + 2 * t;
+    a.uncond_from = (flags & BESO_FLAG_UNCOND) ? 0 : batch;
+    a.cond_lambda = 1.0f; a.sigma_data = cfg->sigma_data;
+    a.plan = flags & BESO_PLAN_MASK;
+    if (precision == BESO_PREC_FP16) a.plan &= ~(BESO_PLAN_PER_OP | BESO_PLAN_BLOCKS);
+    if (small_wanted(lay, a, precision)) return BESO_OK;
+    const int level = precision == BESO_PREC_FP16 ? fused_level_f16(lay, a, BESO_PREC_BF16) : fused_level(lay, a, precision);
+    if (precision == BESO_PREC_FP16 && level != 2) return BESO_ERR_UNSUPPORTED;
+    if (precision == BESO_PREC_BF16X3 && level != 2 && !(level == 1 && fused_has_lin_blocks(lay, precision))) return BESO_ERR_UNSUPPORTED;
+    return BESO_OK;
+}
+
+// beso_loss_fwd's workspace: the forward's, then the forward's input, its output and the per-sample values
+struct LossWorkspace { size_t forward, scaled, pred, rows, total; };
+static bool loss_workspace(const beso_config* cfg, int batch, int t, int precision, LossWorkspace* w) {
+    Layout lay;
+    Workspace ws;
+    if (!make_layout(cfg, precision, &lay) || !make_workspace(cfg, lay, batch, t, precision, 0, &ws)) return false;
+    const size_t na = (size_t)batch * t * lay.act;
+    size_t cur = 0;
+    carve(cur, ws.total);
+    w->forward = ws.total;
+    w->scaled = carve(cur, sizeof(float) * na);
+    w->pred = carve(cur, sizeof(float) * na);
+    w->rows = carve(cur, sizeof(float) * (size_t)batch);
+    w->total = cur;
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // sampling loops: each sampler entry point lists its network evaluations (a plan) and one driver runs the list
 // ---------------------------------------------------------------------------------------------
@@ -873,6 +909,43 @@ int beso_denoise_vjp(const beso_config* cfg, const float* const* params, int n_p
         snprintf(g_last_error, sizeof(g_last_error), "%s (%d) at train.hip:%d", hipGetErrorName(e), (int)e, line);
     }
     return st;
+}
+
+size_t beso_loss_fwd_workspace_bytes(const beso_config* cfg, int batch, int t, int precision) {
+    LossWorkspace w;
+    return loss_workspace(cfg, batch, t, precision, &w) ? w.total : 0;
+}
+
+int beso_loss_fwd(const beso_config* cfg, const void* packed, int precision, const float* state, const float* action,
+                  const float* goal, const float* noise, const float* sigma, float* loss_out, float* per_sample_out,
+                  int batch, int t, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+    int st = validate_config(cfg);
+    if (st != BESO_OK) return st;
+    if (precision != BESO_PREC_BF16 && precision != BESO_PREC_FP32 && precision != BESO_PREC_BF16X3 && precision != BESO_PREC_FP16)
+        return BESO_ERR_BAD_ARG;
+    if (flags & ~(BESO_FLAG_UNCOND | BESO_PLAN_MASK | BESO_FLAG_LAST_ACTION_ONLY)) return BESO_ERR_BAD_ARG;
+    if (batch < 1 || t < 1 || t > cfg->obs_seq_len) return BESO_ERR_BAD_SHAPE;
+    if (!packed || !state || !action || !noise || !sigma || !workspace || (cfg->goal_seq_len > 0 && !goal)) return BESO_ERR_BAD_ARG;
+    if (!loss_out && !per_sample_out) return BESO_ERR_BAD_ARG;
+    LossWorkspace w;
+    if (!loss_workspace(cfg, batch, t, precision, &w)) return BESO_ERR_BAD_SHAPE;
+    if (workspace_bytes < w.total) return BESO_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char* wsp = (char*)workspace;
+    float* scaled = (float*)(wsp + w.scaled);
+    float* pred = (float*)(wsp + w.pred);
+    float* rows = per_sample_out ? per_sample_out : (float*)(wsp + w.rows);
+    const int fwd_flags = flags & (BESO_FLAG_UNCOND | BESO_PLAN_MASK);
+    // the forward's own checks (a shape this precision has no kernel for) before the first launch of this call
+    st = forward_supported(cfg, precision, batch, t, fwd_flags);
+    if (st != BESO_OK) return st;
+    HIP_TRY(launch_loss_prep(action, noise, sigma, scaled, batch, t, cfg->act_dim, cfg->sigma_data, s));
+    // DiffusionGPT.forward at c_in * noised: the reference's operation order (score_wrappers.py:74)
+    st = forward(cfg, packed, precision, state, scaled, goal, sigma, pred, batch, t, fwd_flags, 1.0f, 0, workspace, w.forward, s);
+    if (st != BESO_OK) return st;
+    HIP_TRY(launch_loss_reduce(pred, action, noise, sigma, rows, loss_out, batch, t, cfg->act_dim,
+                               (flags & BESO_FLAG_LAST_ACTION_ONLY) ? 1 : 0, cfg->sigma_data, s));
+    return BESO_OK;
 }
 
 int beso_log_logistic(const double* u, float* out, size_t n, double loc, double scale, double cdf_lo, double cdf_hi, void* stream) {

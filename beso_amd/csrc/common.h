@@ -420,6 +420,11 @@ hipError_t launch_rollout_begin(const float* obs_in, const unsigned char* reset,
                                 float* state_out, float* x_out, int n_envs, int W, int obs, int act, hipStream_t s);
 hipError_t launch_rollout_end(const float* x0, const int* lengths, const double* lo, const double* hi, const float* den_y,
                               const float* mean_y, float* act_ctx, float* pred, int n_envs, int W, int act, hipStream_t s);
+// the gradient-free score-matching loss (lossfwd.hip): the forward's input, then the per-sample values (and, with `loss`, their mean)
+hipError_t launch_loss_prep(const float* action, const float* noise, const float* sigma, float* scaled, int batch, int t, int act,
+                            float sigma_data, hipStream_t s);
+hipError_t launch_loss_reduce(const float* pred, const float* action, const float* noise, const float* sigma, float* per_sample,
+                              float* loss, int batch, int t, int act, int last_only, float sigma_data, hipStream_t s);
 hipError_t launch_adam_ema(const void* chunks, int n_chunks, float* m, float* v, float* ema, float lr, float beta1,
                            float beta2, float eps, float wd, int decoupled, int step, float ema_decay, hipStream_t s);
 

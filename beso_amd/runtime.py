@@ -213,6 +213,36 @@ class ScoreNetRuntime:
         _lib.check(st, "denoise_fwd" if precondition else "score_fwd")
         return out
 
+    def loss(self, packed: PackedWeights, state, action, goal, noise, sigma, uncond: bool = False, last_only: bool = False,
+             per_sample: bool = False):
+        """The gradient-free score-matching objective of the eval-mode network (``beso_loss_fwd``: GCDenoiser.loss under
+        ``torch.no_grad()``, score_wrappers.py:45-79) on the weights of ``packed``: a 0-d tensor, or ``(loss, [B])`` with
+        ``per_sample`` -- the mean of (F(c_in * noised) - target)^2 over every sample's values.  ``last_only`` scores the last
+        step of every window only (the caller has zeroed the noise of the other steps, as GCDenoiser.loss does);
+        ``uncond`` evaluates the unconditional branch.  Fixed-order reductions, no atomics."""
+        if sigma is None:
+            raise ValueError("sigma is required")
+        dev, B, t, state, action, goal, sigma = self._prep(state, action, goal, sigma)
+        if not torch.is_tensor(noise) or tuple(noise.shape) != tuple(action.shape):
+            raise ValueError(f"noise must have the action's shape {tuple(action.shape)}")
+        noise = _f32c(noise, dev)
+        need = self.lib.beso_loss_fwd_workspace_bytes(C.byref(self.cfg), B, t, self.precision)
+        if need == 0:
+            raise ValueError(f"beso_hip: bad shape batch={B} t={t} (t must be in [1, {self.shape.obs_seq_len}])")
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        ws = self._ws
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        rows = torch.empty(B, dtype=torch.float32, device=dev) if per_sample else None
+        flags = (_lib.FLAG_UNCOND if uncond else 0) | (_lib.FLAG_LAST_ACTION_ONLY if last_only else 0) | forward_hints()
+        with torch.cuda.device(dev):
+            st = self.lib.beso_loss_fwd(C.byref(self.cfg), packed.buf.data_ptr(), packed.precision, state.data_ptr(),
+                                        action.data_ptr(), goal.data_ptr() if goal is not None else None, noise.data_ptr(),
+                                        sigma.data_ptr(), out.data_ptr(), rows.data_ptr() if rows is not None else None,
+                                        B, t, flags, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+        _lib.check(st, "loss_fwd")
+        return (out, rows) if per_sample else out
+
     def sample(self, packed: PackedWeights, sampler: str, state, x_t, goal, sigmas, cond_lambda: float = 1.0,
                eta: float = 1.0, s_noise: float = 1.0, order: int = 4, noise=None, stepwise: bool = False, trace=None):
         """One of the sampler loops of ``_lib.SAMPLERS`` (ddim / euler / heun with s_churn = 0, euler_ancestral, dpm_2,

@@ -19,6 +19,8 @@
  *   beso_sample_solver  <- sample_dpm_2(_ancestral) / sample_dpmpp_2s(_ancestral) / sample_dpmpp_2m / sample_lms
  *   beso_loss_grad      <- GCDenoiser.loss + loss.backward()           k_diffusion/score_wrappers.py:45-79, beso_agent.py:228-233
  *                          (+ DiffusionGPT.mask_cond, training mode     k_diffusion/score_gpts.py:298-299, 360-371)
+ *   beso_loss_fwd       <- GCDenoiser.loss under torch.no_grad(), eval mode: the held-out objective, per sample and as a scalar
+ *                                                                      k_diffusion/score_wrappers.py:45-79
  *   beso_goal_mask      <- the Bernoulli mask of DiffusionGPT.mask_cond k_diffusion/score_gpts.py:365-368
  *   beso_dropout_mask   <- the masks of nn.Dropout in training mode      k_diffusion/score_gpts.py:72,79,109,321-325
  *   beso_log_logistic   <- rand_log_logistic (behind the uniform draw)   k_diffusion/utils.py:178-185 (beso_agent.py:227)
@@ -37,7 +39,7 @@
  *     allocates or frees device memory and never synchronises the stream; work is enqueued on
  *     `stream` and the call returns.
  *   - buffers the library writes are handed over UNINITIALISED: the workspace, every output (`out`, `denoised`, `x_grad`,
- *     `dot`, `loss_out`), the solver `history`, `grads_flat` and the `packed` image may hold anything on entry -- NaN bit
+ *     `dot`, `loss_out`, `per_sample_out`), the solver `history`, `grads_flat` and the `packed` image may hold anything on entry -- NaN bit
  *     patterns and what an earlier, larger call left behind included.  No result depends on a byte the call did not write,
  *     every element of a result is written, and nothing outside [ptr, ptr + size) of a buffer is written
  *     (tests/test_buffer_independence.py).  Inputs are read inside their extents only.
@@ -123,7 +125,10 @@ enum {
     BESO_PLAN_SPW8 = 0x300,   /*   8 (larger batches) */
     BESO_PLAN_SPW_MASK = 0x300,
     BESO_PLAN_MASK = 0x3f0,
-    BESO_SAMPLE_STEPWISE = 0x1000  /* beso_sample: enqueue evaluation by evaluation (see there) */
+    BESO_SAMPLE_STEPWISE = 0x1000, /* beso_sample: enqueue evaluation by evaluation (see there) */
+    BESO_FLAG_LAST_ACTION_ONLY = 0x2000 /* beso_loss_fwd: GCDenoiser.loss(pred_last_action_only=True) -- only the last step of
+                                      every window is scored (score_wrappers.py:59-63,76-77; the caller zeroes the other
+                                      steps' noise); what BESO_TRAIN_LAST_ACTION_ONLY is to beso_loss_grad */
 };
 
 /* sampler ids for beso_sample / beso_sampler_step */
@@ -333,6 +338,33 @@ int beso_loss_grad(const beso_config* cfg, const float* const* params, int n_par
 int beso_denoise_vjp(const beso_config* cfg, const float* const* params, int n_params, int precision, const float* state,
                      const float* x, const float* goal, const float* sigma, const float* cot, float* denoised, float* x_grad,
                      float* dot, int batch, int t, int flags, void* workspace, size_t workspace_bytes, void* stream);
+/* The gradient-free score-matching objective: GCDenoiser.loss (score_wrappers.py:45-79) of the EVAL-mode network, as
+ * `with torch.no_grad(): model.loss(state, action, goal, noise, sigma)` returns it -- the held-out loss of validation curves,
+ * early stopping and loss-against-sigma diagnostics -- on the inference path: the network is evaluated from the packed image
+ * (which may be the EMA image) in any precision, nothing is kept for a backward and no parameter gradient exists.
+ * Three steps on `stream`: (1) scaled = (action + noise*sigma[b]) * c_in[b], elementwise; (2) pred = F(state, scaled, goal,
+ * sigma), the launches of beso_score_fwd under the library's own plan choice (flags: BESO_PLAN_* hints, BESO_FLAG_UNCOND for
+ * the unconditional branch's loss); (3) one wave per sample forms target = (action - c_skip*noised)/c_out from action, noise
+ * and sigma again and reduces (pred - target)^2, then ONE workgroup reduces the per-sample values.  F(c_in*noised) is compared
+ * with the target -- the reference's operation order; (D - action)/c_out would cancel at small sigma.  Every product, quotient
+ * and sum of (1) and (3) is rounded on its own, as torch rounds them.
+ *   state [batch,t,obs], action [batch,t,act] (clean), goal [batch,G,obs] (may be NULL when G = 0), noise [batch,t,act],
+ *   sigma [batch] (> 0);  no dropout, no goal masking.
+ *   per_sample_out [batch], may be NULL: the mean of (pred - target)^2 over the sample's t*act values -- with
+ *                  BESO_FLAG_LAST_ACTION_ONLY over the act values of step t-1 only (score_wrappers.py:76-77).
+ *   loss_out       one float, may be NULL: sum_b per_sample[b] / batch, the reference's `.flatten(1).mean()` / `.mean()`.
+ *   At least one of the two must be given.
+ * Both reductions run in a fixed order without atomics: per_sample[b] depends on sample b's values only (it equals the value of
+ * that sample evaluated alone wherever the forward has that property), and two runs give equal bits wherever the forward does.
+ * workspace: beso_loss_fwd_workspace_bytes(cfg, batch, t, precision) bytes (0 on a bad config / shape) -- the forward's
+ * (beso_workspace_bytes(..., 0)) followed by `scaled`, `pred` and the per-sample values of a call without per_sample_out.
+ * Before anything is enqueued: BESO_ERR_BAD_ARG for an unknown precision or flag bit, a NULL required pointer or both outputs
+ * NULL; BESO_ERR_BAD_SHAPE for batch < 1, t < 1, t > obs_seq_len; BESO_ERR_WORKSPACE for a short workspace;
+ * BESO_ERR_UNSUPPORTED where beso_score_fwd has no kernel for the shape in this precision.                              */
+size_t beso_loss_fwd_workspace_bytes(const beso_config* cfg, int batch, int t, int precision);
+int beso_loss_fwd(const beso_config* cfg, const void* packed, int precision, const float* state, const float* action,
+                  const float* goal, const float* noise, const float* sigma, float* loss_out, float* per_sample_out,
+                  int batch, int t, int flags, void* workspace, size_t workspace_bytes, void* stream);
 /* The keep-mask (1.0 / 0.0 per element of goal [batch,G,obs]) that beso_loss_grad applies for (goal_drop, seed):
  * `1 - torch.bernoulli(...)` of DiffusionGPT.mask_cond (score_gpts.py:365-368) with this library's generator.       */
 int beso_goal_mask(float* mask, int batch, int goal_seq_len, int obs_dim, float goal_drop, unsigned int seed, void* stream);
