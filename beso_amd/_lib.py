@@ -16,6 +16,8 @@ FLAG_UNCOND = 1
 # execution-plan hints of the forward calls (include/beso_hip.h: which kernels run, never what they compute)
 PLAN_PER_OP, PLAN_BLOCKS, PLAN_SMALL, PLAN_FUSED = 0x10, 0x20, 0x40, 0x80
 PLAN_SPW2, PLAN_SPW4, PLAN_SPW8 = 0x100, 0x200, 0x300
+# the sigma token shared across a uniform-sigma batch (kitchen-class shape, bf16 / fp16): at any batch size / never
+PLAN_SIGMA_SHARED, PLAN_SIGMA_PRIVATE = 0x400, 0x800
 SAMPLE_STEPWISE = 0x1000
 FLAG_LAST_ACTION_ONLY = 0x2000     # beso_loss_fwd: only the last step of every window is scored
 TRAIN_LAST_ACTION_ONLY, TRAIN_PLAN_PER_OP, TRAIN_PLAN_TILES = 1, 2, 4
@@ -45,7 +47,7 @@ EXPORTS = ["beso_version", "beso_status_string", "beso_last_error", "beso_num_pa
            "beso_dropout_mask", "beso_sample_traced", "beso_rollout_begin", "beso_rollout_end",
            "beso_loss_fwd_workspace_bytes", "beso_loss_fwd"]
 # include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
-DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm"]
+DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm", "beso_debug_sigma_cache_entries"]
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
 
 
@@ -190,6 +192,8 @@ def load_dev() -> C.CDLL:
         lib.beso_debug_set_stamps.argtypes = [C.c_void_p, C.c_int]
         lib.beso_debug_gemm.restype = C.c_int
         lib.beso_debug_gemm.argtypes = [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
+        lib.beso_debug_sigma_cache_entries.restype = C.c_int
+        lib.beso_debug_sigma_cache_entries.argtypes = [C.POINTER(BesoConfig), C.c_void_p, C.c_int]
         _dev = lib
     return _dev
 

@@ -92,7 +92,7 @@ bool make_workspace(const beso_config* c, const Layout& lay, int batch, int t, i
     w->den = carve(cur, f * na); w->x2 = carve(cur, f * na); w->d1 = carve(cur, f * na);
     w->sig = carve(cur, f * batch);
     w->small = carve(cur, f * (size_t)(lay.H + 1) * kSmallProjRows * lay.D);
-    w->fused = carve(cur, 0);
+    w->fused = carve(cur, 256);
     w->total = cur;
     return true;
 }
@@ -279,6 +279,7 @@ static int forward(const beso_config* cfg, const void* packed, int precision, co
     a.cond_lambda = cond_lambda; a.sigma_data = cfg->sigma_data;
     a.plan = flags & BESO_PLAN_MASK;
     if (precision == BESO_PREC_FP16) a.plan &= ~(BESO_PLAN_PER_OP | BESO_PLAN_BLOCKS);      // (no per-op / block form: the hint is ignored, as the header says)
+    a.sig_flag = (uint32_t*)((char*)workspace + ws.fused);
     if (small_wanted(lay, a, precision)) {
         // few samples: the weights, not the samples, are spread over the chip (small.hip)
         hipError_t e = hipSuccess;
@@ -797,6 +798,12 @@ int beso_sample_traced(const beso_config* cfg, const void* packed, int precision
 #if BESO_DEV_API
 // development builds only (include/beso_hip_debug.h; `python -m beso_amd.build --dev` -> libbeso_hip_dev.so)
 void beso_debug_set_stamps(void* device_buf, int capacity_u64) { fused_set_stamps(device_buf, capacity_u64); }
+int beso_debug_sigma_cache_entries(const beso_config* cfg, const void* packed, int precision) {
+    Layout lay;
+    if (!packed || validate_config(cfg) != BESO_OK || (precision != BESO_PREC_BF16 && precision != BESO_PREC_FP16) ||
+        !make_layout(cfg, precision, &lay)) return -1;
+    return fused_sigma_cache_entries(lay, (const char*)packed);
+}
 #endif
 
 int beso_adam_step(const beso_optim_chunk* chunks, int n_chunks, float* exp_avg, float* exp_avg_sq, float* ema,

@@ -304,7 +304,7 @@ struct Workspace {
     size_t d1;     // fp32 [B][t][act]     Heun first derivative d
     size_t sig;    // fp32 [B]             per-step sigma vector of beso_sample
     size_t small;  // fp32 [(H + 1)][kSmallProjRows][D]   small-batch path, few token rows: x_mid + the out-projection's per-head slabs
-    size_t fused;  // scratch of the fused path
+    size_t fused;  // scratch of the fused path: the call's flag word of the shared sigma token (fused.hip SigArgs)
     size_t total;
 };
 
@@ -360,6 +360,7 @@ struct FwdArgs {
     float cond_lambda;
     float sigma_data;
     int plan = 0;     // BESO_PLAN_* bits of the call's flags: which kernels run (never what they compute)
+    uint32_t* sig_flag = nullptr;   // one forward: the call's flag word (Workspace::fused) for the shared sigma token; null: not shared
 };
 
 hipError_t launch_pack_matrix(const float* src, int rows, int cols, void* dst, int rows_p,

@@ -90,6 +90,7 @@ int    fused_train_dgrad(const Layout& lay, const char* img, int layer, int whic
 int    fused_train_dgrad_blocks(int M);
 int    fused_train_bias_reduce(const float* const* slabs, float* const* outs, const int* blocks, int n, int N, hipStream_t s);
 void   fused_set_stamps(void* buf, int cap);     // development builds (BESO_DEV_API): phase stamps of workgroup 0
+int    fused_sigma_cache_entries(const Layout& lay, const char* packed);   // development builds: occupied entries of the image's sigma-token cache (bf16 and fp16 images alike)
 
 // The fp16-operand build of layers_kernel (fused_f16.hip = fused.hip compiled with BESO_OPERAND_F16 = 1): BESO_PREC_FP16.
 // Same image layout and sizes with fp16 weight fragments; `precision` arguments take BESO_PREC_BF16 ("the plain mode").

@@ -1224,9 +1224,37 @@ struct SlotTabs {
     unsigned char row_of_slot[kMT];   // natural row (sample*Tn + position) of a slot; empty slots map to themselves
     unsigned char slot_of_row[kMT];   // inverse
 };
+// SHARED (the five-tile instance of layers_kernel): the sigma token has no slot -- a sample's Tn - 1 other tokens fill the
+// tile, the q/k/v rows keep the natural Tn rows per sample (row 0 of every sample comes from the sigma-token cache).  Empty
+// slots map to rows behind the last sample's rows and the eight V rows the phase zeroes there; the sigma rows map to no slot.
+template <bool SHARED = false>
 __device__ __forceinline__ void build_slot_tabs(SlotTabs* tb, int n_samples, int Tn, int t_win, int G, bool actions_first,
                                                 int pshift = 4) {
     const int slot = threadIdx.x;
+    if constexpr (SHARED) {
+        if (slot < kMT) {
+            const int na = n_samples * t_win, no = Tn - 1 - t_win, nv = n_samples * (Tn - 1);
+            unsigned char sp = 0xFF;
+            int row = slot + n_samples + 8;
+            if (slot < nv) {
+                int sl, p;
+                if (slot < na) { sl = slot / t_win; p = G + 2 + 2 * (slot - sl * t_win); }
+                else {
+                    const int q = slot - na;
+                    sl = q / no;
+                    const int r = q - sl * no + 1;
+                    p = r <= G ? r : G + 1 + 2 * (r - G - 1);
+                }
+                sp = (unsigned char)((sl << pshift) | p);
+                row = sl * Tn + p;
+                tb->slot_of_row[row] = (unsigned char)slot;
+            }
+            tb->sp_of_slot[slot] = sp;
+            tb->row_of_slot[slot] = (unsigned char)row;
+            if (slot < n_samples) tb->slot_of_row[slot * Tn] = 0xFF;
+        }
+        return;
+    }
     if (slot < kMT) {
         const int nv = n_samples * Tn;
         unsigned char sp = 0xFF;
@@ -1945,13 +1973,23 @@ __device__ __forceinline__ void attn_prefetch(u32x4 (&qE)[3], u32x4 (&qO)[3], co
 // the next pair before core(B); each head's projection weights (two k-steps: all of them) are requested
 // before the barrier that precedes its core.
 // HG > 1: a virtual head is HG real heads of `hd` dims side by side (FusedDims); H counts virtual heads.
-template <int RPW, int KS, int HG, int NTP = kNTT, int NTQ = kNTT, class AX = AttnPlain>   // NTP: token tiles that receive the out-projection (last layer:
+// The sigma token (token 0 of every sample: no position, causal attention -- its k / v rows depend on (weights, sigma) alone)
+// shared across a uniform-sigma batch.  SigCapture (the pre-pass: one sample of one token): the layer's k and v rows of the
+// token go out to a cache entry, [2][H kHDP] operand elements per layer, as write_qkv packs them.  SigInject (the five-tile
+// instance): the token has no slot; row 0 of every sample's k and v is copied from the entry (staged in LDS), its q row is
+// zero and its core output is dropped; the eight V rows behind the last sample's (the last sample's 16-row window reaches
+// them with zero probabilities) are zeroed -- no slot writes them.
+struct SigNone { static constexpr int mode = 0; };
+struct SigCapture { static constexpr int mode = 1; uint16_t* dst; };
+struct SigInject { static constexpr int mode = 2; const uint16_t* src; };
+
+template <int RPW, int KS, int HG, int NTP = kNTT, int NTQ = kNTT, class AX = AttnPlain, class SX = SigNone>   // NTP: token tiles that receive the out-projection (last layer:
                                                                      // action tokens only); NTQ: token tiles that hold tokens at all
 __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsigned char* u,
                                            const u32x4* __restrict__ wqkv, const float* __restrict__ bqkv,
                                            const u32x4* __restrict__ wproj, int H, int hd, int Tn, int n_samples,
                                            int w, int lane, const SlotTabs* tb, u32x4 (&qE)[3], u32x4 (&qO)[3], Stamps& st,
-                                           const AX ax = AX{}) {
+                                           const AX ax = AX{}, const SX sx = SX{}) {
     asm volatile("" : "+v"(lane));
     uint16_t* qkv = (uint16_t*)u;                         // [3][kQKVRows][kQKVRow] bf16
     u32x4* yT = (u32x4*)(u + kQKVBytes);                  // [(t*2 + kk)*64 + lane]
@@ -1977,11 +2015,32 @@ __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsig
                 pk.x = pack_op2(qa[i][t][0], qa[i][t][1]);
                 pk.y = pack_op2(qa[i][t][2], qa[i][t][3]);
                 *(uint2*)(dst + (size_t)row[t] * kQKVRow) = pk;
+                if constexpr (SX::mode == 1) {            // the sigma token sits in slot 0 = row 0: its k and v go to the cache entry
+                    if (t == 0 && n == 0 && part >= 1) *(uint2*)(sx.dst + (size_t)(part - 1) * (KS * 32) + vh * kHDP + d0) = pk;
+                }
                 if constexpr (AX::on) {                   // kept for the backward pass: [row][part D + head dims]
                     const int grow = ax.rows.row(t * 16 + n);
                     if (grow >= 0 && d0 < HG * hd && !(BESO_TRAIN_FWD_ABL & 4))
                         *(uint2*)(ax.qkv + (size_t)grow * (3 * ax.D) + part * ax.D + vh * (HG * hd) + d0) = pk;
                 }
+            }
+        }
+    };
+    // SigInject: rows the slots do not write (beside write_qkv of the same head, in front of the barrier before its core) --
+    // 16 bytes per thread: (sample, q | k | v, eight dims) of the samples' sigma rows, then the eight zeroed V rows
+    auto sig_rows = [&](int vh) {
+        if constexpr (SX::mode == 2) {
+            const int tid = w * 64 + ln;
+            if (tid < 24 * kSPW) {
+                const int sl = tid / 24, part = (tid % 24) >> 3, c = tid & 7;
+                if (sl < n_samples) {
+                    u32x4 v = {0u, 0u, 0u, 0u};
+                    if (part) v = *(const u32x4*)(sx.src + (size_t)(part - 1) * (KS * 32) + vh * kHDP + 8 * c);
+                    *(u32x4*)(qkv + ((size_t)part * kQKVRows + sl * Tn) * kQKVRow + 8 * c) = v;
+                }
+            } else if (tid < 24 * kSPW + 64) {
+                const int r = (tid - 24 * kSPW) >> 3, c = tid & 7;
+                *(u32x4*)(qkv + ((size_t)2 * kQKVRows + n_samples * Tn + r) * kQKVRow + 8 * c) = u32x4{0u, 0u, 0u, 0u};
             }
         }
     };
@@ -2078,7 +2137,7 @@ __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsig
                     }
                 }
             }
-            if (n < Tn) {
+            if (n < Tn && (SX::mode != 2 || n > 0)) {
                 const int tok = my_tok;                               // token slot of (sample w, position n)
                 u32x4 ybk[AX::on ? 2 : 1];
 #pragma unroll
@@ -2123,7 +2182,7 @@ __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsig
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
             y[dt] = mfma_op16(va, pb, z);
         }
-        if (n < Tn) {
+        if (n < Tn && (SX::mode != 2 || n > 0)) {              // (SigInject: the sigma token has no slot)
             const int tok = my_tok;                               // token slot of (sample w, position n)
             u32x4 ybk[AX::on ? 2 : 1];
 #pragma unroll
@@ -2159,6 +2218,7 @@ __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsig
         gemm_phase<3, NTQ, kt16(KS)>(qa, qE, qO, qkv_a(pair), 24, xnT + lane, KS * 64, 64, KS);
         prefetch_a<RPW>(aE, aO, proj_a(hA), kWaves * RPW);
         if (hsel == 0) write_qkv(qa, hA);
+        sig_rows(hA);
         stamp(st, 11);
         __syncthreads();
         stamp(st, 12);
@@ -2170,6 +2230,7 @@ __device__ __forceinline__ void attn_phase(Tile<RPW>& T, const u32x4* xnT, unsig
         gemm_phase<RPW, NTP, false, kNTT>(T.acc, aE, aO, proj_a(hA), kWaves * RPW, yT + lane, 2 * 64, 64, 2);
         prefetch_a<RPW>(aE, aO, proj_a(hB), kWaves * RPW);
         if (hsel == 1) write_qkv(qa, hB);
+        sig_rows(hB);
         if (pair + 1 < H / 2) prefetch_a<3>(qE, qO, qkv_a(pair + 1), 24);   // qa's registers are free from here
         stamp(st, 13);
         __syncthreads();
@@ -3091,6 +3152,19 @@ __global__ __launch_bounds__(512, 2) void lin_block_x3_kernel(float* __restrict_
     }
 }
 
+// The sigma-token cache of a packed image (behind the per-model image; zeroed by fused_pack, i.e. whenever the image is
+// (re)packed): a header -- the round-robin counter and one tag per entry, sigma's fp32 bits, 0 = free -- and kSigEntries
+// entries of [L][2: k | v][H kHDP] operand elements (9 KiB at kitchen), what write_qkv gives the token's rows in LDS.
+constexpr int kSigEntries = 128;          // the most evaluations one sampler launch holds (kMaxLoopEvals); a power of two
+constexpr int kSigHdrBytes = 1024;
+struct SigHdr { uint32_t next, pad[3]; uint32_t tag[kSigEntries]; };
+static_assert(sizeof(SigHdr) <= kSigHdrBytes && (kSigEntries & (kSigEntries - 1)) == 0, "sigma cache header");
+struct SigArgs { uint32_t* cache; uint32_t* flag; };      // the image's cache; the call's flag word (its workspace)
+__host__ __device__ inline int sig_entry_bytes(const FusedDims& d) { return d.L * 2 * d.KS * 32 * 2; }
+__host__ __device__ inline bool sig_shape(const FusedDims& d) { return d.attn && d.RPW == 3 && d.KS == 12 && d.HG == 1 && d.head_fused; }
+inline size_t sig_cache_offset(const FusedDims& d) { return ((size_t)d.layer_bytes * d.L + d.global_bytes + 255) / 256 * 256; }
+inline size_t sig_cache_bytes(const FusedDims& d) { return kSigHdrBytes + (size_t)kSigEntries * sig_entry_bytes(d); }
+
 // Whole transformer layers [l0, l1) over the tile's 8 samples; x stays in registers in between.
 // NTL: token tiles that hold the action tokens of a full tile (8 samples x window, rounded up to an even count):
 // in the LAST layer only those go through the out-projection, LayerNorm-2 and the MLP -- nothing else reaches
@@ -3103,15 +3177,30 @@ __global__ __launch_bounds__(512, 2) void lin_block_x3_kernel(float* __restrict_
 // CORE = 1: the long-sequence instance (SPW = 1: a sample of up to 16 NTA tokens per workgroup, tokens in natural order).
 // LOOP = 1: the sampler-loop instance (S.n evaluations, each followed by its update in the head); LOOP = 0 is one forward and
 // compiles to the loop-free code (S is not read).
+// SIG: the sigma token shared across a uniform-sigma batch (kitchen throughput shape; launch_sigma_shared).  Three launches per
+// forward, each reading or writing the call's flag word (SigArgs::flag: bit 31 = the batch shares an entry, low bits = which):
+//   3  the pre-pass, ONE workgroup: reads sigma[0 .. B), looks the value up in the cache's tags and writes the flag; uniform
+//      and not cached: carries the lone sigma token (one sample of one token, the two-sample instance's phases) through all
+//      layers, its k / v rows going to the round-robin entry (SigCapture) -- data first, tag behind a fence, flag last;
+//   2  the five-tile instance (SPW = 8, NTA = 5: ten tokens per sample, SigInject): runs when the flag selects an entry;
+//   1  the six-tile instance as it was: runs when the flag selects none.  The one not selected exits at once.
 static_assert(3 * sizeof(void*) + sizeof(FusedDims) + 6 * sizeof(int) + sizeof(EdgeArgs) + sizeof(SampleSteps) +
-              sizeof(SampleExtra) + sizeof(SampleTrace) + 64 <= 4096, "layers_kernel's arguments stay under the 4 KiB kernel-argument limit");
-template <int RPW, int KS, int HG, int NTL, int SPW = kSPW, int NTA = kNTT, int PX = 0, int CORE = 0, int LOOP = 0>
+              sizeof(SampleExtra) + sizeof(SampleTrace) + sizeof(SigArgs) + 48 <= 4096, "layers_kernel's arguments stay under the 4 KiB kernel-argument limit");
+template <int RPW, int KS, int HG, int NTL, int SPW = kSPW, int NTA = kNTT, int PX = 0, int CORE = 0, int LOOP = 0, int SIG = 0>
 __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, const char* __restrict__ lw0,
                                                         FusedDims d, int l0, int l1, int n_samples_total, int Tn,
                                                         EdgeArgs e, SampleSteps S, unsigned long long* stamps, int cap,
-                                                        SampleExtra X3, SampleTrace TR) {
+                                                        SampleExtra X3, SampleTrace TR, SigArgs SG) {
     Stamps st{stamps, cap, 0};
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    static_assert(SIG == 0 || (PX == 0 && CORE == 0 && LOOP == 0 && HG == 1), "sigma sharing: one forward of the plain instances");
+    [[maybe_unused]] uint32_t sig_entry = 0;
+    if constexpr (SIG == 1) { if (*SG.flag >> 31) return; }
+    if constexpr (SIG == 2) {
+        const uint32_t f = *SG.flag;
+        if (!(f >> 31)) return;
+        sig_entry = f & (kSigEntries - 1);
+    }
     static_assert(CORE == 0 || (SPW == 1 && PX == 0), "long-sequence instance");
     constexpr LdsMap Lb = lds_map(KS, false, CORE == 1 ? NTA : kNTT);
     constexpr LdsMapX3 X = lds_map_x3(KS, NTA);
@@ -3130,9 +3219,45 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
     // action tokens first whenever both network edges are inside the kernel (otherwise x travels in natural order)
     SlotTabs* tb = (SlotTabs*)(lds + L.tab);
     float* xs = (float*)(lds + L.xs);
+    [[maybe_unused]] uint16_t* sig_kv = nullptr;         // SIG = 2: the entry, staged in LDS behind the map; SIG = 3: the entry written
+    if constexpr (SIG == 2) {
+        const int n16 = sig_entry_bytes(d) / 16;
+        const u32x4* src = (const u32x4*)((const char*)SG.cache + kSigHdrBytes + (size_t)sig_entry * sig_entry_bytes(d));
+        for (int i = threadIdx.x; i < n16; i += kBlock) ((u32x4*)(lds + L.total))[i] = src[i];
+        sig_kv = (uint16_t*)(lds + L.total);             // (the barrier behind the prologue's zero fill orders it)
+    }
+    if constexpr (SIG == 3) {
+        // the pre-pass: is sigma one value, and is that value's entry in the cache?
+        SigHdr* hdr = (SigHdr*)SG.cache;
+        const uint32_t* sb = (const uint32_t*)e.sigma;
+        const uint32_t bits = sb[0];
+        int differs = 0;
+        for (int i = threadIdx.x; i < e.B; i += kBlock) differs |= sb[i] != bits;
+        int* sh = (int*)(lds + L.red);
+        if (threadIdx.x == 0) sh[0] = -1;
+        const bool uniform = !__syncthreads_or(differs) && bits != 0u;       // (tag 0 marks a free entry)
+        if (uniform && threadIdx.x < kSigEntries && hdr->tag[threadIdx.x] == bits) sh[0] = threadIdx.x;   // (any match will do)
+        __syncthreads();
+        int idx = sh[0];
+        __syncthreads();
+        if (!uniform || idx >= 0) {
+            if (threadIdx.x == 0) *SG.flag = uniform ? 0x80000000u | (uint32_t)idx : 0u;
+            return;
+        }
+        if (threadIdx.x == 0) {
+            idx = (int)(atomicAdd(&hdr->next, 1u) & (kSigEntries - 1));
+            hdr->tag[idx] = 0u;                          // the entry it replaces is invalid from here on
+            __threadfence();
+            sh[0] = idx;
+        }
+        __syncthreads();
+        sig_entry = (uint32_t)sh[0];
+        __syncthreads();
+        sig_kv = (uint16_t*)((char*)SG.cache + kSigHdrBytes + (size_t)sig_entry * sig_entry_bytes(d));
+    }
     // (CORE = 1: natural order -- the long-sequence core addresses slots by position, and five tiles leave nothing to peel)
     const bool actions_first = CORE == 0;
-    build_slot_tabs(tb, n_samples, Tn, e.t, d.G, actions_first, CORE == 1 ? 7 : 4);
+    build_slot_tabs<SIG == 2>(tb, n_samples, Tn, e.t, d.G, actions_first, CORE == 1 ? 7 : 4);
     // the action windows of the workgroup's real samples (contiguous in `action`): x_T of the sampler loop / the noisy action
     LoopState ls{-1, 0.f, 0.f, 0.f, true, 0.f, 0, 0.f};
     if constexpr (LOOP) { ls.tx = TR.x; ls.tden = TR.den; }
@@ -3182,8 +3307,9 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
     // The last layer (when this launch contains it and the action tokens of the tile fit NTL token tiles) runs its
     // out-projection, LayerNorm-2 and MLP on the action-token tiles only; it is peeled off the loop -- a branch
     // between the two variants INSIDE the loop costs 150 spilled VGPRs.
-    const int n_valid = n_samples * Tn;                 // token slots in use (the empty ones are behind them)
-    const bool peel = actions_first && l1 == d.L && l1 > l0 && n_samples * e.t <= 16 * NTLa && (!PX || NTLa < NTA);
+    const int n_valid = n_samples * (SIG == 2 ? Tn - 1 : Tn);                 // token slots in use (the empty ones are behind them)
+    // (SIG = 3, the pre-pass: launched over all layers with no action token -- it leaves from the peeled last layer's attention)
+    const bool peel = SIG == 3 || (actions_first && l1 == d.L && l1 > l0 && n_samples * e.t <= 16 * NTLa && (!PX || NTLa < NTA));
     const int l_loop_end = peel ? l1 - 1 : l1;
     auto layer_weights = [&](int l) {
 #if BESO_FUSED_ABLATE == 4
@@ -3192,6 +3318,12 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
 #else
         return lw0 + (size_t)l * d.layer_bytes;
 #endif
+    };
+    // the attention phase's sigma hook of layer l: the layer's [2][KS 32] rows of the entry
+    auto sig_hook = [&](int l) {
+        if constexpr (SIG == 2) return SigInject{sig_kv + (size_t)l * (2 * KS * 32)};
+        else if constexpr (SIG == 3) return SigCapture{sig_kv + (size_t)l * (2 * KS * 32)};
+        else return SigNone{};
     };
     if constexpr (PX) {
         auto layer_x3 = [&](const char* lw, auto NTPc) {
@@ -3226,7 +3358,7 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
         else
         attn_phase<RPW, KS, HG, NTA, NTA>(T, (const u32x4*)(lds + L.xnT), lds + L.u, (const u32x4*)(lw + d.o_wqkv),
                                 (const float*)(lw + d.o_bqkv), (const u32x4*)(lw + d.o_wproj), d.Hv, d.hd, Tn, n_samples, w,
-                                lane, tb, qE, qO, st);
+                                lane, tb, qE, qO, st, AttnPlain{}, sig_hook(l));
         stamp(st, 3);
         u32x4 a1r[PF1][kChunkTiles / kWaves];
         mlp_prefetch<KS, kWaves, PF1>(a1r, (const u32x4*)lw, w, lane);
@@ -3246,7 +3378,18 @@ __global__ __launch_bounds__(512, 2) void layers_kernel(float* __restrict__ x, c
         stamp(st, 7);
         attn_phase<RPW, KS, HG, NTLa, NTA>(T, (const u32x4*)(lds + L.xnT), lds + L.u, (const u32x4*)(lw + d.o_wqkv),
                                      (const float*)(lw + d.o_bqkv), (const u32x4*)(lw + d.o_wproj), d.Hv, d.hd, Tn, n_samples, w,
-                                     lane, tb, qE, qO, st);
+                                     lane, tb, qE, qO, st, AttnPlain{}, sig_hook(l1 - 1));
+        if constexpr (SIG == 3) {
+            // the last layer's k / v rows are out: nothing else of the lone token is needed.  Data, fence, tag, flag.
+            __threadfence();
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                SigHdr* hdr = (SigHdr*)SG.cache;
+                hdr->tag[sig_entry] = *(const uint32_t*)e.sigma;
+                *SG.flag = 0x80000000u | sig_entry;
+            }
+            return;
+        }
         stamp(st, 3);
         u32x4 a1r[PF1][kChunkTiles / kWaves];
         mlp_prefetch<KS, kWaves, PF1>(a1r, (const u32x4*)lw, w, lane);
@@ -4008,11 +4151,33 @@ hipError_t launch_tail_block(float* x, const char* lw, const char* lw_next, cons
 }
 
 // One instance of layers_kernel (LOOP = 1: the sampler-loop form, steps.n evaluations).
-template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int PX, int CORE, int LOOP>
+template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int PX, int CORE, int LOOP, int SIG = 0>
 hipError_t launch_instance(size_t lds_bytes, int grid, float* x, const char* lw0, const FusedDims& d, int l0, int l1,
-                           int n_samples, int Tn, const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, hipStream_t s) {
-    return launch_lds<layers_kernel<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, LOOP>>(dim3(grid), dim3(512), lds_bytes, s, x, lw0, d, l0, l1,
-                                                                                 n_samples, Tn, edge, steps, g_stamps, g_stamps_cap, extra, trace);
+                           int n_samples, int Tn, const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, hipStream_t s,
+                           const SigArgs& sig = SigArgs{nullptr, nullptr}) {
+    return launch_lds<layers_kernel<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, LOOP, SIG>>(dim3(grid), dim3(512), lds_bytes, s, x, lw0, d, l0, l1,
+                                                                                      n_samples, Tn, edge, steps, g_stamps, g_stamps_cap, extra, trace, sig);
+}
+
+// The eight-sample forward of the kitchen-class shape with the sigma token shared where the batch's sigma is one value: the
+// pre-pass, the five-tile instance and the six-tile instance, enqueued back to back -- the flag word the pre-pass writes
+// decides on the device which of the two does the work (no copy to the host, no synchronisation).
+template <int RPW, int KS, int HG, int NTL>
+hipError_t launch_sigma_shared(size_t lds_bytes, float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
+                               const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace,
+                               const SigArgs& sig, hipStream_t s) {
+    constexpr int kSmallSPW = 2, kSmallNT = 2, kSigNT = kNTT - 1;
+    const int grid = (n_samples + kSPW - 1) / kSPW;
+    EdgeArgs lone = edge;          // the pre-pass's sample: the sigma token alone (sigma[0 .. B) is what it reads of the call)
+    lone.t = 0; lone.two = 0; lone.uncond_all = 0;
+    hipError_t err = launch_instance<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 0, 0, 0, 3>(lds_bytes, 1, x, lw0, d, l0, l1, 1, 1, lone, steps,
+                                                                                       extra, trace, s, sig);
+    if (err != hipSuccess) return err;
+    err = launch_instance<RPW, KS, HG, NTL, kSPW, kSigNT, 0, 0, 0, 2>(lds_bytes + sig_entry_bytes(d), grid, x, lw0, d, l0, l1, n_samples, Tn,
+                                                                     edge, steps, extra, trace, s, sig);
+    if (err != hipSuccess) return err;
+    return launch_instance<RPW, KS, HG, NTL, kSPW, kNTT, 0, 0, 0, 1>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra,
+                                                                    trace, s, sig);
 }
 template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int PX, int CORE>
 hipError_t launch_either(size_t lds_bytes, float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
@@ -4036,7 +4201,8 @@ constexpr int kSmallBatchMax = 512;    // batches up to this size take the two-s
 // it (the instances compute the same per-sample arithmetic -- equal bits --, so the hint is a performance / test knob only).
 template <int RPW, int KS, int HG, int NTL>
 hipError_t launch_layers(float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, int precision, int plan, hipStream_t s) {
+                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, int precision, int plan, hipStream_t s,
+                         const SigArgs& sig) {
     constexpr LdsMap L = lds_map(KS);
     constexpr int kSmallSPW = 2, kSmallNT = 2, kMidSPW = 4, kMidNT = 4;
     const int want = plan & BESO_PLAN_SPW_MASK;
@@ -4064,11 +4230,31 @@ hipError_t launch_layers(float* x, const char* lw0, const FusedDims& d, int l0, 
     }
 #endif
     const bool mid_ok = tiles_hold_exact(kMidSPW, Tn, kMidNT);
-    // latency instances: the samples' tokens and the last sample's 16-row attention window must fit the token tiles
-    if (small_ok && (want == BESO_PLAN_SPW2 || (!want && n_samples <= kSmallBatchMax)))
+    // the sigma token shared (kitchen-class shape, one forward, the eight-sample plan -- BESO_PLAN_SIGMA_SHARED: at any batch
+    // size; BESO_PLAN_SIGMA_PRIVATE: never): the device decides between the five- and the six-tile instance
+    // samples per workgroup of this call, chosen ONCE: the latency instances where the samples' tokens and the last sample's
+    // 16-row attention window fit their token tiles (two samples up to kSmallBatchMax, four -- one workgroup per CU, two thirds
+    // of the throughput instance's work per workgroup -- up to twice that, or as the hint says), eight otherwise
+    const int spw = (small_ok && (want == BESO_PLAN_SPW2 || (!want && n_samples <= kSmallBatchMax))) ? kSmallSPW
+                    : (mid_ok && (want == BESO_PLAN_SPW4 || (!want && n_samples <= 2 * kSmallBatchMax))) ? kMidSPW : kSPW;
+    // the sigma token shared (kitchen-class shape, one forward, the eight-sample plan -- BESO_PLAN_SIGMA_SHARED: at any batch
+    // size; BESO_PLAN_SIGMA_PRIVATE: never): the device decides between the five- and the six-tile instance.  The other
+    // Tn - 1 tokens of eight samples must fill no more than the five token tiles, and the natural q/k/v rows -- Tn per sample,
+    // the last sample's 16-row window, the eight zeroed V rows behind the last sample -- must fit the rows LDS holds; a
+    // window that does not (Tn = 12: 88 slots) takes the six-tile instance as before.
+    if constexpr (RPW == 3 && KS == 12 && HG == 1) {
+        constexpr int kSigNT = kNTT - 1;
+        const bool fits = kSPW * (Tn - 1) <= 16 * kSigNT && (kSPW - 1) * Tn + 16 <= kQKVRows && kSPW * Tn + 8 <= kQKVRows;
+        if ((spw == kSPW || (plan & BESO_PLAN_SIGMA_SHARED)) && fits && sig.cache && sig.flag && steps.n == 0 &&
+            !(plan & BESO_PLAN_SIGMA_PRIVATE) && sig_shape(d) && edge.t >= 1 && l0 == 0 && l1 == d.L) {
+            static_assert(L.total + 16 * 1024 <= 160 * 1024, "LDS of the five-tile instance: the map plus a staged cache entry");
+            if (sig_entry_bytes(d) > 16 * 1024) return hipErrorInvalidValue;
+            return launch_sigma_shared<RPW, KS, HG, NTL>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, sig, s);
+        }
+    }
+    if (spw == kSmallSPW)
         return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
-    // up to one workgroup of four samples per CU: two thirds of the throughput instance's work per workgroup
-    if (mid_ok && (want == BESO_PLAN_SPW4 || (!want && n_samples <= 2 * kSmallBatchMax)))
+    if (spw == kMidSPW)
         return launch_either<RPW, KS, HG, NTL, kMidSPW, kMidNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
     return launch_either<RPW, KS, HG, NTL, kSPW, kNTT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
 }
@@ -4099,7 +4285,7 @@ size_t fused_packed_bytes(const Layout& lay, int precision) {
     if ((precision != BESO_PREC_BF16 && precision != BESO_PREC_BF16X3) || !fused_dims(lay, &d) || !shape_has_kernel(d)) return 0;
     if (precision == BESO_PREC_BF16X3)
         return (x3_shape(d) || x3_long_shape(d)) ? (size_t)d.x3_delta + (size_t)d.layer_bytes * lay.L : 0;
-    return d.layer_bytes * lay.L + d.global_bytes;
+    return sig_shape(d) ? sig_cache_offset(d) + sig_cache_bytes(d) : (size_t)d.layer_bytes * lay.L + d.global_bytes;
 }
 
 
@@ -4111,6 +4297,10 @@ int fused_pack(const Layout& lay, const float* const* p, char* packed, int preci
     if (precision == BESO_PREC_BF16X3 && !x3_shape(d) && !x3_long_shape(d)) return BESO_ERR_UNSUPPORTED;
     const int D = lay.D;
     const int n_parts = precision == BESO_PREC_BF16X3 ? 2 : 1;
+    // a new image: every entry of its sigma-token cache is free (tags 0; the entries themselves, so that no byte of the image
+    // is left as it was found)
+    if (precision == BESO_PREC_BF16 && sig_shape(d))
+        FTRY(hipMemsetAsync(packed + lay.fused + sig_cache_offset(d), 0, sig_cache_bytes(d), s));
     for (int half = 0; half < n_parts; ++half)               // 0: bf16(w); 1 (BF16X3 only): the low halves
     for (int l = 0; l < lay.L; ++l) {
         // parameter order (include/beso_hip.h): 3 leading tensors, then 16 per block:
@@ -4620,8 +4810,11 @@ int fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float*
     if ((size_t)(d.seq1 ? 1 : kSPW) * a.t * lay.act * sizeof(float) > (size_t)kXsBytes) return BESO_ERR_UNSUPPORTED;
     if (fused_edges) *fused_edges = 3;
     hipError_t err;
-    if (d.RPW == 3 && d.KS == 12 && d.HG == 1) err = launch_layers<3, 12, 1, 2>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, TR, precision, a.plan, s);    // kitchen: 8 x 4 action tokens
-    else if (d.RPW == 2 && d.KS == 8 && d.HG == 3) err = launch_layers<2, 8, 3, 4>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, TR, precision, a.plan, s);   // block-push: 8 x 5
+    // the sigma-token cache of the image (bf16 / fp16 operands; a call without a flag word of its own -- a.sig_flag -- does not share)
+    SigArgs sig{nullptr, nullptr};
+    if (precision == BESO_PREC_BF16 && sig_shape(d) && a.sig_flag) sig = SigArgs{(uint32_t*)(const_cast<char*>(base) + sig_cache_offset(d)), a.sig_flag};
+    if (d.RPW == 3 && d.KS == 12 && d.HG == 1) err = launch_layers<3, 12, 1, 2>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, TR, precision, a.plan, s, sig);    // kitchen: 8 x 4 action tokens
+    else if (d.RPW == 2 && d.KS == 8 && d.HG == 3) err = launch_layers<2, 8, 3, 4>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, TR, precision, a.plan, s, sig);   // block-push: 8 x 5
     else if (d.seq1 && precision == BESO_PREC_BF16) err = launch_layers_long<4, 16, kLongNT>(x, base, d, 0, lay.L, a.batch, a.T, e, S, X3, TR, s);   // long horizon: 1 x 67 tokens
                                                                                                              // (one workgroup per REAL sample: pairs run as two passes)
     else return BESO_ERR_UNSUPPORTED;
@@ -4632,6 +4825,16 @@ int fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float*
 void fused_set_stamps(void* buf, int cap) {
     g_stamps = (unsigned long long*)buf;
     g_stamps_cap = cap;
+}
+// entries of the image's sigma-token cache that hold a value (a synchronous copy of the tags; -1: the image has no cache)
+int fused_sigma_cache_entries(const Layout& lay, const char* packed) {
+    FusedDims d;
+    if (!fused_dims(lay, &d) || !sig_shape(d) || lay.fused == lay.total) return -1;
+    SigHdr h;
+    if (hipMemcpy(&h, packed + lay.fused + sig_cache_offset(d), sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    int n = 0;
+    for (int i = 0; i < kSigEntries; ++i) n += h.tag[i] != 0u;
+    return n;
 }
 #endif
 

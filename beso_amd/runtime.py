@@ -22,7 +22,8 @@ _hints = threading.local()
 @contextlib.contextmanager
 def plan(forward: int = 0, train: int = 0):
     """Execution-plan hints for the library calls the CALLING THREAD makes inside the block: ``forward`` = BESO_PLAN_* bits
-    (``_lib.PLAN_PER_OP``, ``PLAN_BLOCKS``, ``PLAN_SMALL``, ``PLAN_FUSED``, ``PLAN_SPW2 / 4 / 8``) added to the flags of every forward / sampler call,
+    (``_lib.PLAN_PER_OP``, ``PLAN_BLOCKS``, ``PLAN_SMALL``, ``PLAN_FUSED``, ``PLAN_SPW2 / 4 / 8``, ``PLAN_SIGMA_SHARED`` /
+    ``PLAN_SIGMA_PRIVATE``: the sigma token shared across a uniform-sigma kitchen batch at any batch size / never) added to the flags of every forward / sampler call,
     ``train`` = ``_lib.TRAIN_PLAN_PER_OP`` / ``TRAIN_PLAN_TILES`` for ``beso_loss_grad``.  They select WHICH kernels run,
     never what is computed (parity tests: per-op kernels against the fused ones; measurements); each library call carries
     its own flags, so nothing process-wide changes."""
@@ -35,7 +36,8 @@ def plan(forward: int = 0, train: int = 0):
 
 
 def set_plan(forward: Optional[int] = None, train: Optional[int] = None) -> None:
-    """The same hints without a block: they stay with the calling thread until set again (0 = the library's own choice)."""
+    """The same hints without a block: they stay with the calling thread until set again (0 = the library's own choice;
+    ``forward`` takes every BESO_PLAN_* bit, ``_lib.PLAN_SIGMA_SHARED`` / ``PLAN_SIGMA_PRIVATE`` included)."""
     if forward is not None:
         _hints.forward = forward
     if train is not None:

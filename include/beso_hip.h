@@ -48,6 +48,15 @@
  *   - thread-safety: the library keeps no mutable process-wide state; calls on distinct workspaces/streams are
  *     independent (a workspace must not be shared by concurrent calls).  What a call may vary -- which kernels run --
  *     travels in its own `flags` (BESO_PLAN_*); the launch-site timers (beso_profile_*) are per calling thread.
+ *     One piece of state lives in DEVICE memory the caller owns: the sigma-token cache inside a bf16 / fp16 packed image
+ *     of the kitchen-class shape (beso_pack_weights), which forwards of a uniform-sigma batch read and extend.  Calls that
+ *     share an image on one stream, or on streams the caller orders, need nothing.  Calls that share an image on
+ *     streams running CONCURRENTLY are supported only while the image sees at most 128 distinct sigma values between two
+ *     packs (no entry is ever replaced then; two calls that miss the same value at once each write an entry of their own,
+ *     with equal contents).  Beyond that a miss on one stream replaces the oldest entry round-robin, and that entry may be
+ *     the one a forward running on another stream hit and is still reading -- whatever its age when it was hit: such
+ *     callers pass BESO_PLAN_SIGMA_PRIVATE with every concurrent call, or give each stream its own image.
+ *     beso_pack_weights into an image must be ordered against every call that uses it, as before.
  *   - development aids (phase stamps, the GEMM layout probe) are not part of this library: they exist in the
  *     development build only (include/beso_hip_debug.h, libbeso_hip_dev.so).
  */
@@ -124,7 +133,11 @@ enum {
     BESO_PLAN_SPW4 = 0x200,   /*   4 (up to 1024; the split-bf16 mode: above 512), */
     BESO_PLAN_SPW8 = 0x300,   /*   8 (larger batches) */
     BESO_PLAN_SPW_MASK = 0x300,
-    BESO_PLAN_MASK = 0x3f0,
+    BESO_PLAN_SIGMA_SHARED = 0x400,  /* one forward, kitchen-class shape (embed_dim 360, 6 heads), bf16 / fp16: the eight-sample
+                                        plan with the sigma token shared (below, beso_pack_weights) at ANY batch size -- without
+                                        a hint: wherever the eight-sample instance runs (more than 1024 samples, or SPW8) */
+    BESO_PLAN_SIGMA_PRIVATE = 0x800, /* never shared: every sample computes its own sigma token, the image's cache is not touched */
+    BESO_PLAN_MASK = 0xff0,
     BESO_SAMPLE_STEPWISE = 0x1000, /* beso_sample: enqueue evaluation by evaluation (see there) */
     BESO_FLAG_LAST_ACTION_ONLY = 0x2000 /* beso_loss_fwd: GCDenoiser.loss(pred_last_action_only=True) -- only the last step of
                                       every window is scored (score_wrappers.py:59-63,76-77; the caller zeroes the other
@@ -166,7 +179,13 @@ size_t beso_packed_bytes(const beso_config* cfg, int precision);
 /* Re-lay the fp32 parameters (host array `params` of `n_params` DEVICE pointers, order above) into
  * the kernel-ready image `packed` (device, >= beso_packed_bytes): fused QKV rows, bf16 (or fp32)
  * GEMM operands zero-padded to the MFMA tile grid.  Call again whenever a parameter changes
- * (optimizer step, EMA swap, load_state_dict).                                                   */
+ * (optimizer step, EMA swap, load_state_dict).
+ * The bf16 / fp16 image of the kitchen-class shape ends in a sigma-token cache (1.1 MiB): 128 entries, each the k / v rows
+ * of the sigma token in every layer for one sigma value -- token 0 has no position and attends to itself only, so they
+ * depend on (weights, sigma) alone.  Packing zeroes it; a forward whose sigma[0 .. batch) is ONE value (every sampler's
+ * calls) looks that value up on the device, computes the entry once if it is new, and runs the network on the other ten
+ * tokens per sample.  The image is therefore written by the forward calls that take it as `const void* packed`
+ * (that region only).  Results are bit-identical either way.                                      */
 int beso_pack_weights(const beso_config* cfg, const float* const* params, int n_params,
                       void* packed, size_t packed_bytes, int precision, void* stream);
 

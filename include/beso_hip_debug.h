@@ -19,6 +19,10 @@ extern "C" {
  * -DBESO_FUSED_STAMPS=1) appends {phase id, shader clock} pairs to it (NULL / 0 switches it off).               */
 void beso_debug_set_stamps(void* device_buf, int capacity_u64);
 
+/* Occupied entries of the sigma-token cache inside the packed image `packed` (bf16 / fp16, the kitchen-class shape; see
+ * beso_pack_weights in beso_hip.h): a synchronous copy of its tags.  -1: the image has no such cache.                       */
+int beso_debug_sigma_cache_entries(const beso_config* cfg, const void* packed, int precision);
+
 /* Operand layouts of the training GEMM: C[M][N] (fp32, ldc) = sum_k A(m,k) B(n,k);
  * a_kslow / b_kslow = 1: the operand is stored [K][ld] (contraction index slow), 0: [rows][ld] (k contiguous).
  * Supported pairs: (0,0), (0,1), (1,1).  splits > 1 accumulates split-K partial sums into a ZEROED C.

@@ -4,7 +4,10 @@
     python tools/variants.py build  probe=-DBESO_ABL_MASK=1  r5=@7162316  old=@133ba77,-D<SWITCH>=1
                                         (CPU box: hipcc cross-compile; "@rev" = all of csrc/ as of that commit, which is how
                                          an A/B switch that has since left the sources is built again)
-    python tools/variants.py time   [--batch 4096] [--stamps]           (GPU box: times every built variant)
+    python tools/variants.py time   [--batch 4096] [--mode uniform|distinct|ddim64] [--reps 2] [--only name,name]
+                                        (GPU box: times every built variant, runs interleaved.  uniform: one forward, the
+                                         same sigma for every sample -- the benchmark's call; distinct: one forward, `batch`
+                                         distinct sigmas; ddim64: a 10-step DDIM call at B = 64, BASELINE config 1, ms per call)
 
 Variants are libbeso_hip_<name>.so under beso_amd/lib/variants/ (only fused.hip is recompiled; the other
 objects come from the regular build).  `time` runs each variant in its own process (BESO_HIP_LIB).
@@ -69,7 +72,30 @@ def build(specs):
         print("built", lib)
 
 
-def time_one(batch, steps=300):
+def time_ddim64(calls=200):
+    import time
+    import torch
+    from bench import build_model
+    from beso_amd import synthetic as O
+    from beso_amd.agents.diffusion_agents.k_diffusion import gc_sampling as ks
+    dev = "cuda:0"
+    cfg = O.SHAPES["kitchen"]
+    model = build_model(cfg, O.make_weights(cfg, seed=0, std=0.02), os.environ.get("BESO_VARIANT_PRECISION", "bf16"), dev)
+    s, g, a = (torch.from_numpy(v).to(dev) for v in O.make_inputs(cfg, 64, seed=1))
+    x_t = torch.randn_like(a)
+    sigmas = ks.get_sigmas_exponential(10, 0.005, 1.0)
+    with torch.no_grad():
+        for _ in range(50):
+            ks.sample_ddim(model, s, x_t, g, sigmas, disable=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            ks.sample_ddim(model, s, x_t, g, sigmas, disable=True)
+        torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / calls * 1e3
+
+
+def time_one(batch, steps=300, distinct=False):
     import torch
     from bench import build_model
     from beso_amd import synthetic as O
@@ -77,7 +103,7 @@ def time_one(batch, steps=300):
     cfg = O.SHAPES["kitchen"]
     model = build_model(cfg, O.make_weights(cfg, seed=0, std=0.02), os.environ.get("BESO_VARIANT_PRECISION", "bf16"), dev)
     s, g, a = (torch.from_numpy(v).to(dev) for v in O.make_inputs(cfg, batch, seed=1))
-    sig = torch.full((batch,), 0.3, device=dev)
+    sig = torch.linspace(0.05, 1.0, batch, device=dev) if distinct else torch.full((batch,), 0.3, device=dev)
     inner = model.inner_model
     rt, packed = inner.runtime(cfg.sigma_data), inner.packed_weights()
     with torch.no_grad():
@@ -97,21 +123,26 @@ def main():
     if sys.argv[1] == "build":
         return build(sys.argv[2:])
     if sys.argv[1] == "one":
-        print(json.dumps({"ms": time_one(int(sys.argv[2]))}))
+        mode = sys.argv[3] if len(sys.argv) > 3 else "uniform"
+        ms = time_ddim64() if mode == "ddim64" else time_one(int(sys.argv[2]), distinct=mode == "distinct")
+        print(json.dumps({"ms": ms}))
         return
-    batch = 4096
-    if "--batch" in sys.argv:
-        batch = int(sys.argv[sys.argv.index("--batch") + 1])
+    opt = lambda name, default: sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+    batch, mode, reps = int(opt("--batch", 4096)), opt("--mode", "uniform"), int(opt("--reps", 2))
     libs = sorted(f for f in os.listdir(VDIR) if f.endswith(".so"))
-    for rep in range(2):
+    if "--only" in sys.argv:          # --only a,b: those variants
+        libs = [f for f in libs if f[len("libbeso_hip_"):-3] in opt("--only", "").split(",")]
+    for rep in range(reps):
         for f in libs:
             env = dict(os.environ, BESO_HIP_LIB=os.path.join(VDIR, f))
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "one", str(batch)], env=env,
-                               capture_output=True, text=True)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "one", str(batch), mode], env=env,
+                               capture_output=True, text=True, timeout=300)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
             ms = json.loads(line[-1])["ms"] if line else None
             print(f"{f[len('libbeso_hip_'):-3]:24s} {ms if ms is None else round(ms, 4)} ms" + ("" if line else "  " + r.stderr[-300:]))
             sys.stdout.flush()
+            if r.returncode:              # a run that failed: nothing more is started on the GPU
+                raise SystemExit(f"variant {f}: exit status {r.returncode}")
 
 
 if __name__ == "__main__":
