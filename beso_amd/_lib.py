@@ -45,7 +45,7 @@ EXPORTS = ["beso_version", "beso_status_string", "beso_last_error", "beso_num_pa
            "beso_loss_grad_overlap", "beso_grad_early_range", "beso_sample_ancestral", "beso_goal_mask",
            "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp", "beso_sample_solver",
            "beso_dropout_mask", "beso_sample_traced", "beso_rollout_begin", "beso_rollout_end",
-           "beso_loss_fwd_workspace_bytes", "beso_loss_fwd"]
+           "beso_loss_fwd_workspace_bytes", "beso_loss_fwd", "beso_grad_sumsq", "beso_adam_step_clipped"]
 # include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
 DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm", "beso_debug_sigma_cache_entries"]
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
@@ -126,6 +126,11 @@ def load() -> C.CDLL:
         if hasattr(lib, "beso_adam_step") or not os.environ.get("BESO_HIP_LIB"):   # (A/B builds of older revisions)
             lib.beso_adam_step.restype = i32
             lib.beso_adam_step.argtypes = [vp, i32, vp, vp, vp, f32, f32, f32, f32, f32, i32, i32, f32, vp]
+        if hasattr(lib, "beso_grad_sumsq") or not os.environ.get("BESO_HIP_LIB"):
+            lib.beso_grad_sumsq.restype = i32
+            lib.beso_grad_sumsq.argtypes = [vp, i32, vp, vp, vp]
+            lib.beso_adam_step_clipped.restype = i32
+            lib.beso_adam_step_clipped.argtypes = list(lib.beso_adam_step.argtypes[:-1]) + [vp, f32, i32, vp]
         if hasattr(lib, "beso_loss_grad") or not os.environ.get("BESO_HIP_LIB"):
             lib.beso_train_workspace_bytes.restype = sz
             lib.beso_train_workspace_bytes.argtypes = [cfgp, i32, i32, i32]

@@ -8,7 +8,10 @@ attributes (``model``, ``sigma_min/max``, ``use_kde`` ...).  What changes undern
     copies the shadow in and copies the originals back on EVERY call (beso_agent.py:343-345,380-381);
   * ``sample_loop`` hands ddim / euler / heun to the HIP library as one enqueue of all steps;
   * ``train_step`` all-reduces the score-matching gradients over the data-parallel ranks (RCCL over
-    xGMI) before the optimizer step when a process group is initialised.
+    xGMI) before the optimizer step when a process group is initialised;
+  * two optional constructor arguments the reference does not have, ``max_grad_norm`` and ``skip_nonfinite_steps``
+    (after ``patience``, both off by default): global gradient-norm clipping and a guard that drops a step whose
+    gradient is not finite, both inside the fused optimizer launch (``FusedAdam.step``).
 """
 import contextlib
 import logging
@@ -54,7 +57,8 @@ class BesoAgent(BaseAgent):
                  sampler_type: str, sigma_data: float, sigma_min: float, sigma_max: float,
                  sigma_sample_density_type: str, sigma_sample_density_mean: float,
                  sigma_sample_density_std: float, decay: float, update_ema_every_n_steps: int,
-                 window_size: int, goal_window_size: int, use_kde: bool = False, patience: int = 10):
+                 window_size: int, goal_window_size: int, use_kde: bool = False, patience: int = 10,
+                 max_grad_norm: float | None = None, skip_nonfinite_steps: bool = False):
         super().__init__(model, input_encoder, optimization, obs_modalities, goal_modalities, target_modality,
                          device, max_train_steps, eval_every_n_steps, max_epochs)
         self.ema_helper = ExponentialMovingAverage(self.model.get_params(), decay, self.device)
@@ -62,6 +66,17 @@ class BesoAgent(BaseAgent):
         # torch Adam / AdamW on a HIP device -> the one-launch fused step (same hyper-parameters, same
         # param_groups surface for the LR scheduler); any other optimizer class is left as configured
         self.optimizer = maybe_fuse(self.optimizer)
+        # gradient clipping / the non-finite guard: inside the fused launch, from a norm the host never reads.  The eager
+        # optimizers clip through torch.nn.utils.clip_grad_norm_; the guard would need a host read per step there -- the
+        # read it exists to avoid -- and is refused
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be positive (or None)")
+        if skip_nonfinite_steps and not isinstance(self.optimizer, FusedAdam):
+            raise ValueError("skip_nonfinite_steps needs the fused optimizer (torch Adam / AdamW over fp32 parameters on "
+                             "the GPU): the guard lives in its launch")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite_steps = bool(skip_nonfinite_steps)
+        self._eager_grad_norm = None
         self.lr_scheduler = instantiate(lr_scheduler, optimizer=self.optimizer)
         self.gc = goal_conditioned
         self.train_method = train_method
@@ -261,7 +276,10 @@ class BesoAgent(BaseAgent):
                 batch = next(stream)
             loss = self.train_step(batch)
             if not self.steps % 1000:
-                log.info("Step %d: Mean batch loss mse is %s", step, loss)
+                if self.max_grad_norm is not None or self.skip_nonfinite_steps:
+                    log.info("Step %d: Mean batch loss mse is %s, gradient norm %s", step, loss, float(self.last_grad_norm()))
+                else:
+                    log.info("Step %d: Mean batch loss mse is %s", step, loss)
             _wandb_log({"loss": loss, "test_loss": avg_test_mse})
         self.store_model_weights(self.working_dir)
         log.info("Training done!")
@@ -421,12 +439,21 @@ class BesoAgent(BaseAgent):
         if isinstance(self.optimizer, FusedAdam):
             # Adam(W) over all tensors and the EMA of the updated parameters in ONE HIP launch -- over the owned range
             # only in the sharded exchange, followed by the all-gather of the updated parameters
-            self.optimizer.step(ema=self.ema_helper if do_ema else None, shard=shard)
+            if self.max_grad_norm is None and not self.skip_nonfinite_steps:
+                self.optimizer.step(ema=self.ema_helper if do_ema else None, shard=shard)
+            else:
+                # (sharded exchange: each rank reduces the squared norm of its own range; the sum over the ranks is the whole
+                # gradient's.  flat / overlap: every rank holds the full reduced gradient and computes the same norm)
+                self.optimizer.step(ema=self.ema_helper if do_ema else None, shard=shard, max_grad_norm=self.max_grad_norm,
+                                    skip_nonfinite=self.skip_nonfinite_steps,
+                                    reduce_sumsq=bdist.all_reduce_sum if shard is not None else None)
             if shard is not None:
                 self._sharded().all_gather_params()
                 self._ema_partial = getattr(self, "_ema_partial", False) or do_ema
             self.lr_scheduler.step()
         else:
+            if self.max_grad_norm is not None:
+                self._eager_grad_norm = torch.nn.utils.clip_grad_norm_(self.model.get_params(), self.max_grad_norm)
             self.optimizer.step()
             self.lr_scheduler.step()
             if do_ema:
@@ -437,6 +464,24 @@ class BesoAgent(BaseAgent):
         if bdist.is_distributed():
             loss = bdist.all_reduce_mean(loss.detach().clone())      # C3: the logged loss is the global-batch mean
         return loss.item()
+
+    def last_grad_norm(self) -> torch.Tensor:
+        """The global L2 norm of the last training step's gradient, before clipping (``max_grad_norm`` or
+        ``skip_nonfinite_steps`` set): a 0-d tensor on the agent's device.  Calling this does not synchronise; reading the
+        value does, and then waits for the whole step."""
+        if isinstance(self.optimizer, FusedAdam):
+            return self.optimizer.last_grad_norm()
+        if self._eager_grad_norm is None:
+            raise RuntimeError("no training step with max_grad_norm has run yet")
+        return self._eager_grad_norm
+
+    def skipped_steps(self) -> torch.Tensor:
+        """How many training steps ``skip_nonfinite_steps`` has dropped so far (a 0-d device tensor; no synchronisation).
+        ``steps``, the LR scheduler, Adam's bias-correction count and the EMA warm-up count advance over a dropped step as
+        over any other: the host does not know it was dropped."""
+        if not isinstance(self.optimizer, FusedAdam):
+            raise RuntimeError("skipped_steps needs the fused optimizer")
+        return self.optimizer.skipped_steps()
 
     @torch.no_grad()
     def evaluate(self, batch: dict):

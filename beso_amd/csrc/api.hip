@@ -819,6 +819,28 @@ int beso_adam_step(const beso_optim_chunk* chunks, int n_chunks, float* exp_avg,
     return BESO_OK;
 }
 
+int beso_grad_sumsq(const beso_optim_chunk* chunks, int n_chunks, double* partial, double* stats, void* stream) {
+    if (!stats || n_chunks < 0 || (n_chunks > 0 && (!chunks || !partial))) return BESO_ERR_BAD_ARG;
+    hipError_t e = launch_grad_sumsq(chunks, n_chunks, partial, stats, (hipStream_t)stream);     // n_chunks == 0: stats[0] = 0
+    if (e != hipSuccess) return record_hip_error(e, "grad_sumsq_kernel", __LINE__);
+    return BESO_OK;
+}
+
+int beso_adam_step_clipped(const beso_optim_chunk* chunks, int n_chunks, float* exp_avg, float* exp_avg_sq, float* ema,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled_wd, int step,
+                           float ema_decay, double* stats, float max_grad_norm, int skip_nonfinite, void* stream) {
+    if (!chunks || !exp_avg || !exp_avg_sq || !stats || n_chunks < 0 || step < 1) return BESO_ERR_BAD_ARG;
+    if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && lr >= 0.f)) return BESO_ERR_BAD_ARG;
+    if (ema && !(ema_decay >= 0.f && ema_decay <= 1.f)) return BESO_ERR_BAD_ARG;
+    if (!(max_grad_norm > 0.f)) return BESO_ERR_BAD_ARG;                                        // NaN too; +inf = do not clip
+    if (n_chunks == 0) return BESO_OK;
+    hipError_t e = launch_adam_ema_clipped(chunks, n_chunks, exp_avg, exp_avg_sq, ema, lr, beta1, beta2, eps, weight_decay,
+                                           decoupled_wd ? 1 : 0, step, ema_decay, stats, max_grad_norm,
+                                           skip_nonfinite ? 1 : 0, (hipStream_t)stream);
+    if (e != hipSuccess) return record_hip_error(e, "adam_ema_clipped_kernel", __LINE__);
+    return BESO_OK;
+}
+
 int beso_gather_windows(const float* observations, const float* actions, const int* seq_len, int n_traj, int t_max,
                         int obs_dim, int act_dim, const int* slice_traj, const int* slice_start, long long n_slices,
                         const long long* batch_slices, const long long* draws, int batch, int window, int goal_len,

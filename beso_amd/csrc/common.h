@@ -428,5 +428,10 @@ hipError_t launch_loss_reduce(const float* pred, const float* action, const floa
                               float* loss, int batch, int t, int act, int last_only, float sigma_data, hipStream_t s);
 hipError_t launch_adam_ema(const void* chunks, int n_chunks, float* m, float* v, float* ema, float lr, float beta1,
                            float beta2, float eps, float wd, int decoupled, int step, float ema_decay, hipStream_t s);
+// the global gradient norm on the device and the step that consumes it (optim.hip); stats = double[4]
+hipError_t launch_grad_sumsq(const void* chunks, int n_chunks, double* partial, double* stats, hipStream_t s);
+hipError_t launch_adam_ema_clipped(const void* chunks, int n_chunks, float* m, float* v, float* ema, float lr, float beta1,
+                                   float beta2, float eps, float wd, int decoupled, int step, float ema_decay, double* stats,
+                                   float max_norm, int skip_nonfinite, hipStream_t s);
 
 }  // namespace beso

@@ -7,10 +7,15 @@ unchanged.  ``step()`` updates ALL parameters -- and, when an EMA helper is hand
 (ema.py:45-53) -- in one HIP launch (``beso_adam_step``) instead of several hundred eager launches.
 There is no CPU implementation: ``maybe_fuse`` leaves a CPU optimizer untouched.  The moments live in flat
 buffers owned by the optimizer object (not in ``Optimizer.state``): like the reference's training loop
-(``beso_agent.py:466-476`` stores model weights only) optimizer state is not checkpointed."""
+(``beso_agent.py:466-476`` stores model weights only) optimizer state is not checkpointed.
+
+``step(max_grad_norm=..., skip_nonfinite=...)`` adds global gradient-norm clipping and a guard that drops a step whose
+gradient is not finite.  Both consume the norm ON THE DEVICE (``beso_grad_sumsq`` -> ``beso_adam_step_clipped``): the
+host never reads it, so the asynchronous training step stays asynchronous."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -71,12 +76,63 @@ class FusedAdam(torch.optim.Optimizer):
         self._groups[gi] = st
         return st
 
+    def _clip_scratch(self, st: dict):
+        """``stats`` (double[4]: sumsq, norm, coefficient, skipped steps -- include/beso_hip.h) and ``partial`` (one double
+        per chunk) of a group, next to its moments.  ``partial`` is re-made when the chunk table changes; ``stats`` is made
+        once, so that the skip counter and the views the accessors handed out stay valid."""
+        dev = st["m"].device
+        if "stats" not in st:
+            st["stats"] = torch.zeros(4, dtype=torch.float64, device=dev)
+        if st.get("partial") is None or st["partial"].numel() < st["n_chunks"]:
+            st["partial"] = torch.empty(max(st["n_chunks"], 1), dtype=torch.float64, device=dev)
+        return st["partial"], st["stats"]
+
+    def _stats(self, group: int) -> torch.Tensor:
+        st = self._groups[group]
+        if st is None or "stats" not in st:
+            raise RuntimeError("no step with max_grad_norm / skip_nonfinite has run yet")
+        return st["stats"]
+
+    def last_grad_norm(self, group: int = 0) -> torch.Tensor:
+        """The global L2 norm of the gradient the last clipped / guarded step saw (before clipping; the fp32 value, as a
+        0-d float64 DEVICE view: reading it is the caller's synchronisation, calling this is none)."""
+        return self._stats(group)[1]
+
+    def last_clip_coef(self, group: int = 0) -> torch.Tensor:
+        """The coefficient the last clipped / guarded step multiplied the gradient by (1: not clipped, 0: step skipped);
+        a 0-d device view."""
+        return self._stats(group)[2]
+
+    def skipped_steps(self, group: int = 0) -> torch.Tensor:
+        """How many steps ``skip_nonfinite`` has dropped so far; a 0-d device view."""
+        return self._stats(group)[3]
+
     @torch.no_grad()
-    def step(self, closure=None, ema=None, shard=None):
+    def step(self, closure=None, ema=None, shard=None, max_grad_norm=None, skip_nonfinite=False, reduce_sumsq=None):
         """One step.  ``ema``: an ``ExponentialMovingAverage`` over exactly this optimizer's parameters (in
         order) whose shadow is updated in the same launch, with its own warm-up rule.  ``shard = (lo, hi)``: update
         only the elements [lo, hi) of the flat parameter order (one parameter group) -- the sharded data-parallel
-        step, where this rank holds the reduced gradients of that range only."""
+        step, where this rank holds the reduced gradients of that range only.
+
+        ``max_grad_norm``: clip the gradient to this global L2 norm by the rule of ``torch.nn.utils.clip_grad_norm_``
+        (coefficient ``min(1, max_grad_norm / (norm + 1e-6))``), applied inside the step launch.  Unlike
+        ``clip_grad_norm_`` the ``.grad`` tensors are NOT rescaled: they keep the unclipped values.  ``inf`` measures
+        (and guards) without clipping, bit-equal to the plain step.  ``skip_nonfinite``: a step whose squared gradient
+        norm is inf / NaN writes nothing -- parameters, both moments and the EMA shadow keep their bits -- and counts
+        itself in ``skipped_steps()``; alone it means ``max_grad_norm=inf``.  With neither, the step is the plain
+        ``beso_adam_step`` call.  ``reduce_sumsq``: called with the 1-element device view of the squared norm between
+        the reduction and the step, to sum it in place across the ranks of a sharded exchange (each rank's table covers
+        its shard only).  With several parameter groups the norm, the clipping and the guard are PER GROUP.
+        Nothing here synchronises: ``last_grad_norm()``, ``last_clip_coef()`` and ``skipped_steps()`` are device views.
+
+        Host counters on a skipped step: the host cannot know that the device skipped, so the bias-correction step count
+        and the EMA warm-up counter (``ema.next_decay()``, ``ema.version``) advance as on any other step -- a decision,
+        not an oversight: the alternative is the per-step host read this feature exists to avoid."""
+        clipped = max_grad_norm is not None or skip_nonfinite
+        if clipped:
+            max_grad_norm = math.inf if max_grad_norm is None else float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError("max_grad_norm must be positive (inf: measure and guard without clipping)")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -95,9 +151,25 @@ class FusedAdam(torch.optim.Optimizer):
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         for st, group in zip(prepared, self.param_groups):
             st["step"] += 1
+            if clipped:
+                # (an empty table -- a rank that owns nothing of a sharded exchange -- still contributes its 0 to the sum:
+                # reduce_sumsq is a collective)
+                partial, stats = self._clip_scratch(st)
+                table = st["table"].data_ptr() if st["n_chunks"] else None
+                _lib.check(lib.beso_grad_sumsq(table, st["n_chunks"], partial.data_ptr(), stats.data_ptr(), stream),
+                           "beso_grad_sumsq")
+                if reduce_sumsq is not None:
+                    reduce_sumsq(stats[0:1])
             if st["n_chunks"] == 0:
                 continue
             b1, b2 = group["betas"]
+            if clipped:
+                _lib.check(lib.beso_adam_step_clipped(
+                    st["table"].data_ptr(), st["n_chunks"], st["m"].data_ptr(), st["v"].data_ptr(), ema_ptr,
+                    float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                    1 if group["decoupled_weight_decay"] else 0, st["step"], float(ema_decay), stats.data_ptr(),
+                    max_grad_norm, 1 if skip_nonfinite else 0, stream), "beso_adam_step_clipped")
+                continue
             _lib.check(lib.beso_adam_step(st["table"].data_ptr(), st["n_chunks"], st["m"].data_ptr(), st["v"].data_ptr(),
                                           ema_ptr, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                           float(group["weight_decay"]), 1 if group["decoupled_weight_decay"] else 0,

@@ -29,6 +29,8 @@
  *   beso_loss_grad_streams  (same, plus a stream that is released as soon as the loss value is final)
  *   beso_denoise_vjp    <- GCDenoiser.forward + torch.autograd.grad w.r.t. the action   k_diffusion/gc_sampling.py:480-485
  *   beso_adam_step      <- optimizer.step() + ema_helper.update()      beso_agent.py:236-244
+ *   beso_grad_sumsq / beso_adam_step_clipped <- torch.nn.utils.clip_grad_norm_ in front of that step, and a guard that
+ *                          drops a step whose gradient is not finite -- both without a host read (the reference has neither)
  *   beso_gather_windows <- TrajectorySlicerDataset.__getitem__ x batch envs/dataloaders/trajectory_loader.py:160-197
  *   beso_rollout_begin / beso_rollout_end <- the window bookkeeping around the sampler call of BesoAgent.predict, for N
  *                          environments with independent resets            agents/diffusion_agents/beso_agent.py:296-388
@@ -310,6 +312,37 @@ typedef struct beso_optim_chunk {
 int beso_adam_step(const beso_optim_chunk* chunks, int n_chunks, float* exp_avg, float* exp_avg_sq, float* ema,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled_wd, int step,
                    float ema_decay, void* stream);
+
+/* Global gradient-norm clipping and the non-finite guard of the optimizer step, with no host read in between: the squared
+ * L2 norm of the gradients is reduced on the device and the step launch consumes it.
+ *   stats       DEVICE double[4], owned by the caller:
+ *                 [0] sumsq   written by beso_grad_sumsq (a sharded data-parallel step sums it across ranks in place
+ *                             before the step: every rank then applies the norm of the WHOLE gradient)
+ *                 [1] norm    (float)sqrt(sumsq) of the last beso_adam_step_clipped, held as a double
+ *                 [2] coef    the clip coefficient that step applied; 0 when it was skipped
+ *                 [3] skipped number of skipped steps so far: INCREMENTED by a skipped step -- the caller zeroes it once
+ *               [0..2] are fully overwritten on every use and may hold anything on entry (as may `partial`).
+ * beso_grad_sumsq: stats[0] = sum of g^2 over all chunks (the `g` pointers of the table beso_adam_step walks, so a
+ *   sharded table gives the shard's share).  Squares and sums are in double, in a fixed order (per chunk, then over
+ *   partial[0 .. n_chunks)): no atomics, the same inputs give the same bits.  `partial`: at least n_chunks doubles of scratch.
+ *   n_chunks == 0 is valid (chunks and partial may then be NULL) and writes stats[0] = 0.
+ * beso_adam_step_clipped: beso_adam_step with every gradient element multiplied (one rounded fp32 multiply, in registers) by
+ *   coef = min(1, max_grad_norm / (norm + 1e-6f)), norm = (float)sqrt(stats[0]) -- the rule of torch.nn.utils.clip_grad_norm_.
+ *   DEPARTURE from clip_grad_norm_: the gradient buffer itself is NOT rescaled; a caller that reads the gradients after the
+ *   step sees the unclipped values.  max_grad_norm = +inf gives coef == 1 exactly: the step is bit-equal to beso_adam_step
+ *   and only measures (and guards).  max_grad_norm <= 0 or NaN is BESO_ERR_BAD_ARG.
+ *   skip_nonfinite != 0: when stats[0] is inf or NaN the launch stores nothing into the parameters, exp_avg, exp_avg_sq and
+ *   ema (they keep their bits), writes coef = 0 and increments stats[3].  The HOST cannot know: `step` (bias correction) and
+ *   the EMA warm-up counter behind `ema_decay` are the caller's, and a caller that does not read stats[3] advances them over a
+ *   skipped step as over any other.  With skip_nonfinite == 0 nothing is held back: a NaN norm gives
+ *   coef = 1 (fminf drops the NaN), an infinite one coef = 0 under a finite max_grad_norm, and the non-finite gradient
+ *   elements reach the parameters, as they do in torch.
+ *   The norm is over the chunks of the call: a caller with several parameter groups (one call each) clips per group.
+ *   n_chunks == 0 is a no-op that leaves stats untouched.                                                                    */
+int beso_grad_sumsq(const beso_optim_chunk* chunks, int n_chunks, double* partial, double* stats, void* stream);
+int beso_adam_step_clipped(const beso_optim_chunk* chunks, int n_chunks, float* exp_avg, float* exp_avg_sq, float* ema,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled_wd, int step,
+                           float ema_decay, double* stats, float max_grad_norm, int skip_nonfinite, void* stream);
 
 /* Training step, forward + backward: GCDenoiser.loss (score_wrappers.py:45-79; flags: BESO_TRAIN_LAST_ACTION_ONLY) of the
  * training-mode network (score_gpts.py:272-358 with the dropouts of :41,:79,:109) and the gradient of that loss with

@@ -8,7 +8,7 @@ from beso_amd.agents.diffusion_agents.beso_agent import BesoAgent
 from beso_amd.agents.input_encoders.obs_encoder import NoEncoder
 
 
-def build_agent(shape, model_factory, device="cuda:0", sampler="ddim", lr=1e-4):
+def build_agent(shape, model_factory, device="cuda:0", sampler="ddim", lr=1e-4, **extra):
     return BesoAgent(
         model=model_factory,
         input_encoder=functools.partial(NoEncoder, device=device, state_modality="observation", goal_modality="goal_observation"),
@@ -19,4 +19,4 @@ def build_agent(shape, model_factory, device="cuda:0", sampler="ddim", lr=1e-4):
         lr_scheduler=lambda optimizer: torch.optim.lr_scheduler.StepLR(optimizer, 100, 0.99),
         sampler_type=sampler, sigma_data=shape.sigma_data, sigma_min=0.005, sigma_max=1.0,
         sigma_sample_density_type="loglogistic", sigma_sample_density_mean=-0.6, sigma_sample_density_std=1.6, decay=0.999,
-        update_ema_every_n_steps=1, window_size=shape.obs_seq_len, goal_window_size=shape.goal_seq_len)
+        update_ema_every_n_steps=1, window_size=shape.obs_seq_len, goal_window_size=shape.goal_seq_len, **extra)
