@@ -20,7 +20,7 @@ PLAN_SPW2, PLAN_SPW4, PLAN_SPW8 = 0x100, 0x200, 0x300
 PLAN_SIGMA_SHARED, PLAN_SIGMA_PRIVATE = 0x400, 0x800
 SAMPLE_STEPWISE = 0x1000
 FLAG_LAST_ACTION_ONLY = 0x2000     # beso_loss_fwd: only the last step of every window is scored
-TRAIN_LAST_ACTION_ONLY, TRAIN_PLAN_PER_OP, TRAIN_PLAN_TILES = 1, 2, 4
+TRAIN_LAST_ACTION_ONLY, TRAIN_PLAN_PER_OP, TRAIN_PLAN_TILES, TRAIN_DETERMINISTIC = 1, 2, 4, 8
 SAMPLER_IDS = {"ddim": 0, "euler": 1, "heun": 2}
 # beso_sample_solver (include/beso_hip.h BESO_SOLVER_*): the gc_sampling.py function names without "sample_"
 SOLVER_IDS = {"dpm_2": 0, "dpm_2_ancestral": 1, "dpmpp_2s": 2, "dpmpp_2s_ancestral": 3, "dpmpp_2m": 4, "lms": 5}

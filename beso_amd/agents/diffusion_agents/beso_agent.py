@@ -11,7 +11,10 @@ attributes (``model``, ``sigma_min/max``, ``use_kde`` ...).  What changes undern
     xGMI) before the optimizer step when a process group is initialised;
   * two optional constructor arguments the reference does not have, ``max_grad_norm`` and ``skip_nonfinite_steps``
     (after ``patience``, both off by default): global gradient-norm clipping and a guard that drops a step whose
-    gradient is not finite, both inside the fused optimizer launch (``FusedAdam.step``).
+    gradient is not finite, both inside the fused optimizer launch (``FusedAdam.step``);
+  * ``deterministic_training`` (off by default): every HIP training step runs with ``BESO_TRAIN_DETERMINISTIC`` -- the loss
+    and all gradients are summed in a fixed order, so a re-run gives the same bits -- and ``store_training_state`` /
+    ``load_training_state`` save and restore everything a step reads, so that a resumed run continues bit for bit.
 """
 import contextlib
 import logging
@@ -58,7 +61,8 @@ class BesoAgent(BaseAgent):
                  sigma_sample_density_type: str, sigma_sample_density_mean: float,
                  sigma_sample_density_std: float, decay: float, update_ema_every_n_steps: int,
                  window_size: int, goal_window_size: int, use_kde: bool = False, patience: int = 10,
-                 max_grad_norm: float | None = None, skip_nonfinite_steps: bool = False):
+                 max_grad_norm: float | None = None, skip_nonfinite_steps: bool = False,
+                 deterministic_training: bool = False):
         super().__init__(model, input_encoder, optimization, obs_modalities, goal_modalities, target_modality,
                          device, max_train_steps, eval_every_n_steps, max_epochs)
         self.ema_helper = ExponentialMovingAverage(self.model.get_params(), decay, self.device)
@@ -77,6 +81,9 @@ class BesoAgent(BaseAgent):
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite_steps = bool(skip_nonfinite_steps)
         self._eager_grad_norm = None
+        # fixed-order reductions in the HIP training step (BESO_TRAIN_DETERMINISTIC).  The flag lives on the denoiser, which
+        # hands it to every HipTrainStep it gives out: the eager step and the one behind `model.loss()` in the captured graph
+        self.deterministic_training = bool(deterministic_training)
         self.lr_scheduler = instantiate(lr_scheduler, optimizer=self.optimizer)
         self.gc = goal_conditioned
         self.train_method = train_method
@@ -111,6 +118,22 @@ class BesoAgent(BaseAgent):
         self._ema_partial = False        # sharded exchange: the EMA shadow is current for the owned range only
         self._train_graphs = {}          # batch shape -> captured forward+backward (train_step)
         self._train_graph_ok = True
+
+    # ------------------------------------------------------------------ reproducibility
+    @property
+    def deterministic_training(self) -> bool:
+        """Whether the HIP training step runs with BESO_TRAIN_DETERMINISTIC: the denoiser's flag (one place, read by every step)."""
+        den = self._hip_denoiser()
+        return bool(den is not None and getattr(den, "deterministic_training", False))
+
+    @deterministic_training.setter
+    def deterministic_training(self, on: bool):
+        den = self._hip_denoiser()
+        if den is None:
+            if on:
+                raise ValueError("deterministic_training needs the beso_amd GCDenoiser / DiffusionGPT (the HIP training step)")
+            return
+        den.deterministic_training = bool(on)
 
     # ------------------------------------------------------------------ scaler / bounds
     def get_scaler(self, scaler):
@@ -739,6 +762,90 @@ class BesoAgent(BaseAgent):
                 ema[n] = s.detach().clone()
         torch.save(ema, os.path.join(store_path, "model_state_dict.pth"))
         torch.save(raw, os.path.join(store_path, "non_ema_model_state_dict.pth"))
+
+    # ------------------------------------------------------------------ exact resume
+    def _training_state_guard(self):
+        if bdist.is_distributed() and bdist.world_size() > 1:
+            raise NotImplementedError("store_training_state / load_training_state: single process only (sharded EMA shadows and "
+                                      "per-rank generators are not saved)")
+
+    def _sync_device(self):
+        # (the asynchronous loss stream and the step's side streams are drained too: a device-wide synchronise)
+        if torch.device(self.device).type == "cuda":
+            torch.cuda.synchronize(self.device)
+
+    def store_training_state(self, store_path: str, feed=None) -> None:
+        """Everything the next ``train_step`` reads -> ``training_state.pth`` beside the files of ``store_model_weights``:
+        the raw parameters, the EMA shadow with its counters, the optimizer's moments and step counts
+        (``FusedAdam.export_state()``; ``state_dict()`` of an eager optimizer), the LR scheduler, ``steps``, torch's CPU
+        generator (the dropout seed is drawn there) and the device generator (noise, sigma), and the position of ``feed``
+        (a ``DeviceTrajectoryFeed``) when given.  With ``deterministic_training`` a run that loads this file continues with
+        the bits of the run that wrote it.  Synchronises.  Single process only."""
+        self._training_state_guard()
+        self._sync_device()
+        dev = torch.device(self.device)
+        ema = self.ema_helper
+        fused = isinstance(self.optimizer, FusedAdam)
+        state = dict(
+            version=1,
+            params=[p.detach().cpu().clone() for p in self.model.parameters()],
+            ema=dict(flat=ema._flat.detach().cpu().clone(), decay=ema.decay, num_updates=ema.num_updates, steps=ema.steps,
+                     version=ema.version),
+            optimizer_kind="fused" if fused else "eager",
+            optimizer=self.optimizer.export_state() if fused else self.optimizer.state_dict(),
+            lr_scheduler=self.lr_scheduler.state_dict() if self.lr_scheduler is not None else None,
+            steps=int(self.steps),
+            cpu_rng=torch.get_rng_state(),
+            device_rng=torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
+            feed=feed.state_dict() if feed is not None else None)
+        torch.save(state, os.path.join(store_path, "training_state.pth"))
+
+    def load_training_state(self, store_path: str, feed=None) -> None:
+        """Load ``training_state.pth`` written by ``store_training_state`` into an agent of the same construction (and into
+        ``feed``, when the file holds a feed's position).  The packed-weight caches are marked stale and the parameters'
+        version counters bumped, as after an optimizer step.  Synchronises.  Single process only."""
+        self._training_state_guard()
+        self._sync_device()
+        dev = torch.device(self.device)
+        state = torch.load(os.path.join(store_path, "training_state.pth"), map_location="cpu", weights_only=False)
+        params = list(self.model.parameters())
+        saved = state["params"]
+        if len(saved) != len(params) or any(tuple(s.shape) != tuple(p.shape) for s, p in zip(saved, params)):
+            raise ValueError("load_training_state: the saved parameters do not match this model")
+        ema, se = self.ema_helper, state["ema"]
+        if se["flat"].numel() != ema._flat.numel():
+            raise ValueError("load_training_state: the saved EMA shadow does not match this model")
+        fused = isinstance(self.optimizer, FusedAdam)
+        if (state["optimizer_kind"] == "fused") != fused:
+            raise ValueError("load_training_state: the file was written with another optimizer class")
+        if (feed is None) != (state["feed"] is None):
+            raise ValueError("load_training_state: the file %s a feed's position" % ("holds" if feed is None else "does not hold"))
+        with torch.no_grad():
+            for p, s in zip(params, saved):
+                p.data.copy_(s)
+            ema._flat.copy_(se["flat"])
+        ema.decay, ema.num_updates, ema.steps = se["decay"], se["num_updates"], se["steps"]
+        ema.version = max(int(se["version"]), ema.version) + 1        # (never a version this agent has packed an image of)
+        if fused:
+            self.optimizer.import_state(state["optimizer"])
+        else:
+            self.optimizer.load_state_dict(state["optimizer"])
+        if self.lr_scheduler is not None and state["lr_scheduler"] is not None:
+            self.lr_scheduler.load_state_dict(state["lr_scheduler"])
+        self.steps = int(state["steps"])
+        torch.set_rng_state(state["cpu_rng"])
+        if dev.type == "cuda" and state["device_rng"] is not None:
+            torch.cuda.set_rng_state(state["device_rng"], dev)
+        if feed is not None:
+            feed.load_state_dict(state["feed"])
+        # the parameters and the shadow changed under every cache keyed on them
+        torch.autograd.graph.increment_version(params)
+        den = self._hip_denoiser()
+        if den is not None:
+            den.inner_model.mark_weights_dirty()
+        self._ema_packed_key = None
+        self._ema_partial = False
+        self._sync_device()
 
     # ------------------------------------------------------------------ sigma density / schedules
     def make_sample_density(self):

@@ -22,6 +22,7 @@ class GCDenoiser(nn.Module):
         self.inner_model = inner_model if isinstance(inner_model, nn.Module) else instantiate(inner_model)
         self.sigma_data = sigma_data
         self._train_steps = {}
+        self.deterministic_training = False      # BESO_TRAIN_DETERMINISTIC on every HIP training step of this denoiser
 
     # -- reference surface ---------------------------------------------------------------------
     def get_scalings(self, sigma):
@@ -112,6 +113,9 @@ class GCDenoiser(nn.Module):
         step = self._train_steps.get(key)
         if step is None:
             step = self._train_steps[key] = HipTrainStep(inner, key)
+        # (BesoAgent(deterministic_training=True) sets the attribute on its denoiser: every step of it, the one behind
+        # ``loss()`` under autograd included, then runs with BESO_TRAIN_DETERMINISTIC)
+        step.deterministic = bool(self.deterministic_training)
         return step if step.eligible(state, action, goal, noise, sigma) else None
 
     # -- input vector-Jacobian product ---------------------------------------------------------

@@ -17,7 +17,9 @@
 //   LayerNorm backward also carries the residual gradient and emits its operand-typed copy (with the
 //   dropout mask of the consuming linear layer) and that layer's bias gradient; GELU' is the epilogue of the FC2
 //   dgrad GEMM.  Bias / LayerNorm-affine gradients are the only accumulations (block partials + one reduction,
-//   or a handful of atomics per block): the flat gradient buffer is zeroed first.
+//   or a handful of atomics per block): the flat gradient buffer is zeroed first.  BESO_TRAIN_DETERMINISTIC replaces
+//   the atomics (column-sum epilogues, colsum_kernel, loss_kernel) by partial sums in a workspace slab and a second
+//   launch that adds them in index order (kColPart epilogues, colsum_part_kernel, loss_part_kernel).
 // Dropout masks come from a counter-based hash of (seed, site, element index): the backward recomputes them.
 #include <string.h>
 #include <atomic>
@@ -255,6 +257,11 @@ __device__ __forceinline__ int xcd_tile(int b, int nb) {
     return x * per + (x < rem ? x : rem) + i;
 }
 
+// An epilogue with column sums (kColSum) that declares kColPart = true stores them per 64-row wave into a slab instead of
+// adding them with atomics (BESO_TRAIN_DETERMINISTIC: part_reduce_kernel sums the slab's rows in index order).
+template <typename Epi, typename = void> struct EpiColPart : std::false_type {};
+template <typename Epi> struct EpiColPart<Epi, std::enable_if_t<Epi::kColPart>> : std::true_type {};
+
 // One 128 x 128 output tile at (m0, n0), contraction over [k_begin, k_end): 8 waves as 2 (m) x 4 (n), 64 x 32 each.
 // Register-staged pipeline with two register sets (see the loop).  Loads and LDS stores are unconditional -- a
 // stage past k_end is read at a valid address and stored as zeros -- so that the compiler's vmcnt bookkeeping
@@ -370,8 +377,15 @@ __device__ __forceinline__ void tgemm_tile(TileLds& lds, const E* __restrict__ A
                 for (int r = 0; r < 4; ++r) cs[ni][r] += __shfl_xor(cs[ni][r], o, 64);
             const int n = n0 + wne * (16 * NI) + ni * 16 + (le >> 4) * 4;
             if ((le & 15) == 0 && n < N) {
+                if constexpr (EpiColPart<Epi>::value) {
+                    // BESO_TRAIN_DETERMINISTIC: epi.colsum is a slab [2 * row tiles][N]; this wave's 64 rows are its row
+                    // m0 / 64 + wave row, a plain store (every row of the slab is written: rows past M add zeros)
+                    static_assert(kTileMN == 128, "two 64-row waves per tile");
+                    *(f32x4*)(epi.colsum + (size_t)((m0 >> 6) + wme) * N + n) = cs[ni];
+                } else {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) unsafeAtomicAdd(epi.colsum + n + r, cs[ni][r]);
+                    for (int r = 0; r < 4; ++r) unsafeAtomicAdd(epi.colsum + n + r, cs[ni][r]);
+                }
             }
         }
     }
@@ -490,6 +504,9 @@ template <typename E> struct EpiSiluBwd {        // dz = da * SiLU'(z); column s
         return Vec4<E>::rounded(d);
     }
 };
+// ... and their deterministic forms: `colsum` is the slab [2 * ceil(M / 128)][N] (EpiColPart)
+template <typename E> struct EpiGeluBwdPart : EpiGeluBwd<E> { static constexpr bool kColPart = true; };
+template <typename E> struct EpiSiluBwdPart : EpiSiluBwd<E> { static constexpr bool kColPart = true; };
 #if BESO_DEV_API
 struct EpiAtomic {                               // split-K partial sums accumulated with atomics (debug entry point)
     static constexpr bool kColSum = false; static constexpr bool kBiasCol = false;
@@ -1207,6 +1224,71 @@ __global__ __launch_bounds__(256) void colsum_kernel(const E* __restrict__ a, in
         }
     }
 }
+// BESO_TRAIN_DETERMINISTIC: the same sums of the same row block in the same order (a kernel of its own, so that colsum_kernel's
+// instructions stay what they were), stored into row blockIdx.y of the slab part[gridDim.y][cols] instead of added to the output
+template <typename E>
+__global__ __launch_bounds__(256) void colsum_part_kernel(const E* __restrict__ a, int ld, int rows, int cols,
+                                                          float* __restrict__ part, int rows_per_block) {
+    constexpr int EPC = 16 / (int)sizeof(E);
+    __shared__ float red[4][64][EPC];
+    const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+    const int c = (blockIdx.x * 64 + cx) * EPC;
+    const int r0 = blockIdx.y * rows_per_block, r1 = min(rows, r0 + rows_per_block);
+    float acc[EPC];
+#pragma unroll
+    for (int j = 0; j < EPC; ++j) acc[j] = 0.f;
+    if (c < cols) {
+        for (int r = r0 + ry; r < r1; r += 4) {
+            const u32x4 u = *(const u32x4*)(a + (size_t)r * ld + c);
+            if (sizeof(E) == 2) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    acc[2 * j] += __uint_as_float(u[j] << 16);
+                    acc[2 * j + 1] += __uint_as_float(u[j] & 0xffff0000u);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] += __uint_as_float(u[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < EPC; ++j) red[ry][cx][j] = acc[j];
+    __syncthreads();
+    for (int i = threadIdx.x; i < 64 * EPC; i += 256) {
+        const int n = blockIdx.x * 64 * EPC + i;
+        if (n < cols) {
+            const int x = i / EPC, j = i % EPC;
+            part[(size_t)blockIdx.y * cols + n] = red[0][x][j] + red[1][x][j] + red[2][x][j] + red[3][x][j];
+        }
+    }
+}
+
+// out[c] = part[0][c] + part[1][c] + ... + part[nparts - 1][c] over a slab of `nparts` rows of `cols` floats: the second stage of
+// the deterministic column sums (colsum_part_kernel, the kColPart epilogues).  Thread (cx, ry): column cx of the block's 64, slab
+// rows ry, ry + 4, ... with eight loads in flight; then the four row groups in order.  The order of the additions depends on
+// (nparts, cols) only.  `out` is assigned, not accumulated.
+__global__ __launch_bounds__(256) void part_reduce_kernel(const float* __restrict__ part, int nparts, int cols, float* __restrict__ out) {
+    __shared__ float red[4][64];
+    const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6, c = blockIdx.x * 64 + cx;
+    float a[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a[u] = 0.f;
+    if (c < cols) {
+        int b = ry;
+        for (; b + 28 < nparts; b += 32) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(b + 4 * u) * cols + c];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) a[u] += v[u];
+        }
+        for (; b < nparts; b += 4) a[0] += part[(size_t)b * cols + c];
+    }
+    red[ry][cx] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    __syncthreads();
+    if (ry == 0 && c < cols) out[c] = ((red[0][cx] + red[1][cx]) + red[2][cx]) + red[3][cx];
+}
 
 // ---------------------------------------------------------------------------------------------
 // attention of one (sample, head) per wave, forward (training: dropout on the probabilities, score_gpts.py:69-76)
@@ -1766,6 +1848,43 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ pre
     __syncthreads();
     if (threadIdx.x == 0) unsafeAtomicAdd(loss, (part[0] + part[1] + part[2] + part[3]) * inv_count);
 }
+// BESO_TRAIN_DETERMINISTIC: loss_kernel (the same elements per block, the same dpred; a kernel of its own, so that loss_kernel's
+// instructions stay what they were) with the block's share of the loss stored into shares[blockIdx.x]; loss_reduce_kernel adds
+// the shares up in index order
+template <typename E>
+__global__ __launch_bounds__(256) void loss_part_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                        E* __restrict__ dpred, float* __restrict__ shares, int M, int act, int ap,
+                                                        float inv_count, float grad_scale, int t, int last_only) {
+    __shared__ float part[4];
+    float acc = 0.f;
+    const size_t n = (size_t)M * ap;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t m = i / ap;
+        const int a = (int)(i % ap);
+        float g = 0.f;
+        if (a < act && (!last_only || (int)(m % t) == t - 1)) {
+            const float diff = pred[i] - target[m * act + a];
+            acc = fmaf(diff, diff, acc);
+            g = 2.0f * diff * inv_count * grad_scale;
+        }
+        dpred[i] = Act<E>::from(g);
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) shares[blockIdx.x] = (part[0] + part[1] + part[2] + part[3]) * inv_count;
+}
+// loss = part[0] + ... + part[n - 1] in a fixed order: thread i adds part[i], part[i + 256], ..., then the lanes of a wave
+// (wave_sum's butterfly), then the four waves in order.  One block.
+__global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restrict__ part, int n, float* __restrict__ loss) {
+    __shared__ float red[4];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) acc += part[i];
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) *loss = ((red[0] + red[1]) + red[2]) + red[3];
+}
 
 // ---------------------------------------------------------------------------------------------
 // input VJP (beso_denoise_vjp): the seed in place of loss_kernel -- denoised = c_skip x + c_out F (compact action rows), and
@@ -1905,10 +2024,17 @@ struct TrainWs {
     size_t bimg;                                                    // ... of the transposed weights (data-gradient kernel)
     size_t b1slab;                                                  // [L][workgroups][4 D] fp32: FC1 bias sums per workgroup of that kernel
     size_t wslab; int w_splits, w_splits_panel; size_t wslab_floats;   // split weight-gradient launch: [splits][wslab_floats] partial outputs
+    size_t det_part, det_floats;                                    // BESO_TRAIN_DETERMINISTIC: the slab of partial sums (one use at a time)
     TrainLayerWs layer[kMaxLayers];
     size_t total;
 };
 
+// (hp: the padded hidden width of the MLP action head, 0 with the linear head -- wider than 4 D when embed_dim < 32)
+static size_t det_part_floats(size_t M, int D, int hp) {
+    const size_t cols = 4 * (size_t)D > (size_t)hp ? 4 * (size_t)D : (size_t)hp;
+    const size_t n = 2 * ((M + kTileMN - 1) / kTileMN) * cols;
+    return n < 1024 ? 1024 : n;
+}
 static bool make_train_ws(const beso_config* c, int batch, int t, int precision, TrainWs* w) {
     memset(w, 0, sizeof(*w));
     const size_t e = precision == BESO_PREC_FP32 ? 4 : 2, f = 4;
@@ -1937,6 +2063,12 @@ static bool make_train_ws(const beso_config* c, int batch, int t, int precision,
         w->dw_hid = carve_t(cur, f * (size_t)w->Hp * D); w->db_hid = carve_t(cur, f * (size_t)(w->Hp + 8));
         w->hz = carve_t(cur, e * Ma * w->Hp); w->ha = carve_t(cur, e * Ma * w->Hp); w->hdz = carve_t(cur, e * Ma * w->Hp);
     }
+    // The partial sums of the deterministic step: the largest user is the FC1 bias gradient, one row of 4 D sums per 64 token
+    // rows (two per 128-row tile) -- or the MLP head's hidden bias, Hp sums per row, where that is wider; the loss takes one
+    // float per block of loss_kernel's grid (at most 1024).  The uses follow each other on the compute stream, each with its
+    // second-stage launch behind it: one slab serves them all.
+    w->det_floats = det_part_floats(M, D, w->Hp);
+    w->det_part = carve_t(cur, f * w->det_floats);
     w->dx = carve_t(cur, f * M * D); w->dx0b = carve_t(cur, e * M * D); w->dxn = carve_t(cur, f * M * D);
     w->dy = carve_t(cur, e * M * D);
     {
@@ -2072,10 +2204,22 @@ static int capped_grid(size_t n, size_t cap) { const size_t g = (n + 255) / 256;
 template <int N> using Int = std::integral_constant<int, N>;
 template <typename F>
 static void with_ln_vec(int nv, F&& f) { if (nv == 1) f(Int<1>{}); else if (nv == 2) f(Int<2>{}); else f(Int<4>{}); }
+// the second stage of a deterministic sum: out[0 .. cols) = the rows of the slab `part` added in index order
+static hipError_t part_reduce(const float* part, int nparts, int cols, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(part_reduce_kernel, dim3((cols + 63) / 64), dim3(256), 0, s, part, nparts, cols, out);
+    return hipGetLastError();
+}
+// part != nullptr (BESO_TRAIN_DETERMINISTIC): a slab of part_floats floats for the row blocks' sums, added up by a second launch
 template <typename E>
-static hipError_t colsum(const E* a, int ld, int cols, int rows, float* out, hipStream_t s) {
+static hipError_t colsum(const E* a, int ld, int cols, int rows, float* out, hipStream_t s, float* part = nullptr, size_t part_floats = 0) {
     constexpr int EPC = 16 / (int)sizeof(E), rpb = 128;        // rpb: rows per block of the column sums
-    hipLaunchKernelGGL(colsum_kernel<E>, dim3((cols + 64 * EPC - 1) / (64 * EPC), (rows + rpb - 1) / rpb), dim3(256), 0, s, a, ld, rows, cols,
+    const dim3 grid((cols + 64 * EPC - 1) / (64 * EPC), (rows + rpb - 1) / rpb);
+    if (part) {
+        if ((size_t)grid.y * cols > part_floats) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(colsum_part_kernel<E>, grid, dim3(256), 0, s, a, ld, rows, cols, part, rpb);
+        return part_reduce(part, (int)grid.y, cols, out, s);
+    }
+    hipLaunchKernelGGL(colsum_kernel<E>, grid, dim3(256), 0, s, a, ld, rows, cols,
                        out, out, out, 1 << 30, rpb);
     return hipGetLastError();
 }
@@ -2202,6 +2346,7 @@ struct WgradGroup {
     int tiles = 0; uint32_t floats = 0;                   // floats: of the collected problems in a range's slab
     bool off;                                             // input VJP: no weight gradient
     int panel_w, per_op, M, splits, splits_panel; float* slab; size_t slab_floats; hipStream_t s;
+    float* det_part = nullptr; size_t det_floats = 0;     // BESO_TRAIN_DETERMINISTIC: the slab of colsum's partial sums
     int tiles_of(const GProb& q) const {
         if (panel_w) { int o; return wgrad_panel_tiles(q.Mo, q.No, panel_w, &o); }
         return q.nt_n * ((q.Mo + kTileMN - 1) / kTileMN);
@@ -2215,7 +2360,7 @@ struct WgradGroup {
         if (off) return hipSuccess;
         if (gt.n == kMaxGroup) { hipError_t e = flush(); if (e != hipSuccess) return e; }
         if (bias && No % kTileMN == 0) {
-            hipError_t e = colsum(A, lda, Mo, rows, bias, s);
+            hipError_t e = colsum(A, lda, Mo, rows, bias, s, det_part, det_floats);
             if (e != hipSuccess) return e;
             bias = nullptr;
         }
@@ -2312,6 +2457,9 @@ struct TrainStep : TrainCall {
     const TrainParams par = walk_params(c, p, gflat, !vjp);
     const TrainPlan plan = make_train_plan(c, flags, M, T, t, embed_p, resid_p, sizeof(E), fork);
     const LayerPG* const lp = par.lp;
+    // BESO_TRAIN_DETERMINISTIC: the three sums the step otherwise forms with atomics (column-sum epilogues, colsum_kernel, the loss)
+    // go through the slab w.det_part and a second launch each
+    const bool det = flags & BESO_TRAIN_DETERMINISTIC;
     hipEvent_t ev_join = nullptr, ev_copies = nullptr, ev_wcat = nullptr;      // recorded by copy_weights(), waited for by the forward
     static constexpr int kRpw = 4;                        // rows per wave of the LayerNorm backward
     LnPartials ln; WgradGroup<E> wg;
@@ -2322,6 +2470,7 @@ struct TrainStep : TrainCall {
         ln.base = F(w.ln_part); ln.grid = (M + 4 * kRpw - 1) / (4 * kRpw); ln.D = D;
         wg.gt.n = 0; wg.off = vjp != nullptr; wg.panel_w = plan.panel_w; wg.per_op = flags & BESO_TRAIN_PLAN_PER_OP; wg.M = M; wg.s = s;
         wg.splits = w.w_splits; wg.splits_panel = w.w_splits_panel; wg.slab = F(w.wslab); wg.slab_floats = w.wslab_floats;
+        if (det) { wg.det_part = F(w.det_part); wg.det_floats = w.det_floats; }
     }
     float* F(size_t off) const { return (float*)(ws + off); }
     E* P(size_t off) const { return (E*)(ws + off); }
@@ -2529,8 +2678,16 @@ struct TrainStep : TrainCall {
             return BESO_OK;
         }
         const int last_only = flags & BESO_TRAIN_LAST_ACTION_ONLY;
-        hipLaunchKernelGGL(loss_kernel<E>, dim3(grid), dim3(256), 0, s, (const float*)F(w.pred), (const float*)F(w.target), P(w.dpred),
-                           loss_out, Ma, act, ap, 1.0f / (float)((size_t)batch * (last_only ? 1 : t) * act), grad_scale, t, last_only);
+        const float inv_count = 1.0f / (float)((size_t)batch * (last_only ? 1 : t) * act);
+        if (det) {
+            // one share per block, added up in index order -- in FRONT of the event below: the loss is final where loss_stream is released
+            if ((size_t)grid > w.det_floats) { *err = hipErrorInvalidValue; *err_line = __LINE__; return BESO_ERR_HIP; }
+            hipLaunchKernelGGL(loss_part_kernel<E>, dim3(grid), dim3(256), 0, s, (const float*)F(w.pred), (const float*)F(w.target), P(w.dpred),
+                               F(w.det_part), Ma, act, ap, inv_count, grad_scale, t, last_only);
+            hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, s, (const float*)F(w.det_part), grid, loss_out);
+        } else
+            hipLaunchKernelGGL(loss_kernel<E>, dim3(grid), dim3(256), 0, s, (const float*)F(w.pred), (const float*)F(w.target), P(w.dpred),
+                               loss_out, Ma, act, ap, inv_count, grad_scale, t, last_only);
         TRY(hipGetLastError());
         if (loss_stream) {
             // the loss is final here, long before the step is: a stream of the caller's is ordered behind this point, so that
@@ -2542,6 +2699,9 @@ struct TrainStep : TrainCall {
         return BESO_OK;
     }
     // ---- backward
+    // rows of the slab a kColPart epilogue writes for a GEMM over `rows` token rows (one per 64-row wave of every 128-row tile)
+    static int det_rows(int rows) { return 2 * ((rows + kTileMN - 1) / kTileMN); }
+    hipError_t det_rows_fit(int rows, int cols) const { return (size_t)det_rows(rows) * cols <= w.det_floats ? hipSuccess : hipErrorInvalidValue; }
     // (every call launches ln.grid blocks so that the partial slabs have one shape; blocks past `rows` write zeros)
     hipError_t ln_bwd(const float* x, size_t st, const float* gamma, const float* dres_in, float* dres_out, E* dxb, int rows,
                       float* dgam, float* dbet, float* dbias, float p_site, uint32_t site, int skip_mod = 0) {
@@ -2563,11 +2723,16 @@ struct TrainStep : TrainCall {
     // db = its column sums, dxf = dpred W; then ln_f
     int backward_head() {
         if (mlp_head) {
-            if (!vjp) TRY(colsum(P(w.dpred), ap, act, Ma, par.hb.g, s));
+            if (!vjp) TRY(colsum(P(w.dpred), ap, act, Ma, par.hb.g, s, det ? F(w.det_part) : nullptr, w.det_floats));
             // second layer: dW1 = dpred^T a, da = dpred W1 -> dz = da * SiLU'(z) (+ its column sums = db0); first layer:
             // dW0 = dz^T xf, dxf = dz W0.  Padded rows / columns are zeros all the way.
             TRY(wg.add(P(w.dpred), ap, ap, P(w.ha), Hp, Hp, Ma, F(w.dw_head)));
-            TRY((tgemm<E, false, true>(P(w.dpred), ap, P(w.w_head), Hp, Ma, Hp, ap, 1, EpiSiluBwd<E>{P(w.hz), P(w.hdz), F(w.db_hid), Hp}, s)));
+            if (det) {
+                TRY(det_rows_fit(Ma, Hp));
+                TRY((tgemm<E, false, true>(P(w.dpred), ap, P(w.w_head), Hp, Ma, Hp, ap, 1, EpiSiluBwdPart<E>{{P(w.hz), P(w.hdz), F(w.det_part), Hp}}, s)));
+                TRY(part_reduce(F(w.det_part), det_rows(Ma), Hp, F(w.db_hid), s));
+            } else
+                TRY((tgemm<E, false, true>(P(w.dpred), ap, P(w.w_head), Hp, Ma, Hp, ap, 1, EpiSiluBwd<E>{P(w.hz), P(w.hdz), F(w.db_hid), Hp}, s)));
             TRY(wg.add(P(w.hdz), Hp, Hp, P(w.xf), D, D, Ma, F(w.dw_hid)));
             TRY((tgemm<E, false, true>(P(w.hdz), Hp, P(w.w_hid), D, Ma, D, Hp, 1, EpiStore<E>{F(w.dxn), nullptr, nullptr, D}, s)));
         } else {
@@ -2607,7 +2772,12 @@ struct TrainStep : TrainCall {
             }
         } else {
             // per-op: dh = (dyo W2) * GELU'(h) (+ db1), dxn2 = dh W1, LayerNorm-2 backward, dy = dym Wp
-            TRY((tgemm<E, false, true>(P(y.dyo), D, P(y.w_fc2), D4, rows, D4, D, 1, EpiGeluBwd<E>{P(y.h), P(y.dh), lp[l].f1b.g, D4}, s)));
+            if (det) {
+                TRY(det_rows_fit(rows, D4));
+                TRY((tgemm<E, false, true>(P(y.dyo), D, P(y.w_fc2), D4, rows, D4, D, 1, EpiGeluBwdPart<E>{{P(y.h), P(y.dh), F(w.det_part), D4}}, s)));
+                TRY(part_reduce(F(w.det_part), det_rows(rows), D4, lp[l].f1b.g, s));
+            } else
+                TRY((tgemm<E, false, true>(P(y.dyo), D, P(y.w_fc2), D4, rows, D4, D, 1, EpiGeluBwd<E>{P(y.h), P(y.dh), lp[l].f1b.g, D4}, s)));
             TRY((tgemm<E, false, true>(P(y.dh), D4, P(y.w_fc1), D, rows, D, D4, 1, EpiStore<E>{F(w.dxn), nullptr, nullptr, D}, s)));
             TRY(ln_bwd(F(y.x_mid), y.st2, lp[l].ln2w.p, dres, dres, P(y.dym), rows, lp[l].ln2w.g, lp[l].ln2b.g, lp[l].pb.g, resid_p, site2));
             TRY((tgemm<E, false, true>(P(y.dym), D, P(y.w_proj), D, rows, D, D, 1, EpiStore<E>{nullptr, dy_out, nullptr, D}, s)));
@@ -2706,7 +2876,8 @@ static int run_train_step(TrainCall a, int n_params, size_t workspace_bytes) {
     if (c->goal_seq_len > 0 && !a.goal) return BESO_ERR_BAD_ARG;
     if (n_params != 3 + 16 * c->n_layers + 6 + (c->linear_output ? 2 : 4)) return BESO_ERR_BAD_ARG;
     for (int i = 0; i < n_params; ++i) if (!a.p[i]) return BESO_ERR_BAD_ARG;
-    if (a.flags & ~((a.vjp ? 0 : BESO_TRAIN_LAST_ACTION_ONLY) | BESO_TRAIN_PLAN_PER_OP | BESO_TRAIN_PLAN_TILES)) return BESO_ERR_BAD_ARG;
+    // (the input VJP has neither a loss nor a bias gradient: BESO_TRAIN_DETERMINISTIC means nothing there and is refused)
+    if (a.flags & ~((a.vjp ? 0 : BESO_TRAIN_LAST_ACTION_ONLY | BESO_TRAIN_DETERMINISTIC) | BESO_TRAIN_PLAN_PER_OP | BESO_TRAIN_PLAN_TILES)) return BESO_ERR_BAD_ARG;
     if (!(a.attn_p >= 0.f && a.attn_p < 1.f && a.resid_p >= 0.f && a.resid_p < 1.f && a.embed_p >= 0.f && a.embed_p < 1.f &&
           a.goal_p >= 0.f && a.goal_p <= 1.f))
         return BESO_ERR_BAD_ARG;

@@ -88,6 +88,12 @@ class DeviceTrajectoryFeed:
         seed = int(seed)
         self._perm_gen.manual_seed(seed)
         self._draw_gen.manual_seed(seed * 1000003 + 17 + self.rank)
+        # where in an epoch the feed is (state_dict / load_state_dict): the permutation generator's state as the current
+        # epoch's draw found it, the batches of that epoch already handed out, and whether an epoch is under way
+        self._epoch_perm_state = self._perm_gen.get_state()
+        self._yielded = 0
+        self._in_epoch = False
+        self._resume_at = 0                       # batches the next iter() skips (set by load_state_dict)
 
     @classmethod
     def from_sliced(cls, sliced, batch_size: int, device, **kw) -> "DeviceTrajectoryFeed":
@@ -158,11 +164,48 @@ class DeviceTrajectoryFeed:
     # ------------------------------------------------------------------ one epoch
     def __iter__(self) -> Iterator[dict]:
         n = self.n_windows
+        first, self._resume_at = self._resume_at, 0
+        self._epoch_perm_state = self._perm_gen.get_state()
+        self._yielded, self._in_epoch = first, True
         order = (torch.randperm(n, device=self.device, generator=self._perm_gen) if self.shuffle
                  else torch.arange(n, device=self.device))
         pad = self._share() * self.world_size - n
         if pad:
             order = torch.cat([order, order[:pad]])
         mine = order[self.rank::self.world_size]
-        for k in range(len(self)):
-            yield self.gather(mine[k * self.batch_size:(k + 1) * self.batch_size])
+        for k in range(first, len(self)):
+            batch = self.gather(mine[k * self.batch_size:(k + 1) * self.batch_size])
+            self._yielded = k + 1                 # (counted before the consumer sees the batch: a checkpoint taken while it
+            yield batch                           #  holds batch k resumes at batch k + 1)
+        self._in_epoch = False
+
+    # ------------------------------------------------------------------ checkpoint
+    def state_dict(self) -> dict:
+        """Where the feed is, for an exact resume: the permutation generator's state at the start of the current epoch, the
+        goal-draw generator's current state, the number of batches of this epoch already yielded and whether an epoch is in
+        progress -- plus the sizes a matching feed must have.  CPU tensors and integers.  One iterator at a time: the
+        position is that of the most recent ``iter()``."""
+        # (a position that load_state_dict put in and no iter() has taken up yet -- a generator starts at its first next() -- is
+        #  still the feed's position: the permutation generator stands at that epoch's start)
+        pending = self._resume_at > 0 and not self._in_epoch
+        in_epoch = self._in_epoch or pending
+        return dict(version=1, n_windows=self.n_windows, batch_size=self.batch_size, world_size=self.world_size,
+                    perm_state=(self._epoch_perm_state if self._in_epoch else self._perm_gen.get_state()).clone(),
+                    draw_state=self._draw_gen.get_state().clone(),
+                    yielded=self._resume_at if pending else (self._yielded if self._in_epoch else 0), in_epoch=bool(in_epoch))
+
+    def load_state_dict(self, d: dict) -> None:
+        """Continue where ``state_dict()`` was taken: the next ``iter()`` draws the same permutation again and starts behind
+        the batches already yielded (an epoch that had yielded all its batches resumes as an empty remainder); later epochs
+        and all goal draws continue the generators' streams as if nothing had happened.  The feed must be built over the same
+        data with the same window, batch size and world size (ValueError otherwise); its own seed does not matter."""
+        for k in ("n_windows", "batch_size", "world_size"):
+            if int(d[k]) != int(getattr(self, k)):
+                raise ValueError(f"DeviceTrajectoryFeed.load_state_dict: {k} is {getattr(self, k)} here, {d[k]} in the saved state")
+        yielded = int(d["yielded"]) if d["in_epoch"] else 0
+        if not 0 <= yielded <= len(self):
+            raise ValueError(f"DeviceTrajectoryFeed.load_state_dict: {yielded} batches yielded of an epoch of {len(self)}")
+        self._perm_gen.set_state(d["perm_state"].cpu())
+        self._draw_gen.set_state(d["draw_state"].cpu())
+        self._epoch_perm_state = self._perm_gen.get_state()
+        self._resume_at, self._yielded, self._in_epoch = yielded, 0, False

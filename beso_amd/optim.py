@@ -6,8 +6,9 @@ configs/agents/beso_kitchen.yaml:9-12, beso_block_push.yaml:9-11), so LR schedul
 unchanged.  ``step()`` updates ALL parameters -- and, when an EMA helper is handed over, its shadow copy
 (ema.py:45-53) -- in one HIP launch (``beso_adam_step``) instead of several hundred eager launches.
 There is no CPU implementation: ``maybe_fuse`` leaves a CPU optimizer untouched.  The moments live in flat
-buffers owned by the optimizer object (not in ``Optimizer.state``): like the reference's training loop
-(``beso_agent.py:466-476`` stores model weights only) optimizer state is not checkpointed.
+buffers owned by the optimizer object (not in ``Optimizer.state``), so ``state_dict()`` does not carry them (the
+reference's training loop, ``beso_agent.py:466-476``, stores model weights only); ``export_state()`` /
+``import_state()`` save and restore them for an exact resume (``BesoAgent.store_training_state``).
 
 ``step(max_grad_norm=..., skip_nonfinite=...)`` adds global gradient-norm clipping and a guard that drops a step whose
 gradient is not finite.  Both consume the norm ON THE DEVICE (``beso_grad_sumsq`` -> ``beso_adam_step_clipped``): the
@@ -106,6 +107,78 @@ class FusedAdam(torch.optim.Optimizer):
     def skipped_steps(self, group: int = 0) -> torch.Tensor:
         """How many steps ``skip_nonfinite`` has dropped so far; a 0-d device view."""
         return self._stats(group)[3]
+
+    # ------------------------------------------------------------------ checkpoint
+    _HYPER = ("lr", "betas", "eps", "weight_decay", "decoupled_weight_decay")
+
+    def export_state(self) -> dict:
+        """Everything ``step()`` carries from one call to the next, as CPU tensors and scalars: per parameter group the
+        moments ``m`` / ``v`` (flat, parameter order; None before the group's first step), the step count, the four ``stats``
+        doubles of the clipped step when they exist (``skipped_steps()`` survives), the element count, and the group's
+        hyper-parameters (``lr`` as the scheduler left it, and ``initial_lr`` when a scheduler set one).  Synchronises."""
+        groups = []
+        for st, group in zip(self._groups, self.param_groups):
+            total = sum(p.numel() for p in group["params"])
+            g = dict(numel=total, step=0, m=None, v=None, stats=None, hyper={k: group[k] for k in self._HYPER})
+            if "initial_lr" in group:
+                g["hyper"]["initial_lr"] = group["initial_lr"]
+            if st is not None:
+                g.update(step=int(st["step"]), m=st["m"].detach().cpu().clone(), v=st["v"].detach().cpu().clone())
+                if "stats" in st:
+                    g["stats"] = st["stats"].detach().cpu().clone()
+            groups.append(g)
+        return dict(version=1, groups=groups)
+
+    def import_state(self, d: dict) -> None:
+        """Load what ``export_state()`` returned into this optimizer -- before or after its first ``step()``.  The number
+        of groups and every group's element count must match (ValueError otherwise; nothing is changed then).  The chunk
+        tables are rebuilt by the next step; tensors that accessors handed out (``skipped_steps()`` ...) stay valid."""
+        groups = d.get("groups") if isinstance(d, dict) else None
+        if groups is None or len(groups) != len(self.param_groups):
+            raise ValueError(f"FusedAdam.import_state: {0 if groups is None else len(groups)} parameter groups saved, "
+                             f"{len(self.param_groups)} here")
+        for gi, (g, group) in enumerate(zip(groups, self.param_groups)):
+            total = sum(p.numel() for p in group["params"])
+            if int(g["numel"]) != total:
+                raise ValueError(f"FusedAdam.import_state: group {gi} holds {total} elements, the saved state {g['numel']}")
+            for k in ("m", "v"):
+                if g[k] is not None and (g[k].numel() != total or g[k].dtype != torch.float32):
+                    raise ValueError(f"FusedAdam.import_state: group {gi}: '{k}' must be {total} fp32 values")
+            if (g["m"] is None) != (g["v"] is None):
+                raise ValueError(f"FusedAdam.import_state: group {gi}: one moment without the other")
+            if g["stats"] is not None and (g["stats"].numel() != 4 or g["stats"].dtype != torch.float64):
+                raise ValueError(f"FusedAdam.import_state: group {gi}: 'stats' must be four doubles")
+        for gi, (g, group) in enumerate(zip(groups, self.param_groups)):
+            for k, val in g["hyper"].items():
+                group[k] = tuple(val) if k == "betas" else val
+            st = self._groups[gi]
+            if g["m"] is None:                               # saved before the group's first step
+                if st is not None:
+                    st["m"].zero_()
+                    st["v"].zero_()
+                    st["step"] = 0
+                    if "stats" in st:
+                        st["stats"].zero_()
+                continue
+            params = list(group["params"])
+            dev = params[0].device
+            if st is None:
+                offs, total = {}, 0
+                for p in params:
+                    offs[id(p)] = total
+                    total += p.numel()
+                # (sig None: the next step's _prepare builds the chunk table and keeps these buffers)
+                st = self._groups[gi] = dict(m=torch.empty(total, device=dev), v=torch.empty(total, device=dev), step=0,
+                                             offs=offs, total=total, sig=None, table=None, n_chunks=0)
+            st["m"].copy_(g["m"])
+            st["v"].copy_(g["v"])
+            st["step"] = int(g["step"])
+            if g["stats"] is not None:
+                if "stats" not in st:
+                    st["stats"] = torch.zeros(4, dtype=torch.float64, device=dev)
+                st["stats"].copy_(g["stats"])
+            elif "stats" in st:
+                st["stats"].zero_()
 
     @torch.no_grad()
     def step(self, closure=None, ema=None, shard=None, max_grad_norm=None, skip_nonfinite=False, reduce_sumsq=None):

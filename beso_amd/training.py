@@ -43,6 +43,10 @@ class HipTrainStep:
         self.pad_to = 0
         self._views: Optional[List[torch.Tensor]] = None
         self._ws: Optional[torch.Tensor] = None
+        # every call of this step runs with BESO_TRAIN_DETERMINISTIC: GCDenoiser.hip_train_step copies its own
+        # `deterministic_training` here (BesoAgent(deterministic_training=True) sets that), which reaches loss_backward and
+        # GCDenoiser.loss under autograd; run()'s keyword is for a caller that drives the step itself
+        self.deterministic = False
 
     # ------------------------------------------------------------------ eligibility
     @staticmethod
@@ -120,12 +124,14 @@ class HipTrainStep:
 
     def run(self, state, action, goal, noise, sigma, grad_scale: float = 1.0, seed: Optional[int] = None,
             fresh_grads: bool = False, last_action_only: bool = False, early_stream=None, goal_drop: Optional[float] = None,
-            loss_stream=None):
+            loss_stream=None, deterministic: bool = False):
         """-> (loss 0-d tensor, flat gradient tensor, list of per-parameter views).  Inputs are NOT modified.
         ``early_stream`` (a torch.cuda.Stream): ordered behind the completion of ``early_range()`` by the call.
         ``loss_stream`` (a torch.cuda.Stream): ordered behind the point where the loss value is final (the end of the forward
         half) -- a host read of the loss on that stream does not wait for the backward pass.
-        ``goal_drop``: None = the module's ``cond_mask_prob`` (training mode); 0 = the goals are taken as they are."""
+        ``goal_drop``: None = the module's ``cond_mask_prob`` (training mode); 0 = the goals are taken as they are.
+        ``deterministic`` (or ``self.deterministic``): ``BESO_TRAIN_DETERMINISTIC`` -- the loss and every gradient are summed in
+        a fixed order, so the same inputs and ``seed`` give the same bits on every call (include/beso_hip.h)."""
         inner = self.inner
         dev = action.device
         f32 = lambda x: x.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -167,7 +173,8 @@ class HipTrainStep:
             loss.record_stream(loss_stream)          # (read there; the caching allocator must not hand it out before that)
         common = (C.byref(self.cfg), arr, len(params), flat.data_ptr(), precision,
                   state.data_ptr(), action.data_ptr(), gptr, noise.data_ptr(), sigma.data_ptr(),
-                  loss.data_ptr(), B, t, (_lib.TRAIN_LAST_ACTION_ONLY if last_action_only else 0) | train_hints(), float(embed_p), float(attn_p), float(resid_p),
+                  loss.data_ptr(), B, t, (_lib.TRAIN_LAST_ACTION_ONLY if last_action_only else 0) | train_hints()
+                  | (_lib.TRAIN_DETERMINISTIC if (deterministic or self.deterministic) else 0), float(embed_p), float(attn_p), float(resid_p),
                   float(goal_p), C.c_uint(seed & 0xFFFFFFFF), float(grad_scale), ws.data_ptr(), ws.numel(),
                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
                   C.c_void_p(early_stream.cuda_stream) if early_stream is not None else None)

@@ -114,7 +114,18 @@ enum {
      * layer as one launch), the attention backward on the matrix pipe, the weight gradients of >= 18 k token rows in row
      * windows. */
     BESO_TRAIN_PLAN_PER_OP = 2,      /* per-op kernels for every layer, forward and backward (the comparator of the above) */
-    BESO_TRAIN_PLAN_TILES = 4        /* the tile kernel (one launch per layer) wherever the shape has it */
+    BESO_TRAIN_PLAN_TILES = 4,       /* the tile kernel (one launch per layer) wherever the shape has it */
+    /* Bit-reproducible step: every sum the step otherwise accumulates with fp32 atomics -- the FC1 / MLP-head hidden bias
+     * gradients that ride on a data-gradient GEMM's epilogue, the bias gradients formed by a column-sum launch, and the loss
+     * value itself -- is written as per-workgroup (per-wave) partial sums into a slab of the workspace and added up by a
+     * second small launch in slab-index order.  The order of every addition then depends on the shapes of the call only: two
+     * calls with the same inputs, seed, flags, precision and library build give equal bits in the loss and in the whole
+     * gradient buffer, whatever the workspace and the gradient buffer held before.  Orthogonal to the plan hints (every plan
+     * honours it, in both precisions, for both action heads); the weight-matrix gradients are the same bits with and without
+     * it.  The loss is still final where beso_loss_grad_streams releases loss_stream.  Without the flag the step launches
+     * exactly the kernels it launched before the flag existed.  Not promised: equal bits across batch sizes, GPU counts,
+     * plans or library builds.  beso_denoise_vjp has no such sums and rejects the flag. */
+    BESO_TRAIN_DETERMINISTIC = 8
 };
 
 /* flags of the forward calls (beso_score_fwd, beso_denoise_fwd, beso_sample, beso_sample_ancestral) */
@@ -353,7 +364,8 @@ int beso_adam_step_clipped(const beso_optim_chunk* chunks, int n_chunks, float* 
  *               the same order, each tensor contiguous.  OVERWRITTEN: zeroed first, then the weight gradients are
  *               plain stores of one grouped launch (no split-K, no atomics), while the bias / LayerNorm-affine /
  *               embedding gradients are accumulated from block partial sums (a few fp32 atomics per block: two runs
- *               agree to rounding in those tensors, not bit for bit).
+ *               agree to rounding in those tensors and in the loss, not bit for bit, unless BESO_TRAIN_DETERMINISTIC is
+ *               set: then every such sum is formed in a fixed order and two runs give equal bits).
  *   state [batch,t,obs], action [batch,t,act] (clean), goal [batch,G,obs] (UNMASKED: see goal_drop),
  *   noise [batch,t,act], sigma [batch];  loss_out: one device float.
  *   goal_drop   DiffusionGPT's goal_drop (`cond_mask_prob`, configs: cond_mask_prob): training-mode mask_cond
@@ -366,6 +378,11 @@ int beso_adam_step_clipped(const beso_optim_chunk* chunks, int n_chunks, float* 
  *   grad_scale multiplies every gradient (1/world_size for data-parallel averaging); the loss is unscaled.
  *   precision   BESO_PREC_BF16: bf16 GEMM operands (weights, kept activations, gradient operands), fp32 accumulation,
  *               fp32 residual stream / LayerNorm / softmax / loss;  BESO_PREC_FP32: everything fp32 (parity mode).  */
+/* The workspace includes the slab of BESO_TRAIN_DETERMINISTIC's partial sums for every caller (the size does not depend on the
+ * flags): 4 * max(1024, 2 * ceil(batch*T / 128) * max(4 * embed_dim, H)) bytes, T = 1 + goal_seq_len + 2 t, H = 104 with the
+ * MLP action head (linear_output 0) and 0 with the linear one, rounded up to the
+ * workspace's alignment -- 1.0 MB of the 1024-sample kitchen step's workspace.  Like the rest of the workspace it may hold
+ * anything on entry: every slab element a call reads was written by that call. */
 size_t beso_train_workspace_bytes(const beso_config* cfg, int batch, int t, int precision);
 size_t beso_grad_floats(const beso_config* cfg);
 int beso_loss_grad(const beso_config* cfg, const float* const* params, int n_params, float* grads_flat, int precision,

@@ -2,8 +2,9 @@
 """BASELINE config 3 on one GPU's share: kitchen train_step (score-matching loss, backward, AdamW, EMA) at
 1024 samples per step, through BesoAgent.train_step: HIP forward + backward (beso_loss_grad) and the fused
 Adam(W) + EMA launch; `--autograd` times the tests' torch-autograd comparator of the same step beside it;
-`--max-grad-norm X` / `--skip-nonfinite` turn on gradient clipping / the non-finite guard of the fused step.
-    python tools/bench_train.py [batch] [kitchen|block_push] [--autograd] [--max-grad-norm X] [--skip-nonfinite]"""
+`--max-grad-norm X` / `--skip-nonfinite` turn on gradient clipping / the non-finite guard of the fused step;
+`--deterministic` times the step with BESO_TRAIN_DETERMINISTIC (BesoAgent(deterministic_training=True)).
+    python tools/bench_train.py [batch] [kitchen|block_push] [--autograd] [--max-grad-norm X] [--skip-nonfinite] [--deterministic]"""
 import json
 import os
 import sys
@@ -41,6 +42,9 @@ def main():
     if "--skip-nonfinite" in sys.argv:
         sys.argv.remove("--skip-nonfinite")
         clip["skip_nonfinite_steps"] = True
+    det = "--deterministic" in sys.argv       # fixed-order reductions in the step (a second small launch per partial-sum slab)
+    if det:
+        sys.argv.remove("--deterministic")
     if "--autograd" in sys.argv:
         sys.argv.remove("--autograd")
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -75,7 +79,7 @@ def main():
                     mod.p = resid_p
         return m
 
-    agent = build_agent(cfg, model, device=dev, **clip)
+    agent = build_agent(cfg, model, device=dev, deterministic_training=det, **clip)
     rng = np.random.default_rng(0)
     agent.get_scaler(Scaler(rng.standard_normal((256, cfg.obs_dim)).astype(np.float32),
                             rng.standard_normal((256, cfg.act_dim)).astype(np.float32), True, dev))
@@ -111,7 +115,7 @@ def main():
     if clip:                                    # (read after the timed window: the read synchronises)
         clip = dict(clip, grad_norm=float(agent.last_grad_norm()), clip_coef=float(agent.optimizer.last_clip_coef()),
                     skipped_steps=float(agent.skipped_steps()))
-    print(json.dumps({**clip, "config": ("3: kitchen train_step" if name == "kitchen" else name + " train_step"), "n_gpus": world, "batch": B, "attn_pdrop": attn_p, "resid_pdrop": resid_p, "seconds_per_step": dt,
+    print(json.dumps({**clip, "deterministic": det, "config": ("3: kitchen train_step" if name == "kitchen" else name + " train_step"), "n_gpus": world, "batch": B, "attn_pdrop": attn_p, "resid_pdrop": resid_p, "seconds_per_step": dt,
                       "samples_per_s": B / dt, "tflops_fwd_bwd": flops / dt / 1e12, "loss": loss,
                       "path": ("HIP forward/backward (bf16 operands)" if getattr(agent, "_hip_step", None) is not None
                                else "torch autograd fp32 forward/backward") + " + " + type(agent.optimizer).__name__ + " (+EMA)"}))
