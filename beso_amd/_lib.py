@@ -45,7 +45,8 @@ EXPORTS = ["beso_version", "beso_status_string", "beso_last_error", "beso_num_pa
            "beso_loss_grad_overlap", "beso_grad_early_range", "beso_sample_ancestral", "beso_goal_mask",
            "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp", "beso_sample_solver",
            "beso_dropout_mask", "beso_sample_traced", "beso_rollout_begin", "beso_rollout_end",
-           "beso_loss_fwd_workspace_bytes", "beso_loss_fwd", "beso_grad_sumsq", "beso_adam_step_clipped"]
+           "beso_loss_fwd_workspace_bytes", "beso_loss_fwd", "beso_grad_sumsq", "beso_adam_step_clipped",
+           "beso_loss_grad_inputs", "beso_denoise_vjp_inputs"]
 # include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
 DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm", "beso_debug_sigma_cache_entries"]
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
@@ -150,11 +151,17 @@ def load() -> C.CDLL:
                 if hasattr(lib, "beso_loss_grad_streams") or not os.environ.get("BESO_HIP_LIB"):     # (HipTrainStep.run probes it too)
                     lib.beso_loss_grad_streams.restype = i32
                     lib.beso_loss_grad_streams.argtypes = lib.beso_loss_grad.argtypes + [vp, vp]
+                if hasattr(lib, "beso_loss_grad_inputs") or not os.environ.get("BESO_HIP_LIB"):
+                    lib.beso_loss_grad_inputs.restype = i32
+                    lib.beso_loss_grad_inputs.argtypes = lib.beso_loss_grad.argtypes + [vp, vp, vp, vp]
                 lib.beso_grad_early_range.restype = i32
                 lib.beso_grad_early_range.argtypes = [cfgp, C.POINTER(sz), C.POINTER(sz)]
         if hasattr(lib, "beso_denoise_vjp") or not os.environ.get("BESO_HIP_LIB"):
             lib.beso_denoise_vjp.restype = i32
             lib.beso_denoise_vjp.argtypes = [cfgp, C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
+            if hasattr(lib, "beso_denoise_vjp_inputs") or not os.environ.get("BESO_HIP_LIB"):
+                lib.beso_denoise_vjp_inputs.restype = i32
+                lib.beso_denoise_vjp_inputs.argtypes = lib.beso_denoise_vjp.argtypes + [vp, vp]
         if hasattr(lib, "beso_loss_fwd") or not os.environ.get("BESO_HIP_LIB"):
             lib.beso_loss_fwd_workspace_bytes.restype = sz
             lib.beso_loss_fwd_workspace_bytes.argtypes = [cfgp, i32, i32, i32]

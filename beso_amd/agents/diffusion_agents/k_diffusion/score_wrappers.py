@@ -46,7 +46,9 @@ class GCDenoiser(nn.Module):
 
     def loss(self, state, action, goal, noise, sigma, **kwargs):
         """Score-matching objective (score_wrappers.py:45-79).  Mutates ``noise`` in place when
-        ``pred_last_action_only`` is set, like the reference (:63).  Under autograd: the HIP training step.  With autograd
+        ``pred_last_action_only`` is set, like the reference (:63).  Under autograd: the HIP training step -- ``backward()``
+        delivers the parameter gradients and, where ``state`` / ``goal`` require grad (the outputs of a trainable observation or
+        goal encoder), the gradients with respect to those; ``action``, ``noise`` and ``sigma`` must not require grad.  With autograd
         disabled and the module in eval mode: the held-out objective on the inference path (``beso_loss_fwd``), a plain
         tensor without ``grad_fn``, in the module's precision and on the weights ``packed_weights()`` returns (the EMA image
         inside ``use_weights``); in training mode that call raises -- the masked, dropped-out loss is a training-step quantity."""
@@ -119,10 +121,12 @@ class GCDenoiser(nn.Module):
         return step if step.eligible(state, action, goal, noise, sigma) else None
 
     # -- input vector-Jacobian product ---------------------------------------------------------
-    def denoise_vjp(self, state, action, goal, sigma, cot, uncond: bool = False):
+    def denoise_vjp(self, state, action, goal, sigma, cot, uncond: bool = False, input_grads: bool = False):
         """-> (denoised, x_grad, dot): ``forward`` at ``action`` (eval mode), ``(d denoised / d action)^T cot`` and
         ``(cot * x_grad).flatten(1).sum(1)`` -- what the reference's log_likelihood gets from torch.autograd.grad
-        (gc_sampling.py:480-485), as one HIP call (``beso_denoise_vjp``).  No parameter gradient is touched."""
+        (gc_sampling.py:480-485), as one HIP call (``beso_denoise_vjp``).  No parameter gradient is touched.
+        ``input_grads``: -> (denoised, x_grad, dot, state_grad, goal_grad), the same product with respect to ``state`` and
+        ``goal`` as well (``HipTrainStep.denoise_vjp``)."""
         inner = self.inner_model
         if not isinstance(inner, DiffusionGPT):
             raise NotImplementedError("GCDenoiser.denoise_vjp needs a beso_amd DiffusionGPT inside (the HIP kernels)")
@@ -130,7 +134,7 @@ class GCDenoiser(nn.Module):
         step = self._train_steps.get(key)
         if step is None:
             step = self._train_steps[key] = HipTrainStep(inner, key)
-        return step.denoise_vjp(state, action, goal, sigma, cot, uncond=uncond)
+        return step.denoise_vjp(state, action, goal, sigma, cot, uncond=uncond, input_grads=input_grads)
 
     def _why_no_hip_step(self, state, action, goal, noise, sigma) -> str:
         inner = self.inner_model
@@ -138,8 +142,12 @@ class GCDenoiser(nn.Module):
             return f"embed_dim={inner.embed_dim} is not a multiple of 8 (the HIP training kernels need that)"
         if not (torch.is_tensor(action) and action.is_cuda):
             return "the inputs are not on the GPU (beso_amd has no CPU path)"
+        if any(torch.is_tensor(x) and x.requires_grad for x in (action, noise, sigma)):
+            return ("gradients with respect to action, noise and sigma are not computed (state and goal may require grad; "
+                    "action / noise / sigma must not)")
         return ("parameters must be contiguous fp32 HIP tensors that require grad, and state / action / goal / noise / "
-                "sigma HIP tensors that do not")
+                "sigma HIP tensors (state and goal may require grad; gradients with respect to action, noise and sigma are "
+                "not computed)")
 
     # -- fused path ----------------------------------------------------------------------------
     @staticmethod

@@ -1940,6 +1940,110 @@ __global__ __launch_bounds__(256) void vjp_input_kernel(const float* __restrict_
     if (threadIdx.x == 0 && dot) dot[b] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
+// ... and onto the state and goal inputs (beso_loss_grad_inputs, beso_denoise_vjp_inputs): the rows of dx0 that belong to state
+// and goal tokens (train_embed_kernel's layout: goal j at row 1 + j, state i at row G + 1 + 2 i) times W_tok = tok_emb.weight
+// [D][obs], in fp32:
+//   state_grad[b][i][c] = sum_d m(row, d) dx0[row][d] W_tok[d][c]
+//   goal_grad[b][j][c]  = keep(b, j, c) sum_d m(row, d) dx0[row][d] W_tok[d][c]
+// dx0 is the fp32 residual gradient layer 0's LayerNorm-1 backward leaves, i.e. the gradient of the embedding BEHIND its
+// dropout: m is that dropout's keep-scale (embed_p = 0: 1), recomputed here as train_embed_kernel drew it; keep is mask_cond's
+// keep-mask of the goal element (goal_p = 0: 1), so an element the mask zeroed on the way in gets exactly 0.
+// A small GEMM ([rows][D] x [D][obs], obs <= 30 at the shipped shapes) on the VALU.  A workgroup stages a tile of kIgRows rows
+// row-major in LDS (wave w its rows 8 w .. 8 w + 7: a lane loads 16 bytes of each, eight independent loads in flight, and
+// stores them to consecutive banks) beside the columns [c0, c0 + kIgCols) of W_tok; thread (g, c) owns the four outputs of rows
+// 4 g .. 4 g + 3 at column c and sums over d in index order, four features per step: one 16-byte read per row (the 32 lanes of
+// a row group read one address) and four reads of the weight per sixteen multiply-adds.  No atomics, the same bits on every
+// call.  D is walked in chunks of dc_max features (the LDS budget; D % 8 == 0 keeps every chunk a multiple of four); where one
+// chunk covers D the weights are staged once per workgroup.  Either output may be nullptr (its rows are then left out of the
+// tiles).
+constexpr int kIgRows = 32, kIgCols = 32, kIgPad = 4, kIgChunk = 240;    // (32 (240 + 4) + 240 32) floats = 61,952 bytes of LDS
+__global__ __launch_bounds__(256) void input_grad_kernel(const float* __restrict__ dx0, const float* __restrict__ tok_w,
+                                                         float* __restrict__ state_grad, float* __restrict__ goal_grad,
+                                                         int batch, int t, int T, int G, int D, int obs, int dc_max,
+                                                         float embed_p, float goal_p, uint32_t seed) {
+    extern __shared__ __attribute__((aligned(16))) float ig_lds[];
+    const int ldx = dc_max + kIgPad;                      // row stride of the tile, a multiple of four floats
+    float* xl = ig_lds;                                   // [kIgRows][ldx]
+    float* wl = ig_lds + (size_t)kIgRows * ldx;           // [dc][kIgCols]
+    const int n_g = goal_grad ? G : 0, n_s = state_grad ? t : 0, per = n_g + n_s;
+    const int rows = batch * per;
+    const int c0 = blockIdx.y * kIgCols, cw = min(kIgCols, obs - c0);
+    const int g = threadIdx.x >> 5, cl = threadIdx.x & 31;
+    const float inv_keep = embed_p > 0.f ? 1.0f / (1.0f - embed_p) : 1.f;
+    // token row of tile row vr (sample b, k-th differentiated token of it: the goals first)
+    auto token_row = [&](int b, int k) { return (size_t)b * T + (k < n_g ? 1 + k : G + 1 + 2 * (k - n_g)); };
+    bool w_staged = false;
+    for (int r0 = blockIdx.x * kIgRows; r0 < rows; r0 += gridDim.x * kIgRows) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int d0 = 0; d0 < D; d0 += dc_max) {
+            const int dc = min(dc_max, D - d0);
+            __syncthreads();                              // (the previous chunk has been read)
+            if (!w_staged) {
+                for (int i = threadIdx.x; i < dc * kIgCols; i += 256) {
+                    const int dd = i >> 5, c = i & 31;
+                    wl[i] = c < cw ? tok_w[(size_t)(d0 + dd) * obs + c0 + c] : 0.f;
+                }
+                w_staged = dc_max >= D;
+            }
+            {
+                constexpr int kRw = kIgRows / 4;          // rows per wave
+                const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+                size_t trow[kRw];
+#pragma unroll
+                for (int j = 0; j < kRw; ++j) {
+                    const int vr = min(r0 + kRw * w + j, rows - 1);       // (a row past the end re-reads the last one; stored as zeros)
+                    const int b = vr / per;
+                    trow[j] = token_row(b, vr - b * per);
+                }
+                for (int dd = 4 * lane; dd < dc; dd += 256) {
+                    f32x4 v[kRw];
+#pragma unroll
+                    for (int j = 0; j < kRw; ++j) v[j] = *(const f32x4*)(dx0 + trow[j] * D + d0 + dd);
+#pragma unroll
+                    for (int j = 0; j < kRw; ++j) {
+                        if (embed_p > 0.f) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                v[j][e] *= drop_scale(seed, kEmbedSite, drop_idx_row(trow[j], D, d0 + dd + e), embed_p, inv_keep);
+                        }
+                        if (r0 + kRw * w + j >= rows) v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        *(f32x4*)(xl + (size_t)(kRw * w + j) * ldx + dd) = v[j];
+                    }
+                }
+            }
+            __syncthreads();
+            if (cl < cw) {
+                const float* xr = xl + (size_t)(4 * g) * ldx;
+                for (int dd = 0; dd < dc; dd += 4) {
+                    f32x4 xv[4];
+                    float wv[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) xv[j] = *(const f32x4*)(xr + (size_t)j * ldx + dd);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) wv[e] = wl[(dd + e) * kIgCols + cl];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[j] = fmaf(xv[j][e], wv[e], acc[j]);
+                }
+            }
+        }
+        if (cl < cw) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int vr = r0 + 4 * g + j;
+                if (vr >= rows) break;
+                const int b = vr / per, k = vr - b * per, c = c0 + cl;
+                if (k < n_g) {
+                    const size_t idx = ((size_t)b * G + k) * obs + c;
+                    const bool kept = !(goal_p > 0.f) || goal_keep(seed, idx, goal_p) != 0.f;
+                    goal_grad[idx] = kept ? acc[j] : 0.f;
+                } else state_grad[((size_t)b * t + (k - n_g)) * obs + c] = acc[j];
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -2240,6 +2344,7 @@ struct TrainCall {
     const float *state, *action, *goal, *noise, *sigma; float* loss_out;
     int batch, t, flags; float embed_p, attn_p, resid_p, goal_p; uint32_t seed; float grad_scale;
     char* ws; hipStream_t s, early_stream, loss_stream; hipError_t* err; int* err_line; const VjpIo* vjp;
+    float *state_grad, *goal_grad;                        // the gradients with respect to the state / goal inputs (nullptr: not asked for)
 };
 
 // ---- parameters: the parameter / gradient pointers, order of beso_pack_weights
@@ -2829,6 +2934,7 @@ struct TrainStep : TrainCall {
             hipLaunchKernelGGL(vjp_input_kernel, dim3(batch), dim3(256), 0, s, (const float*)F(w.dx), par.actw.p, sigma, vjp->cot,
                                vjp->x_grad, vjp->dot, t, T, G, D, act, c->sigma_data);
             TRY(hipGetLastError());
+            if (state_grad || goal_grad) TRY(input_grads());
             return BESO_OK;
         }
         // embeddings: dWcat[Ke][D] = Xemb^T dx0, routed to pos_emb / tok_emb / action_emb / sigma_emb after the launch
@@ -2861,7 +2967,20 @@ struct TrainStep : TrainCall {
         hipLaunchKernelGGL(scatter_emb_kernel, dim3(64), dim3(256), 0, s, (const float*)F(w.dw_cat), par.pos.g, par.tokw.g, par.tokb.g,
                            par.sigw.g, par.sigb.g, par.actw.g, par.actb.g, D, obs, act, seq);
         TRY(hipGetLastError());
+        if (state_grad || goal_grad) TRY(input_grads());
         return BESO_OK;
+    }
+    // F(w.dx), the fp32 gradient of x0 BEHIND the embedding dropout (the LayerNorm-1 backward of layer 0 stores it before it
+    // applies that mask to the typed copy dx0b), onto the state / goal inputs through tok_emb.weight; the kernel applies the
+    // embedding dropout and mask_cond's goal mask of this call (both off in the input-VJP mode)
+    hipError_t input_grads() {
+        const int rows = batch * ((state_grad ? t : 0) + (goal_grad ? G : 0));
+        const int dc = D < kIgChunk ? D : kIgChunk;
+        const int tiles = (rows + kIgRows - 1) / kIgRows;
+        hipLaunchKernelGGL(input_grad_kernel, dim3(tiles < 1024 ? tiles : 1024, (obs + kIgCols - 1) / kIgCols), dim3(256),
+                           sizeof(float) * ((size_t)kIgRows * (dc + kIgPad) + (size_t)dc * kIgCols), s, (const float*)F(w.dx), par.tokw.p, state_grad, goal_grad,
+                           batch, t, T, G, D, obs, dc, embed_p, goal_p, seed);
+        return hipGetLastError();
     }
 };
 
@@ -2874,6 +2993,7 @@ static int run_train_step(TrainCall a, int n_params, size_t workspace_bytes) {
     if (!a.p || !a.state || !a.action || !a.sigma || !a.ws) return BESO_ERR_BAD_ARG;
     if (a.vjp ? (!a.vjp->cot || !a.vjp->denoised || !a.vjp->x_grad) : (!a.gflat || !a.noise || !a.loss_out)) return BESO_ERR_BAD_ARG;
     if (c->goal_seq_len > 0 && !a.goal) return BESO_ERR_BAD_ARG;
+    if ((a.goal_grad && c->goal_seq_len == 0) || (((uintptr_t)a.state_grad | (uintptr_t)a.goal_grad) & 3)) return BESO_ERR_BAD_ARG;
     if (n_params != 3 + 16 * c->n_layers + 6 + (c->linear_output ? 2 : 4)) return BESO_ERR_BAD_ARG;
     for (int i = 0; i < n_params; ++i) if (!a.p[i]) return BESO_ERR_BAD_ARG;
     // (the input VJP has neither a loss nor a bias gradient: BESO_TRAIN_DETERMINISTIC means nothing there and is refused)
@@ -2899,19 +3019,20 @@ int train_loss_grad(const beso_config* c, const float* const* params, int n_para
                     float* loss_out, int batch, int t, int flags, float embed_pdrop, float attn_pdrop, float resid_pdrop,
                     float goal_drop, uint32_t seed, float grad_scale,
                     void* workspace, size_t workspace_bytes, hipStream_t s, hipStream_t early_stream, hipStream_t loss_stream,
-                    hipError_t* err, int* err_line) {
+                    float* state_grad, float* goal_grad, hipError_t* err, int* err_line) {
     return run_train_step(TrainCall{c, params, grads_flat, precision, state, action, goal, noise, sigma, loss_out, batch, t, flags,
                                     embed_pdrop, attn_pdrop, resid_pdrop, goal_drop, seed, grad_scale, (char*)workspace, s, early_stream,
-                                    loss_stream, err, err_line, nullptr}, n_params, workspace_bytes);
+                                    loss_stream, err, err_line, nullptr, state_grad, goal_grad}, n_params, workspace_bytes);
 }
 
 int train_denoise_vjp(const beso_config* c, const float* const* params, int n_params, int precision, const float* state,
                       const float* x, const float* goal, const float* sigma, const float* cot, float* denoised, float* x_grad,
                       float* dot, int batch, int t, int flags, void* workspace, size_t workspace_bytes, hipStream_t s,
-                      hipError_t* err, int* err_line) {
+                      float* state_grad, float* goal_grad, hipError_t* err, int* err_line) {
     const VjpIo io{cot, denoised, x_grad, dot};
     return run_train_step(TrainCall{c, params, nullptr, precision, state, x, goal, nullptr, sigma, nullptr, batch, t, flags, 0.f, 0.f,
-                                    0.f, 0.f, 0u, 1.f, (char*)workspace, s, nullptr, nullptr, err, err_line, &io}, n_params, workspace_bytes);
+                                    0.f, 0.f, 0u, 1.f, (char*)workspace, s, nullptr, nullptr, err, err_line, &io, state_grad, goal_grad},
+                          n_params, workspace_bytes);
 }
 
 int train_goal_mask(float* mask, size_t n, float goal_drop, uint32_t seed, hipStream_t s, hipError_t* err, int* err_line) {

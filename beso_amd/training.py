@@ -75,8 +75,11 @@ class HipTrainStep:
         elif not all(p.requires_grad for p in params):
             return False
         for x in (state, action, noise, sigma) + ((goal,) if goal is not None else ()):
-            if not torch.is_tensor(x) or not x.is_cuda or x.requires_grad:
+            if not torch.is_tensor(x) or not x.is_cuda:
                 return False
+        # (state / goal may require grad: run(input_grads=True).  Gradients with respect to action, noise and sigma are not computed)
+        if action.requires_grad or noise.requires_grad or sigma.requires_grad:
+            return False
         if self.inner.goal_seq_len > 0 and goal is None:
             return False
         return self.supported(self.inner)
@@ -124,8 +127,12 @@ class HipTrainStep:
 
     def run(self, state, action, goal, noise, sigma, grad_scale: float = 1.0, seed: Optional[int] = None,
             fresh_grads: bool = False, last_action_only: bool = False, early_stream=None, goal_drop: Optional[float] = None,
-            loss_stream=None, deterministic: bool = False):
+            loss_stream=None, deterministic: bool = False, input_grads: bool = False):
         """-> (loss 0-d tensor, flat gradient tensor, list of per-parameter views).  Inputs are NOT modified.
+        ``input_grads``: the result gains ``(state_grad, goal_grad)`` -- the gradient of the loss (times ``grad_scale``) with
+        respect to ``state`` [B,t,obs] and to the goals as the kernel saw them [B,G,obs] (a goal given without batch dimension
+        was expanded over the batch: sum over dim 0 for its own gradient), fp32, with this call's embedding dropout and goal
+        mask; ``goal_grad`` is None when G = 0 (``beso_loss_grad_inputs``).
         ``early_stream`` (a torch.cuda.Stream): ordered behind the completion of ``early_range()`` by the call.
         ``loss_stream`` (a torch.cuda.Stream): ordered behind the point where the loss value is final (the end of the forward
         half) -- a host read of the loss on that stream does not wait for the backward pass.
@@ -178,8 +185,15 @@ class HipTrainStep:
                   float(goal_p), C.c_uint(seed & 0xFFFFFFFF), float(grad_scale), ws.data_ptr(), ws.numel(),
                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
                   C.c_void_p(early_stream.cuda_stream) if early_stream is not None else None)
+        state_grad = goal_grad = None
+        if input_grads:
+            state_grad = torch.empty_like(state)
+            goal_grad = torch.empty_like(goal) if G > 0 else None
         with torch.cuda.device(dev):
-            if hasattr(self.lib, "beso_loss_grad_streams"):
+            if input_grads:
+                st = self.lib.beso_loss_grad_inputs(*common, C.c_void_p(loss_stream.cuda_stream) if loss_stream is not None else None,
+                                                    state_grad.data_ptr(), goal_grad.data_ptr() if goal_grad is not None else None)
+            elif hasattr(self.lib, "beso_loss_grad_streams"):
                 st = self.lib.beso_loss_grad_streams(*common, C.c_void_p(loss_stream.cuda_stream) if loss_stream is not None else None)
             else:
                 # (a library loaded through BESO_HIP_LIB that predates the loss stream -- tools/variants.py's '@<revision>' A/B
@@ -189,13 +203,18 @@ class HipTrainStep:
                 if loss_stream is not None:
                     loss_stream.wait_stream(torch.cuda.current_stream(dev))
         _lib.check(st, "loss_grad")
+        if input_grads:
+            return loss, flat, views, state_grad, goal_grad
         return loss, flat, views
 
-    def denoise_vjp(self, state, x, goal, sigma, cot, uncond: bool = False):
+    def denoise_vjp(self, state, x, goal, sigma, cot, uncond: bool = False, input_grads: bool = False):
         """-> (denoised, x_grad, dot): ``GCDenoiser.forward`` in eval mode at x, the vector-Jacobian product
         (d denoised / d x)^T cot and its per-sample dot product with cot, as ONE enqueue of ``beso_denoise_vjp``
         (the training step's forward and data-gradient chain, no weight gradient).  The parameters need not require
-        grad and the call works under ``torch.no_grad()``; no ``.grad`` is created or changed."""
+        grad and the call works under ``torch.no_grad()``; no ``.grad`` is created or changed.
+        ``input_grads``: -> (denoised, x_grad, dot, state_grad, goal_grad) with (d denoised / d state)^T cot [B,t,obs] and
+        (d denoised / d goal)^T cot [B,G,obs] (``beso_denoise_vjp_inputs``); ``goal_grad`` is None when G = 0 and exactly zero
+        with ``uncond`` (the goals are replaced by zeros there)."""
         inner = self.inner
         if inner.training and any(p > 0 for p in inner._pdrops):
             raise RuntimeError("beso_amd: denoise_vjp evaluates the eval-mode function; call eval() on a model with dropout")
@@ -224,7 +243,7 @@ class HipTrainStep:
         if sigma.numel() != B:
             raise ValueError("sigma must be a scalar or [B]")
         G = inner.goal_seq_len
-        gptr = None
+        gptr, goal_given = None, goal
         if G > 0:
             if uncond or goal is None:
                 goal = torch.zeros(B, G, inner.obs_dim, dtype=torch.float32, device=dev)     # (score_gpts.py:301-302)
@@ -242,12 +261,25 @@ class HipTrainStep:
         denoised, x_grad = torch.empty_like(x), torch.empty_like(x)
         dot = torch.empty(B, dtype=torch.float32, device=dev)
         flags = train_hints() & (_lib.TRAIN_PLAN_PER_OP | _lib.TRAIN_PLAN_TILES)
+        args = (C.byref(self.cfg), self._arr, len(params), precision, state.data_ptr(), x.data_ptr(), gptr, sigma.data_ptr(),
+                cot.data_ptr(), denoised.data_ptr(), x_grad.data_ptr(), dot.data_ptr(), B, t, flags, ws.data_ptr(), ws.numel(),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        state_grad = goal_grad = None
+        # the goals are a live input of this call; uncond or no goal: DiffusionGPT.forward puts zeros in their place, nothing
+        # depends on them -- the kernel gets no goal output (NULL) and the gradient is zeros
+        goal_live = G > 0 and not uncond and goal_given is not None
+        if input_grads:
+            state_grad = torch.empty_like(state)
+            if G > 0:
+                goal_grad = torch.empty_like(goal) if goal_live else torch.zeros_like(goal)
         with torch.cuda.device(dev):
-            st = self.lib.beso_denoise_vjp(C.byref(self.cfg), self._arr, len(params), precision, state.data_ptr(), x.data_ptr(),
-                                           gptr, sigma.data_ptr(), cot.data_ptr(), denoised.data_ptr(), x_grad.data_ptr(),
-                                           dot.data_ptr(), B, t, flags, ws.data_ptr(), ws.numel(),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if input_grads:
+                st = self.lib.beso_denoise_vjp_inputs(*args, state_grad.data_ptr(), goal_grad.data_ptr() if goal_live else None)
+            else:
+                st = self.lib.beso_denoise_vjp(*args)
         _lib.check(st, "denoise_vjp")
+        if input_grads:
+            return denoised, x_grad, dot, state_grad, goal_grad
         return denoised, x_grad, dot
 
     def goal_mask(self, batch: int, seed: int, goal_drop: Optional[float] = None, device=None) -> torch.Tensor:
@@ -297,17 +329,18 @@ class HipTrainStep:
         return scale
 
     def loss_backward(self, state, action, goal, noise, sigma, grad_scale: float = 1.0, seed: Optional[int] = None,
-                      early_stream=None, loss_stream=None):
+                      early_stream=None, loss_stream=None, input_grads: bool = False):
         """The training step's ``loss = model.loss(...); loss.backward()``: returns the loss and leaves the
-        gradients in ``p.grad`` (views of the persistent flat buffer; accumulated into an existing ``.grad``)."""
-        loss, flat, views = self.run(state, action, goal, noise, sigma, grad_scale, seed, fresh_grads=False,
-                                     early_stream=early_stream, loss_stream=loss_stream)
+        gradients in ``p.grad`` (views of the persistent flat buffer; accumulated into an existing ``.grad``).
+        ``input_grads``: -> (loss, state_grad, goal_grad) as ``run`` returns them (no ``.grad`` of an input is touched)."""
+        loss, flat, views, *extra = self.run(state, action, goal, noise, sigma, grad_scale, seed, fresh_grads=False,
+                                             early_stream=early_stream, loss_stream=loss_stream, input_grads=input_grads)
         for p, v in zip(self._params()[0], views):
             if p.grad is None or p.grad.data_ptr() == v.data_ptr():
                 p.grad = v
             else:
                 p.grad.add_(v)
-        return loss
+        return (loss, *extra) if input_grads else loss
 
     def flat_grads_padded(self) -> Optional[torch.Tensor]:
         """flat_grads() with its zero tail (``pad_to`` floats in all), for the reduce-scatter of the sharded exchange."""
@@ -324,13 +357,31 @@ class HipTrainStep:
 
 
 class ScoreMatchingLoss(torch.autograd.Function):
-    """loss = GCDenoiser.loss(...) with the parameter gradients computed alongside (HIP); backward hands them over."""
+    """loss = GCDenoiser.loss(...) with the parameter gradients computed alongside (HIP); backward hands them over --
+    and, where ``state`` / ``goal`` require grad (the outputs of a trainable encoder), the gradients with respect to those.
+    Gradients with respect to action, noise and sigma are not computed (None)."""
 
     @staticmethod
     def forward(ctx, step: HipTrainStep, last_action_only: bool, state, action, goal, noise, sigma, *params):
-        loss, flat, views = step.run(state, action, goal, noise, sigma, fresh_grads=True, last_action_only=last_action_only)
-        ctx.flat, ctx.views = flat, views
+        # (argument positions of forward: step 0, last_action_only 1, state 2, action 3, goal 4)
+        want_state, want_goal = ctx.needs_input_grad[2], ctx.needs_input_grad[4] and step.inner.goal_seq_len > 0
+        out = step.run(state, action, goal, noise, sigma, fresh_grads=True, last_action_only=last_action_only,
+                       input_grads=want_state or want_goal)
+        loss, ctx.flat, ctx.views = out[:3]
+        # (fp32 gradient as run() returned it, the input's own shape, its dtype) per differentiated input
+        ctx.state_grad = (out[3], state.shape, state.dtype) if want_state else None
+        ctx.goal_grad = (out[4], goal.shape, goal.dtype) if want_goal else None
         return loss
+
+    @staticmethod
+    def _input_grad(kept, grad_out):
+        """grad_out times the kept fp32 gradient, in the input's own shape and dtype: a goal given as [G,obs] or [1,G,obs] was
+        expanded over the batch by run(), so its gradient is the sum over the samples.  Out of place, like the parameter
+        gradients; a constant to autograd (no double backward)."""
+        if kept is None:
+            return None
+        g, shape, dtype = kept
+        return (g * grad_out.to(g.dtype)).sum_to_size(shape).to(dtype)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -339,4 +390,5 @@ class ScoreMatchingLoss(torch.autograd.Function):
         for v in ctx.views:
             grads.append(scaled[off:off + v.numel()].view_as(v))
             off += v.numel()
-        return (None,) * 7 + tuple(grads)
+        return (None, None, ScoreMatchingLoss._input_grad(ctx.state_grad, grad_out), None,
+                ScoreMatchingLoss._input_grad(ctx.goal_grad, grad_out), None, None) + tuple(grads)

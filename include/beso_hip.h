@@ -28,6 +28,9 @@
  *   beso_loss_grad_overlap  (same, with the early gradient range for the overlapped all-reduce: SURVEY 8(e) C1)
  *   beso_loss_grad_streams  (same, plus a stream that is released as soon as the loss value is final)
  *   beso_denoise_vjp    <- GCDenoiser.forward + torch.autograd.grad w.r.t. the action   k_diffusion/gc_sampling.py:480-485
+ *   beso_loss_grad_inputs   (beso_loss_grad_streams, plus the gradient of the loss with respect to `state` and `goal`: what
+ *                          loss.backward() hands to a trainable observation / goal encoder in front of the denoiser)
+ *   beso_denoise_vjp_inputs (beso_denoise_vjp, plus the same product with respect to `state` and `goal`)
  *   beso_adam_step      <- optimizer.step() + ema_helper.update()      beso_agent.py:236-244
  *   beso_grad_sumsq / beso_adam_step_clipped <- torch.nn.utils.clip_grad_norm_ in front of that step, and a guard that
  *                          drops a step whose gradient is not finite -- both without a host read (the reference has neither)
@@ -41,7 +44,7 @@
  *     allocates or frees device memory and never synchronises the stream; work is enqueued on
  *     `stream` and the call returns.
  *   - buffers the library writes are handed over UNINITIALISED: the workspace, every output (`out`, `denoised`, `x_grad`,
- *     `dot`, `loss_out`, `per_sample_out`), the solver `history`, `grads_flat` and the `packed` image may hold anything on entry -- NaN bit
+ *     `dot`, `loss_out`, `per_sample_out`, `state_grad`, `goal_grad`), the solver `history`, `grads_flat` and the `packed` image may hold anything on entry -- NaN bit
  *     patterns and what an earlier, larger call left behind included.  No result depends on a byte the call did not write,
  *     every element of a result is written, and nothing outside [ptr, ptr + size) of a buffer is written
  *     (tests/test_buffer_independence.py).  Inputs are read inside their extents only.
@@ -564,6 +567,31 @@ int beso_loss_grad_streams(const beso_config* cfg, const float* const* params, i
                            float* loss_out, int batch, int t, int flags, float embed_pdrop, float attn_pdrop, float resid_pdrop,
                            float goal_drop, unsigned int seed, float grad_scale, void* workspace, size_t workspace_bytes,
                            void* stream, void* early_stream, void* loss_stream);
+/* ... and with the gradient of the loss with respect to the INPUTS `state` and `goal` -- what the reference's `loss.backward()`
+ * passes on to whatever trainable module produced them (an observation or goal encoder).  One more launch at the end of the
+ * call's work on `stream`: the rows of the fp32 gradient of the embedded sequence that belong to state and goal tokens,
+ * projected back through tok_emb.weight, with this call's embedding dropout applied per (token, feature) and, for the goals,
+ * mask_cond's keep-mask per element (the masks of `seed`: beso_dropout_mask(BESO_DROP_EMBED) / beso_goal_mask) -- a goal element
+ * the mask zeroed gets gradient exactly 0.  grad_scale is included, as in grads_flat.
+ *   state_grad [batch,t,obs], goal_grad [batch,G,obs]: fp32 out, UNINITIALISED on entry, every element written.  Either may be
+ *   NULL (not computed); with both NULL the call is beso_loss_grad_streams and enqueues exactly what that enqueues.
+ * Every element is summed by one thread in index order, without atomics: equal bits on every call with the same dx, with or
+ * without BESO_TRAIN_DETERMINISTIC; the loss and grads_flat do not depend on whether the outputs are asked for.
+ * Gradients with respect to action, noise and sigma are not computed.
+ * BESO_ERR_BAD_ARG, before anything is enqueued and in addition to beso_loss_grad's checks: goal_grad != NULL with
+ * goal_seq_len == 0, an output pointer that is not 4-byte aligned.                                                        */
+int beso_loss_grad_inputs(const beso_config* cfg, const float* const* params, int n_params, float* grads_flat, int precision,
+                          const float* state, const float* action, const float* goal, const float* noise, const float* sigma,
+                          float* loss_out, int batch, int t, int flags, float embed_pdrop, float attn_pdrop, float resid_pdrop,
+                          float goal_drop, unsigned int seed, float grad_scale, void* workspace, size_t workspace_bytes,
+                          void* stream, void* early_stream, void* loss_stream, float* state_grad, float* goal_grad);
+/* beso_denoise_vjp with the same two outputs: (d denoised / d state)^T cot [batch,t,obs] and (d denoised / d goal)^T cot
+ * [batch,G,obs] (eval mode: no mask applies; for the unconditional branch the caller passed zero goals and the product with
+ * respect to the goals it replaced is zero -- pass goal_grad = NULL).  Same kernel, same checks and NULL rules as above. */
+int beso_denoise_vjp_inputs(const beso_config* cfg, const float* const* params, int n_params, int precision, const float* state,
+                            const float* x, const float* goal, const float* sigma, const float* cot, float* denoised, float* x_grad,
+                            float* dot, int batch, int t, int flags, void* workspace, size_t workspace_bytes, void* stream,
+                            float* state_grad, float* goal_grad);
 /* Launch-site timers (bench.py's roofline, the launch-count assertions of the tests): while a site is selected ON THE
  * CALLING THREAD, HIP events are recorded on the launch stream around every launch that thread makes at that site (site 0 =
  * off).  beso_profile_read synchronises the events the calling thread recorded, returns their summed elapsed time and count,

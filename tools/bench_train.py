@@ -3,8 +3,11 @@
 1024 samples per step, through BesoAgent.train_step: HIP forward + backward (beso_loss_grad) and the fused
 Adam(W) + EMA launch; `--autograd` times the tests' torch-autograd comparator of the same step beside it;
 `--max-grad-norm X` / `--skip-nonfinite` turn on gradient clipping / the non-finite guard of the fused step;
-`--deterministic` times the step with BESO_TRAIN_DETERMINISTIC (BesoAgent(deterministic_training=True)).
-    python tools/bench_train.py [batch] [kitchen|block_push] [--autograd] [--max-grad-norm X] [--skip-nonfinite] [--deterministic]"""
+`--deterministic` times the step with BESO_TRAIN_DETERMINISTIC (BesoAgent(deterministic_training=True));
+`--input-grads` makes every step also compute the gradients with respect to state and goal (beso_loss_grad_inputs: one more
+launch and two output tensors per step; the agent itself does not use them).
+    python tools/bench_train.py [batch] [kitchen|block_push] [--autograd] [--max-grad-norm X] [--skip-nonfinite] [--deterministic]
+                                [--input-grads]"""
 import json
 import os
 import sys
@@ -45,6 +48,20 @@ def main():
     det = "--deterministic" in sys.argv       # fixed-order reductions in the step (a second small launch per partial-sum slab)
     if det:
         sys.argv.remove("--deterministic")
+    input_grads = "--input-grads" in sys.argv
+    if input_grads:                             # the agent's HIP step with the state / goal gradients asked for (and dropped)
+        sys.argv.remove("--input-grads")
+        # (BesoAgent._loss_backward calls step.loss_backward(state, action, goal, noise, sigma, **keywords); the counter below
+        #  is checked after the timed window, so a changed call site cannot turn this into a silent flag-off run)
+        from beso_amd.training import HipTrainStep
+        plain, taken = HipTrainStep.loss_backward, [0]
+
+        def with_input_grads(self, *a, **k):
+            loss, state_grad, goal_grad = plain(self, *a, input_grads=True, **k)
+            assert state_grad is not None
+            taken[0] += 1
+            return loss
+        HipTrainStep.loss_backward = with_input_grads
     if "--autograd" in sys.argv:
         sys.argv.remove("--autograd")
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -108,6 +125,8 @@ def main():
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
+    if input_grads:
+        assert taken[0] == 3 + n, f"--input-grads: {taken[0]} of {3 + n} steps went through HipTrainStep.loss_backward"
     if rank != 0:
         return
     B = B * world                                                              # samples per step of the whole job
@@ -115,7 +134,7 @@ def main():
     if clip:                                    # (read after the timed window: the read synchronises)
         clip = dict(clip, grad_norm=float(agent.last_grad_norm()), clip_coef=float(agent.optimizer.last_clip_coef()),
                     skipped_steps=float(agent.skipped_steps()))
-    print(json.dumps({**clip, "deterministic": det, "config": ("3: kitchen train_step" if name == "kitchen" else name + " train_step"), "n_gpus": world, "batch": B, "attn_pdrop": attn_p, "resid_pdrop": resid_p, "seconds_per_step": dt,
+    print(json.dumps({**clip, "deterministic": det, "input_grads": input_grads, "config": ("3: kitchen train_step" if name == "kitchen" else name + " train_step"), "n_gpus": world, "batch": B, "attn_pdrop": attn_p, "resid_pdrop": resid_p, "seconds_per_step": dt,
                       "samples_per_s": B / dt, "tflops_fwd_bwd": flops / dt / 1e12, "loss": loss,
                       "path": ("HIP forward/backward (bf16 operands)" if getattr(agent, "_hip_step", None) is not None
                                else "torch autograd fp32 forward/backward") + " + " + type(agent.optimizer).__name__ + " (+EMA)"}))
