@@ -9,7 +9,11 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BESO_HIP_LIB points the binding at another build of the same library (kernel experiments: tools/variants.py)
 LIB_PATH = os.environ.get("BESO_HIP_LIB") or os.path.join(_HERE, "lib", "libbeso_hip.so")
+DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
 
+# Every upper-case integer below is BESO_<name> of include/beso_hip.h, and every table one of its enums
+# (tests/test_cabi.py compares the values, and SIGNATURES with the prototypes, against the header's text).
+OK, ERR_BAD_CONFIG, ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_WORKSPACE, ERR_UNSUPPORTED, ERR_HIP = 0, -1, -2, -3, -4, -5, -6
 PREC_BF16, PREC_FP32, PREC_BF16X3, PREC_FP16 = 0, 1, 2, 3
 PRECISIONS = {"bf16": PREC_BF16, "fp32": PREC_FP32, "bf16x3": PREC_BF16X3, "fp16": PREC_FP16}
 FLAG_UNCOND = 1
@@ -37,20 +41,6 @@ STEP_DDIM, STEP_EULER, STEP_HEUN_PREDICT, STEP_HEUN_CORRECT = 0, 1, 2, 3
 SITES = {"off": 0, "gemm_qkv": 1, "gemm_proj": 2, "gemm_fc1": 3, "gemm_fc2": 4, "attention": 5,
          "layernorm": 6, "embed": 7, "head": 8, "forward": 9, "fused_layer": 10, "small": 11}
 
-# every symbol include/beso_hip.h declares (tests check that the library exports all of them)
-EXPORTS = ["beso_version", "beso_status_string", "beso_last_error", "beso_num_params", "beso_packed_bytes", "beso_pack_weights",
-           "beso_workspace_bytes", "beso_score_fwd", "beso_denoise_fwd", "beso_sampler_step", "beso_sample",
-           "beso_profile_enable", "beso_profile_read", "beso_adam_step",
-           "beso_train_workspace_bytes", "beso_grad_floats", "beso_loss_grad", "beso_gather_windows",
-           "beso_loss_grad_overlap", "beso_grad_early_range", "beso_sample_ancestral", "beso_goal_mask",
-           "beso_loss_grad_streams", "beso_log_logistic", "beso_scale_rows", "beso_denoise_vjp", "beso_sample_solver",
-           "beso_dropout_mask", "beso_sample_traced", "beso_rollout_begin", "beso_rollout_end",
-           "beso_loss_fwd_workspace_bytes", "beso_loss_fwd", "beso_grad_sumsq", "beso_adam_step_clipped",
-           "beso_loss_grad_inputs", "beso_denoise_vjp_inputs"]
-# include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
-DEV_EXPORTS = ["beso_debug_set_stamps", "beso_debug_gemm", "beso_debug_sigma_cache_entries"]
-DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
-
 
 class BesoConfig(C.Structure):
     """struct beso_config (include/beso_hip.h)."""
@@ -59,8 +49,79 @@ class BesoConfig(C.Structure):
                 ("obs_seq_len", C.c_int32), ("linear_output", C.c_int32), ("sigma_data", C.c_float)]
 
 
+vp, i32, u32, i64, f32, f64, sz, cstr = (C.c_void_p, C.c_int, C.c_uint, C.c_longlong, C.c_float, C.c_double, C.c_size_t,
+                                         C.c_char_p)
+cfgp, vpp, floats = C.POINTER(BesoConfig), C.POINTER(vp), C.POINTER(f32)
+# argument lists that several entry points share: each of those is this list plus its own trailing arguments
+_adam = [vp, i32, vp, vp, vp, f32, f32, f32, f32, f32, i32, i32, f32]           # beso_adam_step without its stream
+_loss_grad = [cfgp, vpp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, u32, f32, vp, sz, vp]
+_denoise_vjp = [cfgp, vpp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
+
+# every function include/beso_hip.h declares, in its order: name -> (restype, argtypes)
+SIGNATURES = {
+    "beso_version": (cstr, []),
+    "beso_status_string": (cstr, [i32]),
+    "beso_last_error": (cstr, []),
+    "beso_num_params": (i32, [cfgp]),
+    "beso_packed_bytes": (sz, [cfgp, i32]),
+    "beso_pack_weights": (i32, [cfgp, vpp, i32, vp, sz, i32, vp]),
+    "beso_workspace_bytes": (sz, [cfgp, i32, i32, i32, i32]),
+    "beso_score_fwd": (i32, [cfgp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    "beso_denoise_fwd": (i32, [cfgp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]),
+    "beso_sampler_step": (i32, [i32, vp, vp, vp, vp, vp, f32, f32, sz, vp]),
+    "beso_sample": (i32, [cfgp, vp, i32, i32, vp, vp, vp, i32, i32, floats, i32, f32, i32, vp, sz, vp]),
+    "beso_sample_ancestral": (i32, [cfgp, vp, i32, vp, vp, vp, i32, i32, floats, i32, f32, f32, vp, i32, vp, sz, vp]),
+    "beso_sample_solver": (i32, [cfgp, vp, i32, i32, vp, vp, vp, i32, i32, floats, i32, f32, f32, f32, i32, vp, vp, i32,
+                                 vp, sz, vp]),
+    "beso_sample_traced": (i32, [cfgp, vp, i32, i32, i32, vp, vp, vp, i32, i32, floats, i32, f32, f32, f32, i32, vp, vp,
+                                 vp, sz, vp, sz, i32, vp, sz, vp]),
+    "beso_adam_step": (i32, _adam + [vp]),
+    "beso_grad_sumsq": (i32, [vp, i32, vp, vp, vp]),
+    "beso_adam_step_clipped": (i32, _adam + [vp, f32, i32, vp]),
+    "beso_train_workspace_bytes": (sz, [cfgp, i32, i32, i32]),
+    "beso_grad_floats": (sz, [cfgp]),
+    "beso_loss_grad": (i32, _loss_grad),
+    "beso_denoise_vjp": (i32, _denoise_vjp),
+    "beso_loss_fwd_workspace_bytes": (sz, [cfgp, i32, i32, i32]),
+    "beso_loss_fwd": (i32, [cfgp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    "beso_goal_mask": (i32, [vp, i32, i32, i32, f32, u32, vp]),
+    "beso_dropout_mask": (i32, [cfgp, vp, i32, i32, i32, i32, f32, u32, vp]),
+    "beso_gather_windows": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp,
+                                  vp]),
+    "beso_rollout_begin": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "beso_rollout_end": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "beso_log_logistic": (i32, [vp, vp, sz, f64, f64, f64, f64, vp]),
+    "beso_scale_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, vp]),
+    "beso_grad_early_range": (i32, [cfgp, C.POINTER(sz), C.POINTER(sz)]),
+    "beso_loss_grad_overlap": (i32, _loss_grad + [vp]),                 # + early_stream
+    "beso_loss_grad_streams": (i32, _loss_grad + [vp, vp]),             # + loss_stream
+    "beso_loss_grad_inputs": (i32, _loss_grad + [vp, vp, vp, vp]),      # + state_grad, goal_grad
+    "beso_denoise_vjp_inputs": (i32, _denoise_vjp + [vp, vp]),          # + state_grad, goal_grad
+    "beso_profile_enable": (None, [i32]),
+    "beso_profile_read": (i32, [C.POINTER(f64), C.POINTER(i32)]),
+}
+# include/beso_hip_debug.h: the development build only (libbeso_hip_dev.so); the product library exports none of them
+DEV_SIGNATURES = {
+    "beso_debug_set_stamps": (None, [vp, i32]),
+    "beso_debug_sigma_cache_entries": (i32, [cfgp, vp, i32]),
+    "beso_debug_gemm": (i32, [i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+}
+EXPORTS, DEV_EXPORTS = list(SIGNATURES), list(DEV_SIGNATURES)
+
+
 class BesoHipError(RuntimeError):
     pass
+
+
+def _bind(lib: C.CDLL, table, tolerant: bool) -> C.CDLL:
+    """Declare every function of `table` on `lib`.  A symbol the library lacks raises (AttributeError), unless `tolerant`:
+    then that symbol alone stays unbound and a caller that needs it fails on first use."""
+    for name, (restype, argtypes) in table.items():
+        if tolerant and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
+    return lib
 
 
 _lib = None
@@ -84,107 +145,9 @@ def load() -> C.CDLL:
             raise BesoHipError(
                 f"{LIB_PATH} not found: build it with `python -m beso_amd.build` (hipcc, gfx950). "
                 "beso_amd has no CPU or eager fallback for the score-denoising path.")
-        lib = C.CDLL(LIB_PATH)
-        vp, i32, f32, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-        cfgp = C.POINTER(BesoConfig)
-        lib.beso_version.restype = C.c_char_p
-        lib.beso_version.argtypes = []
-        lib.beso_status_string.restype = C.c_char_p
-        lib.beso_status_string.argtypes = [i32]
-        lib.beso_last_error.restype = C.c_char_p
-        lib.beso_last_error.argtypes = []
-        lib.beso_num_params.restype = i32
-        lib.beso_num_params.argtypes = [cfgp]
-        lib.beso_packed_bytes.restype = sz
-        lib.beso_packed_bytes.argtypes = [cfgp, i32]
-        lib.beso_pack_weights.restype = i32
-        lib.beso_pack_weights.argtypes = [cfgp, C.POINTER(vp), i32, vp, sz, i32, vp]
-        lib.beso_workspace_bytes.restype = sz
-        lib.beso_workspace_bytes.argtypes = [cfgp, i32, i32, i32, i32]
-        lib.beso_score_fwd.restype = i32
-        lib.beso_score_fwd.argtypes = [cfgp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
-        lib.beso_denoise_fwd.restype = i32
-        lib.beso_denoise_fwd.argtypes = [cfgp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, sz, vp]
-        lib.beso_sampler_step.restype = i32
-        lib.beso_sampler_step.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, sz, vp]
-        lib.beso_sample.restype = i32
-        lib.beso_sample.argtypes = [cfgp, vp, i32, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_float), i32, f32, i32,
-                                    vp, sz, vp]
-        if hasattr(lib, "beso_sample_ancestral") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_sample_ancestral.restype = i32
-            lib.beso_sample_ancestral.argtypes = [cfgp, vp, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_float), i32, f32, f32, vp,
-                                                  i32, vp, sz, vp]
-        if hasattr(lib, "beso_sample_solver") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_sample_solver.restype = i32
-            lib.beso_sample_solver.argtypes = [cfgp, vp, i32, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_float), i32, f32, f32, f32,
-                                               i32, vp, vp, i32, vp, sz, vp]
-        if hasattr(lib, "beso_sample_traced") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_sample_traced.restype = i32
-            lib.beso_sample_traced.argtypes = [cfgp, vp, i32, i32, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_float), i32, f32, f32,
-                                               f32, i32, vp, vp, vp, sz, vp, sz, i32, vp, sz, vp]
-        lib.beso_profile_enable.restype = None
-        lib.beso_profile_enable.argtypes = [i32]
-        if hasattr(lib, "beso_adam_step") or not os.environ.get("BESO_HIP_LIB"):   # (A/B builds of older revisions)
-            lib.beso_adam_step.restype = i32
-            lib.beso_adam_step.argtypes = [vp, i32, vp, vp, vp, f32, f32, f32, f32, f32, i32, i32, f32, vp]
-        if hasattr(lib, "beso_grad_sumsq") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_grad_sumsq.restype = i32
-            lib.beso_grad_sumsq.argtypes = [vp, i32, vp, vp, vp]
-            lib.beso_adam_step_clipped.restype = i32
-            lib.beso_adam_step_clipped.argtypes = list(lib.beso_adam_step.argtypes[:-1]) + [vp, f32, i32, vp]
-        if hasattr(lib, "beso_loss_grad") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_train_workspace_bytes.restype = sz
-            lib.beso_train_workspace_bytes.argtypes = [cfgp, i32, i32, i32]
-            lib.beso_grad_floats.restype = sz
-            lib.beso_grad_floats.argtypes = [cfgp]
-            lib.beso_loss_grad.restype = i32
-            lib.beso_loss_grad.argtypes = [cfgp, C.POINTER(vp), i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32,
-                                           f32, f32, C.c_uint, f32, vp, sz, vp]
-            lib.beso_goal_mask.restype = i32
-            lib.beso_goal_mask.argtypes = [vp, i32, i32, i32, f32, C.c_uint, vp]
-            if hasattr(lib, "beso_dropout_mask") or not os.environ.get("BESO_HIP_LIB"):
-                lib.beso_dropout_mask.restype = i32
-                lib.beso_dropout_mask.argtypes = [cfgp, vp, i32, i32, i32, i32, f32, C.c_uint, vp]
-            if hasattr(lib, "beso_loss_grad_overlap") or not os.environ.get("BESO_HIP_LIB"):
-                lib.beso_loss_grad_overlap.restype = i32
-                lib.beso_loss_grad_overlap.argtypes = lib.beso_loss_grad.argtypes + [vp]
-                if hasattr(lib, "beso_loss_grad_streams") or not os.environ.get("BESO_HIP_LIB"):     # (HipTrainStep.run probes it too)
-                    lib.beso_loss_grad_streams.restype = i32
-                    lib.beso_loss_grad_streams.argtypes = lib.beso_loss_grad.argtypes + [vp, vp]
-                if hasattr(lib, "beso_loss_grad_inputs") or not os.environ.get("BESO_HIP_LIB"):
-                    lib.beso_loss_grad_inputs.restype = i32
-                    lib.beso_loss_grad_inputs.argtypes = lib.beso_loss_grad.argtypes + [vp, vp, vp, vp]
-                lib.beso_grad_early_range.restype = i32
-                lib.beso_grad_early_range.argtypes = [cfgp, C.POINTER(sz), C.POINTER(sz)]
-        if hasattr(lib, "beso_denoise_vjp") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_denoise_vjp.restype = i32
-            lib.beso_denoise_vjp.argtypes = [cfgp, C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
-            if hasattr(lib, "beso_denoise_vjp_inputs") or not os.environ.get("BESO_HIP_LIB"):
-                lib.beso_denoise_vjp_inputs.restype = i32
-                lib.beso_denoise_vjp_inputs.argtypes = lib.beso_denoise_vjp.argtypes + [vp, vp]
-        if hasattr(lib, "beso_loss_fwd") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_loss_fwd_workspace_bytes.restype = sz
-            lib.beso_loss_fwd_workspace_bytes.argtypes = [cfgp, i32, i32, i32]
-            lib.beso_loss_fwd.restype = i32
-            lib.beso_loss_fwd.argtypes = [cfgp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]
-        if hasattr(lib, "beso_scale_rows") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_scale_rows.restype = i32
-            lib.beso_scale_rows.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp]
-        if hasattr(lib, "beso_log_logistic") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_log_logistic.restype = i32
-            lib.beso_log_logistic.argtypes = [vp, vp, sz, C.c_double, C.c_double, C.c_double, C.c_double, vp]
-        if hasattr(lib, "beso_rollout_begin") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_rollout_begin.restype = i32
-            lib.beso_rollout_begin.argtypes = [vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-            lib.beso_rollout_end.restype = i32
-            lib.beso_rollout_end.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
-        if hasattr(lib, "beso_gather_windows") or not os.environ.get("BESO_HIP_LIB"):
-            lib.beso_gather_windows.restype = i32
-            lib.beso_gather_windows.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, C.c_longlong, vp, vp, i32, i32, i32,
-                                                i32, i32, vp, vp, vp, vp]
-        lib.beso_profile_read.restype = i32
-        lib.beso_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(i32)]
-        _lib = lib
+        # a library named by BESO_HIP_LIB may be an A/B build of an older revision (tools/variants.py '@<revision>') that
+        # predates some entry points: those are skipped, one by one.  The tree's own library must have them all.
+        _lib = _bind(C.CDLL(LIB_PATH), SIGNATURES, tolerant=bool(os.environ.get("BESO_HIP_LIB")))
     return _lib
 
 
@@ -199,14 +162,7 @@ def load_dev() -> C.CDLL:
         import torch  # noqa: F401      (the HIP runtime of the process: see load())
         if not os.path.exists(DEV_LIB_PATH):
             raise BesoHipError(f"{DEV_LIB_PATH} not found: build it with `python -m beso_amd.build --dev`")
-        lib = C.CDLL(DEV_LIB_PATH)
-        lib.beso_debug_set_stamps.restype = None
-        lib.beso_debug_set_stamps.argtypes = [C.c_void_p, C.c_int]
-        lib.beso_debug_gemm.restype = C.c_int
-        lib.beso_debug_gemm.argtypes = [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]
-        lib.beso_debug_sigma_cache_entries.restype = C.c_int
-        lib.beso_debug_sigma_cache_entries.argtypes = [C.POINTER(BesoConfig), C.c_void_p, C.c_int]
-        _dev = lib
+        _dev = _bind(C.CDLL(DEV_LIB_PATH), DEV_SIGNATURES, tolerant=False)
     return _dev
 
 
@@ -214,12 +170,12 @@ def check(status: int, what: str = "") -> None:
     """Non-zero status -> exception.  Shape/config/argument errors are ValueError, matching the
     reference's conventions (ValueError for unknown sampler / schedule: beso_agent.py:455,598;
     `assert t <= block_size`: score_gpts.py:282); runtime failures are BesoHipError."""
-    if status == 0:
+    if status == OK:
         return
     msg = load().beso_status_string(status).decode()
     text = f"beso_hip: {what + ': ' if what else ''}{msg} (status {status})"
-    if status in (-1, -2, -3, -5):
+    if status in (ERR_BAD_CONFIG, ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
         raise ValueError(text)
-    if status == -6:
+    if status == ERR_HIP:
         text += ": " + load().beso_last_error().decode()
     raise BesoHipError(text)

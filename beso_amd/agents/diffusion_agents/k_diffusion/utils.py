@@ -40,12 +40,12 @@ def rand_log_logistic(shape, loc=0., scale=1., min_value=0., max_value=float('in
     if u.is_cuda and dtype == torch.float32 and hasattr(_hip_lib(), "beso_log_logistic"):      # (older A/B libraries: the chain below)
         # the transform behind the draw as ONE HIP launch (beso_log_logistic: the same float64 operations in the same order)
         # instead of seven elementwise ones -- the training step draws its sigmas here every step (beso_agent.py:227)
-        import ctypes as C
         from .... import _lib
+        from ....runtime import stream_ptr
         out = torch.empty(u.shape, device=u.device, dtype=torch.float32)
         with torch.cuda.device(u.device):
             _lib.check(_lib.load().beso_log_logistic(u.data_ptr(), out.data_ptr(), u.numel(), float(loc), float(scale), lo, hi,
-                                                     C.c_void_p(torch.cuda.current_stream(u.device).cuda_stream)), "log_logistic")
+                                                     stream_ptr(u.device)), "log_logistic")
         return out
     return (u * (hi - lo) + lo).logit().mul(scale).add(loc).exp().to(dtype)
 

@@ -16,7 +16,6 @@ CPU implementation: on a machine without the HIP library construction fails.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Iterator, Optional, Sequence
 
 import numpy as np
@@ -24,6 +23,7 @@ import torch
 
 from .. import _lib
 from .. import distributed as bdist
+from ..runtime import stream_ptr
 
 
 def window_table(seq_lengths: Sequence[int], window: int):
@@ -154,7 +154,7 @@ class DeviceTrajectoryFeed:
                 self.obs_dim, self.act_dim, self._traj.data_ptr(), self._start.data_ptr(), self.n_windows, ids.data_ptr(),
                 draws.data_ptr() if draws is not None else None, B, self.window, self.goal_len, self.goal_mode,
                 self.min_future_sep, obs.data_ptr(), act.data_ptr(), goal.data_ptr() if goal is not None else None,
-                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+                stream_ptr(self.device))
         _lib.check(st, "gather_windows")
         batch = {"observation": obs, "action": act}
         if goal is not None:

@@ -77,6 +77,7 @@ class Scaler:
             return [self.scale_input(x) if which == "x" else self.scale_output(x) for x, which in items]
         import ctypes as C
         from ... import _lib
+        from ...runtime import stream_ptr
         n = len(plan)
         outs = [torch.empty_like(x) for x, _, _ in plan]
         vp = C.c_void_p * n
@@ -86,7 +87,7 @@ class Scaler:
         cols = (C.c_int * n)(*[x.shape[-1] for x, _, _ in plan])
         dev = plan[0][0].device
         with torch.cuda.device(dev):
-            _lib.check(lib.beso_scale_rows(src, dst, mean, den, rows, cols, n, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+            _lib.check(lib.beso_scale_rows(src, dst, mean, den, rows, cols, n, stream_ptr(dev)),
                        "scale_rows")
         return outs
 

@@ -15,12 +15,12 @@ gradient is not finite.  Both consume the norm ON THE DEVICE (``beso_grad_sumsq`
 host never reads it, so the asynchronous training step stays asynchronous."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
 
 from . import _lib
+from .runtime import stream_ptr
 
 CHUNK = 4096
 
@@ -221,7 +221,7 @@ class FusedAdam(torch.optim.Optimizer):
                 raise ValueError("fused EMA needs one parameter group that matches the EMA helper")
             ema_decay = ema.next_decay()
             ema_ptr = ema._flat.data_ptr()
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = stream_ptr()
         for st, group in zip(prepared, self.param_groups):
             st["step"] += 1
             if clipped:

@@ -11,11 +11,10 @@ through a sampler loop without anything reading them.  No denoiser o
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from .runtime import stream_ptr
 
 
 class VectorRollout:
@@ -159,7 +158,7 @@ class VectorRollout:
         x = torch.empty((N, W, self.act_dim), dtype=torch.float32, device=dev)
         ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = stream_ptr(dev)
             _lib.check(self.lib.beso_rollout_begin(
                 obs.data_ptr(), self._reset.data_ptr() if self._reset_pending else None, noise.data_ptr(),
                 ptr(xs and xs[0]), ptr(xs and xs[1]), float(agent.sigma_max), self.lengths.data_ptr(), self.obs_ctx.data_ptr(),
@@ -179,7 +178,7 @@ class VectorRollout:
         if ys is not None:
             pred = torch.empty((N, self.act_dim), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                stream = stream_ptr(dev)
                 _lib.check(self.lib.beso_rollout_end(
                     x0.data_ptr(), self.lengths.data_ptr(), ys[0].data_ptr(), ys[1].data_ptr(), ptr(ys[2]), ptr(ys[3]),
                     self.act_ctx.data_ptr(), pred.data_ptr(), N, W, self.act_dim, stream), "rollout_end")

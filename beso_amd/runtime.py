@@ -89,14 +89,68 @@ class PackedWeights:
         self.key = key
 
 
-def _stream_ptr(device) -> int:
+def stream_ptr(device=None) -> int:
+    """The current stream of ``device`` as the ``void* stream`` of the C ABI."""
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def train_precision(name: str) -> int:
+    """The ``_lib.PREC_*`` a training step (``beso_loss_grad``, ``beso_denoise_vjp``) runs in for a model of precision
+    ``name``: the split-bf16 and fp16 modes are inference instances of the fused kernel; their steps are the fp32 / bf16 ones."""
+    return _lib.PRECISIONS[{"bf16x3": "fp32", "fp16": "bf16"}.get(name, name)]
+
+
+def workspace(owner, need: int, device) -> torch.Tensor:
+    """The grow-only scratch buffer ``owner._ws``: kept while it holds ``need`` bytes on ``device``, else released and
+    allocated anew."""
+    ws = owner._ws
+    if ws is None or ws.numel() < need or ws.device != device:
+        owner._ws = ws = None
+        owner._ws = ws = torch.empty(int(need), dtype=torch.uint8, device=device)
+    return ws
 
 
 def _f32c(x: torch.Tensor, device) -> torch.Tensor:
     if x.device != device or x.dtype != torch.float32:
         x = x.to(device=device, dtype=torch.float32)
     return x.contiguous()
+
+
+def prepare_inputs(state, action, goal, sigma, obs_dim: int, act_dim: int, goal_seq_len: int, device=None):
+    """The tensors a forward / training call hands to the library, from what the reference's callers pass: contiguous fp32 on
+    ``device`` (default: the action's), ``state`` [B,t,obs], ``action`` (or x, x_t) [B,t,act], ``goal`` [B,G,obs] -- given as
+    that, as [1,G,obs] or as [G,obs]; None when the model takes no goals (``goal_seq_len`` 0), whatever was passed -- and
+    ``sigma`` [B] from B values or one (None stays None).  Any other shape is a ValueError.  Works on any device: what must be
+    on the GPU, and what stands in for a missing input, is the caller's."""
+    if state.dim() != 3 or action.dim() != 3:
+        raise ValueError("state must be [B,t,obs] and action [B,t,act]")
+    B, t, _ = state.shape
+    if action.shape[0] != B or action.shape[1] != t or action.shape[2] != act_dim:
+        raise ValueError(f"action shape {tuple(action.shape)} does not match state {tuple(state.shape)}")
+    if state.shape[2] != obs_dim:
+        raise ValueError(f"state feature dim {state.shape[2]} != obs_dim {obs_dim}")
+    device = action.device if device is None else device
+    state = _f32c(state, device)
+    action = _f32c(action, device)
+    if goal_seq_len > 0:
+        if goal is None:
+            raise ValueError("goal is required for a goal-conditioned model")
+        if goal.dim() == 2:
+            goal = goal.unsqueeze(0)
+        if goal.dim() == 3 and goal.shape[0] == 1 and B > 1:
+            goal = goal.expand(B, -1, -1)
+        if tuple(goal.shape) != (B, goal_seq_len, obs_dim):
+            raise ValueError(f"goal shape {tuple(goal.shape)} != {(B, goal_seq_len, obs_dim)}")
+        goal = _f32c(goal, device)
+    else:
+        goal = None
+    if sigma is not None:
+        sigma = _f32c(sigma.reshape(-1), device)
+        if sigma.numel() == 1 and B > 1:
+            sigma = sigma.expand(B).contiguous()
+        if sigma.numel() != B:
+            raise ValueError(f"sigma must have {B} entries, got {sigma.numel()}")
+    return state, action, goal, sigma
 
 
 class ScoreNetRuntime:
@@ -140,7 +194,7 @@ class ScoreNetRuntime:
         arr = (C.c_void_p * len(keep))(*[p.data_ptr() for p in keep])
         with torch.cuda.device(dev):
             st = self.lib.beso_pack_weights(C.byref(self.cfg), arr, len(keep), buf.data_ptr(), nbytes,
-                                            self.precision, _stream_ptr(dev))
+                                            self.precision, stream_ptr(dev))
         _lib.check(st, "pack_weights")
         if into is not None and buf is into.buf:
             into.key = key
@@ -152,9 +206,7 @@ class ScoreNetRuntime:
         need = self.lib.beso_workspace_bytes(C.byref(self.cfg), batch, t, self.precision, int(two))
         if need == 0:
             raise ValueError(f"beso_hip: bad shape batch={batch} t={t} (t must be in [1, {self.shape.obs_seq_len}])")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(int(need * 1.0), dtype=torch.uint8, device=dev)
-        return self._ws
+        return workspace(self, need, dev)
 
     # ------------------------------------------------------------------ forward calls
     def _prep(self, state, action, goal, sigma):
@@ -162,34 +214,9 @@ class ScoreNetRuntime:
         if dev.type != "cuda":
             raise RuntimeError("beso_amd: the score-denoising path runs on the GPU only (no CPU fallback); "
                                "move the inputs to the MI355X")
-        if state.dim() != 3 or action.dim() != 3:
-            raise ValueError("state must be [B,t,obs] and action [B,t,act]")
+        state, action, goal, sigma = prepare_inputs(state, action, goal, sigma, self.shape.obs_dim, self.shape.act_dim,
+                                                    self.shape.goal_seq_len, dev)
         B, t, _ = state.shape
-        if action.shape[0] != B or action.shape[1] != t or action.shape[2] != self.shape.act_dim:
-            raise ValueError(f"action shape {tuple(action.shape)} does not match state {tuple(state.shape)}")
-        if state.shape[2] != self.shape.obs_dim:
-            raise ValueError(f"state feature dim {state.shape[2]} != obs_dim {self.shape.obs_dim}")
-        state = _f32c(state, dev)
-        action = _f32c(action, dev)
-        G = self.shape.goal_seq_len
-        if G > 0:
-            if goal is None:
-                raise ValueError("goal is required for a goal-conditioned model")
-            if goal.dim() == 2:
-                goal = goal.unsqueeze(0)
-            if goal.shape[0] == 1 and B > 1:
-                goal = goal.expand(B, -1, -1)
-            if tuple(goal.shape) != (B, G, self.shape.obs_dim):
-                raise ValueError(f"goal shape {tuple(goal.shape)} != {(B, G, self.shape.obs_dim)}")
-            goal = _f32c(goal, dev)
-        else:
-            goal = None
-        if sigma is not None:
-            sigma = _f32c(sigma.reshape(-1), dev)
-            if sigma.numel() == 1 and B > 1:
-                sigma = sigma.expand(B).contiguous()
-            if sigma.numel() != B:
-                raise ValueError(f"sigma must have {B} entries, got {sigma.numel()}")
         return dev, B, t, state, action, goal, sigma
 
     def denoise(self, packed: PackedWeights, state, action, goal, sigma, uncond: bool = False,
@@ -206,12 +233,12 @@ class ScoreNetRuntime:
                 st = self.lib.beso_denoise_fwd(C.byref(self.cfg), packed.buf.data_ptr(), packed.precision,
                                                state.data_ptr(), action.data_ptr(), gp, sigma.data_ptr(),
                                                out.data_ptr(), B, t, flags, float(cond_lambda), ws.data_ptr(),
-                                               ws.numel(), _stream_ptr(dev))
+                                               ws.numel(), stream_ptr(dev))
             else:
                 st = self.lib.beso_score_fwd(C.byref(self.cfg), packed.buf.data_ptr(), packed.precision,
                                              state.data_ptr(), action.data_ptr(), gp, sigma.data_ptr(),
                                              out.data_ptr(), B, t, flags, ws.data_ptr(), ws.numel(),
-                                             _stream_ptr(dev))
+                                             stream_ptr(dev))
         _lib.check(st, "denoise_fwd" if precondition else "score_fwd")
         return out
 
@@ -231,9 +258,7 @@ class ScoreNetRuntime:
         need = self.lib.beso_loss_fwd_workspace_bytes(C.byref(self.cfg), B, t, self.precision)
         if need == 0:
             raise ValueError(f"beso_hip: bad shape batch={B} t={t} (t must be in [1, {self.shape.obs_seq_len}])")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
-        ws = self._ws
+        ws = workspace(self, need, dev)
         out = torch.empty((), dtype=torch.float32, device=dev)
         rows = torch.empty(B, dtype=torch.float32, device=dev) if per_sample else None
         flags = (_lib.FLAG_UNCOND if uncond else 0) | (_lib.FLAG_LAST_ACTION_ONLY if last_only else 0) | forward_hints()
@@ -241,7 +266,7 @@ class ScoreNetRuntime:
             st = self.lib.beso_loss_fwd(C.byref(self.cfg), packed.buf.data_ptr(), packed.precision, state.data_ptr(),
                                         action.data_ptr(), goal.data_ptr() if goal is not None else None, noise.data_ptr(),
                                         sigma.data_ptr(), out.data_ptr(), rows.data_ptr() if rows is not None else None,
-                                        B, t, flags, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+                                        B, t, flags, ws.data_ptr(), ws.numel(), stream_ptr(dev))
         _lib.check(st, "loss_fwd")
         return (out, rows) if per_sample else out
 
@@ -290,7 +315,7 @@ class ScoreNetRuntime:
                 float(cond_lambda))
         nz = noise.data_ptr() if noise is not None else None
         flags = (_lib.SAMPLE_STEPWISE if stepwise else 0) | forward_hints()
-        tail = (ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+        tail = (ws.data_ptr(), ws.numel(), stream_ptr(dev))
         if trace:
             n = len(sig) - 1
             out = {}

@@ -25,7 +25,23 @@ from typing import List, Optional
 import torch
 
 from . import _lib
-from .runtime import train_hints
+from .runtime import _f32c, prepare_inputs, stream_ptr, train_hints, train_precision, workspace
+
+# The training entry points, widest first: (name, how many trailing arguments it takes behind `stream`).  On the C side each
+# is the next one with trailing NULLs: a call passes all of them, None where it has nothing, cut to the entry point's count.
+_LOSS_GRAD = (("beso_loss_grad_inputs", 4), ("beso_loss_grad_streams", 2), ("beso_loss_grad_overlap", 1))
+_DENOISE_VJP = (("beso_denoise_vjp_inputs", 2), ("beso_denoise_vjp", 0))
+
+
+def _entry(lib, entries, need: int, most: int):
+    """-> (function, its trailing-argument count): the widest of ``entries`` that ``lib`` has among those that take at least
+    the ``need`` trailing arguments the call cannot do without and at most the ``most`` it has a use for (a library loaded
+    through BESO_HIP_LIB may predate the wider ones: tools/variants.py's '@<revision>' A/B builds)."""
+    for name, n in entries:
+        fn = getattr(lib, name, None) if need <= n <= most else None
+        if fn is not None:
+            return fn, n
+    raise _lib.BesoHipError(f"beso_hip: the loaded library has none of {[name for name, n in entries if need <= n <= most]}")
 
 
 class HipTrainStep:
@@ -112,10 +128,7 @@ class HipTrainStep:
         need = int(self.lib.beso_train_workspace_bytes(C.byref(self.cfg), batch, t, precision))
         if need == 0:
             raise ValueError(f"beso_hip: training step unsupported for batch={batch} t={t} with this model shape")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._ws
+        return workspace(self, need, dev)
 
     # ------------------------------------------------------------------ the call
     def early_range(self):
@@ -141,21 +154,15 @@ class HipTrainStep:
         a fixed order, so the same inputs and ``seed`` give the same bits on every call (include/beso_hip.h)."""
         inner = self.inner
         dev = action.device
-        f32 = lambda x: x.detach().to(device=dev, dtype=torch.float32).contiguous()
-        state, action, noise, sigma = f32(state), f32(action), f32(noise), f32(sigma).reshape(-1)
-        if state.dim() != 3 or action.dim() != 3:
-            raise ValueError("state must be [B,t,obs] and action [B,t,act]")
-        B, t, _ = state.shape
-        if action.shape[:2] != (B, t) or noise.shape != action.shape or sigma.numel() != B:
-            raise ValueError("action / noise must be [B,t,act] and sigma [B]")
         G = inner.goal_seq_len
-        gptr = None
-        if G > 0:
-            goal = f32(goal)
-            if goal.dim() == 2:
-                goal = goal.unsqueeze(0)
-            goal = goal.expand(B, G, inner.obs_dim).contiguous()
-            gptr = goal.data_ptr()
+        n_sigma = sigma.numel()
+        state, action, goal, sigma = prepare_inputs(state.detach(), action.detach(), None if goal is None else goal.detach(),
+                                                    sigma.detach(), inner.obs_dim, inner.action_dim, G, dev)
+        B, t, _ = state.shape
+        noise = _f32c(noise.detach(), dev)
+        if noise.shape != action.shape or n_sigma != B:          # (one sigma per sample: no scalar is spread over a training batch)
+            raise ValueError("action / noise must be [B,t,act] and sigma [B]")
+        gptr = goal.data_ptr() if goal is not None else None
         embed_p, attn_p, resid_p = inner._pdrops
         # training-mode goal masking (DiffusionGPT.mask_cond, score_gpts.py:298-299) is part of the kernel: the goals
         # go in unmasked together with the drop probability
@@ -167,8 +174,7 @@ class HipTrainStep:
                 # the seed is a host scalar: a captured graph would replay one mask forever
                 raise RuntimeError("beso_amd: the HIP training step with dropout cannot be captured into a graph")
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,), device="cpu").item())
-        # the split-bf16 and fp16 modes are inference instances of the fused kernel; their training steps are the fp32 / bf16 ones
-        precision = _lib.PRECISIONS[{"bf16x3": "fp32", "fp16": "bf16"}.get(inner.precision, inner.precision)]
+        precision = train_precision(inner.precision)
         params, ptrs = self._params()
         if self.__dict__.get("_arr_ptrs") != ptrs:
             self._arr, self._arr_ptrs = (C.c_void_p * len(ptrs))(*ptrs), ptrs
@@ -182,26 +188,24 @@ class HipTrainStep:
                   state.data_ptr(), action.data_ptr(), gptr, noise.data_ptr(), sigma.data_ptr(),
                   loss.data_ptr(), B, t, (_lib.TRAIN_LAST_ACTION_ONLY if last_action_only else 0) | train_hints()
                   | (_lib.TRAIN_DETERMINISTIC if (deterministic or self.deterministic) else 0), float(embed_p), float(attn_p), float(resid_p),
-                  float(goal_p), C.c_uint(seed & 0xFFFFFFFF), float(grad_scale), ws.data_ptr(), ws.numel(),
-                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-                  C.c_void_p(early_stream.cuda_stream) if early_stream is not None else None)
+                  float(goal_p), C.c_uint(seed & 0xFFFFFFFF), float(grad_scale), ws.data_ptr(), ws.numel(), stream_ptr(dev))
         state_grad = goal_grad = None
         if input_grads:
             state_grad = torch.empty_like(state)
             goal_grad = torch.empty_like(goal) if G > 0 else None
+        trailing = (early_stream.cuda_stream if early_stream is not None else None,
+                    loss_stream.cuda_stream if loss_stream is not None else None,
+                    state_grad.data_ptr() if state_grad is not None else None,
+                    goal_grad.data_ptr() if goal_grad is not None else None)
+        # (the input gradients need their entry point; a call without them stays on beso_loss_grad_streams, the symbol that
+        # tools/train_host_profile.py and the flag test of tests/test_reproducible_training.py wrap)
+        fn, n = _entry(self.lib, _LOSS_GRAD, 4 if input_grads else 1, 4 if input_grads else 2)
         with torch.cuda.device(dev):
-            if input_grads:
-                st = self.lib.beso_loss_grad_inputs(*common, C.c_void_p(loss_stream.cuda_stream) if loss_stream is not None else None,
-                                                    state_grad.data_ptr(), goal_grad.data_ptr() if goal_grad is not None else None)
-            elif hasattr(self.lib, "beso_loss_grad_streams"):
-                st = self.lib.beso_loss_grad_streams(*common, C.c_void_p(loss_stream.cuda_stream) if loss_stream is not None else None)
-            else:
-                # (a library loaded through BESO_HIP_LIB that predates the loss stream -- tools/variants.py's '@<revision>' A/B
-                # builds: the loss is then final at the end of the call's work on the compute stream; order the caller's stream
-                # behind that instead of failing)
-                st = self.lib.beso_loss_grad_overlap(*common)
-                if loss_stream is not None:
-                    loss_stream.wait_stream(torch.cuda.current_stream(dev))
+            st = fn(*common, *trailing[:n])
+            if n < 2 and loss_stream is not None:
+                # (a library that predates the loss stream: the loss is then final at the end of the call's work on the
+                # compute stream; order the caller's stream behind that instead of failing)
+                loss_stream.wait_stream(torch.cuda.current_stream(dev))
         _lib.check(st, "loss_grad")
         if input_grads:
             return loss, flat, views, state_grad, goal_grad
@@ -230,31 +234,21 @@ class HipTrainStep:
         dev = x.device
         if not x.is_cuda:
             raise ValueError("beso_amd: denoise_vjp inputs must be on the GPU (there is no CPU path)")
-        f32 = lambda v: v.detach().to(device=dev, dtype=torch.float32).contiguous()
-        state, x, cot = f32(state), f32(x), f32(cot)
-        if state.dim() != 3 or x.dim() != 3 or cot.shape != x.shape:
-            raise ValueError("state must be [B,t,obs], x and cot [B,t,act]")
-        B, t, _ = state.shape
-        if x.shape[:2] != (B, t):
-            raise ValueError("state and x disagree on [B,t]")
-        sigma = f32(torch.as_tensor(sigma)).reshape(-1)
-        if sigma.numel() == 1:
-            sigma = sigma.expand(B).contiguous()
-        if sigma.numel() != B:
-            raise ValueError("sigma must be a scalar or [B]")
         G = inner.goal_seq_len
-        gptr, goal_given = None, goal
-        if G > 0:
-            if uncond or goal is None:
-                goal = torch.zeros(B, G, inner.obs_dim, dtype=torch.float32, device=dev)     # (score_gpts.py:301-302)
-            else:
-                goal = f32(goal)
-                if goal.dim() == 2:
-                    goal = goal.unsqueeze(0)
-                goal = goal.expand(B, G, inner.obs_dim).contiguous()
-            gptr = goal.data_ptr()
-        # (as run(): the split-bf16 and fp16 inference modes map to the fp32 / bf16 steps)
-        precision = _lib.PRECISIONS[{"bf16x3": "fp32", "fp16": "bf16"}.get(inner.precision, inner.precision)]
+        # the goals are a live input of this call; uncond or no goal: DiffusionGPT.forward puts zeros in their place
+        # (score_gpts.py:301-302), nothing depends on them -- the kernel gets no goal output (NULL) and the gradient is zeros
+        goal_live = G > 0 and not uncond and goal is not None
+        state, x, goal, sigma = prepare_inputs(state.detach(), x.detach(), goal.detach() if goal_live else None,
+                                               torch.as_tensor(sigma).detach(), inner.obs_dim, inner.action_dim,
+                                               G if goal_live else 0, dev)
+        B, t, _ = state.shape
+        cot = _f32c(cot.detach(), dev)
+        if cot.shape != x.shape:
+            raise ValueError("state must be [B,t,obs], x and cot [B,t,act]")
+        if G > 0 and not goal_live:
+            goal = torch.zeros(B, G, inner.obs_dim, dtype=torch.float32, device=dev)
+        gptr = goal.data_ptr() if goal is not None else None
+        precision = train_precision(inner.precision)
         if self.__dict__.get("_arr_ptrs") != ptrs:
             self._arr, self._arr_ptrs = (C.c_void_p * len(ptrs))(*ptrs), ptrs
         ws = self._workspace(B, t, precision, dev)
@@ -263,20 +257,18 @@ class HipTrainStep:
         flags = train_hints() & (_lib.TRAIN_PLAN_PER_OP | _lib.TRAIN_PLAN_TILES)
         args = (C.byref(self.cfg), self._arr, len(params), precision, state.data_ptr(), x.data_ptr(), gptr, sigma.data_ptr(),
                 cot.data_ptr(), denoised.data_ptr(), x_grad.data_ptr(), dot.data_ptr(), B, t, flags, ws.data_ptr(), ws.numel(),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                stream_ptr(dev))
         state_grad = goal_grad = None
-        # the goals are a live input of this call; uncond or no goal: DiffusionGPT.forward puts zeros in their place, nothing
-        # depends on them -- the kernel gets no goal output (NULL) and the gradient is zeros
-        goal_live = G > 0 and not uncond and goal_given is not None
         if input_grads:
             state_grad = torch.empty_like(state)
             if G > 0:
                 goal_grad = torch.empty_like(goal) if goal_live else torch.zeros_like(goal)
+        trailing = (state_grad.data_ptr() if state_grad is not None else None,
+                    goal_grad.data_ptr() if goal_live and goal_grad is not None else None)
+        n = 2 if input_grads else 0
+        fn, n = _entry(self.lib, _DENOISE_VJP, n, n)
         with torch.cuda.device(dev):
-            if input_grads:
-                st = self.lib.beso_denoise_vjp_inputs(*args, state_grad.data_ptr(), goal_grad.data_ptr() if goal_live else None)
-            else:
-                st = self.lib.beso_denoise_vjp(*args)
+            st = fn(*args, *trailing[:n])
         _lib.check(st, "denoise_vjp")
         if input_grads:
             return denoised, x_grad, dot, state_grad, goal_grad
@@ -291,7 +283,7 @@ class HipTrainStep:
         with torch.cuda.device(dev):
             _lib.check(self.lib.beso_goal_mask(mask.data_ptr(), batch, inner.goal_seq_len, inner.obs_dim, p,
                                                C.c_uint(seed & 0xFFFFFFFF),
-                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "goal_mask")
+                                               stream_ptr(dev)), "goal_mask")
         return mask
 
     def dropout_mask(self, kind, layer: int, batch: int, t: int, seed: int, p: Optional[float] = None, device=None) -> torch.Tensor:
@@ -325,7 +317,7 @@ class HipTrainStep:
         with torch.cuda.device(dev):
             _lib.check(self.lib.beso_dropout_mask(C.byref(self.cfg), scale.data_ptr(), k, int(layer), int(batch), int(t), float(p),
                                                   C.c_uint(seed & 0xFFFFFFFF),
-                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "dropout_mask")
+                                                  stream_ptr(dev)), "dropout_mask")
         return scale
 
     def loss_backward(self, state, action, goal, noise, sigma, grad_scale: float = 1.0, seed: Optional[int] = None,

@@ -441,8 +441,9 @@ def test_a_small_call_after_a_large_one_equals_a_fresh_modules(cfg_name, precisi
 
 # ------------------------------------------------------------------------------------------------ Test 4
 class _PoisonedTorch:
-    """Stands in for the `torch` name of beso_amd.training: torch.empty / empty_like hand out memory that is `byte` everywhere --
-    the workspace, the fresh gradient buffer, the loss scalar, denoised / x_grad / dot."""
+    """Stands in for the `torch` name of beso_amd.training, and of beso_amd.runtime whose workspace() allocates the step's
+    workspace: torch.empty / empty_like hand out memory that is `byte` everywhere -- the workspace, the fresh gradient buffer,
+    the loss scalar, denoised / x_grad / dot."""
 
     def __init__(self, byte):
         self._byte = byte
@@ -495,7 +496,7 @@ _TRAIN_CASES = [
 
 
 def _train_step_runs(cfg_name, B, t, precision, mkw, rkw, monkeypatch, modes=("none", "early", "both")):
-    from beso_amd import training
+    from beso_amd import runtime, training
     from beso_amd.training import HipTrainStep
     cfg = _CFGS[cfg_name]
     m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, **mkw)
@@ -513,6 +514,7 @@ def _train_step_runs(cfg_name, B, t, precision, mkw, rkw, monkeypatch, modes=("n
             step._ws = None                                     # a fresh, pre-filled workspace every time
             with monkeypatch.context() as mp:
                 mp.setattr(training, "torch", _PoisonedTorch(byte))
+                mp.setattr(runtime, "torch", _PoisonedTorch(byte))
                 loss, flat, _ = step.run(*inputs, seed=1234, fresh_grads=True, early_stream=early if mode != "none" else None,
                                          loss_stream=lossq if mode == "both" else None, **rkw)
             torch.cuda.synchronize()
@@ -594,7 +596,7 @@ def test_denoise_vjp_does_not_depend_on_what_its_buffers_held(cfg_name, B, preci
     """GCDenoiser.denoise_vjp with the workspace, denoised, x_grad and dot starting as each fill.  It has no weight gradients and
     no atomics: where two ZERO runs are bit-equal (checked first), the three fills must be bit-equal too; otherwise they agree
     within the training bounds."""
-    from beso_amd import training
+    from beso_amd import runtime, training
     cfg = _CFGS[cfg_name]
     m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision).eval()
     state, x, goal, cot, sigma = _train_inputs(cfg, B, seed=2)
@@ -606,6 +608,7 @@ def test_denoise_vjp_does_not_depend_on_what_its_buffers_held(cfg_name, B, preci
             step_of()._ws = None
         with monkeypatch.context() as mp:
             mp.setattr(training, "torch", _PoisonedTorch(byte))
+            mp.setattr(runtime, "torch", _PoisonedTorch(byte))
             out = m.denoise_vjp(*ins)
         torch.cuda.synchronize()
         return [o.clone() for o in out]

@@ -197,3 +197,117 @@ def test_product_path_has_no_cpu_fallback():
     s, a, g = torch.zeros(2, 3, 7), torch.zeros(2, 3, 3), torch.zeros(2, 2, 7)
     with torch.no_grad(), pytest.raises(RuntimeError, match="GPU"):
         m(s, a, g, torch.ones(2))
+
+
+# ------------------------------------------------------------------ the binding's tables against the headers' text (no library)
+def _header(name, keep_preprocessor=False):
+    """The header without block comments, // comments and (unless asked for) preprocessor lines."""
+    text = open(os.path.join(ROOT, "include", name)).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    if not keep_preprocessor:
+        text = "\n".join(ln for ln in text.splitlines() if not ln.lstrip().startswith("#"))
+    return text
+
+
+_C_CLASSES = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "unsigned int": C.c_uint,
+              "long long": C.c_longlong}
+
+
+def _c_class(ctype):
+    """A C type as the class of its ctypes counterpart: 'pointer', one of _C_CLASSES' values, None for void.  Anything else
+    is an error, not a skip."""
+    ctype = " ".join(ctype.replace("*", " * ").split())
+    if "*" in ctype:
+        return "pointer"
+    ctype = " ".join(w for w in ctype.split() if w != "const")
+    if ctype == "void":
+        return None
+    assert ctype in _C_CLASSES, f"C type {ctype!r} has no ctypes class in this test"
+    return _C_CLASSES[ctype]
+
+
+def _ctypes_class(t):
+    if t is None:
+        return None
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "pointer"
+    assert t in _C_CLASSES.values(), f"ctypes type {t!r} has no C type in this test"
+    return t
+
+
+def _prototypes(name):
+    """{function: (class of the return type, [class of every argument])} of every prototype the header declares."""
+    protos = {}
+    for ret, fn, args in re.findall(r"([A-Za-z_][A-Za-z_0-9 *]*?)\b(beso_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", _header(name)):
+        assert fn not in protos, fn
+        args = [] if args.strip() == "void" else [re.fullmatch(r"(.*?)[A-Za-z_]\w*", a.strip(), flags=re.S).group(1) for a in args.split(",")]
+        protos[fn] = (_c_class(ret), [_c_class(a) for a in args])
+    return protos
+
+
+@pytest.mark.parametrize("header,table,count", [("beso_hip.h", "SIGNATURES", 37), ("beso_hip_debug.h", "DEV_SIGNATURES", 3)])
+def test_signature_table_matches_the_header_prototypes(header, table, count):
+    """Every prototype of the header against the binding's table: the same set of functions (a declaration the parser
+    skipped, or one the table lacks, fails here), and per function the argument count, the class of every argument (any
+    pointer / int / float / double / size_t / unsigned int / long long) and the return type.  A wrong width or a missing
+    argument in the table would otherwise show only as a corrupted call on the GPU."""
+    protos, sigs = _prototypes(header), getattr(_lib, table)
+    assert sorted(protos) == sorted(sigs) == declared_symbols(header)
+    assert len(protos) == count
+    for fn, (ret, args) in protos.items():
+        restype, argtypes = sigs[fn]
+        assert len(argtypes) == len(args), f"{fn}: the header declares {len(args)} arguments, the table {len(argtypes)}"
+        for i, (want, have) in enumerate(zip(args, argtypes)):
+            assert _ctypes_class(have) == want, f"{fn}: argument {i} is {have!r} in the table, {want!r} in the header"
+        assert _ctypes_class(restype) == ret, f"{fn}: return type {restype!r} in the table, {ret!r} in the header"
+    assert list(getattr(_lib, table.replace("SIGNATURES", "EXPORTS"))) == list(sigs)
+
+
+def _header_constants():
+    """{BESO_X: value} of every enumerator `BESO_X = v` and every `#define BESO_X v` of beso_hip.h."""
+    text = _header("beso_hip.h", keep_preprocessor=True)
+    number = r"(-?(?:0[xX][0-9a-fA-F]+|\d+))\b"
+    found = re.findall(r"\b(BESO_[A-Z0-9_]+)\s*=\s*" + number, text) + re.findall(r"#\s*define\s+(BESO_[A-Z0-9_]+)[ \t]+" + number, text)
+    consts = {k: int(v, 0) for k, v in found}
+    assert len(consts) == len(found) and len(consts) >= 60, len(consts)       # no name twice; the enums were actually read
+    return consts
+
+
+def test_constants_match_the_header():
+    """Every upper-case integer of the binding is BESO_<name> of the header with the same value (none without a
+    counterpart), and every name -> id table is one of the header's groups: the same names, the same values."""
+    consts = _header_constants()
+    ints = {k: v for k, v in vars(_lib).items() if k.isupper() and type(v) is int}
+    assert {"OK", "ERR_HIP", "PREC_BF16", "PLAN_SPW8", "TRAIN_DETERMINISTIC", "DROP_MLP", "STEP_HEUN_CORRECT"} <= set(ints)
+    for k, v in ints.items():
+        assert "BESO_" + k in consts, f"_lib.{k} has no BESO_{k} in include/beso_hip.h"
+        assert consts["BESO_" + k] == v, f"_lib.{k} = {v:#x}, BESO_{k} = {consts['BESO_' + k]:#x}"
+    entry = {"beso_sample": "SAMPLE", "beso_sample_ancestral": "ANCESTRAL", "beso_sample_solver": "SOLVER"}
+    for table, prefix, key in (("PRECISIONS", "BESO_PREC_", str.upper), ("SAMPLER_IDS", "BESO_SAMPLER_", str.upper),
+                               ("SOLVER_IDS", "BESO_SOLVER_", str.upper), ("SITES", "BESO_SITE_", str.upper),
+                               ("DROP_KINDS", "BESO_DROP_", str.upper), ("ENTRY_IDS", "BESO_ENTRY_", entry.__getitem__)):
+        have = {prefix + key(k): v for k, v in getattr(_lib, table).items()}
+        want = {k: v for k, v in consts.items() if k.startswith(prefix)}
+        assert have == want, f"_lib.{table} and the header's {prefix}* disagree: {sorted(set(have.items()) ^ set(want.items()))}"
+
+
+def test_config_struct_matches_the_header():
+    """BesoConfig._fields_ has the names, order and types of struct beso_config."""
+    body = re.search(r"typedef\s+struct\s+beso_config\s*\{(.*?)\}\s*beso_config\s*;", _header("beso_hip.h"), flags=re.S).group(1)
+    fields = [tuple(f.split()) for f in body.split(";") if f.strip()]
+    types = {"int32_t": C.c_int32, "float": C.c_float}
+    assert [(name, types[ctype]) for ctype, name in fields] == list(_lib.BesoConfig._fields_)
+    assert len(fields) == 9 and C.sizeof(_lib.BesoConfig) == 36
+
+
+def test_check_classifies_statuses_by_name(lib):
+    """check(): BAD_CONFIG / BAD_SHAPE / BAD_ARG / UNSUPPORTED are ValueError, the rest BesoHipError (HIP with the detail of
+    beso_last_error appended), OK nothing."""
+    assert _lib.check(_lib.OK) is None
+    for st in (_lib.ERR_BAD_CONFIG, _lib.ERR_BAD_SHAPE, _lib.ERR_BAD_ARG, _lib.ERR_UNSUPPORTED):
+        with pytest.raises(ValueError, match=rf"status {st}\)"):
+            _lib.check(st, "x")
+    for st in (_lib.ERR_WORKSPACE, _lib.ERR_HIP, -99):
+        with pytest.raises(_lib.BesoHipError, match=rf"status {st}\)"):
+            _lib.check(st)

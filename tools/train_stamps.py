@@ -5,7 +5,6 @@ LAST launch of the step: layer 0's train_mlp_bwd_kernel (kind 2) or layer 0's q|
     python tools/variants.py build st2=-DBESO_DEV_API=1,-DBESO_FUSED_STAMPS=2 st3=-DBESO_DEV_API=1,-DBESO_FUSED_STAMPS=3
     BESO_HIP_LIB=beso_amd/lib/variants/libbeso_hip_st2.so python tools/train_stamps.py 8192 [kitchen|block_push]"""
 import collections
-import ctypes as C
 import os
 import sys
 
@@ -63,8 +62,7 @@ def main():
     lib = _lib.load()
     if not hasattr(lib, "beso_debug_set_stamps"):
         raise SystemExit("run with BESO_HIP_LIB=<a -DBESO_DEV_API=1 -DBESO_FUSED_STAMPS=2|3 build> (see the docstring)")
-    lib.beso_debug_set_stamps.restype = None
-    lib.beso_debug_set_stamps.argtypes = [C.c_void_p, C.c_int]
+    lib.beso_debug_set_stamps.restype, lib.beso_debug_set_stamps.argtypes = _lib.DEV_SIGNATURES["beso_debug_set_stamps"]
     buf = torch.zeros(8 * 2048, dtype=torch.int64, device=dev)
     for _ in range(5):
         agent.train_step(batch)
