@@ -68,7 +68,8 @@ bool make_layout(const beso_config* c, int precision, Layout* o) {
         y.w_qkv = carve(cur, e * o->Nqkv * o->Kd); y.w_proj = carve(cur, e * o->Nd * o->Kd);
         y.w_fc1 = carve(cur, e * o->Nh * o->Kd); y.w_fc2 = carve(cur, e * o->Nd * o->Kh);
     }
-    o->fused = carve(cur, precision == BESO_PREC_FP16 ? fused_packed_bytes_f16(*o, BESO_PREC_BF16) : fused_packed_bytes(*o, precision));
+    const FusedUnit fu = fused_unit(precision);
+    o->fused = carve(cur, fu.packed_bytes(*o, fu.precision));
     o->total = cur;
     return true;
 }
@@ -151,15 +152,14 @@ static int forward_generic(const Layout& lay, const Workspace& ws, const char* p
     if (fused == 2) {
         // embed -> all transformer layers -> head as ONE launch: the residual tile of 8 samples never leaves
         // the CU's registers (shapes whose head cannot be fused store x and run the head kernel)
-        const bool f16 = precision == BESO_PREC_FP16;
-        if (!((f16 ? fused_layer_edges_f16(lay) : fused_layer_edges(lay)) & 1)) {
+        const FusedUnit fu = fused_unit(precision);
+        if (!(fu.layer_edges(lay) & 1)) {
             profile_begin(BESO_SITE_EMBED, s);
             HIP_TRY(launch_embed(lay, packed, a, x, s));
             profile_end(BESO_SITE_EMBED, s);
         }
         profile_begin(BESO_SITE_FUSED_LAYER, s);
-        int st = f16 ? fused_layers_f16(lay, packed, a, x, &fused_edges, BESO_PREC_BF16, s)
-                     : fused_layers(lay, packed, a, x, &fused_edges, precision, s);
+        int st = fu.layers(lay, packed, a, x, &fused_edges, fu.precision, s, nullptr, nullptr, nullptr);
         profile_end(BESO_SITE_FUSED_LAYER, s);
         if (st != BESO_OK) return st;
     } else {
@@ -288,7 +288,8 @@ static int forward(const beso_config* cfg, const void* packed, int precision, co
         profile_end(BESO_SITE_FORWARD, s);
         return r == BESO_ERR_HIP ? record_hip_error(e, "forward_small", __LINE__) : r;
     }
-    const int level = precision == BESO_PREC_FP16 ? fused_level_f16(lay, a, BESO_PREC_BF16) : fused_level(lay, a, precision);
+    const FusedUnit fu = fused_unit(precision);
+    const int level = fu.level(lay, a, fu.precision);
     // BF16X3 / FP16 are instances of the one-launch kernel (layers_kernel) -- BF16X3 also of its block-kernel form on the
     // long-sequence shape -- and have no per-op form
     if (precision == BESO_PREC_FP16 && level != 2) return BESO_ERR_UNSUPPORTED;
@@ -312,7 +313,8 @@ static int forward_supported(const beso_config* cfg, int precision, int batch, i
     a.plan = flags & BESO_PLAN_MASK;
     if (precision == BESO_PREC_FP16) a.plan &= ~(BESO_PLAN_PER_OP | BESO_PLAN_BLOCKS);
     if (small_wanted(lay, a, precision)) return BESO_OK;
-    const int level = precision == BESO_PREC_FP16 ? fused_level_f16(lay, a, BESO_PREC_BF16) : fused_level(lay, a, precision);
+    const FusedUnit fu = fused_unit(precision);
+    const int level = fu.level(lay, a, fu.precision);
     if (precision == BESO_PREC_FP16 && level != 2) return BESO_ERR_UNSUPPORTED;
     if (precision == BESO_PREC_BF16X3 && level != 2 && !(level == 1 && fused_has_lin_blocks(lay, precision))) return BESO_ERR_UNSUPPORTED;
     return BESO_OK;
@@ -544,10 +546,10 @@ static int run_plan(const SampleCall& c, const Plan& p) {
     float* d1 = (float*)(wsp + c.ws.d1);
     float* sig = (float*)(wsp + c.ws.sig);
     const size_t n = (size_t)c.batch * c.t * c.lay.act;
-    const bool f16 = c.precision == BESO_PREC_FP16;
+    const FusedUnit fu = fused_unit(c.precision);
     if (c.trace_x) HIP_TRY(hipMemcpyAsync(c.trace_x, c.x, n * sizeof(float), hipMemcpyDeviceToDevice, c.s));
     if (!(c.flags & BESO_SAMPLE_STEPWISE) && !small_wanted(c.lay, c.a, c.precision) &&
-        (f16 ? fused_can_loop_f16(c.lay, c.a, BESO_PREC_BF16) : fused_can_loop(c.lay, c.a, c.precision))) {
+        fu.can_loop(c.lay, c.a, fu.precision)) {
         FwdArgs a = c.a;
         a.aux = c.history ? c.history : d1;
         const size_t n_steps = p.first.size() - 1;
@@ -567,8 +569,8 @@ static int run_plan(const SampleCall& c, const Plan& p) {
             // (slab i0 + 1 of trace_x is x behind the launch's first step, slab i0 of trace_den that step's denoised value)
             const SampleTrace TR{c.trace_x ? c.trace_x + (i0 + 1) * n : nullptr, c.trace_den ? c.trace_den + i0 * n : nullptr};
             profile_begin(BESO_SITE_FUSED_LAYER, c.s);
-            const int st = f16 ? fused_layers_f16(c.lay, (const char*)c.packed, a, (float*)(wsp + c.ws.x), nullptr, BESO_PREC_BF16, c.s, &S, &X3, &TR)
-                               : fused_layers(c.lay, (const char*)c.packed, a, (float*)(wsp + c.ws.x), nullptr, c.precision, c.s, &S, &X3, &TR);
+            const int st = fu.layers(c.lay, (const char*)c.packed, a, (float*)(wsp + c.ws.x), nullptr, fu.precision, c.s, &S, &X3,
+                                     &TR);
             profile_end(BESO_SITE_FUSED_LAYER, c.s);
             if (st != BESO_OK) return st;
         }
@@ -717,8 +719,8 @@ int beso_pack_weights(const beso_config* cfg, const float* const* p, int n_param
 #undef PACK32
 #undef PACKW
     if (i != n_params) return BESO_ERR_BAD_ARG;
-    if (precision == BESO_PREC_FP16) return fused_pack_f16(lay, p, pk, BESO_PREC_BF16, s);
-    return fused_pack(lay, p, pk, precision, s);
+    const FusedUnit fu = fused_unit(precision);
+    return fu.pack(lay, p, pk, fu.precision, s);
 }
 
 size_t beso_workspace_bytes(const beso_config* cfg, int batch, int t, int precision, int cfg_guidance) {

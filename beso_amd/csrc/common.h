@@ -344,6 +344,14 @@ template <auto Kernel, typename... Args>
 hipError_t launch_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
     return launch_lds_attr<Kernel>(lds_bytes, grid, block, lds_bytes, s, args...);
 }
+// ... and of a kernel without dynamic LDS: clear the last error -> launch -> the launch's error.
+template <auto Kernel, typename... Args>
+hipError_t launch_plain(dim3 grid, dim3 block, hipStream_t s, const Args&... args) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(Kernel, grid, block, 0, s, args...);
+    return hipGetLastError();
+}
+inline int to_status(hipError_t e) { return e == hipSuccess ? BESO_OK : BESO_ERR_HIP; }
 
 // ---- kernel launchers (each enqueues on `s`, returns hipError_t) -------------------------------
 struct FwdArgs {

@@ -32,8 +32,7 @@ int    fused_pack(const Layout& lay, const float* const* params, char* packed, i
 int    fused_level(const Layout& lay, const FwdArgs& a, int precision);   // 0 none, 1 MLP block, 2 whole layers
 int    fused_layer_edges(const Layout& lay);        // bit 0: fused_layers embeds, bit 1: it runs the head
 int    fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,
-                    hipStream_t s, const SampleSteps* steps = nullptr, const SampleExtra* extra = nullptr,
-                    const SampleTrace* trace = nullptr);
+                    hipStream_t s, const SampleSteps* steps, const SampleExtra* extra, const SampleTrace* trace);   // (each may be null)
 bool   fused_can_loop(const Layout& lay, const FwdArgs& a, int precision);   // the whole sampler loop can run inside one launch
 int    fused_mlp_block(const Layout& lay, const char* packed, int layer, float* x, int M, hipStream_t s);
 bool   fused_has_lin_blocks(const Layout& lay, int precision);
@@ -99,8 +98,20 @@ int    fused_pack_f16(const Layout& lay, const float* const* params, char* packe
 int    fused_level_f16(const Layout& lay, const FwdArgs& a, int precision);
 int    fused_layer_edges_f16(const Layout& lay);
 int    fused_layers_f16(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,
-                        hipStream_t s, const SampleSteps* steps = nullptr, const SampleExtra* extra = nullptr,
-                        const SampleTrace* trace = nullptr);
+                        hipStream_t s, const SampleSteps* steps, const SampleExtra* extra, const SampleTrace* trace);
 bool   fused_can_loop_f16(const Layout& lay, const FwdArgs& a, int precision);
+
+// The unit that serves a precision: its six entry points, and the precision value to pass them.
+struct FusedUnit {
+    decltype(&fused_packed_bytes) packed_bytes; decltype(&fused_pack) pack; decltype(&fused_level) level;
+    decltype(&fused_layer_edges) layer_edges; decltype(&fused_layers) layers; decltype(&fused_can_loop) can_loop;
+    int precision;
+};
+inline FusedUnit fused_unit(int precision) {
+    if (precision == BESO_PREC_FP16)
+        return {fused_packed_bytes_f16, fused_pack_f16, fused_level_f16, fused_layer_edges_f16, fused_layers_f16, fused_can_loop_f16,
+                BESO_PREC_BF16};
+    return {fused_packed_bytes, fused_pack, fused_level, fused_layer_edges, fused_layers, fused_can_loop, precision};
+}
 
 }  // namespace beso

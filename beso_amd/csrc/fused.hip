@@ -175,10 +175,41 @@ bool fused_dims(const Layout& lay, FusedDims* d) {
 // (KS = 12: D = 360 and KS = 8: D = 240 qualify; the KS = 16 instance serves D = 512, a full tail.)
 constexpr bool kt16(int KS) { return KS == 12 || KS == 8; }
 
+// The shipped shapes, spelled out here only: RPW row tiles per wave, KS k-steps of K = D, HG heads per virtual head, NTL
+// action-token tiles of the last layer, PFA k-steps of weight fragments in flight per wave of the backward (0: none).
+template <int RPW_, int KS_, int HG_, int NTL_, int PFA_>
+struct Shape { static constexpr int RPW = RPW_, KS = KS_, HG = HG_, NTL = NTL_, PFA = PFA_; };
+using Kitchen = Shape<3, 12, 1, 2, 6>;              // D = 360: 8 samples x 4 action tokens
+using BlockPush = Shape<2, 8, 3, 4, 4>;             // D = 240: 8 x 5
+using LongHorizon = Shape<4, 16, 1, kLongNT, 0>;    // D = 512: one sample of up to 16 kLongNT tokens per workgroup
+// (bits: a set of classes is a mask)
+enum ShapeClass : unsigned { kNoShape = 0, kKitchen = 1, kBlockPush = 2, kLongHorizon = 4, kShortShapes = 3, kAnyShape = 7 };
+
+// by rows: (RPW, KS) alone -- what the GEMM phases (MLP / tail / lin blocks, the training tail and backward) depend on
+template <typename S>
+constexpr bool has_rows(const FusedDims& d) { return d.RPW == S::RPW && d.KS == S::KS; }
+constexpr ShapeClass rows_class(const FusedDims& d) {
+    return has_rows<Kitchen>(d) ? kKitchen : has_rows<BlockPush>(d) ? kBlockPush : has_rows<LongHorizon>(d) ? kLongHorizon : kNoShape;
+}
+// by full instance: rows and the head grouping -- what the kernels with the attention phase inside depend on
+constexpr ShapeClass instance_class(const FusedDims& d) {
+    const ShapeClass c = rows_class(d);
+    const int hg = c == kKitchen ? Kitchen::HG : c == kBlockPush ? BlockPush::HG : LongHorizon::HG;
+    return d.HG == hg ? c : kNoShape;
+}
+// f(record) of class c, or `none` where c is not among Allowed (whose other records f is never instantiated with)
+template <unsigned Allowed, typename R, typename F>
+R with_shape(ShapeClass c, R none, F&& f) {
+    if constexpr ((Allowed & kKitchen) != 0) if (c == kKitchen) return f(Kitchen{});
+    if constexpr ((Allowed & kBlockPush) != 0) if (c == kBlockPush) return f(BlockPush{});
+    if constexpr ((Allowed & kLongHorizon) != 0) if (c == kLongHorizon) return f(LongHorizon{});
+    return none;
+}
+
 bool shape_has_kernel(const FusedDims& d) {
-    // instantiated (RPW, KS): kitchen D=360 -> (3, 12); block-push D=240 -> (2, 8); long-horizon D=512 -> (4, 16), MLP block only
+    // kitchen D=360, block-push D=240; long-horizon D=512: MLP block only
     if (kt16(d.KS) && d.D > 32 * (d.KS - 1) + 16) return false;
-    return (d.RPW == 3 && d.KS == 12) || (d.RPW == 2 && d.KS == 8) || (d.RPW == 4 && d.KS == 16);
+    return rows_class(d) != kNoShape;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3161,7 +3192,7 @@ struct SigHdr { uint32_t next, pad[3]; uint32_t tag[kSigEntries]; };
 static_assert(sizeof(SigHdr) <= kSigHdrBytes && (kSigEntries & (kSigEntries - 1)) == 0, "sigma cache header");
 struct SigArgs { uint32_t* cache; uint32_t* flag; };      // the image's cache; the call's flag word (its workspace)
 __host__ __device__ inline int sig_entry_bytes(const FusedDims& d) { return d.L * 2 * d.KS * 32 * 2; }
-__host__ __device__ inline bool sig_shape(const FusedDims& d) { return d.attn && d.RPW == 3 && d.KS == 12 && d.HG == 1 && d.head_fused; }
+__host__ __device__ inline bool sig_shape(const FusedDims& d) { return d.attn && instance_class(d) == kKitchen && d.head_fused; }
 inline size_t sig_cache_offset(const FusedDims& d) { return ((size_t)d.layer_bytes * d.L + d.global_bytes + 255) / 256 * 256; }
 inline size_t sig_cache_bytes(const FusedDims& d) { return kSigHdrBytes + (size_t)kSigEntries * sig_entry_bytes(d); }
 
@@ -4124,68 +4155,44 @@ constexpr unsigned long long* g_stamps = nullptr;
 constexpr int g_stamps_cap = 0;
 #endif
 
-template <int RPW, int KS, int NW>
-hipError_t launch_mlp_block(float* x, const char* lw, const FusedDims& d, int M, hipStream_t s) {
-    constexpr LdsMap L = lds_map(KS, true);
-    return launch_lds<mlp_block_kernel<RPW, KS, NW>>(dim3((M + kMT - 1) / kMT), dim3(64 * NW), L.total, s, x, lw, d, M, g_stamps,
-                                                     g_stamps_cap);
-}
-
-template <int RPW, int KS>
-hipError_t launch_lin_blocks(int which, float* x, const char* lw, const FusedDims& d, int M, void* buf, int ld, hipStream_t s) {
-    constexpr LdsMap L = lds_map(KS, true);
-    const dim3 grid((M + kMT - 1) / kMT), block(512);
-    if (which == 0)
-        return launch_lds<qkv_block_kernel<RPW, KS>>(grid, block, L.total, s, (const float*)x, lw, d, M, (uint16_t*)buf, g_stamps,
-                                                     g_stamps_cap);
-    return launch_lds<proj_block_kernel<RPW, KS>>(grid, block, L.total, s, x, lw, d, M, (const uint16_t*)buf, ld, g_stamps,
-                                                  g_stamps_cap);
-}
-
-template <int RPW, int KS>
-hipError_t launch_tail_block(float* x, const char* lw, const char* lw_next, const FusedDims& d, int M, const void* y, int ld_y,
-                             void* qkv, hipStream_t s) {
-    constexpr LdsMap L = lds_map(KS, true);
-    return launch_lds<tail_block_kernel<RPW, KS>>(dim3((M + kMT - 1) / kMT), dim3(512), L.total, s, x, lw, lw_next, d, M,
-                                                  (const uint16_t*)y, ld_y, (uint16_t*)qkv, g_stamps, g_stamps_cap);
-}
+// What one call brings to the layers_kernel launch path (fused_layers assembles it): the kernel's arguments, the precision and
+// plan hint the selection reads, the stream.  The levels below add only what each decides itself.
+struct LayersCall {
+    float* x; const char* lw0; const FusedDims& d; int l0, l1, n_samples, Tn;
+    EdgeArgs edge; const SampleSteps& steps; const SampleExtra& extra; SampleTrace trace;
+    SigArgs sig;                   // the sigma-token cache: only the SIG instances are handed it
+    int precision, plan; hipStream_t s;
+};
 
 // One instance of layers_kernel (LOOP = 1: the sampler-loop form, steps.n evaluations).
-template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int PX, int CORE, int LOOP, int SIG = 0>
-hipError_t launch_instance(size_t lds_bytes, int grid, float* x, const char* lw0, const FusedDims& d, int l0, int l1,
-                           int n_samples, int Tn, const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, hipStream_t s,
-                           const SigArgs& sig = SigArgs{nullptr, nullptr}) {
-    return launch_lds<layers_kernel<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, LOOP, SIG>>(dim3(grid), dim3(512), lds_bytes, s, x, lw0, d, l0, l1,
-                                                                                      n_samples, Tn, edge, steps, g_stamps, g_stamps_cap, extra, trace, sig);
+template <typename S, int NTL, int SPW, int NTA, int PX, int CORE, int LOOP, int SIG = 0>
+hipError_t launch_instance(const LayersCall& c, size_t lds_bytes, int grid) {
+    return launch_lds<layers_kernel<S::RPW, S::KS, S::HG, NTL, SPW, NTA, PX, CORE, LOOP, SIG>>(
+        dim3(grid), dim3(512), lds_bytes, c.s, c.x, c.lw0, c.d, c.l0, c.l1, c.n_samples, c.Tn, c.edge, c.steps, g_stamps,
+        g_stamps_cap, c.extra, c.trace, SIG != 0 ? c.sig : SigArgs{nullptr, nullptr});
 }
 
 // The eight-sample forward of the kitchen-class shape with the sigma token shared where the batch's sigma is one value: the
 // pre-pass, the five-tile instance and the six-tile instance, enqueued back to back -- the flag word the pre-pass writes
 // decides on the device which of the two does the work (no copy to the host, no synchronisation).
-template <int RPW, int KS, int HG, int NTL>
-hipError_t launch_sigma_shared(size_t lds_bytes, float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                               const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace,
-                               const SigArgs& sig, hipStream_t s) {
+template <typename S>
+hipError_t launch_sigma_shared(const LayersCall& c, size_t lds_bytes) {
     constexpr int kSmallSPW = 2, kSmallNT = 2, kSigNT = kNTT - 1;
-    const int grid = (n_samples + kSPW - 1) / kSPW;
-    EdgeArgs lone = edge;          // the pre-pass's sample: the sigma token alone (sigma[0 .. B) is what it reads of the call)
-    lone.t = 0; lone.two = 0; lone.uncond_all = 0;
-    hipError_t err = launch_instance<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 0, 0, 0, 3>(lds_bytes, 1, x, lw0, d, l0, l1, 1, 1, lone, steps,
-                                                                                       extra, trace, s, sig);
+    const int grid = (c.n_samples + kSPW - 1) / kSPW;
+    LayersCall lone = c;           // the pre-pass's sample: the sigma token alone (sigma[0 .. B) is what it reads of the call)
+    lone.n_samples = 1; lone.Tn = 1;
+    lone.edge.t = 0; lone.edge.two = 0; lone.edge.uncond_all = 0;
+    hipError_t err = launch_instance<S, S::NTL, kSmallSPW, kSmallNT, 0, 0, 0, 3>(lone, lds_bytes, 1);
     if (err != hipSuccess) return err;
-    err = launch_instance<RPW, KS, HG, NTL, kSPW, kSigNT, 0, 0, 0, 2>(lds_bytes + sig_entry_bytes(d), grid, x, lw0, d, l0, l1, n_samples, Tn,
-                                                                     edge, steps, extra, trace, s, sig);
+    err = launch_instance<S, S::NTL, kSPW, kSigNT, 0, 0, 0, 2>(c, lds_bytes + sig_entry_bytes(c.d), grid);
     if (err != hipSuccess) return err;
-    return launch_instance<RPW, KS, HG, NTL, kSPW, kNTT, 0, 0, 0, 1>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra,
-                                                                    trace, s, sig);
+    return launch_instance<S, S::NTL, kSPW, kNTT, 0, 0, 0, 1>(c, lds_bytes, grid);
 }
-template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int PX, int CORE>
-hipError_t launch_either(size_t lds_bytes, float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, hipStream_t s) {
-    const int grid = (n_samples + SPW - 1) / SPW;
-    if (steps.n > 0)
-        return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 1>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
-    return launch_instance<RPW, KS, HG, NTL, SPW, NTA, PX, CORE, 0>(lds_bytes, grid, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
+template <typename S, int NTL, int SPW, int NTA, int PX, int CORE>
+hipError_t launch_either(const LayersCall& c, size_t lds_bytes) {
+    const int grid = (c.n_samples + SPW - 1) / SPW;
+    if (c.steps.n > 0) return launch_instance<S, NTL, SPW, NTA, PX, CORE, 1>(c, lds_bytes, grid);
+    return launch_instance<S, NTL, SPW, NTA, PX, CORE, 0>(c, lds_bytes, grid);
 }
 
 // samples of Tn tokens in NT token tiles: the tokens, and the last sample's 16-row attention window, must fit
@@ -4199,16 +4206,16 @@ constexpr int kSmallBatchMax = 512;    // batches up to this size take the two-s
 
 // Which instance of layers_kernel a call runs: by batch size, or as the call's BESO_PLAN_SPW* hint says where the shape allows
 // it (the instances compute the same per-sample arithmetic -- equal bits --, so the hint is a performance / test knob only).
-template <int RPW, int KS, int HG, int NTL>
-hipError_t launch_layers(float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                         const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, int precision, int plan, hipStream_t s,
-                         const SigArgs& sig) {
-    constexpr LdsMap L = lds_map(KS);
+template <typename S>
+hipError_t launch_layers(const LayersCall& c) {
+    constexpr int NTL = S::NTL;
+    constexpr LdsMap L = lds_map(S::KS);
     constexpr int kSmallSPW = 2, kSmallNT = 2, kMidSPW = 4, kMidNT = 4;
+    const int n_samples = c.n_samples, Tn = c.Tn, plan = c.plan;
     const int want = plan & BESO_PLAN_SPW_MASK;
     const bool small_ok = tiles_hold_exact(kSmallSPW, Tn, kSmallNT);
 #if !BESO_OPERAND_F16
-    if (precision == BESO_PREC_BF16X3) {
+    if (c.precision == BESO_PREC_BF16X3) {
         // The split-bf16 instances keep both halves of every activation fragment in LDS, which bounds the token tiles per
         // workgroup at three (145 KiB; four would need 182 KiB).  Every workgroup streams BOTH weight images (40 MB, kitchen):
         // samples per weight byte is what sets this mode's speed, so batches beyond one workgroup of two samples per CU take
@@ -4220,18 +4227,16 @@ hipError_t launch_layers(float* x, const char* lw0, const FusedDims& d, int l0, 
         constexpr int kX3SPW = 4, kX3NT = 3, kX3NTL = (NTL + 1) / 2;
         const bool four_ok = tiles_hold(kX3SPW, Tn, kX3NT);
         if (four_ok && (want == BESO_PLAN_SPW4 || (want != BESO_PLAN_SPW2 && n_samples > kSmallBatchMax) || !small_ok)) {
-            constexpr LdsMapX3 X = lds_map_x3(KS, kX3NT);
+            constexpr LdsMapX3 X = lds_map_x3(S::KS, kX3NT);
             static_assert(X.total <= 160 * 1024, "LDS of the four-sample split-bf16 instance");
-            return launch_either<RPW, KS, HG, kX3NTL, kX3SPW, kX3NT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
+            return launch_either<S, kX3NTL, kX3SPW, kX3NT, 1, 0>(c, X.total);
         }
         if (!small_ok) return hipErrorInvalidValue;
-        constexpr LdsMapX3 X = lds_map_x3(KS, kSmallNT);
-        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 1, 0>(X.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
+        constexpr LdsMapX3 X = lds_map_x3(S::KS, kSmallNT);
+        return launch_either<S, NTL, kSmallSPW, kSmallNT, 1, 0>(c, X.total);
     }
 #endif
     const bool mid_ok = tiles_hold_exact(kMidSPW, Tn, kMidNT);
-    // the sigma token shared (kitchen-class shape, one forward, the eight-sample plan -- BESO_PLAN_SIGMA_SHARED: at any batch
-    // size; BESO_PLAN_SIGMA_PRIVATE: never): the device decides between the five- and the six-tile instance
     // samples per workgroup of this call, chosen ONCE: the latency instances where the samples' tokens and the last sample's
     // 16-row attention window fit their token tiles (two samples up to kSmallBatchMax, four -- one workgroup per CU, two thirds
     // of the throughput instance's work per workgroup -- up to twice that, or as the hint says), eight otherwise
@@ -4242,30 +4247,27 @@ hipError_t launch_layers(float* x, const char* lw0, const FusedDims& d, int l0, 
     // Tn - 1 tokens of eight samples must fill no more than the five token tiles, and the natural q/k/v rows -- Tn per sample,
     // the last sample's 16-row window, the eight zeroed V rows behind the last sample -- must fit the rows LDS holds; a
     // window that does not (Tn = 12: 88 slots) takes the six-tile instance as before.
-    if constexpr (RPW == 3 && KS == 12 && HG == 1) {
+    if constexpr (std::is_same_v<S, Kitchen>) {
         constexpr int kSigNT = kNTT - 1;
         const bool fits = kSPW * (Tn - 1) <= 16 * kSigNT && (kSPW - 1) * Tn + 16 <= kQKVRows && kSPW * Tn + 8 <= kQKVRows;
-        if ((spw == kSPW || (plan & BESO_PLAN_SIGMA_SHARED)) && fits && sig.cache && sig.flag && steps.n == 0 &&
-            !(plan & BESO_PLAN_SIGMA_PRIVATE) && sig_shape(d) && edge.t >= 1 && l0 == 0 && l1 == d.L) {
+        if ((spw == kSPW || (plan & BESO_PLAN_SIGMA_SHARED)) && fits && c.sig.cache && c.sig.flag && c.steps.n == 0 &&
+            !(plan & BESO_PLAN_SIGMA_PRIVATE) && sig_shape(c.d) && c.edge.t >= 1 && c.l0 == 0 && c.l1 == c.d.L) {
             static_assert(L.total + 16 * 1024 <= 160 * 1024, "LDS of the five-tile instance: the map plus a staged cache entry");
-            if (sig_entry_bytes(d) > 16 * 1024) return hipErrorInvalidValue;
-            return launch_sigma_shared<RPW, KS, HG, NTL>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, sig, s);
+            if (sig_entry_bytes(c.d) > 16 * 1024) return hipErrorInvalidValue;
+            return launch_sigma_shared<S>(c, L.total);
         }
     }
-    if (spw == kSmallSPW)
-        return launch_either<RPW, KS, HG, NTL, kSmallSPW, kSmallNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
-    if (spw == kMidSPW)
-        return launch_either<RPW, KS, HG, NTL, kMidSPW, kMidNT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
-    return launch_either<RPW, KS, HG, NTL, kSPW, kNTT, 0, 0>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
+    if (spw == kSmallSPW) return launch_either<S, NTL, kSmallSPW, kSmallNT, 0, 0>(c, L.total);
+    if (spw == kMidSPW) return launch_either<S, NTL, kMidSPW, kMidNT, 0, 0>(c, L.total);
+    return launch_either<S, NTL, kSPW, kNTT, 0, 0>(c, L.total);
 }
 
-// The long-sequence instance: one sample (Tn <= 16 NT tokens) per workgroup.
-template <int RPW, int KS, int NT>
-hipError_t launch_layers_long(float* x, const char* lw0, const FusedDims& d, int l0, int l1, int n_samples, int Tn,
-                              const EdgeArgs& edge, const SampleSteps& steps, const SampleExtra& extra, const SampleTrace& trace, hipStream_t s) {
-    constexpr LdsMap L = lds_map(KS, false, NT);
-    static_assert(L.total <= 160 * 1024, "LDS of the long-sequence instance");
-    return launch_either<RPW, KS, 1, NT, 1, NT, 0, 1>(L.total, x, lw0, d, l0, l1, n_samples, Tn, edge, steps, extra, trace, s);
+// The long-sequence instance: one sample (Tn <= 16 NTL tokens) per workgroup.
+template <typename S>
+hipError_t launch_layers_long(const LayersCall& c) {
+    constexpr LdsMap L = lds_map(S::KS, false, S::NTL);
+    static_assert(S::HG == 1 && L.total <= 160 * 1024, "LDS of the long-sequence instance");
+    return launch_either<S, S::NTL, 1, S::NTL, 0, 1>(c, L.total);
 }
 
 }  // namespace
@@ -4273,11 +4275,15 @@ hipError_t launch_layers_long(float* x, const char* lw0, const FusedDims& d, int
 // ---------------------------------------------------------------------------------------------
 static bool x3_shape(const FusedDims& d) {
     // BF16X3 as an instance of layers_kernel: the shipped shapes with the fused attention phase
-    return d.attn && !d.seq1 && ((d.RPW == 3 && d.KS == 12 && d.HG == 1) || (d.RPW == 2 && d.KS == 8 && d.HG == 3));
+    return d.attn && !d.seq1 && (instance_class(d) & kShortShapes) != 0;
+}
+// the shape of the lin blocks (fused_has_lin_blocks): no fused attention phase or the long form of it, full long-horizon rows
+static bool lin_blocks_shape(const FusedDims& d) {
+    return d.lin && rows_class(d) == kLongHorizon && d.D == 16 * kWaves * d.RPW;
 }
 static bool x3_long_shape(const FusedDims& d) {
     // ... and as the split-bf16 block kernels (lin_block_x3_kernel + the fp32 attention kernel) for the long-sequence shape
-    return d.seq1 && d.lin && d.RPW == 4 && d.KS == 16 && d.D == 16 * kWaves * d.RPW;
+    return d.seq1 && lin_blocks_shape(d);
 }
 
 size_t fused_packed_bytes(const Layout& lay, int precision) {
@@ -4288,14 +4294,16 @@ size_t fused_packed_bytes(const Layout& lay, int precision) {
     return sig_shape(d) ? sig_cache_offset(d) + sig_cache_bytes(d) : (size_t)d.layer_bytes * lay.L + d.global_bytes;
 }
 
-
 #define FTRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return BESO_ERR_HIP; } while (0)
+// one launch of a pack kernel (256 threads per workgroup); a launch that fails ends the call there
+#define FPACK(kernel, grid, ...) FTRY(launch_plain<kernel>(dim3(grid), dim3(256), s, __VA_ARGS__))
 
 int fused_pack(const Layout& lay, const float* const* p, char* packed, int precision, hipStream_t s) {
     FusedDims d;
     if ((precision != BESO_PREC_BF16 && precision != BESO_PREC_BF16X3) || !fused_dims(lay, &d) || !shape_has_kernel(d)) return BESO_OK;
     if (precision == BESO_PREC_BF16X3 && !x3_shape(d) && !x3_long_shape(d)) return BESO_ERR_UNSUPPORTED;
     const int D = lay.D;
+    const float* const no_scale = nullptr;
     const int n_parts = precision == BESO_PREC_BF16X3 ? 2 : 1;
     // a new image: every entry of its sigma-token cache is free (tags 0; the entries themselves, so that no byte of the image
     // is left as it was found)
@@ -4311,47 +4319,32 @@ int fused_pack(const Layout& lay, const float* const* p, char* packed, int preci
         const float *f1w = q[12], *f1b = q[13], *f2w = q[14], *f2b = q[15];
         char* base = packed + lay.fused + (size_t)l * d.layer_bytes + (half ? (size_t)d.x3_delta : 0);
         const int rt1 = d.NCH * kChunkTiles, rt2 = d.RPW * kWaves;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(pack_mfma_a_kernel, dim3(1024), dim3(256), 0, s, f1w, 4 * D, D, ln2w, (uint16_t*)base, rt1,
-                           d.KS, kChunkTiles, half);
-        hipLaunchKernelGGL(pack_mfma_a_kernel, dim3(1024), dim3(256), 0, s, f2w, D, 4 * D, (const float*)nullptr,
-                           (uint16_t*)(base + d.o_w2), rt2, d.KS2p, rt2, half);
+        FPACK(pack_mfma_a_kernel, 1024, f1w, 4 * D, D, ln2w, (uint16_t*)base, rt1, d.KS, kChunkTiles, half);
+        FPACK(pack_mfma_a_kernel, 1024, f2w, D, 4 * D, no_scale, (uint16_t*)(base + d.o_w2), rt2, d.KS2p, rt2, half);
         if (d.attn) {
-            hipLaunchKernelGGL(pack_qkv_kernel, dim3(1024), dim3(256), 0, s, qw, kw, vw, ln1w,
-                               (uint16_t*)(base + d.o_wqkv), D, d.Hv, d.hdv, d.KS, half);
-            hipLaunchKernelGGL(pack_proj_kernel, dim3(512), dim3(256), 0, s, pw, (uint16_t*)(base + d.o_wproj), D, d.Hv,
-                               d.hdv, rt2, half);
+            FPACK(pack_qkv_kernel, 1024, qw, kw, vw, ln1w, (uint16_t*)(base + d.o_wqkv), D, d.Hv, d.hdv, d.KS, half);
+            FPACK(pack_proj_kernel, 512, pw, (uint16_t*)(base + d.o_wproj), D, d.Hv, d.hdv, rt2, half);
         }
+        const float* ws3[3] = {qw, kw, vw};
         if (d.lin) {
-            const float* ws3[3] = {qw, kw, vw};
             for (int part = 0; part < 3; ++part)      // q / k / v in natural row order (block kernels)
-                hipLaunchKernelGGL(pack_mfma_a_kernel, dim3(1024), dim3(256), 0, s, ws3[part], D, D, ln1w,
-                                   (uint16_t*)(base + d.o_wqkv_lin + (size_t)part * d.part_bytes), rt2, d.KS, rt2, half);
-            hipLaunchKernelGGL(pack_mfma_a_kernel, dim3(1024), dim3(256), 0, s, pw, D, D, (const float*)nullptr,
-                               (uint16_t*)(base + d.o_wproj_lin), rt2, d.KS, rt2, half);
+                FPACK(pack_mfma_a_kernel, 1024, ws3[part], D, D, ln1w,
+                      (uint16_t*)(base + d.o_wqkv_lin + (size_t)part * d.part_bytes), rt2, d.KS, rt2, half);
+            FPACK(pack_mfma_a_kernel, 1024, pw, D, D, no_scale, (uint16_t*)(base + d.o_wproj_lin), rt2, d.KS, rt2, half);
         }
-        FTRY(hipGetLastError());
         if (half) continue;                      // the low image holds weight fragments only
-        hipLaunchKernelGGL(fold_bias_kernel, dim3((rt1 * 16 + 3) / 4), dim3(256), 0, s, f1w, f1b, ln2b,
-                           (float*)(base + d.o_b1), 4 * D, D, rt1 * 16);
-        FTRY(hipGetLastError());
+        FPACK(fold_bias_kernel, (rt1 * 16 + 3) / 4, f1w, f1b, ln2b, (float*)(base + d.o_b1), 4 * D, D, rt1 * 16);
         FTRY(launch_pack_matrix(f2b, 1, D, base + d.o_b2, 1, rt2 * 16, -1, s));
         if (d.attn) {
-            (void)hipGetLastError();
-            hipLaunchKernelGGL(fold_qkv_bias_kernel, dim3((d.Hv * 3 * kHDP + 3) / 4), dim3(256), 0, s, qw, kw, vw,
-                               qb, kb, vb, ln1b, (float*)(base + d.o_bqkv), D, d.Hv, d.hdv);
-            FTRY(hipGetLastError());
+            FPACK(fold_qkv_bias_kernel, (d.Hv * 3 * kHDP + 3) / 4, qw, kw, vw, qb, kb, vb, ln1b, (float*)(base + d.o_bqkv), D,
+                  d.Hv, d.hdv);
             FTRY(launch_pack_matrix(pb, 1, D, base + d.o_bproj, 1, rt2 * 16, -1, s));
         }
         if (d.lin) {
-            const float* ws3[3] = {qw, kw, vw};
             const float* bs3[3] = {qb, kb, vb};
-            (void)hipGetLastError();
-            for (int part = 0; part < 3; ++part) {      // q / k / v
-                hipLaunchKernelGGL(fold_bias_kernel, dim3((rt2 * 16 + 3) / 4), dim3(256), 0, s, ws3[part], bs3[part], ln1b,
-                                   (float*)(base + d.o_bqkv_lin) + (size_t)part * rt2 * 16, D, D, rt2 * 16);
-            }
-            FTRY(hipGetLastError());
+            for (int part = 0; part < 3; ++part)      // q / k / v
+                FPACK(fold_bias_kernel, (rt2 * 16 + 3) / 4, ws3[part], bs3[part], ln1b,
+                      (float*)(base + d.o_bqkv_lin) + (size_t)part * rt2 * 16, D, D, rt2 * 16);
             FTRY(launch_pack_matrix(pb, 1, D, base + d.o_bproj_lin, 1, rt2 * 16, -1, s));
         }
     }
@@ -4362,36 +4355,28 @@ int fused_pack(const Layout& lay, const float* const* p, char* packed, int preci
         const float* const* tail = p + 3 + 16 * lay.L;
         const float *pos = p[0], *tokw = p[1], *tokb = p[2];
         const float *lnfw = tail[0], *lnfb = tail[1], *sigw = tail[2], *sigb = tail[3], *actw = tail[4], *actb = tail[5];
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(transpose_pad_kernel, dim3((lay.obs * d.Dp + 255) / 256), dim3(256), 0, s, tokw, D, lay.obs,
-                           (float*)(gw + d.g_tokT), d.Dp);
-        hipLaunchKernelGGL(transpose_pad_kernel, dim3((lay.act * d.Dp + 255) / 256), dim3(256), 0, s, actw, D, lay.act,
-                           (float*)(gw + d.g_actT), d.Dp);
-        {
-            // split-bf16 A fragments of the two embedding matrices ([D][obs], [D][act]: one k-step each)
-            const int rt2 = d.RPW * kWaves;
-            for (int half = 0; half < 2; ++half) {
-                hipLaunchKernelGGL(pack_mfma_a_kernel, dim3(32), dim3(256), 0, s, tokw, D, lay.obs, (const float*)nullptr,
-                                   (uint16_t*)(gw + d.g_tokA + (size_t)half * rt2 * 1024), rt2, 1, rt2, half);
-                hipLaunchKernelGGL(pack_mfma_a_kernel, dim3(32), dim3(256), 0, s, actw, D, lay.act, (const float*)nullptr,
-                                   (uint16_t*)(gw + d.g_actA + (size_t)half * rt2 * 1024), rt2, 1, rt2, half);
-            }
+        FPACK(transpose_pad_kernel, (lay.obs * d.Dp + 255) / 256, tokw, D, lay.obs, (float*)(gw + d.g_tokT), d.Dp);
+        FPACK(transpose_pad_kernel, (lay.act * d.Dp + 255) / 256, actw, D, lay.act, (float*)(gw + d.g_actT), d.Dp);
+        // split-bf16 A fragments of the two embedding matrices ([D][obs], [D][act]: one k-step each)
+        const int rt2 = d.RPW * kWaves;
+        for (int half = 0; half < 2; ++half) {
+            FPACK(pack_mfma_a_kernel, 32, tokw, D, lay.obs, no_scale, (uint16_t*)(gw + d.g_tokA + (size_t)half * rt2 * 1024),
+                  rt2, 1, rt2, half);
+            FPACK(pack_mfma_a_kernel, 32, actw, D, lay.act, no_scale, (uint16_t*)(gw + d.g_actA + (size_t)half * rt2 * 1024),
+                  rt2, 1, rt2, half);
         }
-        FTRY(hipGetLastError());
         FTRY(launch_pack_matrix(tokb, 1, D, gw + d.g_tokb, 1, d.Dp, -1, s));
         FTRY(launch_pack_matrix(actb, 1, D, gw + d.g_actb, 1, d.Dp, -1, s));
         FTRY(launch_pack_matrix(sigw, 1, D, gw + d.g_sigw, 1, d.Dp, -1, s));
         FTRY(launch_pack_matrix(sigb, 1, D, gw + d.g_sigb, 1, d.Dp, -1, s));
         FTRY(launch_pack_matrix(pos, lay.seq_size, D, gw + d.g_pos, lay.seq_size, d.Dp, -1, s));
-        if (d.head_fused) {
-            (void)hipGetLastError();
-            hipLaunchKernelGGL(pack_head_kernel, dim3((16 * d.Dp + 255) / 256), dim3(256), 0, s, tail[6], tail[7], lnfw,
-                               lnfb, (float*)(gw + d.g_headw), (float*)(gw + d.g_headb), lay.act, D, d.Dp);
-            FTRY(hipGetLastError());
-        }
+        if (d.head_fused)
+            FPACK(pack_head_kernel, (16 * d.Dp + 255) / 256, tail[6], tail[7], lnfw, lnfb, (float*)(gw + d.g_headw),
+                  (float*)(gw + d.g_headb), lay.act, D, d.Dp);
     }
     return BESO_OK;
 }
+#undef FPACK
 
 // 0: no fused kernel, 1: MLP block / tail block kernels, 2: the whole network in one launch.  The call's plan hint caps it
 // (BESO_PLAN_PER_OP: 0, BESO_PLAN_BLOCKS: 1): the per-op kernels are the parity reference of the fused ones in the same
@@ -4420,13 +4405,11 @@ int fused_mlp_block(const Layout& lay, const char* packed, int layer, float* x, 
     FusedDims d;
     if (!fused_dims(lay, &d)) return BESO_ERR_UNSUPPORTED;
     const char* base = packed + lay.fused + (size_t)layer * d.layer_bytes;
-    hipError_t e;
     // (a 4-wave, 512-VGPR instance <6, 12, 4> of the same phase code was measured no faster than <3, 12, 8>)
-    if (d.RPW == 3 && d.KS == 12) e = launch_mlp_block<3, 12, 8>(x, base, d, M, s);
-    else if (d.RPW == 2 && d.KS == 8) e = launch_mlp_block<2, 8, 8>(x, base, d, M, s);
-    else if (d.RPW == 4 && d.KS == 16) e = launch_mlp_block<4, 16, 8>(x, base, d, M, s);
-    else return BESO_ERR_UNSUPPORTED;
-    return e == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return with_shape<kAnyShape, int>(rows_class(d), BESO_ERR_UNSUPPORTED, [&](auto sh) {
+        return to_status(launch_lds<mlp_block_kernel<sh.RPW, sh.KS, kWaves>>(dim3((M + kMT - 1) / kMT), dim3(kBlock), lds_map(sh.KS, true).total,
+                                                                            s, x, base, d, M, g_stamps, g_stamps_cap));
+    });
 }
 
 // LN1 + q/k/v (which = 0: buf = qkv[M][3D] bf16 out) / proj + residual (which = 1: buf = y[M][ld] bf16 in) blocks
@@ -4435,7 +4418,7 @@ bool fused_has_lin_blocks(const Layout& lay, int precision) {
     FusedDims d;
     if ((precision != BESO_PREC_BF16 && precision != BESO_PREC_BF16X3) || lay.fused == lay.total || !fused_dims(lay, &d) ||
         !shape_has_kernel(d)) return false;
-    return d.lin && d.RPW == 4 && d.KS == 16 && d.D == 16 * kWaves * d.RPW;
+    return lin_blocks_shape(d);
 }
 
 // BF16X3, long-sequence shape: [tail of `layer` (y = fp32 attention output, ld_y floats per row)] and / or [LN1 + q/k/v of
@@ -4445,13 +4428,13 @@ int fused_lin_x3(const Layout& lay, const char* packed, int layer, int next_laye
     FusedDims d;
     if (!fused_dims(lay, &d) || !x3_long_shape(d)) return BESO_ERR_UNSUPPORTED;
     constexpr int NT = 3;
-    using L = LdsMapLinX3<NT, 16>;
+    using S = LongHorizon;
+    using L = LdsMapLinX3<NT, S::KS>;
     const char* base = packed + lay.fused;
     const char* lw = layer >= 0 ? base + (size_t)layer * d.layer_bytes : nullptr;
     const char* lwn = next_layer >= 0 ? base + (size_t)next_layer * d.layer_bytes : nullptr;
-    const hipError_t e = launch_lds<lin_block_x3_kernel<4, 16, NT>>(dim3((M + 16 * NT - 1) / (16 * NT)), dim3(512), L::total, s, x, lw,
-                                                                    lwn, d, M, y, ld_y, qkv_next);
-    return e == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return to_status(launch_lds<lin_block_x3_kernel<S::RPW, S::KS, NT>>(dim3((M + 16 * NT - 1) / (16 * NT)), dim3(512), L::total,
+                                                                        s, x, lw, lwn, d, M, y, ld_y, qkv_next));
 }
 
 int fused_lin_block(const Layout& lay, const char* packed, int layer, int which, float* x, void* buf, int ld, int M,
@@ -4459,10 +4442,14 @@ int fused_lin_block(const Layout& lay, const char* packed, int layer, int which,
     FusedDims d;
     if (!fused_dims(lay, &d) || !d.lin) return BESO_ERR_UNSUPPORTED;
     const char* base = packed + lay.fused + (size_t)layer * d.layer_bytes;
-    hipError_t e;
-    if (d.RPW == 4 && d.KS == 16) e = launch_lin_blocks<4, 16>(which, x, base, d, M, buf, ld, s);
-    else return BESO_ERR_UNSUPPORTED;
-    return e == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return with_shape<kLongHorizon, int>(rows_class(d), BESO_ERR_UNSUPPORTED, [&](auto sh) {
+        const dim3 grid((M + kMT - 1) / kMT), block(kBlock);
+        const size_t lds = lds_map(sh.KS, true).total;
+        return to_status(which == 0 ? launch_lds<qkv_block_kernel<sh.RPW, sh.KS>>(grid, block, lds, s, (const float*)x, base, d, M,
+                                                                                 (uint16_t*)buf, g_stamps, g_stamps_cap)
+                                    : launch_lds<proj_block_kernel<sh.RPW, sh.KS>>(grid, block, lds, s, x, base, d, M, (const uint16_t*)buf,
+                                                                                  ld, g_stamps, g_stamps_cap));
+    });
 }
 
 // proj + residual + LN2 + MLP of `layer`, and -- unless it is the last -- LN1 + q/k/v of layer + 1 (qkv_next [M][3D] bf16),
@@ -4473,22 +4460,21 @@ int fused_lin_tail(const Layout& lay, const char* packed, int layer, float* x, c
     if (!fused_dims(lay, &d) || !d.lin) return BESO_ERR_UNSUPPORTED;
     const char* base = packed + lay.fused + (size_t)layer * d.layer_bytes;
     const char* next = layer + 1 < lay.L ? base + d.layer_bytes : nullptr;
-    hipError_t e;
-    if (d.RPW == 4 && d.KS == 16) e = launch_tail_block<4, 16>(x, base, next, d, M, y, ld_y, qkv_next, s);
-    else return BESO_ERR_UNSUPPORTED;
-    return e == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return with_shape<kLongHorizon, int>(rows_class(d), BESO_ERR_UNSUPPORTED, [&](auto sh) {
+        return to_status(launch_lds<tail_block_kernel<sh.RPW, sh.KS>>(dim3((M + kMT - 1) / kMT), dim3(kBlock), lds_map(sh.KS, true).total, s, x,
+                                                                     base, next, d, M, (const uint16_t*)y, ld_y, (uint16_t*)qkv_next,
+                                                                     g_stamps, g_stamps_cap));
+    });
 }
 
 static int launch_train_pack(const TrainPackTable& t, char* img, hipStream_t s) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(train_pack_kernel, dim3(t.blocks), dim3(256), 0, s, t, img);
-    return hipGetLastError() == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return to_status(launch_plain<train_pack_kernel>(dim3(t.blocks), dim3(256), s, t, img));
 }
 
 // ---- training forward through the tail block (train.hip) -----------------------------------------------------------
 static bool train_tail_dims(const Layout& lay, FusedDims* d) {
     if (!fused_dims(lay, d) || !shape_has_kernel(*d)) return false;
-    return (d->RPW == 3 && d->KS == 12) || (d->RPW == 2 && d->KS == 8);
+    return (rows_class(*d) & kShortShapes) != 0;
 }
 
 bool fused_train_supported(const Layout& lay) { FusedDims d; return train_tail_dims(lay, &d); }
@@ -4541,9 +4527,10 @@ int fused_train_tail(const Layout& lay, const char* img, int layer, int M, const
     TrainTailArgs a{x_in, (const uint16_t*)y, ld_y, x_mid, x_out, st2, (uint16_t*)xn2, (uint16_t*)h, (uint16_t*)g,
                     st1n, (uint16_t*)xn1n, (uint16_t*)qkvn};
     const dim3 grid((M + kMT - 1) / kMT), block(512);
-    const hipError_t e = d.RPW == 3 ? launch_lds<train_tail_kernel<3, 12>>(grid, block, lds_map(12, true).total, s, lw, lw_next, d, ti, M, a)
-                                    : launch_lds<train_tail_kernel<2, 8>>(grid, block, lds_map(8, true).total, s, lw, lw_next, d, ti, M, a);
-    return e == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return with_shape<kShortShapes, int>(rows_class(d), BESO_ERR_UNSUPPORTED, [&](auto sh) {
+        constexpr LdsMap L = lds_map(sh.KS, true);
+        return to_status(launch_lds<train_tail_kernel<sh.RPW, sh.KS>>(grid, block, L.total, s, lw, lw_next, d, ti, M, a));
+    });
 }
 
 // ---- training forward of all layers as one launch (train_fwd_kernel) ---------------------------------------------------
@@ -4551,10 +4538,11 @@ int fused_train_tail(const Layout& lay, const char* img, int layer, int M, const
 // BASELINE config 3's per-GPU share), eight in six beyond
 static bool train_whole_dims(const Layout& lay, int T, int t, FusedDims* d) {
     if (!train_tail_dims(lay, d) || !d->attn || d->seq1 || d->lin) return false;
-    if (!((d->RPW == 3 && d->KS == 12 && d->HG == 1) || (d->RPW == 2 && d->KS == 8 && d->HG == 3))) return false;
     if (lay.L < 1 || lay.L * 16 > kTrainPackSegs) return false;
-    const int NTL = d->RPW == 3 ? 2 : 4;                    // the instances' action-token tiles (fused_layers)
-    return kSPW * T <= kMT && tiles_hold(kSPW, T, kNTT) && kSPW * t <= 16 * NTL;
+    // (the instance's action-token tiles hold the eight samples' steps)
+    return with_shape<kShortShapes>(instance_class(*d), false, [&](auto sh) {
+        return kSPW * T <= kMT && tiles_hold(kSPW, T, kNTT) && kSPW * t <= 16 * decltype(sh)::NTL;
+    });
 }
 
 bool fused_train_whole_supported(const Layout& lay, int T, int t) { FusedDims d; return train_whole_dims(lay, T, t, &d); }
@@ -4593,18 +4581,15 @@ int fused_train_whole_pack(const Layout& lay, const float* const* p, char* img, 
     return launch_train_pack(b.t, img, s);
 }
 
-template <int RPW, int KS, int HG, int NTL, int SPW, int NTA, int RD>
-static hipError_t launch_train_fwd_rd(const char* img, const FusedDims& d, const TrainImgW& ti, int batch, int T,
-                                      const TrainWholeBufs& a, hipStream_t s) {
-    constexpr LdsMap L = lds_map(KS);
-    return launch_lds<train_fwd_kernel<RPW, KS, HG, NTL, SPW, NTA, RD>>(dim3((batch + SPW - 1) / SPW), dim3(512), L.total, s, img, d, ti,
-                                                                        batch, T, a);
-}
-template <int RPW, int KS, int HG, int NTL, int SPW, int NTA>
+// (RD = 1: with the dropout on the out-projection and MLP outputs)
+template <typename S, int SPW, int NTA>
 static hipError_t launch_train_fwd(const char* img, const FusedDims& d, const TrainImgW& ti, int batch, int T,
                                    const TrainWholeBufs& a, hipStream_t s) {
-    return a.p_resid > 0.f ? launch_train_fwd_rd<RPW, KS, HG, NTL, SPW, NTA, 1>(img, d, ti, batch, T, a, s)
-                           : launch_train_fwd_rd<RPW, KS, HG, NTL, SPW, NTA, 0>(img, d, ti, batch, T, a, s);
+    constexpr LdsMap L = lds_map(S::KS);
+    const dim3 grid((batch + SPW - 1) / SPW), block(kBlock);
+    if (a.p_resid > 0.f)
+        return launch_lds<train_fwd_kernel<S::RPW, S::KS, S::HG, S::NTL, SPW, NTA, 1>>(grid, block, L.total, s, img, d, ti, batch, T, a);
+    return launch_lds<train_fwd_kernel<S::RPW, S::KS, S::HG, S::NTL, SPW, NTA, 0>>(grid, block, L.total, s, img, d, ti, batch, T, a);
 }
 
 int fused_train_whole(const Layout& lay, const char* img, int batch, int T, const TrainWholeBufs& a, hipStream_t s) {
@@ -4617,16 +4602,12 @@ int fused_train_whole(const Layout& lay, const char* img, int batch, int T, cons
     // "318.7 GFLOP issued for 211 algorithmic" at 1024 samples; the last sample's 16-row attention window ends in the pad rows
     // behind slot 48, as in the split-bf16 inference instance)
     const bool mid3 = mid && tiles_hold(kMidSPW, T, 3) && kMidSPW * a.t <= 16 * 2 ;
-    hipError_t e;
-    if (d.RPW == 3)
-        e = mid3 ? launch_train_fwd<3, 12, 1, 2, kMidSPW, 3>(img, d, ti, batch, T, a, s)
-            : mid ? launch_train_fwd<3, 12, 1, 2, kMidSPW, kMidNT>(img, d, ti, batch, T, a, s)
-                : launch_train_fwd<3, 12, 1, 2, kSPW, kNTT>(img, d, ti, batch, T, a, s);
-    else
-        e = mid3 ? launch_train_fwd<2, 8, 3, 4, kMidSPW, 3>(img, d, ti, batch, T, a, s)
-            : mid ? launch_train_fwd<2, 8, 3, 4, kMidSPW, kMidNT>(img, d, ti, batch, T, a, s)
-                : launch_train_fwd<2, 8, 3, 4, kSPW, kNTT>(img, d, ti, batch, T, a, s);
-    return e == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return with_shape<kShortShapes, int>(instance_class(d), BESO_ERR_UNSUPPORTED, [&](auto sh) {
+        using S = decltype(sh);
+        return to_status(mid3  ? launch_train_fwd<S, kMidSPW, 3>(img, d, ti, batch, T, a, s)
+                         : mid ? launch_train_fwd<S, kMidSPW, kMidNT>(img, d, ti, batch, T, a, s)
+                               : launch_train_fwd<S, kSPW, kNTT>(img, d, ti, batch, T, a, s));
+    });
 }
 
 // ---- training backward: data-gradient GEMMs in the transposed formulation (train_dgrad_kernel) ------------------------
@@ -4637,7 +4618,8 @@ static bool train_dgrad_dims(const Layout& lay, FusedDims* d, TrainBwdImgW* t) {
     if (!train_tail_dims(lay, d)) return false;
     const int RT = d->RPW * kWaves;
     if (lay.D > 16 * RT || lay.D % 8 != 0) return false;
-    const int pfa = d->RPW == 3 ? 6 : 4;                         // k-steps of weight fragments in flight per wave (train_dgrad_kernel)
+    // k-steps of weight fragments in flight per wave (train_dgrad_kernel)
+    const int pfa = with_shape<kShortShapes>(rows_class(*d), 0, [](auto sh) { return decltype(sh)::PFA; });
     t->kt_d = d->KS;                                             // 12 / 8: a multiple of pfa
     t->kt_h = ((4 * lay.D + 31) / 32 + pfa - 1) / pfa * pfa;
     t->n_chunks = (4 * lay.D / 16 + RT - 1) / RT;
@@ -4682,8 +4664,6 @@ int fused_train_dgrad_pack(const Layout& lay, const float* const* p, char* img, 
 // rows of a bias slab of fused_train_dgrad(which = 3) over M token rows; fused_train_bias_reduce adds n slabs up into n vectors
 int fused_train_dgrad_blocks(int M) { return (M + 16 * 3 - 1) / (16 * 3); }
 int fused_train_bias_reduce(const float* const* slabs, float* const* outs, const int* blocks, int n, int N, hipStream_t s) {
-    if (n < 1) return BESO_OK;
-    (void)hipGetLastError();
     // (slabs of different heights -- the compact last layer -- get launches of their own)
     int i = 0;
     while (i < n) {
@@ -4691,9 +4671,9 @@ int fused_train_bias_reduce(const float* const* slabs, float* const* outs, const
         t.n = 0;
         const int nb = blocks[i];
         while (i < n && blocks[i] == nb && t.n < kMaxLayers) { t.slab[t.n] = slabs[i]; t.out[t.n] = outs[i]; ++t.n; ++i; }
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((N + 15) / 16, t.n), dim3(256), 0, s, t, nb, N);
+        FTRY(launch_plain<slab_reduce_kernel>(dim3((N + 15) / 16, t.n), dim3(256), s, t, nb, N));
     }
-    return hipGetLastError() == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return BESO_OK;
 }
 
 // the attribute is the kernels' fixed LDS ceiling, the launch takes what the call's tile needs
@@ -4703,12 +4683,13 @@ static LnBwdEpi make_epi(const TrainLnBwd& ln) {
                     ln.p, ln.p > 0.f ? 1.0f / (1.0f - ln.p) : 1.f, ln.seed, ln.site, ln.skip_mod, ln.x_bf16};
 }
 // MODE of train_dgrad_kernel: 0 no LayerNorm epilogue, 1 with it, 2 with it on bf16 rows
-template <int RPW, int NT, int PFA>
-static hipError_t launch_dgrad(int mode, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const char* wimg, const DgradArgs& a,
+template <typename S, int NT>
+static hipError_t launch_dgrad(int mode, dim3 grid, dim3 block, size_t lds, hipStream_t s, const char* wimg, const DgradArgs& a,
                                const LnBwdEpi& ep) {
-    if (mode == 2) return launch_lds_attr<train_dgrad_kernel<RPW, NT, PFA, 2>>(kTrainBwdLdsAttr, grid, block, lds_bytes, s, wimg, a, ep, g_stamps, g_stamps_cap);
-    if (mode == 1) return launch_lds_attr<train_dgrad_kernel<RPW, NT, PFA, 1>>(kTrainBwdLdsAttr, grid, block, lds_bytes, s, wimg, a, ep, g_stamps, g_stamps_cap);
-    return launch_lds_attr<train_dgrad_kernel<RPW, NT, PFA, 0>>(kTrainBwdLdsAttr, grid, block, lds_bytes, s, wimg, a, ep, g_stamps, g_stamps_cap);
+    constexpr size_t attr = kTrainBwdLdsAttr;
+    if (mode == 2) return launch_lds_attr<train_dgrad_kernel<S::RPW, NT, S::PFA, 2>>(attr, grid, block, lds, s, wimg, a, ep, g_stamps, g_stamps_cap);
+    if (mode == 1) return launch_lds_attr<train_dgrad_kernel<S::RPW, NT, S::PFA, 1>>(attr, grid, block, lds, s, wimg, a, ep, g_stamps, g_stamps_cap);
+    return launch_lds_attr<train_dgrad_kernel<S::RPW, NT, S::PFA, 0>>(attr, grid, block, lds, s, wimg, a, ep, g_stamps, g_stamps_cap);
 }
 
 int fused_train_dgrad(const Layout& lay, const char* img, int layer, int which, int M, const void* in, float* out32, void* out16,
@@ -4737,9 +4718,9 @@ int fused_train_dgrad(const Layout& lay, const char* img, int layer, int which, 
     if (lds_bytes < (size_t)16 * NT * kRedTok * sizeof(float)) lds_bytes = (size_t)16 * NT * kRedTok * sizeof(float);
     const dim3 grid((M + 16 * NT - 1) / (16 * NT)), block(512);
     const int mode = ln == nullptr ? 0 : (ln->x_bf16 ? 2 : 1);
-    const hipError_t e = d.RPW == 3 ? launch_dgrad<3, NT, 6>(mode, grid, block, lds_bytes, s, wimg, a, ep)
-                                    : launch_dgrad<2, NT, 4>(mode, grid, block, lds_bytes, s, wimg, a, ep);
-    return e == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return with_shape<kShortShapes, int>(rows_class(d), BESO_ERR_UNSUPPORTED, [&](auto sh) {
+        return to_status(launch_dgrad<decltype(sh), NT>(mode, grid, block, lds_bytes, s, wimg, a, ep));
+    });
 }
 
 // the second half of a layer's backward (train_mlp_bwd_kernel): the launches which = 3, 2 (with ln), 1 of fused_train_dgrad in one
@@ -4761,10 +4742,10 @@ int fused_train_mlp_bwd(const Layout& lay, const char* img, int layer, int M, co
     const int KC = d.RPW * kWaves / 2;
     const size_t lds_bytes = (size_t)NT * (bi.kt_d + 2 * KC) * 1024;
     const dim3 grid((M + 16 * NT - 1) / (16 * NT)), block(512);
-    const hipError_t e =
-        d.RPW == 3 ? launch_lds_attr<train_mlp_bwd_kernel<3, NT, 6>>(kTrainBwdLdsAttr, grid, block, lds_bytes, s, lw, a, ep, g_stamps, g_stamps_cap)
-                   : launch_lds_attr<train_mlp_bwd_kernel<2, NT, 4>>(kTrainBwdLdsAttr, grid, block, lds_bytes, s, lw, a, ep, g_stamps, g_stamps_cap);
-    return e == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return with_shape<kShortShapes, int>(rows_class(d), BESO_ERR_UNSUPPORTED, [&](auto sh) {
+        return to_status(launch_lds_attr<train_mlp_bwd_kernel<sh.RPW, NT, sh.PFA>>(kTrainBwdLdsAttr, grid, block, lds_bytes, s, lw, a, ep,
+                                                                                  g_stamps, g_stamps_cap));
+    });
 }
 
 #endif   // !BESO_OPERAND_F16
@@ -4789,36 +4770,32 @@ int fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float*
                  hipStream_t s, const SampleSteps* steps, const SampleExtra* extra, const SampleTrace* trace) {
     FusedDims d;
     if (!fused_dims(lay, &d) || !d.attn) return BESO_ERR_UNSUPPORTED;
-    static const SampleSteps no_steps{};
-    static const SampleExtra no_extra{};
-    const SampleTrace TR = trace ? *trace : SampleTrace{nullptr, nullptr};
-    const SampleSteps& S = steps ? *steps : no_steps;
-    const SampleExtra& X3 = extra ? *extra : no_extra;
-    const char* base = packed + lay.fused;
-    EdgeArgs e;
-    e.state = a.state; e.action = a.action; e.goal = a.goal; e.sigma = a.sigma; e.out = a.out;
-    e.aux = a.aux;
-    e.noise = a.noise;
-    e.B = a.batch; e.t = a.t; e.precondition = a.precondition;
-    e.two = a.vbatch > a.batch ? 1 : 0;
-    e.uncond_all = (!e.two && a.uncond_from == 0) ? 1 : 0;
-    e.cond_lambda = a.cond_lambda; e.sigma_data = a.sigma_data;
     // with a classifier-free pair the virtual samples are interleaved (2b, 2b+1) so that both halves of a
     // pair live in one workgroup; that ordering only exists inside the kernel, so the head must be fused too
     if (!d.head_fused) return BESO_ERR_UNSUPPORTED;
     // every instance stages its workgroup's action windows in the kXsBytes of `xs`
     if ((size_t)(d.seq1 ? 1 : kSPW) * a.t * lay.act * sizeof(float) > (size_t)kXsBytes) return BESO_ERR_UNSUPPORTED;
+    static const SampleSteps no_steps{};
+    static const SampleExtra no_extra{};
+    const char* base = packed + lay.fused;
+    const int two = a.vbatch > a.batch ? 1 : 0, uncond_all = (!two && a.uncond_from == 0) ? 1 : 0;
+    // (the long-horizon instance: one workgroup per REAL sample, a pair runs as two passes)
+    LayersCall c{x, base, d, 0, lay.L, d.seq1 ? a.batch : a.vbatch, a.T,
+                 EdgeArgs{a.state, a.action, a.goal, a.sigma, a.out, a.aux, a.noise, a.batch, a.t, a.precondition, uncond_all, two,
+                          a.cond_lambda, a.sigma_data},
+                 steps ? *steps : no_steps, extra ? *extra : no_extra, trace ? *trace : SampleTrace{nullptr, nullptr},
+                 SigArgs{nullptr, nullptr}, precision, a.plan, s};
     if (fused_edges) *fused_edges = 3;
-    hipError_t err;
     // the sigma-token cache of the image (bf16 / fp16 operands; a call without a flag word of its own -- a.sig_flag -- does not share)
-    SigArgs sig{nullptr, nullptr};
-    if (precision == BESO_PREC_BF16 && sig_shape(d) && a.sig_flag) sig = SigArgs{(uint32_t*)(const_cast<char*>(base) + sig_cache_offset(d)), a.sig_flag};
-    if (d.RPW == 3 && d.KS == 12 && d.HG == 1) err = launch_layers<3, 12, 1, 2>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, TR, precision, a.plan, s, sig);    // kitchen: 8 x 4 action tokens
-    else if (d.RPW == 2 && d.KS == 8 && d.HG == 3) err = launch_layers<2, 8, 3, 4>(x, base, d, 0, lay.L, a.vbatch, a.T, e, S, X3, TR, precision, a.plan, s, sig);   // block-push: 8 x 5
-    else if (d.seq1 && precision == BESO_PREC_BF16) err = launch_layers_long<4, 16, kLongNT>(x, base, d, 0, lay.L, a.batch, a.T, e, S, X3, TR, s);   // long horizon: 1 x 67 tokens
-                                                                                                             // (one workgroup per REAL sample: pairs run as two passes)
-    else return BESO_ERR_UNSUPPORTED;
-    return err == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    if (precision == BESO_PREC_BF16 && sig_shape(d) && a.sig_flag)
+        c.sig = SigArgs{(uint32_t*)(const_cast<char*>(base) + sig_cache_offset(d)), a.sig_flag};
+    return with_shape<kAnyShape, int>(instance_class(d), BESO_ERR_UNSUPPORTED, [&](auto sh) {
+        using S = decltype(sh);
+        if constexpr (std::is_same_v<S, LongHorizon>)
+            return d.seq1 && precision == BESO_PREC_BF16 ? to_status(launch_layers_long<S>(c)) : (int)BESO_ERR_UNSUPPORTED;
+        else
+            return to_status(launch_layers<S>(c));
+    });
 }
 
 #if !BESO_OPERAND_F16 && BESO_DEV_API
