@@ -27,12 +27,6 @@ int validate_config(const beso_config* c) {
     return BESO_OK;
 }
 
-static size_t carve(size_t& cur, size_t bytes) {
-    size_t off = cur;
-    cur = round_up_sz(cur + bytes, 256);
-    return off;
-}
-
 bool make_layout(const beso_config* c, int precision, Layout* o) {
     if (validate_config(c) != BESO_OK) return false;
     if (precision != BESO_PREC_BF16 && precision != BESO_PREC_FP32 && precision != BESO_PREC_BF16X3 && precision != BESO_PREC_FP16)
@@ -646,7 +640,7 @@ const char* beso_status_string(int st) {
 
 int beso_num_params(const beso_config* cfg) {
     if (validate_config(cfg) != BESO_OK) return 0;
-    return 3 + 16 * cfg->n_layers + 6 + (cfg->linear_output ? 2 : 4);
+    return ModelParams(cfg).count;
 }
 
 size_t beso_packed_bytes(const beso_config* cfg, int precision) {
@@ -664,63 +658,48 @@ int beso_pack_weights(const beso_config* cfg, const float* const* p, int n_param
     if ((precision == BESO_PREC_BF16X3 || precision == BESO_PREC_FP16) && lay.fused == lay.total)
         return BESO_ERR_UNSUPPORTED;   // no fused instance for this shape
     if (!p || !packed_v) return BESO_ERR_BAD_ARG;
-    if (n_params != beso_num_params(cfg)) return BESO_ERR_BAD_ARG;
-    for (int i = 0; i < n_params; ++i) if (!p[i]) return BESO_ERR_BAD_ARG;
+    ModelParams m(cfg);
+    if (m.read(p, n_params) != BESO_OK) return BESO_ERR_BAD_ARG;
     if (packed_bytes < lay.total) return BESO_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char* pk = (char*)packed_v;
     const int D = lay.D;
-    int i = 0;
-    // fp32 sections: precision -1
-#define PACK32(off, rows, cols, rp, cp) HIP_TRY(launch_pack_matrix(p[i++], rows, cols, pk + (off), rp, cp, -1, s))
+    // one tensor into the section at `off`, zero padded to [rp][cp]; prec -1: an fp32 section
+    auto pack = [&](const Param& x, size_t off, int rp, int cp, int prec) {
+        return launch_pack_matrix(x.p, x.rows, x.cols, pk + off, rp, cp, prec, s);
+    };
+    auto pack32 = [&](const Param& x, size_t off) { return pack(x, off, x.rows, x.cols, -1); };
     // (the GEMM operands of the per-op path are not used by BF16X3 / FP16: their weights live in the fused image only)
-#define PACKW(src, off, rows, cols, rp, cp) \
-    do { if (precision != BESO_PREC_BF16X3 && precision != BESO_PREC_FP16) \
-             HIP_TRY(launch_pack_matrix(src, rows, cols, pk + (off), rp, cp, precision, s)); } while (0)
-    PACK32(lay.pos_emb, lay.seq_size, D, lay.seq_size, D);
-    PACK32(lay.tok_w, D, lay.obs, D, lay.obs);
-    PACK32(lay.tok_b, 1, D, 1, D);
+    const bool operands = precision != BESO_PREC_BF16X3 && precision != BESO_PREC_FP16;
+    auto packw = [&](const Param& x, size_t off, int rp, int cp) { return operands ? pack(x, off, rp, cp, precision) : hipSuccess; };
+    HIP_TRY(pack32(m.pos, lay.pos_emb)); HIP_TRY(pack32(m.tokw, lay.tok_w)); HIP_TRY(pack32(m.tokb, lay.tok_b));
     for (int l = 0; l < lay.L; ++l) {
         const LayerOff& o = lay.layer[l];
-        PACK32(o.ln1_w, 1, D, 1, D); PACK32(o.ln1_b, 1, D, 1, D);
-        PACK32(o.ln2_w, 1, D, 1, D); PACK32(o.ln2_b, 1, D, 1, D);
-        // reference order: key, query, value, proj (score_gpts.py:33-39).  Fused rows: [q | k | v].
-        const float *kw = p[i], *kb = p[i + 1], *qw = p[i + 2], *qb = p[i + 3], *vw = p[i + 4], *vb = p[i + 5];
-        const float *pw = p[i + 6], *pb = p[i + 7];
-        i += 8;
+        const LayerParams& y = m.layer[l];
+        HIP_TRY(pack32(y.ln1w, o.ln1_w)); HIP_TRY(pack32(y.ln1b, o.ln1_b));
+        HIP_TRY(pack32(y.ln2w, o.ln2_w)); HIP_TRY(pack32(y.ln2b, o.ln2_b));
+        const Qkv qkv = y.qkv();
         const size_t e = lay.elem_bytes;
         // zero the whole padded operand first (rows 3D..Nqkv), then drop q,k,v in
         HIP_TRY(hipMemsetAsync(pk + o.w_qkv, 0, e * lay.Nqkv * lay.Kd, s));
         HIP_TRY(hipMemsetAsync(pk + o.b_qkv, 0, sizeof(float) * lay.Nqkv, s));
-        PACKW(qw, o.w_qkv, D, D, D, lay.Kd);
-        PACKW(kw, o.w_qkv + e * (size_t)D * lay.Kd, D, D, D, lay.Kd);
-        PACKW(vw, o.w_qkv + e * (size_t)2 * D * lay.Kd, D, D, D, lay.Kd);
-        HIP_TRY(launch_pack_matrix(qb, 1, D, pk + o.b_qkv, 1, D, -1, s));
-        HIP_TRY(launch_pack_matrix(kb, 1, D, pk + o.b_qkv + sizeof(float) * D, 1, D, -1, s));
-        HIP_TRY(launch_pack_matrix(vb, 1, D, pk + o.b_qkv + sizeof(float) * 2 * D, 1, D, -1, s));
-        PACKW(pw, o.w_proj, D, D, lay.Nd, lay.Kd);
-        HIP_TRY(launch_pack_matrix(pb, 1, D, pk + o.b_proj, 1, lay.Nd, -1, s));
-        const float *f1w = p[i], *f1b = p[i + 1], *f2w = p[i + 2], *f2b = p[i + 3];
-        i += 4;
-        PACKW(f1w, o.w_fc1, 4 * D, D, lay.Nh, lay.Kd);
-        HIP_TRY(launch_pack_matrix(f1b, 1, 4 * D, pk + o.b_fc1, 1, lay.Nh, -1, s));
-        PACKW(f2w, o.w_fc2, D, 4 * D, lay.Nd, lay.Kh);
-        HIP_TRY(launch_pack_matrix(f2b, 1, D, pk + o.b_fc2, 1, lay.Nd, -1, s));
+        for (int part = 0; part < 3; ++part) HIP_TRY(packw(qkv.w[part], o.w_qkv + e * (size_t)part * D * lay.Kd, D, lay.Kd));
+        for (int part = 0; part < 3; ++part) HIP_TRY(pack32(qkv.b[part], o.b_qkv + sizeof(float) * part * D));
+        HIP_TRY(packw(y.pw, o.w_proj, lay.Nd, lay.Kd));
+        HIP_TRY(pack(y.pb, o.b_proj, 1, lay.Nd, -1));
+        HIP_TRY(packw(y.f1w, o.w_fc1, lay.Nh, lay.Kd));
+        HIP_TRY(pack(y.f1b, o.b_fc1, 1, lay.Nh, -1));
+        HIP_TRY(packw(y.f2w, o.w_fc2, lay.Nd, lay.Kh));
+        HIP_TRY(pack(y.f2b, o.b_fc2, 1, lay.Nd, -1));
     }
-    PACK32(lay.lnf_w, 1, D, 1, D); PACK32(lay.lnf_b, 1, D, 1, D);
-    PACK32(lay.sig_w, 1, D, 1, D); PACK32(lay.sig_b, 1, D, 1, D);          // sigma_emb.weight is [D,1]
-    PACK32(lay.act_w, D, lay.act, D, lay.act); PACK32(lay.act_b, 1, D, 1, D);
-    if (lay.linear_output) {
-        PACK32(lay.head_w0, lay.act, D, lay.act, D); PACK32(lay.head_b0, 1, lay.act, 1, lay.act);
-    } else {
-        PACK32(lay.head_w0, kHeadHidden, D, kHeadHidden, D); PACK32(lay.head_b0, 1, kHeadHidden, 1, kHeadHidden);
-        PACK32(lay.head_w1, lay.act, kHeadHidden, lay.act, kHeadHidden); PACK32(lay.head_b1, 1, lay.act, 1, lay.act);
-    }
-#undef PACK32
-#undef PACKW
-    if (i != n_params) return BESO_ERR_BAD_ARG;
+    HIP_TRY(pack32(m.lnfw, lay.lnf_w)); HIP_TRY(pack32(m.lnfb, lay.lnf_b));
+    HIP_TRY(pack32(m.sigw, lay.sig_w)); HIP_TRY(pack32(m.sigb, lay.sig_b));
+    HIP_TRY(pack32(m.actw, lay.act_w)); HIP_TRY(pack32(m.actb, lay.act_b));
+    // (the linear head's tensors are the image's head_w1 = head_w0 and head_b1 = head_b0)
+    if (!lay.linear_output) { HIP_TRY(pack32(m.h0w, lay.head_w0)); HIP_TRY(pack32(m.h0b, lay.head_b0)); }
+    HIP_TRY(pack32(m.hw, lay.head_w1)); HIP_TRY(pack32(m.hb, lay.head_b1));
     const FusedUnit fu = fused_unit(precision);
-    return fu.pack(lay, p, pk, fu.precision, s);
+    return fu.pack(lay, m, pk, fu.precision, s);
 }
 
 size_t beso_workspace_bytes(const beso_config* cfg, int batch, int t, int precision, int cfg_guidance) {

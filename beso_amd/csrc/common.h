@@ -271,6 +271,13 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 // GEMM operands are [Np][Kp] (torch Linear layout = B^T, k contiguous), Np = ceil128(N),
 // Kp = ceil64(K), zero padded, element type = bf16 or fp32 by precision.
 // ---------------------------------------------------------------------------------------------
+// the next 256-B aligned section of an image or a workspace: its offset; `cur` moves behind it
+inline size_t carve(size_t& cur, size_t bytes) {
+    const size_t off = cur;
+    cur = round_up_sz(cur + bytes, 256);
+    return off;
+}
+
 struct LayerOff {
     size_t ln1_w, ln1_b, ln2_w, ln2_b;   // fp32 [D]
     size_t b_qkv, b_proj, b_fc1, b_fc2;  // fp32 [Np]

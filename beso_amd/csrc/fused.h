@@ -1,6 +1,6 @@
 // Fused score-network path (kernels specialised for the shipped model shapes).  See fused.hip.
 #pragma once
-#include "common.h"
+#include "params.h"
 
 namespace beso {
 
@@ -28,7 +28,7 @@ struct SampleTrace { float* x; float* den; };
 constexpr int kLoopMaxElems = 512;   // action-window elements per workgroup the loop can carry (one per thread)
 
 size_t fused_packed_bytes(const Layout& lay, int precision);
-int    fused_pack(const Layout& lay, const float* const* params, char* packed, int precision, hipStream_t s);
+int    fused_pack(const Layout& lay, const ModelParams& params, char* packed, int precision, hipStream_t s);
 int    fused_level(const Layout& lay, const FwdArgs& a, int precision);   // 0 none, 1 MLP block, 2 whole layers
 int    fused_layer_edges(const Layout& lay);        // bit 0: fused_layers embeds, bit 1: it runs the head
 int    fused_layers(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,
@@ -45,7 +45,7 @@ int    fused_lin_tail(const Layout& lay, const char* packed, int layer, float* x
 // training forward through the tail block (train.hip): per-step fragment image of the weights + one launch per layer
 bool   fused_train_supported(const Layout& lay);
 size_t fused_train_image_bytes(const Layout& lay);
-int    fused_train_pack(const Layout& lay, const float* const* params, char* img, hipStream_t s);
+int    fused_train_pack(const Layout& lay, const ModelParams& params, char* img, hipStream_t s);
 int    fused_train_tail(const Layout& lay, const char* img, int layer, int M, const float* x_in, const void* y, int ld_y,
                         float* x_mid, float* x_out, float* st2, void* xn2, void* h, void* g, float* st1n, void* xn1n,
                         void* qkvn, hipStream_t s);
@@ -64,13 +64,13 @@ struct TrainWholeBufs {
 };
 bool   fused_train_whole_supported(const Layout& lay, int T, int t);
 size_t fused_train_whole_image_bytes(const Layout& lay);
-int    fused_train_whole_pack(const Layout& lay, const float* const* params, char* img, hipStream_t s);
+int    fused_train_whole_pack(const Layout& lay, const ModelParams& params, char* img, hipStream_t s);
 int    fused_train_whole(const Layout& lay, const char* img, int batch, int T, const TrainWholeBufs& a, hipStream_t s);
 // training backward: the data-gradient GEMMs in the transposed formulation (train_dgrad_kernel; per-step image of the
 // transposed weights).  which: 0 q|k|v, 1 out-projection (bf16 out), 2 FC1, 3 FC2 + GELU' (dh + FC1 bias column sums)
 bool   fused_train_dgrad_supported(const Layout& lay);
 size_t fused_train_dgrad_image_bytes(const Layout& lay);
-int    fused_train_dgrad_pack(const Layout& lay, const float* const* params, char* img, hipStream_t s);
+int    fused_train_dgrad_pack(const Layout& lay, const ModelParams& params, char* img, hipStream_t s);
 // ln (which = 0 or 2): the LayerNorm backward behind this data gradient runs as the kernel's epilogue (dxn is not written)
 struct TrainLnBwd {
     const float* x; const float* stats; const float* gamma;     // LayerNorm input [M][D], (mean, rstd) [M][2], gamma [D]
@@ -94,7 +94,7 @@ int    fused_sigma_cache_entries(const Layout& lay, const char* packed);   // de
 // The fp16-operand build of layers_kernel (fused_f16.hip = fused.hip compiled with BESO_OPERAND_F16 = 1): BESO_PREC_FP16.
 // Same image layout and sizes with fp16 weight fragments; `precision` arguments take BESO_PREC_BF16 ("the plain mode").
 size_t fused_packed_bytes_f16(const Layout& lay, int precision);
-int    fused_pack_f16(const Layout& lay, const float* const* params, char* packed, int precision, hipStream_t s);
+int    fused_pack_f16(const Layout& lay, const ModelParams& params, char* packed, int precision, hipStream_t s);
 int    fused_level_f16(const Layout& lay, const FwdArgs& a, int precision);
 int    fused_layer_edges_f16(const Layout& lay);
 int    fused_layers_f16(const Layout& lay, const char* packed, const FwdArgs& a, float* x, int* fused_edges, int precision,

@@ -4298,7 +4298,7 @@ size_t fused_packed_bytes(const Layout& lay, int precision) {
 // one launch of a pack kernel (256 threads per workgroup); a launch that fails ends the call there
 #define FPACK(kernel, grid, ...) FTRY(launch_plain<kernel>(dim3(grid), dim3(256), s, __VA_ARGS__))
 
-int fused_pack(const Layout& lay, const float* const* p, char* packed, int precision, hipStream_t s) {
+int fused_pack(const Layout& lay, const ModelParams& m, char* packed, int precision, hipStream_t s) {
     FusedDims d;
     if ((precision != BESO_PREC_BF16 && precision != BESO_PREC_BF16X3) || !fused_dims(lay, &d) || !shape_has_kernel(d)) return BESO_OK;
     if (precision == BESO_PREC_BF16X3 && !x3_shape(d) && !x3_long_shape(d)) return BESO_ERR_UNSUPPORTED;
@@ -4311,12 +4311,11 @@ int fused_pack(const Layout& lay, const float* const* p, char* packed, int preci
         FTRY(hipMemsetAsync(packed + lay.fused + sig_cache_offset(d), 0, sig_cache_bytes(d), s));
     for (int half = 0; half < n_parts; ++half)               // 0: bf16(w); 1 (BF16X3 only): the low halves
     for (int l = 0; l < lay.L; ++l) {
-        // parameter order (include/beso_hip.h): 3 leading tensors, then 16 per block:
-        // ln1.w ln1.b ln2.w ln2.b key.w key.b query.w query.b value.w value.b proj.w proj.b fc1.w fc1.b fc2.w fc2.b
-        const float* const* q = p + 3 + 16 * l;
-        const float *ln1w = q[0], *ln1b = q[1], *ln2w = q[2], *ln2b = q[3];
-        const float *kw = q[4], *kb = q[5], *qw = q[6], *qb = q[7], *vw = q[8], *vb = q[9], *pw = q[10], *pb = q[11];
-        const float *f1w = q[12], *f1b = q[13], *f2w = q[14], *f2b = q[15];
+        const LayerParams& y = m.layer[l];
+        const float *ln1w = y.ln1w.p, *ln1b = y.ln1b.p, *ln2w = y.ln2w.p, *ln2b = y.ln2b.p;
+        const float *kw = y.kw.p, *kb = y.kb.p, *qw = y.qw.p, *qb = y.qb.p, *vw = y.vw.p, *vb = y.vb.p, *pw = y.pw.p, *pb = y.pb.p;
+        const float *f1w = y.f1w.p, *f1b = y.f1b.p, *f2w = y.f2w.p, *f2b = y.f2b.p;
+        const Qkv qkv = y.qkv();
         char* base = packed + lay.fused + (size_t)l * d.layer_bytes + (half ? (size_t)d.x3_delta : 0);
         const int rt1 = d.NCH * kChunkTiles, rt2 = d.RPW * kWaves;
         FPACK(pack_mfma_a_kernel, 1024, f1w, 4 * D, D, ln2w, (uint16_t*)base, rt1, d.KS, kChunkTiles, half);
@@ -4325,10 +4324,9 @@ int fused_pack(const Layout& lay, const float* const* p, char* packed, int preci
             FPACK(pack_qkv_kernel, 1024, qw, kw, vw, ln1w, (uint16_t*)(base + d.o_wqkv), D, d.Hv, d.hdv, d.KS, half);
             FPACK(pack_proj_kernel, 512, pw, (uint16_t*)(base + d.o_wproj), D, d.Hv, d.hdv, rt2, half);
         }
-        const float* ws3[3] = {qw, kw, vw};
         if (d.lin) {
             for (int part = 0; part < 3; ++part)      // q / k / v in natural row order (block kernels)
-                FPACK(pack_mfma_a_kernel, 1024, ws3[part], D, D, ln1w,
+                FPACK(pack_mfma_a_kernel, 1024, qkv.w[part].p, D, D, ln1w,
                       (uint16_t*)(base + d.o_wqkv_lin + (size_t)part * d.part_bytes), rt2, d.KS, rt2, half);
             FPACK(pack_mfma_a_kernel, 1024, pw, D, D, no_scale, (uint16_t*)(base + d.o_wproj_lin), rt2, d.KS, rt2, half);
         }
@@ -4341,20 +4339,17 @@ int fused_pack(const Layout& lay, const float* const* p, char* packed, int preci
             FTRY(launch_pack_matrix(pb, 1, D, base + d.o_bproj, 1, rt2 * 16, -1, s));
         }
         if (d.lin) {
-            const float* bs3[3] = {qb, kb, vb};
             for (int part = 0; part < 3; ++part)      // q / k / v
-                FPACK(fold_bias_kernel, (rt2 * 16 + 3) / 4, ws3[part], bs3[part], ln1b,
+                FPACK(fold_bias_kernel, (rt2 * 16 + 3) / 4, qkv.w[part].p, qkv.b[part].p, ln1b,
                       (float*)(base + d.o_bqkv_lin) + (size_t)part * rt2 * 16, D, D, rt2 * 16);
             FTRY(launch_pack_matrix(pb, 1, D, base + d.o_bproj_lin, 1, rt2 * 16, -1, s));
         }
     }
     if (d.attn) {
-        // per-model image: parameter order pos_emb, tok_emb.{w,b}, blocks..., ln_f.{w,b}, sigma_emb.{w,b},
-        // action_emb.{w,b}, action_pred.{w,b}
+        // per-model image
         char* gw = packed + lay.fused + (size_t)lay.L * d.layer_bytes;
-        const float* const* tail = p + 3 + 16 * lay.L;
-        const float *pos = p[0], *tokw = p[1], *tokb = p[2];
-        const float *lnfw = tail[0], *lnfb = tail[1], *sigw = tail[2], *sigb = tail[3], *actw = tail[4], *actb = tail[5];
+        const float *pos = m.pos.p, *tokw = m.tokw.p, *tokb = m.tokb.p;
+        const float *lnfw = m.lnfw.p, *lnfb = m.lnfb.p, *sigw = m.sigw.p, *sigb = m.sigb.p, *actw = m.actw.p, *actb = m.actb.p;
         FPACK(transpose_pad_kernel, (lay.obs * d.Dp + 255) / 256, tokw, D, lay.obs, (float*)(gw + d.g_tokT), d.Dp);
         FPACK(transpose_pad_kernel, (lay.act * d.Dp + 255) / 256, actw, D, lay.act, (float*)(gw + d.g_actT), d.Dp);
         // split-bf16 A fragments of the two embedding matrices ([D][obs], [D][act]: one k-step each)
@@ -4371,7 +4366,7 @@ int fused_pack(const Layout& lay, const float* const* p, char* packed, int preci
         FTRY(launch_pack_matrix(sigb, 1, D, gw + d.g_sigb, 1, d.Dp, -1, s));
         FTRY(launch_pack_matrix(pos, lay.seq_size, D, gw + d.g_pos, lay.seq_size, d.Dp, -1, s));
         if (d.head_fused)
-            FPACK(pack_head_kernel, (16 * d.Dp + 255) / 256, tail[6], tail[7], lnfw, lnfb, (float*)(gw + d.g_headw),
+            FPACK(pack_head_kernel, (16 * d.Dp + 255) / 256, m.hw.p, m.hb.p, lnfw, lnfb, (float*)(gw + d.g_headw),     // (head_fused: the linear head)
                   (float*)(gw + d.g_headb), lay.act, D, d.Dp);
     }
     return BESO_OK;
@@ -4485,9 +4480,8 @@ size_t fused_train_image_bytes(const Layout& lay) {
     return (size_t)train_img(d).layer_bytes * lay.L;
 }
 
-// params: the parameter list of beso_pack_weights.  Packs layers [0, L) (fragment-ordered bf16 weights, padded fp32 biases
-// and LayerNorm affine parameters) into img.
-int fused_train_pack(const Layout& lay, const float* const* p, char* img, hipStream_t s) {
+// Packs layers [0, L) (fragment-ordered bf16 weights, padded fp32 biases and LayerNorm affine parameters) into img.
+int fused_train_pack(const Layout& lay, const ModelParams& m, char* img, hipStream_t s) {
     FusedDims d;
     if (!train_tail_dims(lay, &d)) return BESO_ERR_UNSUPPORTED;
     const TrainImg ti = train_img(d);
@@ -4495,22 +4489,21 @@ int fused_train_pack(const Layout& lay, const float* const* p, char* img, hipStr
     TrainPackBuilder b;
     const int D = lay.D, rt1 = d.NCH * kChunkTiles, rt2 = d.RPW * kWaves;
     for (int l = 0; l < lay.L; ++l) {
-        const float* const* q = p + 3 + 16 * l;        // ln1.w ln1.b ln2.w ln2.b key.w key.b query.w query.b value.w value.b proj.w proj.b fc1.w fc1.b fc2.w fc2.b
+        const LayerParams& y = m.layer[l];
         const uint32_t base = (uint32_t)l * ti.layer_bytes;
-        b.mat(q[12], base + ti.o_w1, 4 * D, D, rt1, d.KS, kChunkTiles);
-        b.vec(q[13], base + ti.o_b1, 4 * D, rt1 * 16);
-        b.mat(q[14], base + ti.o_w2, D, 4 * D, rt2, d.KS2p, rt2);
-        b.vec(q[15], base + ti.o_b2, D, rt2 * 16);
-        const float* w3[3] = {q[6], q[4], q[8]};       // query, key, value: the [q | k | v] row order of the training buffers
-        const float* b3[3] = {q[7], q[5], q[9]};
+        b.mat(y.f1w.p, base + ti.o_w1, 4 * D, D, rt1, d.KS, kChunkTiles);
+        b.vec(y.f1b.p, base + ti.o_b1, 4 * D, rt1 * 16);
+        b.mat(y.f2w.p, base + ti.o_w2, D, 4 * D, rt2, d.KS2p, rt2);
+        b.vec(y.f2b.p, base + ti.o_b2, D, rt2 * 16);
+        const Qkv qkv = y.qkv();                       // the [q | k | v] row order of the training buffers
         for (int part = 0; part < 3; ++part) {
-            b.mat(w3[part], base + ti.o_wqkv + (uint32_t)part * ti.part_bytes, D, D, rt2, d.KS, rt2);
-            b.vec(b3[part], base + ti.o_bqkv + (uint32_t)part * rt2 * 16 * (uint32_t)sizeof(float), D, rt2 * 16);
+            b.mat(qkv.w[part].p, base + ti.o_wqkv + (uint32_t)part * ti.part_bytes, D, D, rt2, d.KS, rt2);
+            b.vec(qkv.b[part].p, base + ti.o_bqkv + (uint32_t)part * rt2 * 16 * (uint32_t)sizeof(float), D, rt2 * 16);
         }
-        b.mat(q[10], base + ti.o_wproj, D, D, rt2, d.KS, rt2);
-        b.vec(q[11], base + ti.o_bproj, D, rt2 * 16);
-        b.vec(q[0], base + ti.o_ln1w, D, rt2 * 16); b.vec(q[1], base + ti.o_ln1b, D, rt2 * 16);
-        b.vec(q[2], base + ti.o_ln2w, D, rt2 * 16); b.vec(q[3], base + ti.o_ln2b, D, rt2 * 16);
+        b.mat(y.pw.p, base + ti.o_wproj, D, D, rt2, d.KS, rt2);
+        b.vec(y.pb.p, base + ti.o_bproj, D, rt2 * 16);
+        b.vec(y.ln1w.p, base + ti.o_ln1w, D, rt2 * 16); b.vec(y.ln1b.p, base + ti.o_ln1b, D, rt2 * 16);
+        b.vec(y.ln2w.p, base + ti.o_ln2w, D, rt2 * 16); b.vec(y.ln2b.p, base + ti.o_ln2b, D, rt2 * 16);
     }
     return launch_train_pack(b.t, img, s);
 }
@@ -4553,30 +4546,29 @@ size_t fused_train_whole_image_bytes(const Layout& lay) {
     return (size_t)train_img_whole(d).layer_bytes * lay.L;
 }
 
-// params: the parameter list of beso_pack_weights.  All layers' fragment images, biases and LayerNorm parameters: one launch.
-int fused_train_whole_pack(const Layout& lay, const float* const* p, char* img, hipStream_t s) {
+// All layers' fragment images, biases and LayerNorm parameters: one launch.
+int fused_train_whole_pack(const Layout& lay, const ModelParams& m, char* img, hipStream_t s) {
     FusedDims d;
     if (!train_tail_dims(lay, &d) || !d.attn || d.lin || lay.L * 16 > kTrainPackSegs) return BESO_ERR_UNSUPPORTED;
     const TrainImgW ti = train_img_whole(d);
     TrainPackBuilder b;
     const int D = lay.D, rt1 = d.NCH * kChunkTiles, rt2 = d.RPW * kWaves;
     for (int l = 0; l < lay.L; ++l) {
-        const float* const* q = p + 3 + 16 * l;        // ln1.w ln1.b ln2.w ln2.b key.w key.b query.w query.b value.w value.b proj.w proj.b fc1.w fc1.b fc2.w fc2.b
+        const LayerParams& y = m.layer[l];
         const uint32_t base = (uint32_t)l * ti.layer_bytes;
-        b.mat(q[12], base, 4 * D, D, rt1, d.KS, kChunkTiles);
-        b.vec(q[13], base + d.o_b1, 4 * D, rt1 * 16);
-        b.mat(q[14], base + d.o_w2, D, 4 * D, rt2, d.KS2p, rt2);
-        b.vec(q[15], base + d.o_b2, D, rt2 * 16);
-        const float* w3[3] = {q[6], q[4], q[8]};       // query, key, value = parts 0, 1, 2 of the attention phase
-        const float* b3[3] = {q[7], q[5], q[9]};
+        b.mat(y.f1w.p, base, 4 * D, D, rt1, d.KS, kChunkTiles);
+        b.vec(y.f1b.p, base + d.o_b1, 4 * D, rt1 * 16);
+        b.mat(y.f2w.p, base + d.o_w2, D, 4 * D, rt2, d.KS2p, rt2);
+        b.vec(y.f2b.p, base + d.o_b2, D, rt2 * 16);
+        const Qkv qkv = y.qkv();                       // query, key, value = parts 0, 1, 2 of the attention phase
         for (int part = 0; part < 3; ++part) {
-            b.seg(w3[part], base + d.o_wqkv, d.hdv, D, d.Hv, d.KS, part, 2, (size_t)d.Hv * d.KS * 4 * 512);
-            b.seg(b3[part], base + d.o_bqkv, d.hdv, d.Hv * kHDP, 0, 0, part, 4, 0);
+            b.seg(qkv.w[part].p, base + d.o_wqkv, d.hdv, D, d.Hv, d.KS, part, 2, (size_t)d.Hv * d.KS * 4 * 512);
+            b.seg(qkv.b[part].p, base + d.o_bqkv, d.hdv, d.Hv * kHDP, 0, 0, part, 4, 0);
         }
-        b.mat(q[10], base + d.o_wproj, D, d.hdv, rt2, 2 * d.Hv, 0, 3);
-        b.vec(q[11], base + d.o_bproj, D, rt2 * 16);
-        b.vec(q[0], base + ti.o_ln1w, D, rt2 * 16); b.vec(q[1], base + ti.o_ln1b, D, rt2 * 16);
-        b.vec(q[2], base + ti.o_ln2w, D, rt2 * 16); b.vec(q[3], base + ti.o_ln2b, D, rt2 * 16);
+        b.mat(y.pw.p, base + d.o_wproj, D, d.hdv, rt2, 2 * d.Hv, 0, 3);
+        b.vec(y.pb.p, base + d.o_bproj, D, rt2 * 16);
+        b.vec(y.ln1w.p, base + ti.o_ln1w, D, rt2 * 16); b.vec(y.ln1b.p, base + ti.o_ln1b, D, rt2 * 16);
+        b.vec(y.ln2w.p, base + ti.o_ln2w, D, rt2 * 16); b.vec(y.ln2b.p, base + ti.o_ln2b, D, rt2 * 16);
     }
     return launch_train_pack(b.t, img, s);
 }
@@ -4641,20 +4633,20 @@ size_t fused_train_dgrad_image_bytes(const Layout& lay) {
     FusedDims d; TrainBwdImgW t;
     return train_dgrad_dims(lay, &d, &t) ? (size_t)t.layer_bytes * lay.L : 0;
 }
-int fused_train_dgrad_pack(const Layout& lay, const float* const* p, char* img, hipStream_t s) {
+int fused_train_dgrad_pack(const Layout& lay, const ModelParams& m, char* img, hipStream_t s) {
     FusedDims d; TrainBwdImgW bi;
     if (!train_dgrad_dims(lay, &d, &bi)) return BESO_ERR_UNSUPPORTED;
     TrainPackBuilder b;
     const int D = lay.D, RT = d.RPW * kWaves;
     // transposed images (tr = 1): A[r][c] = src[c][r], src is [cols][rows]
     for (int l = 0; l < lay.L; ++l) {
-        const float* const* q = p + 3 + 16 * l;        // ln1.w ln1.b ln2.w ln2.b key.w key.b query.w query.b value.w value.b proj.w proj.b fc1.w fc1.b fc2.w fc2.b
+        const LayerParams& y = m.layer[l];
         const uint32_t base = (uint32_t)l * bi.layer_bytes;
-        const float* w3[3] = {q[6], q[4], q[8]};       // query, key, value: the [q | k | v] column order of dqkv
-        for (int part = 0; part < 3; ++part) b.mat(w3[part], base + bi.o_qkvT + (uint32_t)part * bi.dd_bytes, D, D, RT, bi.kt_d, RT, 1);
-        b.mat(q[10], base + bi.o_pT, D, D, RT, bi.kt_d, RT, 1);
-        b.mat(q[12], base + bi.o_w1T, D, 4 * D, RT, bi.kt_h, RT, 1);                      // fc1.weight [4D][D]: A[n in D][k in 4D]
-        b.mat(q[14], base + bi.o_w2T, 4 * D, D, bi.n_chunks * RT, bi.kt_d, RT, 1);        // fc2.weight [D][4D]: A[n in 4D][k in D]
+        const Qkv qkv = y.qkv();                       // the [q | k | v] column order of dqkv
+        for (int part = 0; part < 3; ++part) b.mat(qkv.w[part].p, base + bi.o_qkvT + (uint32_t)part * bi.dd_bytes, D, D, RT, bi.kt_d, RT, 1);
+        b.mat(y.pw.p, base + bi.o_pT, D, D, RT, bi.kt_d, RT, 1);
+        b.mat(y.f1w.p, base + bi.o_w1T, D, 4 * D, RT, bi.kt_h, RT, 1);                    // fc1.weight [4D][D]: A[n in D][k in 4D]
+        b.mat(y.f2w.p, base + bi.o_w2T, 4 * D, D, bi.n_chunks * RT, bi.kt_d, RT, 1);      // fc2.weight [D][4D]: A[n in 4D][k in D]
     }
     return launch_train_pack(b.t, img, s);
 }

@@ -2105,11 +2105,6 @@ static hipError_t record_event(int which, hipStream_t st, hipEvent_t* ev) {
     const hipError_t e = step_event(which, ev);
     return e != hipSuccess ? e : hipEventRecord(*ev, st);
 }
-static size_t carve_t(size_t& cur, size_t bytes) {
-    const size_t off = cur;
-    cur = round_up_sz(cur + bytes, 256);
-    return off;
-}
 
 struct TrainLayerWs {
     size_t w_qkv, b_qkv, w_proj, w_fc1, w_fc2;                    // operand-typed weight copies (b_qkv fp32 [3D])
@@ -2150,44 +2145,44 @@ static bool make_train_ws(const beso_config* c, int batch, int t, int precision,
     w->ap = round_up(c->act_dim, 16);
     size_t cur = 0;
     const size_t na = (size_t)batch * t * c->act_dim;
-    w->noised = carve_t(cur, f * na); w->target = carve_t(cur, f * na);
-    w->x0 = carve_t(cur, f * M * D); w->xemb = carve_t(cur, e * M * w->Ke);
-    w->xemb32 = carve_t(cur, e == 4 ? 0 : f * M * w->Ke); w->wcat = carve_t(cur, f * (size_t)D * w->Ke);
+    w->noised = carve(cur, f * na); w->target = carve(cur, f * na);
+    w->x0 = carve(cur, f * M * D); w->xemb = carve(cur, e * M * w->Ke);
+    w->xemb32 = carve(cur, e == 4 ? 0 : f * M * w->Ke); w->wcat = carve(cur, f * (size_t)D * w->Ke);
     if (e == 4) w->xemb32 = w->xemb;                                // (fp32 mode: the operand-typed matrix IS the fp32 one)
-    w->stf = carve_t(cur, f * M * 2); w->xf = carve_t(cur, e * M * D);
-    w->pred = carve_t(cur, f * M * w->ap); w->dpred = carve_t(cur, e * M * w->ap);
-    w->b_head = carve_t(cur, f * w->ap);
-    w->dw_cat = carve_t(cur, f * (size_t)w->Ke * D);
+    w->stf = carve(cur, f * M * 2); w->xf = carve(cur, e * M * D);
+    w->pred = carve(cur, f * M * w->ap); w->dpred = carve(cur, e * M * w->ap);
+    w->b_head = carve(cur, f * w->ap);
+    w->dw_cat = carve(cur, f * (size_t)w->Ke * D);
     w->Hp = c->linear_output ? 0 : round_up(kHeadHidden, 8);
     {
         // linear head: w_head [ap][D]; MLP head: w_hid [Hp][D] (first layer) and w_head [ap][Hp] (second layer)
         const size_t Kh = w->Hp ? (size_t)w->Hp : (size_t)D, Ma = (size_t)batch * t;
-        w->w_head = carve_t(cur, e * (size_t)w->ap * Kh); w->dw_head = carve_t(cur, f * (size_t)w->ap * Kh);
-        w->w_hid = carve_t(cur, e * (size_t)w->Hp * D); w->b_hid = carve_t(cur, f * (size_t)(w->Hp + 8));
-        w->dw_hid = carve_t(cur, f * (size_t)w->Hp * D); w->db_hid = carve_t(cur, f * (size_t)(w->Hp + 8));
-        w->hz = carve_t(cur, e * Ma * w->Hp); w->ha = carve_t(cur, e * Ma * w->Hp); w->hdz = carve_t(cur, e * Ma * w->Hp);
+        w->w_head = carve(cur, e * (size_t)w->ap * Kh); w->dw_head = carve(cur, f * (size_t)w->ap * Kh);
+        w->w_hid = carve(cur, e * (size_t)w->Hp * D); w->b_hid = carve(cur, f * (size_t)(w->Hp + 8));
+        w->dw_hid = carve(cur, f * (size_t)w->Hp * D); w->db_hid = carve(cur, f * (size_t)(w->Hp + 8));
+        w->hz = carve(cur, e * Ma * w->Hp); w->ha = carve(cur, e * Ma * w->Hp); w->hdz = carve(cur, e * Ma * w->Hp);
     }
     // The partial sums of the deterministic step: the largest user is the FC1 bias gradient, one row of 4 D sums per 64 token
     // rows (two per 128-row tile) -- or the MLP head's hidden bias, Hp sums per row, where that is wider; the loss takes one
     // float per block of loss_kernel's grid (at most 1024).  The uses follow each other on the compute stream, each with its
     // second-stage launch behind it: one slab serves them all.
     w->det_floats = det_part_floats(M, D, w->Hp);
-    w->det_part = carve_t(cur, f * w->det_floats);
-    w->dx = carve_t(cur, f * M * D); w->dx0b = carve_t(cur, e * M * D); w->dxn = carve_t(cur, f * M * D);
-    w->dy = carve_t(cur, e * M * D);
+    w->det_part = carve(cur, f * w->det_floats);
+    w->dx = carve(cur, f * M * D); w->dx0b = carve(cur, e * M * D); w->dxn = carve(cur, f * M * D);
+    w->dy = carve(cur, e * M * D);
     {
         const size_t Ma = (size_t)batch * t;
-        w->ya = carve_t(cur, e * Ma * D); w->xa = carve_t(cur, f * Ma * D);
-        w->dxa = carve_t(cur, f * Ma * D); w->dya = carve_t(cur, e * Ma * D);
+        w->ya = carve(cur, e * Ma * D); w->xa = carve(cur, f * Ma * D);
+        w->dxa = carve(cur, f * Ma * D); w->dya = carve(cur, e * Ma * D);
     }
-    w->ln_part = carve_t(cur, f * (size_t)(2 * c->n_layers + 1) * ((M + 15) / 16) * 3 * D);     // LayerNorm backward block partials
+    w->ln_part = carve(cur, f * (size_t)(2 * c->n_layers + 1) * ((M + 15) / 16) * 3 * D);     // LayerNorm backward block partials
     {
         Layout lay;
         const bool img = precision == BESO_PREC_BF16 && make_layout(c, BESO_PREC_BF16, &lay);
         const size_t tail_b = img ? fused_train_image_bytes(lay) : 0, whole_b = img ? fused_train_whole_image_bytes(lay) : 0;
-        w->fimg = carve_t(cur, tail_b > whole_b ? tail_b : whole_b);
-        w->bimg = carve_t(cur, img ? fused_train_dgrad_image_bytes(lay) : 0);
-        w->b1slab = carve_t(cur, img && fused_train_dgrad_supported(lay)
+        w->fimg = carve(cur, tail_b > whole_b ? tail_b : whole_b);
+        w->bimg = carve(cur, img ? fused_train_dgrad_image_bytes(lay) : 0);
+        w->b1slab = carve(cur, img && fused_train_dgrad_supported(lay)
                                      ? f * (size_t)c->n_layers * fused_train_dgrad_blocks((int)M) * 4 * D : 0);
     }
     {
@@ -2213,19 +2208,19 @@ static bool make_train_ws(const beso_config* c, int batch, int t, int precision,
         const int sp_max = w->w_splits > w->w_splits_panel ? w->w_splits : w->w_splits_panel;
         const size_t Kh = w->Hp ? (size_t)w->Hp : (size_t)D;
         w->wslab_floats = train_grad_floats(c) + (size_t)w->Ke * D + (size_t)w->ap * Kh + (size_t)w->Hp * D + 8 * (size_t)(6 * c->n_layers + 8);
-        w->wslab = carve_t(cur, sp_max > 1 ? f * sp_max * w->wslab_floats : 0);
+        w->wslab = carve(cur, sp_max > 1 ? f * sp_max * w->wslab_floats : 0);
     }
     for (int l = 0; l < c->n_layers; ++l) {
         TrainLayerWs& y = w->layer[l];
-        y.w_qkv = carve_t(cur, e * (size_t)3 * D * D); y.b_qkv = carve_t(cur, f * (size_t)3 * D);
-        y.w_proj = carve_t(cur, e * (size_t)D * D);
-        y.w_fc1 = carve_t(cur, e * (size_t)4 * D * D); y.w_fc2 = carve_t(cur, e * (size_t)4 * D * D);
-        y.x_mid = carve_t(cur, f * M * D); y.x_out = carve_t(cur, f * M * D);
-        y.st1 = carve_t(cur, f * M * 2); y.st2 = carve_t(cur, f * M * 2);
-        y.xn1 = carve_t(cur, e * M * D); y.qkv = carve_t(cur, e * M * 3 * D); y.y = carve_t(cur, e * M * D);
-        y.xn2 = carve_t(cur, e * M * D); y.h = carve_t(cur, e * M * 4 * D); y.g = carve_t(cur, e * M * 4 * D);
-        y.dyo = carve_t(cur, e * M * D); y.dym = carve_t(cur, e * M * D); y.dh = carve_t(cur, e * M * 4 * D);
-        y.dqkv = carve_t(cur, e * M * 3 * D);
+        y.w_qkv = carve(cur, e * (size_t)3 * D * D); y.b_qkv = carve(cur, f * (size_t)3 * D);
+        y.w_proj = carve(cur, e * (size_t)D * D);
+        y.w_fc1 = carve(cur, e * (size_t)4 * D * D); y.w_fc2 = carve(cur, e * (size_t)4 * D * D);
+        y.x_mid = carve(cur, f * M * D); y.x_out = carve(cur, f * M * D);
+        y.st1 = carve(cur, f * M * 2); y.st2 = carve(cur, f * M * 2);
+        y.xn1 = carve(cur, e * M * D); y.qkv = carve(cur, e * M * 3 * D); y.y = carve(cur, e * M * D);
+        y.xn2 = carve(cur, e * M * D); y.h = carve(cur, e * M * 4 * D); y.g = carve(cur, e * M * 4 * D);
+        y.dyo = carve(cur, e * M * D); y.dym = carve(cur, e * M * D); y.dh = carve(cur, e * M * 4 * D);
+        y.dqkv = carve(cur, e * M * 3 * D);
     }
     w->total = cur;
     return true;
@@ -2267,24 +2262,13 @@ int train_early_layer(const beso_config* c) {
     return L - n;
 }
 void train_early_range(const beso_config* c, size_t* begin, size_t* end) {
-    const size_t D = (size_t)c->embed_dim, seq = (size_t)c->goal_seq_len + c->obs_seq_len + 1;
-    const size_t per_layer = 4 * D + 4 * (D * D + D) + (4 * D * D + 4 * D) + (4 * D * D + D);
-    const size_t layers0 = seq * D + D * (size_t)c->obs_dim + D;
     const int l0 = train_early_layer(c);
     if (l0 < 1) { *begin = *end = 0; return; }                     // fewer than two layers: nothing is early
-    *begin = layers0 + per_layer * (size_t)l0;
-    *end = layers0 + per_layer * (size_t)c->n_layers + 2 * D;      // ... + ln_f weight and bias
+    const ModelParams m(c);
+    *begin = m.layer[l0].ln1w.offset;
+    *end = m.lnfb.offset + m.lnfb.count();
 }
-size_t train_grad_floats(const beso_config* c) {
-    if (validate_config(c) != BESO_OK) return 0;
-    const size_t D = c->embed_dim, seq = c->goal_seq_len + c->obs_seq_len + 1;
-    size_t n = seq * D + D * c->obs_dim + D;
-    n += (size_t)c->n_layers * (4 * D + 4 * (D * D + D) + (4 * D * D + 4 * D) + (4 * D * D + D));
-    n += 2 * D + 2 * D + D * c->act_dim + D;
-    n += c->linear_output ? (size_t)c->act_dim * D + c->act_dim
-                          : (size_t)kHeadHidden * D + kHeadHidden + (size_t)c->act_dim * kHeadHidden + c->act_dim;
-    return n;
-}
+size_t train_grad_floats(const beso_config* c) { return validate_config(c) == BESO_OK ? ModelParams(c).floats : 0; }
 
 // The tail-block forward pays off once its 96-token tiles are several rounds of workgroups (measured on MI355X, kitchen:
 // 8192 samples = 939 tiles 16.57 vs 17.41 ms per step; 1024 samples = 118 tiles 3.43 vs 3.39 ms -- at under one round both
@@ -2346,38 +2330,6 @@ struct TrainCall {
     char* ws; hipStream_t s, early_stream, loss_stream; hipError_t* err; int* err_line; const VjpIo* vjp;
     float *state_grad, *goal_grad;                        // the gradients with respect to the state / goal inputs (nullptr: not asked for)
 };
-
-// ---- parameters: the parameter / gradient pointers, order of beso_pack_weights
-struct PG { const float* p; float* g; };
-struct LayerPG { PG ln1w, ln1b, ln2w, ln2b, kw, kb, qw, qb, vw, vb, pw, pb, f1w, f1b, f2w, f2b; };
-struct TrainParams {
-    PG pos, tokw, tokb;
-    LayerPG lp[kMaxLayers];
-    PG lnfw, lnfb, sigw, sigb, actw, actb, h0w, h0b, hw, hb;
-    size_t n_grad;                                        // floats of the flat gradient buffer
-};
-// advance = false (input VJP): every gradient pointer stays on `gflat`, the scratch slab
-static TrainParams walk_params(const beso_config* c, const float* const* q, float* gflat, bool advance) {
-    const size_t D = c->embed_dim, D4 = 4 * D, act = c->act_dim, seq = c->goal_seq_len + c->obs_seq_len + 1;
-    TrainParams r;
-    float* g = gflat;
-    auto take = [&](size_t n) { PG x{*q, g}; ++q; if (advance) g += n; return x; };
-    r.pos = take(seq * D); r.tokw = take(D * c->obs_dim); r.tokb = take(D);
-    for (int l = 0; l < c->n_layers; ++l) {
-        LayerPG& y = r.lp[l];
-        y.ln1w = take(D); y.ln1b = take(D); y.ln2w = take(D); y.ln2b = take(D);
-        y.kw = take(D * D); y.kb = take(D); y.qw = take(D * D); y.qb = take(D);
-        y.vw = take(D * D); y.vb = take(D); y.pw = take(D * D); y.pb = take(D);
-        y.f1w = take(D4 * D); y.f1b = take(D4); y.f2w = take(D * D4); y.f2b = take(D);
-    }
-    r.lnfw = take(D); r.lnfb = take(D); r.sigw = take(D); r.sigb = take(D); r.actw = take(D * act); r.actb = take(D);
-    // action head: Linear(D, act), or Linear(D, 100) - SiLU - Linear(100, act)   (score_gpts.py:184-191)
-    const bool mlp_head = !c->linear_output;
-    r.h0w = mlp_head ? take((size_t)kHeadHidden * D) : PG{nullptr, nullptr}; r.h0b = mlp_head ? take(kHeadHidden) : PG{nullptr, nullptr};
-    r.hw = take(act * (mlp_head ? (size_t)kHeadHidden : D)); r.hb = take(act);
-    r.n_grad = (size_t)(g - gflat);
-    return r;
-}
 
 // ---- plan: which form every part of the step takes.  A pure host function of the call's shape and flags.
 struct TrainPlan {
@@ -2551,6 +2503,7 @@ struct WgradGroup {
 template <typename E>
 struct TrainStep : TrainCall {
     const TrainWs& w;
+    const ModelParams& par;                               // the call's parameters and their gradients (VJP: all on the scratch slab)
     const int D = c->embed_dim, H = c->n_heads, hd = D / H, L = c->n_layers, G = c->goal_seq_len, obs = c->obs_dim, act = c->act_dim;
     const int seq = G + c->obs_seq_len + 1, M = w.M, T = w.T, Ke = w.Ke, ap = w.ap, D3 = 3 * D, D4 = 4 * D;
     const int Ma = batch * t;                             // compact action rows (last layer's projection, MLP, ln_f, head)
@@ -2559,9 +2512,8 @@ struct TrainStep : TrainCall {
     const float attn_ik = attn_p > 0.f ? 1.0f / (1.0f - attn_p) : 1.f, resid_ik = resid_p > 0.f ? 1.0f / (1.0f - resid_p) : 1.f;
     const bool fork = loss_stream != nullptr;             // the weight copies run on the caller's second stream: ps
     const hipStream_t ps = fork ? loss_stream : s;
-    const TrainParams par = walk_params(c, p, gflat, !vjp);
     const TrainPlan plan = make_train_plan(c, flags, M, T, t, embed_p, resid_p, sizeof(E), fork);
-    const LayerPG* const lp = par.lp;
+    const LayerParams* const lp = par.layer;
     // BESO_TRAIN_DETERMINISTIC: the three sums the step otherwise forms with atomics (column-sum epilogues, colsum_kernel, the loss)
     // go through the slab w.det_part and a second launch each
     const bool det = flags & BESO_TRAIN_DETERMINISTIC;
@@ -2571,7 +2523,7 @@ struct TrainStep : TrainCall {
     // FC1 bias gradients of the transposed-formulation data-gradient kernel: per-workgroup sums in a slab per layer, added up
     // (assigned, not accumulated) where the LayerNorm partial sums are
     const float* b1_slabs[kMaxLayers]; float* b1_outs[kMaxLayers]; int b1_blocks[kMaxLayers]; int b1_n = 0;
-    TrainStep(const TrainCall& call, const TrainWs& ws_) : TrainCall(call), w(ws_) {
+    TrainStep(const TrainCall& call, const TrainWs& ws_, const ModelParams& par_) : TrainCall(call), w(ws_), par(par_) {
         ln.base = F(w.ln_part); ln.grid = (M + 4 * kRpw - 1) / (4 * kRpw); ln.D = D;
         wg.gt.n = 0; wg.off = vjp != nullptr; wg.panel_w = plan.panel_w; wg.per_op = flags & BESO_TRAIN_PLAN_PER_OP; wg.M = M; wg.s = s;
         wg.splits = w.w_splits; wg.splits_panel = w.w_splits_panel; wg.slab = F(w.wslab); wg.slab_floats = w.wslab_floats;
@@ -2611,12 +2563,12 @@ struct TrainStep : TrainCall {
             TRY(pack_wcat(ps));
             TRY(record_event(kEvWcat, ps, &ev_wcat));
         }
-        if (!vjp) TRY(hipMemsetAsync(gflat, 0, sizeof(float) * par.n_grad, ps));
+        if (!vjp) TRY(hipMemsetAsync(gflat, 0, sizeof(float) * par.floats, ps));
         // (first what the forward launch needs -- its fragment image --, then the plain copies the backward pass reads)
-        if (plan.use_whole) TRY_ST(fused_train_whole_pack(plan.lay, p, ws + w.fimg, ps));
-        else if (plan.use_tail) TRY_ST(fused_train_pack(plan.lay, p, ws + w.fimg, ps));
+        if (plan.use_whole) TRY_ST(fused_train_whole_pack(plan.lay, par, ws + w.fimg, ps));
+        else if (plan.use_tail) TRY_ST(fused_train_pack(plan.lay, par, ws + w.fimg, ps));
         if (fork) TRY(record_event(kEvJoin, ps, &ev_join));
-        if (plan.use_dgrad) TRY_ST(fused_train_dgrad_pack(plan.lay, p, ws + w.bimg, ps));
+        if (plan.use_dgrad) TRY_ST(fused_train_dgrad_pack(plan.lay, par, ws + w.bimg, ps));
         // (nobody reads the operand-typed copies when the forward is the one-launch kernel and the data gradients take the transposed weights)
         if (!(plan.use_whole && plan.use_dgrad)) TRY(pack_layer_weights());
         if (mlp_head) {
@@ -2686,7 +2638,7 @@ struct TrainStep : TrainCall {
         }
         return BESO_OK;
     }
-    hipError_t ln_fwd(const float* x, PG gamma, PG beta, E* out, float* st, int rows) {
+    hipError_t ln_fwd(const float* x, const Param& gamma, const Param& beta, E* out, float* st, int rows) {
         with_ln_vec(plan.nv, [&](auto nv) {
             hipLaunchKernelGGL((ln_fwd_kernel<E, decltype(nv)::value>), dim3((rows + 3) / 4), dim3(256), 0, s, x, gamma.p, beta.p, out, st, rows, D);
         });
@@ -2994,8 +2946,8 @@ static int run_train_step(TrainCall a, int n_params, size_t workspace_bytes) {
     if (a.vjp ? (!a.vjp->cot || !a.vjp->denoised || !a.vjp->x_grad) : (!a.gflat || !a.noise || !a.loss_out)) return BESO_ERR_BAD_ARG;
     if (c->goal_seq_len > 0 && !a.goal) return BESO_ERR_BAD_ARG;
     if ((a.goal_grad && c->goal_seq_len == 0) || (((uintptr_t)a.state_grad | (uintptr_t)a.goal_grad) & 3)) return BESO_ERR_BAD_ARG;
-    if (n_params != 3 + 16 * c->n_layers + 6 + (c->linear_output ? 2 : 4)) return BESO_ERR_BAD_ARG;
-    for (int i = 0; i < n_params; ++i) if (!a.p[i]) return BESO_ERR_BAD_ARG;
+    ModelParams par(c);
+    if (par.read(a.p, n_params) != BESO_OK) return BESO_ERR_BAD_ARG;
     // (the input VJP has neither a loss nor a bias gradient: BESO_TRAIN_DETERMINISTIC means nothing there and is refused)
     if (a.flags & ~((a.vjp ? 0 : BESO_TRAIN_LAST_ACTION_ONLY | BESO_TRAIN_DETERMINISTIC) | BESO_TRAIN_PLAN_PER_OP | BESO_TRAIN_PLAN_TILES)) return BESO_ERR_BAD_ARG;
     if (!(a.attn_p >= 0.f && a.attn_p < 1.f && a.resid_p >= 0.f && a.resid_p < 1.f && a.embed_p >= 0.f && a.embed_p < 1.f &&
@@ -3010,8 +2962,9 @@ static int run_train_step(TrainCall a, int n_params, size_t workspace_bytes) {
         a.gflat = (float*)(a.ws + w.dw_cat);
         (void)hipGetLastError();
     }
-    if (a.precision == BESO_PREC_FP32) return TrainStep<float>(a, w).run();
-    return TrainStep<uint16_t>(a, w).run();
+    par.set_grads(a.gflat, !a.vjp);
+    if (a.precision == BESO_PREC_FP32) return TrainStep<float>(a, w, par).run();
+    return TrainStep<uint16_t>(a, w, par).run();
 }
 
 int train_loss_grad(const beso_config* c, const float* const* params, int n_params, float* grads_flat, int precision,

@@ -186,7 +186,8 @@ const char* beso_last_error(void);
 /* Number of parameter tensors, in the order of the reference module's named_parameters():
  * pos_emb, tok_emb.{weight,bias}, per block {ln1,ln2}.{weight,bias}, attn.{key,query,value,proj}.{weight,bias},
  * mlp.{0,2}.{weight,bias}; ln_f.{weight,bias}, sigma_emb.{weight,bias}, action_emb.{weight,bias},
- * action_pred[.0/.2].{weight,bias}.  Linear weights are torch layout [out, in], fp32.            */
+ * action_pred[.0/.2].{weight,bias}.  Linear weights are torch layout [out, in], fp32.
+ * (beso_amd/csrc/params.h is the only implementation of this order.)                            */
 int beso_num_params(const beso_config* cfg);
 
 /* Size of the packed-weight image for `precision`, in bytes (0 on bad config). */

@@ -158,23 +158,33 @@ def test_feed_argument_errors_do_not_touch_the_device(lib):
     assert call(batch=0, goal_mode=_lib.GOAL_TAIL, draws=None) == 0
 
 
+_LAYOUT_CASES = [
+    dict(state_dim=7, action_dim=3, embed_dim=48, n_layers=4, n_heads=6, goal_seq_len=2, obs_seq_len=3, linear_output=True),
+    dict(state_dim=5, action_dim=2, embed_dim=32, n_layers=3, n_heads=4, goal_seq_len=1, obs_seq_len=4, linear_output=False),
+    dict(state_dim=5, action_dim=2, embed_dim=32, n_layers=1, n_heads=4, goal_seq_len=1, obs_seq_len=4, linear_output=True),
+    # the library's parameter table (csrc/params.h) against the module: every depth, both heads, both widths, with and without goals
+    *[dict(state_dim=6, action_dim=3, embed_dim=D, n_layers=L, n_heads=4, goal_seq_len=G, obs_seq_len=3, linear_output=lin)
+      for L in (1, 2, 3, 6) for lin in (True, False) for D, G in ((32, 2), (48, 0))],
+]
+
+
 def test_early_gradient_range_matches_parameter_layout(lib):
-    """beso_grad_early_range = [offset of blocks[l0].ln1.weight, end of ln_f.bias) in the order of the parameters, 1 <= l0 < L."""
+    """The module's named_parameters() are the library's list: beso_num_params tensors, beso_grad_floats floats, and
+    beso_grad_early_range = [offset of blocks[l0].ln1.weight, end of ln_f.bias) in their order, 1 <= l0 < L."""
     import torch
     from beso_amd.agents.diffusion_agents.k_diffusion.score_gpts import DiffusionGPT
-    for kw in (dict(state_dim=7, action_dim=3, embed_dim=48, n_layers=4, n_heads=6, goal_seq_len=2, obs_seq_len=3, linear_output=True),
-               dict(state_dim=5, action_dim=2, embed_dim=32, n_layers=3, n_heads=4, goal_seq_len=1, obs_seq_len=4,
-                    linear_output=False),
-               dict(state_dim=5, action_dim=2, embed_dim=32, n_layers=1, n_heads=4, goal_seq_len=1, obs_seq_len=4, linear_output=True)):
+    for kw in _LAYOUT_CASES:
         net = DiffusionGPT(device="cpu", goal_conditioned=True, embed_pdrob=0.0, attn_pdrop=0.0, resid_pdrop=0.0, **kw)
         cfg = net.shape(0.5).c_struct()
+        assert cfg.goal_seq_len == kw["goal_seq_len"] and cfg.n_layers == kw["n_layers"] and cfg.embed_dim == kw["embed_dim"], kw
         b, e = C.c_size_t(7), C.c_size_t(7)
         assert lib.beso_grad_early_range(C.byref(cfg), C.byref(b), C.byref(e)) == 0
         offs, off = {}, 0
         for name, prm in net.named_parameters():
             offs[name] = (off, off + prm.numel())
             off += prm.numel()
-        assert off == lib.beso_grad_floats(C.byref(cfg))
+        assert len(offs) == lib.beso_num_params(C.byref(cfg)), kw
+        assert off == lib.beso_grad_floats(C.byref(cfg)), kw
         L = kw["n_layers"]
         if L < 2:
             assert b.value == e.value
