@@ -6,18 +6,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import beso_oracle as O
 from conftest import load_golden, weights_from_fixture, rel_err
-from test_gpu_parity import make_module, G, _weights, set_level
+from support import make_denoiser, to_dev
+from test_gpu_parity import _weights, set_level
 
 for fixture, cfg_name in [("kitchen_forward_std002.npz", "kitchen"), ("kitchen_forward_std008.npz", "kitchen"),
                           ("block_push_forward.npz", "block_push")]:
     fx = load_golden(fixture); cfg = O.CONFIGS[cfg_name]
     for prec in ("fp32", "bf16", "bf16x3"):
-        m = make_module(cfg, _weights(fx, cfg), prec)
+        m = make_denoiser(cfg, _weights(fx, cfg), prec)
         worst = 0.0
         with torch.no_grad():
             for t in fx["ts"]:
                 p = f"t{int(t)}::"
-                s, a, g, sg = (G(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
+                s, a, g, sg = (to_dev(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
                 e1 = rel_err(m(s, a, g, sg).cpu().numpy(), fx[p + "denoised"])
                 e2 = rel_err(m(s, a, g, sg, uncond=True).cpu().numpy(), fx[p + "denoised_uncond"])
                 e3 = rel_err(m.inner_model(s, a, g, sg).cpu().numpy(), fx[p + "inner"])
@@ -27,7 +28,7 @@ for fixture, cfg_name in [("kitchen_forward_std002.npz", "kitchen"), ("kitchen_f
 from beso_amd import synthetic as S
 cfg = S.SHAPES["kitchen"]; w = S.make_weights(cfg, seed=0, std=0.02)
 for prec in ("bf16", "bf16x3"):
-    m = make_module(O.CONFIGS["kitchen"], w, prec)
+    m = make_denoiser(O.CONFIGS["kitchen"], w, prec)
     for B in (64, 512, 4096):
         s_np, g_np, a_np = S.make_inputs(cfg, B, seed=1)
         s, g, a = (torch.from_numpy(v).cuda() for v in (s_np, g_np, a_np))
@@ -47,12 +48,12 @@ fns = {"ddim": ks.sample_ddim, "euler": ks.sample_euler, "heun": ks.sample_heun,
 for fixture, cfg_name in [("kitchen_samplers.npz", "kitchen"), ("block_push_heun_cfg.npz", "block_push")]:
     fx = load_golden(fixture); cfg = O.CONFIGS[cfg_name]
     for prec in ("fp32", "bf16x3"):
-        m = make_module(cfg, _weights(fx, cfg), prec)
+        m = make_denoiser(cfg, _weights(fx, cfg), prec)
         lam = float(fx["cond_lambda"])
         model = m if lam < 0 else ClassifierFreeSampleModel(m, lam)
         for key in sorted(k[:-5] for k in fx if k.endswith("::out")):
             n = int(key.split("_")[-2]); sampler = key[: key.index(f"_{n}_")]
-            out = fns[sampler](model, G(fx["state"]), G(fx["x_t"]), G(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]), disable=True)
+            out = fns[sampler](model, to_dev(fx["state"]), to_dev(fx["x_t"]), to_dev(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]), disable=True)
             print(f"{fixture}:{key} {prec}: {rel_err(out.cpu().numpy(), fx[key + '::out']):.3e}", flush=True)
 
 # ---- fused bf16 kernel against the per-op bf16 kernels (same arithmetic type, different rounding points)
@@ -62,10 +63,10 @@ for cfg_name in ("kitchen", "block_push"):
     cfg = O.CONFIGS[cfg_name]
     for std in (0.02, 0.08):
         wts = O.make_weights(cfg, seed=3, std=std)
-        m = make_module(cfg, wts, "bf16")
+        m = make_denoiser(cfg, wts, "bf16")
         s_np, g_np, a_np = O.make_inputs(cfg, 256, seed=9)
         sg_np = np.linspace(0.05, 1.0, 256).astype(np.float32)
-        s, a, g, sg = G(s_np), G(a_np), G(g_np), G(sg_np)
+        s, a, g, sg = to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)
         ref = O.denoise(wts, cfg, s_np, a_np, g_np, sg_np)
         outs = {}
         with torch.no_grad():

@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 def main():
     import test_gpu_parity as T
+    from support import make_denoiser, to_dev
     from beso_amd import _lib
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     O = T.O
@@ -31,7 +32,7 @@ def main():
         cfg = O.CONFIGS[name]
         if name not in mods:
             w = O.make_weights(cfg, seed=11, std=0.03)
-            mods[name] = (w, T.make_module(cfg, w, "bf16"))
+            mods[name] = (w, make_denoiser(cfg, w, "bf16"))
         w, m = mods[name]
         B = int(rng.choice([1, 2, 3, 7, 8, 9, 31, 64, 65, 200, 513, int(rng.integers(1, 700))]))
         if name == "long_horizon":
@@ -46,7 +47,7 @@ def main():
             with torch.no_grad():
                 for lvl in (2, 0):
                     T.set_level(lvl)
-                    outs[lvl] = model(T.G(s_np), T.G(a_np), T.G(g_np), T.G(sg_np)).cpu().numpy()
+                    outs[lvl] = model(to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)).cpu().numpy()
         finally:
             T.set_level(2)
         e = T.rel_err(outs[2], outs[0])

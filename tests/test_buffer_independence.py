@@ -42,7 +42,7 @@ import torch
 
 from oracle import beso_oracle as O
 from beso_amd import _lib
-from test_gpu_parity import make_module, G, _train_module, _train_inputs, _grad_errors
+from support import grad_errors, make_denoiser, to_dev, train_inputs
 
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -144,7 +144,7 @@ def _stream():
 @functools.lru_cache(maxsize=None)
 def _env(cfg_name, precision):
     cfg = _CFGS[cfg_name]
-    m = make_module(cfg, O.make_weights(cfg, seed=4, std=0.03), precision)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=4, std=0.03), precision)
     inner = m.inner_model
     return cfg, m, inner, inner.runtime(cfg.sigma_data)
 
@@ -155,7 +155,7 @@ def _inputs(cfg_name, B, t):
     s, g, a = O.make_inputs(cfg, B, seed=B + 3 * t, t=t)
     rng = np.random.default_rng(B + 7 * t)
     noise = rng.standard_normal((5,) + a.shape).astype(np.float32)            # up to five steps' draws
-    return G(s), G(g), G(a), G(np.linspace(0.1, 0.9, B).astype(np.float32)), G(noise)
+    return to_dev(s), to_dev(g), to_dev(a), to_dev(np.linspace(0.1, 0.9, B).astype(np.float32)), to_dev(noise)
 
 
 _SIG3 = (1.0, 0.3, 0.05, 0.0)                  # three steps
@@ -415,7 +415,7 @@ def test_a_small_call_after_a_large_one_equals_a_fresh_modules(cfg_name, precisi
     from beso_amd.runtime import plan
     cfg = O.CONFIGS[cfg_name]
     w = O.make_weights(cfg, seed=4, std=0.03)
-    T = lambda B, t, seed: tuple(G(v) for v in O.make_inputs(cfg, B, seed=seed, t=t))
+    T = lambda B, t, seed: tuple(to_dev(v) for v in O.make_inputs(cfg, B, seed=seed, t=t))
     sig = torch.tensor(_SIG3)
 
     def denoise(m, s, g, a, sg):
@@ -425,13 +425,13 @@ def test_a_small_call_after_a_large_one_equals_a_fresh_modules(cfg_name, precisi
     for hint in (0, _lib.PLAN_FUSED):
         with plan(forward=hint), torch.no_grad():
             s3, g3, a3 = T(3, 2, 11)
-            sg3 = G(np.array([0.2, 0.5, 0.8], dtype=np.float32))
-            fresh = make_module(cfg, w, precision)
+            sg3 = to_dev(np.array([0.2, 0.5, 0.8], dtype=np.float32))
+            fresh = make_denoiser(cfg, w, precision)
             ref = denoise(fresh, s3, g3, a3, sg3).clone()
             ref_lms = fresh.fused_sampler("lms", s3, a3, g3, sig, cond_lambda=lam, order=4).clone()
-            used = make_module(cfg, w, precision)
+            used = make_denoiser(cfg, w, precision)
             sb, gb, ab = T(big, cfg.obs_seq_len, 12)
-            denoise(used, sb, gb, ab, G(np.linspace(0.1, 0.9, big).astype(np.float32)))
+            denoise(used, sb, gb, ab, to_dev(np.linspace(0.1, 0.9, big).astype(np.float32)))
             got = denoise(used, s3, g3, a3, sg3)
             assert torch.isfinite(got).all() and torch.equal(got, ref), (cfg_name, precision, hex(hint), "denoise after a large call")
             used.fused_sampler("dpmpp_2m", sb, ab, gb, torch.tensor(_SIG5), cond_lambda=lam)
@@ -499,10 +499,10 @@ def _train_step_runs(cfg_name, B, t, precision, mkw, rkw, monkeypatch, modes=("n
     from beso_amd import runtime, training
     from beso_amd.training import HipTrainStep
     cfg = _CFGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, **mkw)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, train=True, **mkw)
     step = HipTrainStep(m.inner_model, float(cfg.sigma_data))
     params = list(m.inner_model.parameters())
-    raw = _train_inputs(cfg, B, seed=1)
+    raw = train_inputs(cfg, B, seed=1)
     if t is not None:
         raw = tuple(v[:, :t].contiguous() if i in (0, 1, 3) else v for i, v in enumerate(raw))
     early, lossq = torch.cuda.Stream(), torch.cuda.Stream()
@@ -527,7 +527,7 @@ def _train_step_runs(cfg_name, B, t, precision, mkw, rkw, monkeypatch, modes=("n
                 ref = (loss.item(), [g.clone() for g in got])   # ZERO, no side streams
                 continue
             le = abs(loss.item() - ref[0]) / abs(ref[0])
-            errs = _grad_errors(got, ref[1], floor)
+            errs = grad_errors(got, ref[1], floor)
             print(f"[buffers] {tag}: loss {le:.2e}, worst gradient {max(errs):.2e}")
             if not le < ltol:
                 failures.append(f"{tag}: loss differs from the ZERO run by {le:.3e} (bound {ltol})")
@@ -555,7 +555,7 @@ def test_training_step_does_not_depend_on_what_its_buffers_held(cfg_name, B, t, 
         ref_loss.backward()
         ltol, gtol, floor = _bounds(precision)
         assert abs(ref[0] - ref_loss.item()) < ltol * abs(ref_loss.item())
-        errs = _grad_errors(ref[1], [p.grad for p in m.inner_model.parameters()], floor)
+        errs = grad_errors(ref[1], [p.grad for p in m.inner_model.parameters()], floor)
         assert max(errs) < gtol, errs
 
 
@@ -573,19 +573,19 @@ def test_a_small_training_step_after_a_large_one_equals_a_fresh_steps(precision)
     against a fresh step object, within the same bounds."""
     from beso_amd.training import HipTrainStep
     cfg = O.KITCHEN
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, train=True)
     params = list(m.inner_model.parameters())
     used, fresh = HipTrainStep(m.inner_model, float(cfg.sigma_data)), HipTrainStep(m.inner_model, float(cfg.sigma_data))
-    small = _train_inputs(cfg, 37, seed=8)
+    small = train_inputs(cfg, 37, seed=8)
     loss_f, flat_f, _ = fresh.run(*small, seed=5, fresh_grads=True)
-    used.run(*_train_inputs(cfg, 200, seed=7), seed=6, fresh_grads=True)
+    used.run(*train_inputs(cfg, 200, seed=7), seed=6, fresh_grads=True)
     ws_before = used._ws.data_ptr()
     loss_u, flat_u, _ = used.run(*small, seed=5, fresh_grads=True)
     torch.cuda.synchronize()
     assert used._ws.data_ptr() == ws_before                    # the small step ran inside the large one's workspace
     ltol, gtol, floor = _bounds(precision)
     assert torch.isfinite(flat_u).all() and abs(loss_u.item() - loss_f.item()) < ltol * abs(loss_f.item())
-    errs = _grad_errors(_split(flat_u, params), _split(flat_f, params), floor)
+    errs = grad_errors(_split(flat_u, params), _split(flat_f, params), floor)
     assert max(errs) < gtol, max(errs)
 
 
@@ -598,8 +598,8 @@ def test_denoise_vjp_does_not_depend_on_what_its_buffers_held(cfg_name, B, preci
     within the training bounds."""
     from beso_amd import runtime, training
     cfg = _CFGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision).eval()
-    state, x, goal, cot, sigma = _train_inputs(cfg, B, seed=2)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision)
+    state, x, goal, cot, sigma = train_inputs(cfg, B, seed=2)
     step_of = lambda: m._train_steps[float(cfg.sigma_data)]
 
     def run(byte):
@@ -638,13 +638,13 @@ def test_no_writes_outside_the_training_steps_buffers(cfg_name, B, precision):
     bands of each fill; nothing outside [ptr, ptr + size) changes, every result is finite and within the training bounds of
     the ZERO run."""
     cfg = _CFGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, train=True)
     inner, lib = m.inner_model, _lib.load()
     ccfg = inner.shape(float(cfg.sigma_data)).c_struct()
     params = [p.detach() for p in inner.parameters()]
     arr = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
     prec = _lib.PRECISIONS[precision]
-    state, action, goal, noise, sigma = _train_inputs(cfg, B, seed=1)
+    state, action, goal, noise, sigma = train_inputs(cfg, B, seed=1)
     t = state.shape[1]
     n_grad = int(lib.beso_grad_floats(C.byref(ccfg)))
     wsb = int(lib.beso_train_workspace_bytes(C.byref(ccfg), B, t, prec))
@@ -674,7 +674,7 @@ def test_no_writes_outside_the_training_steps_buffers(cfg_name, B, precision):
                 ref = (lv, _split(flat, params))
                 continue
             assert abs(lv - ref[0]) < ltol * abs(ref[0]), (entry, name, lv, ref[0])
-            errs = _grad_errors(_split(flat, params), ref[1], floor)
+            errs = grad_errors(_split(flat, params), ref[1], floor)
             assert max(errs) < gtol, (entry, name, max(errs))
         # the input VJP: x = action, cotangent = noise
         n_out = action.numel() * 4

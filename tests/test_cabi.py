@@ -8,15 +8,9 @@ import pytest
 
 from beso_amd import _lib
 from beso_amd.runtime import ScoreNetShape
+from support import lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from beso_amd.build import build
-    build(verbose=False)
-    return _lib.load()
 
 
 def test_library_is_built_from_the_sources_in_the_tree(lib):

@@ -2,7 +2,6 @@
 step (C1), the weight broadcast (C2), batch sharding of the inference path, and that a 2-rank
 train_step equals a single-process step on the concatenated batch."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -11,13 +10,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from support import free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _make_agent(seed):
@@ -156,7 +151,7 @@ def _worker(rank, world, port, out):
 @pytest.mark.parametrize("c1_mode", ["overlap", "sharded", "flat"])
 def test_two_rank_gloo_training_step_matches_single_process(tmp_path, autograd_training, c1_mode, monkeypatch):
     out = str(tmp_path / "dp.pt")
-    port = _free_port()
+    port = free_port()
     monkeypatch.setenv("TEST_C1_MODE", c1_mode)          # (inherited by the spawned ranks)
     mp.spawn(_worker, args=(2, port, out), nprocs=2, join=True)
     dp = torch.load(out)
@@ -273,7 +268,7 @@ def test_a_rank_without_test_data_still_joins_the_ema_all_gather(tmp_path, mode,
     (rank 1 goes straight to job_mean's all-reduce)."""
     monkeypatch.setenv("TEST_FORCE_EMA_PARTIAL", "1")
     out = str(tmp_path / "loops.pt")
-    mp.spawn(_loop_worker, args=(2, _free_port(), out, mode, "sharded", True), nprocs=2, join=True)
+    mp.spawn(_loop_worker, args=(2, free_port(), out, mode, "sharded", True), nprocs=2, join=True)
     c = torch.load(out)["counts"]
     assert c[0][1:] == c[1][1:], c
 
@@ -287,7 +282,7 @@ def test_two_rank_training_loops_take_joint_decisions(tmp_path, mode, c1, use_em
     times, stop at the same epoch and end with identical weights -- with the sharded C1 exchange (whose checkpoint path
     holds an all-gather of the EMA shadow) and without EMA evaluation included.  A rank deciding alone would hang here."""
     out = str(tmp_path / "loops.pt")
-    mp.spawn(_loop_worker, args=(2, _free_port(), out, mode, c1, use_ema), nprocs=2, join=True)
+    mp.spawn(_loop_worker, args=(2, free_port(), out, mode, c1, use_ema), nprocs=2, join=True)
     c = torch.load(out)["counts"]
     assert c[0][1:] == c[1][1:], c                      # same number of checkpoints, same number of optimizer steps
     if mode == "steps":
@@ -332,4 +327,4 @@ def _bench_train_worker(rank, world, port, c1):
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("c1", ["overlap", "sharded", "flat"])
 def test_bench_train_workload_keeps_two_gloo_replicas_identical(c1):
-    mp.spawn(_bench_train_worker, args=(2, _free_port(), c1), nprocs=2, join=True)
+    mp.spawn(_bench_train_worker, args=(2, free_port(), c1), nprocs=2, join=True)

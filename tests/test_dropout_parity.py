@@ -10,7 +10,6 @@ Bounds (those of test_hip_training_goal_masking: the same comparator on the same
 fp32 loss 2e-5, gradients 1e-4 per tensor (floor 1e-4); bf16 loss 2e-3, gradients 2.6e-2 per tensor (floor 2e-3)."""
 import contextlib
 import ctypes as C
-import functools
 
 import pytest
 import torch
@@ -18,21 +17,14 @@ import torch
 from beso_amd import _lib
 from beso_amd.runtime import ScoreNetShape
 from oracle import beso_oracle as O
+from support import Scale, TRAIN_BOUNDS, count_site_launches, grad_errors, lib, make_denoiser, train_inputs  # noqa: F401
 
 DEV = "cuda:0"
-BOUNDS = {"fp32": (2e-5, 1e-4, 1e-4), "bf16": (2e-3, 2.6e-2, 2e-3)}       # loss, per-tensor gradient, floor
 
 
 # -------------------------------------------------------------------------------------------------
 # CPU: the entry point exists and rejects bad arguments before anything is enqueued
 # -------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from beso_amd.build import build
-    build(verbose=False)
-    return _lib.load()
-
-
 def test_dropout_mask_is_exported_and_bound(lib):
     assert "beso_dropout_mask" in _lib.EXPORTS
     fn = lib.beso_dropout_mask
@@ -62,68 +54,6 @@ def test_dropout_mask_argument_errors_do_not_touch_the_device(lib):
         _lib.check(call(layer=2), "dropout_mask")
 
 
-# -------------------------------------------------------------------------------------------------
-# helpers (restated from test_gpu_parity.py: _train_module, _train_inputs, _grad_errors, count_fused_launches)
-# -------------------------------------------------------------------------------------------------
-def _train_module(cfg, w, precision, attn_pdrop=0.0, resid_pdrop=0.0, embed_pdrop=0.0, goal_drop=0.0):
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_gpts import DiffusionGPT
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_wrappers import GCDenoiser
-    inner = functools.partial(
-        DiffusionGPT, state_dim=cfg.obs_dim, device=DEV, goal_conditioned=cfg.goal_conditioned,
-        action_dim=cfg.act_dim, embed_dim=cfg.embed_dim, embed_pdrob=embed_pdrop, attn_pdrop=attn_pdrop,
-        resid_pdrop=resid_pdrop, n_layers=cfg.n_layers, n_heads=cfg.n_heads, goal_seq_len=cfg.goal_seq_len,
-        obs_seq_len=cfg.obs_seq_len, sigma_vocab_size=3, time_embedding_fn=None, goal_drop=goal_drop,
-        linear_output=cfg.linear_output, precision=precision)
-    m = GCDenoiser(inner, sigma_data=cfg.sigma_data)
-    sd = m.state_dict()
-    for k, v in w.items():
-        sd[k] = torch.from_numpy(v.copy())
-    m.load_state_dict(sd)
-    return m.to(DEV).train()
-
-
-def _train_inputs(cfg, B, seed=0):
-    """state, action, goal [B, G, obs] (one goal per sample: the kernel draws the embedding mask per sample row), noise, sigma"""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    r = lambda *s: torch.randn(*s, generator=g).to(DEV)                      # noqa: E731
-    return (r(B, cfg.obs_seq_len, cfg.obs_dim), r(B, cfg.obs_seq_len, cfg.act_dim), r(B, cfg.goal_seq_len, cfg.obs_dim),
-            r(B, cfg.obs_seq_len, cfg.act_dim), (torch.rand(B, generator=g) * 0.9 + 0.05).to(DEV))
-
-
-def _grad_errors(got, ref, floor=1e-4):
-    """per tensor ||got - ref|| / max(||ref||, floor * largest gradient entry * sqrt(numel))"""
-    gmax = max(r.abs().max().item() for r in ref)
-    return [((g - r).norm() / max(r.norm().item(), floor * gmax * r.numel() ** 0.5)).item() for g, r in zip(got, ref)]
-
-
-def _count_fused_launches(fn):
-    """fn() with the launch-site timer on the one-launch kernels' site; returns the number of launches it recorded."""
-    lib = _lib.load()
-    lib.beso_profile_enable(_lib.SITES["fused_layer"])
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, n = C.c_double(0.0), C.c_int(0)
-        assert lib.beso_profile_read(C.byref(ms), C.byref(n)) == 0
-    finally:
-        lib.beso_profile_enable(0)
-    return n.value
-
-
-class _Scale(torch.nn.Module):
-    """Stands in for an nn.Dropout: multiplies by preset keep-scales, one tensor per call, in call order."""
-
-    def __init__(self, *scales):
-        super().__init__()
-        self.scales, self.calls = scales, 0
-
-    def forward(self, x):
-        s = self.scales[self.calls % len(self.scales)]
-        self.calls += 1
-        assert s.shape == x.shape, (tuple(s.shape), tuple(x.shape))
-        return x * s
-
-
 @contextlib.contextmanager
 def injected_masks(inner, step, batch, t, seed, attn_after_v_layer=None):
     """The module's nn.Dropout layers replaced by the library's masks for (batch, t, seed); restored afterwards.  Only the
@@ -144,7 +74,7 @@ def injected_masks(inner, step, batch, t, seed, attn_after_v_layer=None):
     try:
         if embed_p > 0:
             e = step.dropout_mask("embed", 0, batch, t, seed)
-            swap(inner, "drop", _Scale(e[:, G + 1::2], e[:, G + 2::2], e[:, 1:G + 1]))
+            swap(inner, "drop", Scale(e[:, G + 1::2], e[:, G + 2::2], e[:, 1:G + 1]))
         for l, blk in enumerate(inner.blocks):
             if attn_p > 0:
                 a = step.dropout_mask("attn", l, batch, t, seed)
@@ -159,10 +89,10 @@ def injected_masks(inner, step, batch, t, seed, attn_after_v_layer=None):
                         return ((y.view(b, T, H, D // H) * diag.transpose(1, 2).unsqueeze(-1)).reshape(b, T, D),)
                     hooks.append(blk.attn.proj.register_forward_pre_hook(after_v))
                 else:
-                    swap(blk.attn, "attn_drop", _Scale(a))
+                    swap(blk.attn, "attn_drop", Scale(a))
             if resid_p > 0:
-                swap(blk.attn, "resid_drop", _Scale(step.dropout_mask("proj", l, batch, t, seed)))
-                swap(blk.mlp, "3", _Scale(step.dropout_mask("mlp", l, batch, t, seed)))
+                swap(blk.attn, "resid_drop", Scale(step.dropout_mask("proj", l, batch, t, seed)))
+                swap(blk.mlp, "3", Scale(step.dropout_mask("mlp", l, batch, t, seed)))
         yield
     finally:
         for h in hooks:
@@ -173,9 +103,9 @@ def injected_masks(inner, step, batch, t, seed, attn_after_v_layer=None):
 
 def _case(cfg_name, B, t, precision, attn_p=0.0, resid_p=0.0, embed_p=0.0, goal_drop=0.0):
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, attn_pdrop=attn_p, resid_pdrop=resid_p,
-                      embed_pdrop=embed_p, goal_drop=goal_drop)
-    state, action, goal, noise, sigma = _train_inputs(cfg, B, seed=4)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, attn_pdrop=attn_p, resid_pdrop=resid_p,
+                      embed_pdrop=embed_p, goal_drop=goal_drop, train=True)
+    state, action, goal, noise, sigma = train_inputs(cfg, B, seed=4)
     if t is not None:
         state, action, noise = state[:, :t].contiguous(), action[:, :t].contiguous(), noise[:, :t].contiguous()
     return m, (state, action, goal, noise, sigma)
@@ -190,7 +120,7 @@ def _hip(m, inputs, seed, per_op=False):
     out = {}
     set_plan(train=_lib.TRAIN_PLAN_PER_OP if per_op else 0)
     try:
-        n = _count_fused_launches(lambda: out.update(r=step.run(*inputs, seed=seed, fresh_grads=True)))
+        n = count_site_launches("fused_layer", lambda: out.update(r=step.run(*inputs, seed=seed, fresh_grads=True)))
     finally:
         set_plan(train=0)
     loss, _, views = out["r"]
@@ -220,9 +150,9 @@ def _autograd(m, step, inputs, seed, mask_seed=None, attn_after_v_layer=None):
 
 
 def _compare(tag, m, precision, got_loss, got, ref_loss, ref):
-    _, _, floor = BOUNDS[precision]
+    _, _, floor = TRAIN_BOUNDS[precision]
     lerr = abs(got_loss - ref_loss) / abs(ref_loss)
-    errs = _grad_errors(got, ref, floor)
+    errs = grad_errors(got, ref, floor)
     worst = max(range(len(errs)), key=lambda i: errs[i])
     print(f"[parity] dropout step {tag} {precision}: loss rel err {lerr:.2e}, worst gradient {errs[worst]:.2e} "
           f"({list(dict(m.named_parameters()))[worst]})")
@@ -240,7 +170,7 @@ def test_mask_properties(kind, p):
     ones for p = 0 and on the rows the step draws no mask for."""
     from beso_amd.training import HipTrainStep
     cfg = O.KITCHEN                                                          # L = 6, H = 6, D = 360, G = 2, W = 4
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32", attn_pdrop=0.3, resid_pdrop=0.05, embed_pdrop=0.1)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32", attn_pdrop=0.3, resid_pdrop=0.05, embed_pdrop=0.1, train=True)
     step = HipTrainStep(m.inner_model, cfg.sigma_data)
     B, t, seed, G = 8, 4, 4242, cfg.goal_seq_len
     T = 1 + G + 2 * t
@@ -290,7 +220,7 @@ def test_every_element_of_the_mask_is_written_and_nothing_behind_it(kind, B, t):
     not a multiple of the 16-byte store -- the last chunk is stored by element.)"""
     from beso_amd.training import HipTrainStep
     cfg = O.KITCHEN
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32", attn_pdrop=0.3, resid_pdrop=0.05, embed_pdrop=0.1)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32", attn_pdrop=0.3, resid_pdrop=0.05, embed_pdrop=0.1, train=True)
     step = HipTrainStep(m.inner_model, cfg.sigma_data)
     T = 1 + cfg.goal_seq_len + 2 * t
     n = B * cfg.n_heads * T * T if kind == "attn" else B * T * cfg.embed_dim
@@ -340,7 +270,7 @@ def test_dropout_step_matches_autograd_with_the_librarys_masks(cfg_name, B, t, p
     whole = precision == "bf16" and not per_op and cfg_name in ("kitchen", "block_push")
     assert launches == (1 if whole else 0), launches
     ref_loss, ref = _autograd(m, step, inputs, seed)
-    ltol, gtol, _ = BOUNDS[precision]
+    ltol, gtol, _ = TRAIN_BOUNDS[precision]
     lerr, gerr = _compare(f"{cfg_name} B={B} t={t} {drops}{' per-op' if per_op else ''}", m, precision, loss, got, ref_loss, ref)
     assert lerr < ltol, lerr
     assert gerr < gtol, gerr
@@ -354,7 +284,7 @@ def test_the_comparison_bites():
     m, inputs = _case("kitchen", 48, None, "fp32", attn_p=0.3)
     seed = 20240
     step, loss, got, _ = _hip(m, inputs, seed)
-    ltol, gtol, _ = BOUNDS["fp32"]
+    ltol, gtol, _ = TRAIN_BOUNDS["fp32"]
     lerr, gerr = _compare("kitchen B=48 (right masks)", m, "fp32", loss, got, *_autograd(m, step, inputs, seed))
     assert lerr < ltol and gerr < gtol
     lerr, gerr = _compare("kitchen B=48 (masks of seed + 1)", m, "fp32", loss, got, *_autograd(m, step, inputs, seed, mask_seed=seed + 1))

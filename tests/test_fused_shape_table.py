@@ -6,20 +6,12 @@ import os
 import sys
 
 import numpy as np
-import pytest
 
-from beso_amd import _lib
+from support import lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import record_fused_shape_table as rec  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from beso_amd.build import build
-    build(verbose=False)
-    return _lib.load()
 
 
 def test_sweep_holds_the_cases_where_the_predicates_disagree():

@@ -4,16 +4,15 @@ CPU: the C ABI's argument checks.
 GPU: the one-launch loop against the step-by-step form (bit for bit, with launch counts) in every instance of the kernel, against
 the CPU oracle, against today's Python loop, at the agent level, the fallbacks that keep the Python loop, and determinism."""
 import ctypes as C
-import functools
 import os
 import subprocess
 
-import numpy as np
 import pytest
 import torch
 
 from oracle import beso_oracle as O
 from conftest import rel_err
+from support import build_agent, count_site_launches, lib, make_denoiser, to_dev  # noqa: F401
 from beso_amd import _lib
 from beso_amd.runtime import ScoreNetShape
 
@@ -29,13 +28,6 @@ def n_evals(solver, n_steps):
 
 
 # ------------------------------------------------------------------------------------------------ CPU
-@pytest.fixture(scope="module")
-def lib():
-    from beso_amd.build import build
-    build(verbose=False)
-    return _lib.load()
-
-
 def test_sample_solver_is_exported_and_checks_its_arguments(lib):
     from beso_amd.build import LIB
     out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
@@ -74,38 +66,8 @@ def test_sample_solver_is_exported_and_checks_its_arguments(lib):
 
 
 # ------------------------------------------------------------------------------------------------ GPU helpers
-def G(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
 def make_module(cfg, precision, seed=3, std=0.03):
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_gpts import DiffusionGPT
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_wrappers import GCDenoiser
-    inner = functools.partial(
-        DiffusionGPT, state_dim=cfg.obs_dim, device=DEV, goal_conditioned=cfg.goal_conditioned,
-        action_dim=cfg.act_dim, embed_dim=cfg.embed_dim, embed_pdrob=0.0, attn_pdrop=0.0, resid_pdrop=0.0,
-        n_layers=cfg.n_layers, n_heads=cfg.n_heads, goal_seq_len=cfg.goal_seq_len, obs_seq_len=cfg.obs_seq_len,
-        sigma_vocab_size=3, time_embedding_fn=None, goal_drop=0.0, linear_output=cfg.linear_output, precision=precision)
-    m = GCDenoiser(inner, sigma_data=cfg.sigma_data)
-    sd = m.state_dict()
-    for k, v in O.make_weights(cfg, seed=seed, std=std).items():
-        sd[k] = torch.from_numpy(v.copy())
-    m.load_state_dict(sd)
-    return m.to(DEV).eval()
-
-
-def count_fused_launches(fn):
-    """Runs fn() with the launch-site timer on the fused kernel's site; returns the number of launches it recorded."""
-    lib = _lib.load()
-    lib.beso_profile_enable(_lib.SITES["fused_layer"])
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, n = C.c_double(0.0), C.c_int(0)
-        assert lib.beso_profile_read(C.byref(ms), C.byref(n)) == 0
-    finally:
-        lib.beso_profile_enable(0)
-    return n.value
+    return make_denoiser(cfg, O.make_weights(cfg, seed=seed, std=std), precision)
 
 
 @pytest.fixture
@@ -141,7 +103,7 @@ def test_solver_loop_is_one_launch_and_equals_the_stepwise_loop(fused_plan, cfg_
     s_np, g_np, x_np = O.make_inputs(cfg, B, seed=11)
     with torch.no_grad():
         for t in sorted({cfg.obs_seq_len, max(1, cfg.obs_seq_len - 2)}):
-            s, g, x = G(s_np[:, :t]), G(g_np), G(x_np[:, :t])
+            s, g, x = to_dev(s_np[:, :t]), to_dev(g_np), to_dev(x_np[:, :t])
             keep = x.clone()
             for solver in SOLVERS:
                 long = 130 if solver in ("dpmpp_2m", "lms") else 70
@@ -157,8 +119,8 @@ def test_solver_loop_is_one_launch_and_equals_the_stepwise_loop(fused_plan, cfg_
                     nz = torch.randn((n_steps,) + tuple(x.shape), device=DEV, generator=torch.Generator(DEV).manual_seed(5))
                     kw = dict(cond_lambda=lam, eta=eta, noise=nz, order=order, s_noise=0.75)
                     out = {}
-                    n_loop = count_fused_launches(lambda: out.__setitem__("loop", m.fused_sampler(solver, s, x, g, sig, **kw)))
-                    n_step = count_fused_launches(lambda: out.__setitem__(
+                    n_loop = count_site_launches("fused_layer", lambda: out.__setitem__("loop", m.fused_sampler(solver, s, x, g, sig, **kw)))
+                    n_step = count_site_launches("fused_layer", lambda: out.__setitem__(
                         "step", m.fused_sampler(solver, s, x, g, sig, stepwise=True, **kw)))
                     ne = n_evals(solver, n_steps)
                     what = (cfg_name, precision, B, t, solver, n_steps, eta, order)
@@ -194,7 +156,7 @@ def test_solvers_against_the_oracle(fused_plan, precision, tol):
             box = {}
             with torch.no_grad():
                 ref = fn(oracle, *(torch.from_numpy(v.copy()) for v in (s_np, x_np, g_np)), sig, disable=True, **kw)
-                n = count_fused_launches(lambda: box.__setitem__("x", fn(model, G(s_np), G(x_np), G(g_np), sig, disable=True,
+                n = count_site_launches("fused_layer", lambda: box.__setitem__("x", fn(model, to_dev(s_np), to_dev(x_np), to_dev(g_np), sig, disable=True,
                                                                         **kw)))
             assert n == 1, (cfg_name, solver, n)
             err = rel_err(box["x"].cpu().numpy(), ref.numpy())
@@ -221,10 +183,10 @@ def test_solvers_against_the_python_loop(fused_plan, precision, stepwise):
             with torch.no_grad():
                 torch.manual_seed(7)
                 box = {}
-                n = count_fused_launches(lambda: box.__setitem__("one", fn(model, G(s_np), G(x_np), G(g_np), sig, disable=True,
+                n = count_site_launches("fused_layer", lambda: box.__setitem__("one", fn(model, to_dev(s_np), to_dev(x_np), to_dev(g_np), sig, disable=True,
                                                                           **kw)))
                 torch.manual_seed(7)
-                loop = fn(model, G(s_np), G(x_np), G(g_np), sig, disable=True, callback=lambda d: None, **kw)
+                loop = fn(model, to_dev(s_np), to_dev(x_np), to_dev(g_np), sig, disable=True, callback=lambda d: None, **kw)
             if not stepwise:
                 assert n == 1, (cfg_name, solver, n)
             err = rel_err(box["one"].cpu().numpy(), loop.cpu().numpy())
@@ -236,7 +198,6 @@ def test_solvers_against_the_python_loop(fused_plan, precision, stepwise):
 def test_agent_sample_loop_runs_each_solver_as_one_launch():
     """BesoAgent.sample_loop with the sampler types of the six solvers: one fused launch each (kitchen bf16, B = 64)."""
     from beso_amd.agents.diffusion_agents.k_diffusion import gc_sampling as ks
-    from test_host_logic import build_agent
     cfg = O.KITCHEN
     agent = build_agent(cfg, lambda: make_module(cfg, "bf16"), device=DEV)
     agent.model.eval()
@@ -245,7 +206,7 @@ def test_agent_sample_loop_runs_each_solver_as_one_launch():
     with torch.no_grad():
         for sampler_type in ("dpm", "ancestral", "lms", "dpmpp_2s", "dpmpp_2s_ancestral", "dpmpp_2m"):
             box = {}
-            n = count_fused_launches(lambda: box.__setitem__("x", agent.sample_loop(sig, G(x_np), G(s_np), G(g_np), sampler_type)))
+            n = count_site_launches("fused_layer", lambda: box.__setitem__("x", agent.sample_loop(sig, to_dev(x_np), to_dev(s_np), to_dev(g_np), sampler_type)))
             assert n == 1, (sampler_type, n)
             assert torch.isfinite(box["x"]).all() and box["x"].shape == (64, cfg.obs_seq_len, cfg.act_dim)
 
@@ -278,16 +239,16 @@ def test_fallbacks_keep_the_python_loop_off_the_runtime_sampler(monkeypatch):
         for fn, kw, evals in cases:
             torch.manual_seed(3)
             box = {}
-            n = count_fused_launches(lambda: box.__setitem__("x", fn(m, G(s_np), G(x_np), G(g_np), sig, disable=True, **kw)))
+            n = count_site_launches("fused_layer", lambda: box.__setitem__("x", fn(m, to_dev(s_np), to_dev(x_np), to_dev(g_np), sig, disable=True, **kw)))
             torch.manual_seed(3)
             loop_kw = dict(kw, callback=noop) if "extra_args" not in kw else kw
-            ref = fn(m, G(s_np), G(x_np), G(g_np), sig, disable=True, **loop_kw)
+            ref = fn(m, to_dev(s_np), to_dev(x_np), to_dev(g_np), sig, disable=True, **loop_kw)
             assert not calls, (fn.__name__, kw, calls)
             assert n == evals, (fn.__name__, kw, n)
             assert torch.equal(box["x"], ref), (fn.__name__, kw)
     # ... and the plain call does reach it
     with torch.no_grad():
-        ks.sample_lms(m, G(s_np), G(x_np), G(g_np), sig, disable=True)
+        ks.sample_lms(m, to_dev(s_np), to_dev(x_np), to_dev(g_np), sig, disable=True)
     assert calls == ["lms"]
 
 
@@ -299,7 +260,7 @@ def test_solvers_are_deterministic():
     m = make_module(cfg, "bf16")
     for B in (64, 1100):
         s_np, g_np, x_np = O.make_inputs(cfg, B, seed=61)
-        s, g, x = G(s_np), G(g_np), G(x_np)
+        s, g, x = to_dev(s_np), to_dev(g_np), to_dev(x_np)
         sig = ks.get_sigmas_exponential(7, 0.05, 1.0)
         nz = torch.randn((7,) + tuple(x.shape), device=DEV, generator=torch.Generator(DEV).manual_seed(9))
         with torch.no_grad():

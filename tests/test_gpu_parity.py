@@ -6,7 +6,6 @@ Tolerances (relative to max |reference| over the output tensor):
   bf16 mode  (bf16 MFMA, fp32 acc)  : 3e-2 on a single denoiser call with synthetic weights; the
               measured values are printed and recorded in DESIGN.md (typically 2e-3 .. 8e-3).
 """
-import functools
 import os
 
 import numpy as np
@@ -15,6 +14,7 @@ import torch
 
 from oracle import beso_oracle as O
 from conftest import load_golden, weights_from_fixture, rel_err
+from support import (count_site_launches, free_port, grad_errors, make_denoiser, to_dev, train_inputs)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,22 +41,6 @@ def _fused_kernels_unless_a_test_asks_for_the_small_batch_path():
     set_plan(forward=0, train=0)
 
 
-def count_site_launches(site, fn):
-    """Runs fn() with the launch-site timer on `site`; returns the number of timed regions it recorded."""
-    from beso_amd import _lib
-    import ctypes as C
-    lib = _lib.load()
-    lib.beso_profile_enable(_lib.SITES[site])
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, n = C.c_double(0.0), C.c_int(0)
-        assert lib.beso_profile_read(C.byref(ms), C.byref(n)) == 0
-    finally:
-        lib.beso_profile_enable(0)
-    return n.value
-
-
 def set_level(lvl):
     """Which kernels the forward calls of this thread may use (BESO_PLAN_* hints carried by every call): 2 the one-launch
     kernel where the shape has it (the library's own choice), 1 at most the block kernels, 0 the per-op kernels."""
@@ -81,44 +65,6 @@ def set_train_tail(on):
     set_plan(train={0: _lib.TRAIN_PLAN_PER_OP, 1: 0, 2: _lib.TRAIN_PLAN_TILES}[on])
 
 
-def count_fused_launches(fn):
-    """Runs fn() with the launch-site timer on the fused kernel's site; returns the number of launches it recorded."""
-    from beso_amd import _lib
-    import ctypes as C
-    lib = _lib.load()
-    lib.beso_profile_enable(_lib.SITES["fused_layer"])
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, n = C.c_double(0.0), C.c_int(0)
-        assert lib.beso_profile_read(C.byref(ms), C.byref(n)) == 0
-    finally:
-        lib.beso_profile_enable(0)
-    return n.value
-
-
-def make_module(cfg, w=None, precision="fp32", **kw):
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_gpts import DiffusionGPT
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_wrappers import GCDenoiser
-    inner = functools.partial(
-        DiffusionGPT, state_dim=cfg.obs_dim, device=DEV, goal_conditioned=cfg.goal_conditioned,
-        action_dim=cfg.act_dim, embed_dim=cfg.embed_dim, embed_pdrob=0.0, attn_pdrop=kw.get("attn_pdrop", 0.0),
-        resid_pdrop=0.0, n_layers=cfg.n_layers, n_heads=cfg.n_heads, goal_seq_len=cfg.goal_seq_len,
-        obs_seq_len=cfg.obs_seq_len, sigma_vocab_size=3, time_embedding_fn=None, goal_drop=0.0,
-        linear_output=cfg.linear_output, precision=precision)
-    m = GCDenoiser(inner, sigma_data=cfg.sigma_data)
-    if w is not None:
-        sd = m.state_dict()
-        for k, v in w.items():
-            sd[k] = torch.from_numpy(v.copy())
-        m.load_state_dict(sd)
-    return m.to(DEV).eval()
-
-
-def G(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
 def _weights(fx, cfg):
     w = weights_from_fixture(fx)
     return w if w else O.make_weights(cfg, seed=int(fx["seed"]), std=float(fx["std"]))
@@ -134,7 +80,7 @@ def test_native_library_is_what_runs():
     assert B.is_current(), "libbeso_hip.so was not built from the sources in this tree (stale binary)"
     maps = open("/proc/self/maps").read()
     assert "libbeso_hip.so" in maps
-    m = make_module(O.TINY, O.make_weights(O.TINY))
+    m = make_denoiser(O.TINY, O.make_weights(O.TINY))
     with torch.no_grad(), pytest.raises(RuntimeError):
         m(torch.zeros(1, 3, 7), torch.zeros(1, 3, 3), torch.zeros(1, 2, 7), torch.ones(1))
 
@@ -149,12 +95,12 @@ def test_forward_vs_reference_vectors(fixture, cfg_name, precision):
     """GCDenoiser.forward / DiffusionGPT.forward, t in {1, W/2, W}, cond and uncond."""
     fx = load_golden(fixture)
     cfg = O.CONFIGS[cfg_name]
-    m = make_module(cfg, _weights(fx, cfg), precision)
+    m = make_denoiser(cfg, _weights(fx, cfg), precision)
     worst = 0.0
     with torch.no_grad():
         for t in fx["ts"]:
             p = f"t{int(t)}::"
-            s, a, g, sg = (G(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
+            s, a, g, sg = (to_dev(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
             e1 = rel_err(m(s, a, g, sg).cpu().numpy(), fx[p + "denoised"])
             e2 = rel_err(m(s, a, g, sg, uncond=True).cpu().numpy(), fx[p + "denoised_uncond"])
             e3 = rel_err(m.inner_model(s, a, g, sg).cpu().numpy(), fx[p + "inner"])
@@ -173,7 +119,7 @@ def test_fp16_forward_through_the_one_launch_kernel(fixture, cfg_name):
     cfg = O.CONFIGS[cfg_name]
     worst = {}
     for precision in ("fp16", "bf16"):
-        m = make_module(cfg, _weights(fx, cfg), precision)
+        m = make_denoiser(cfg, _weights(fx, cfg), precision)
         worst[precision] = 0.0
         calls = 0
 
@@ -181,7 +127,7 @@ def test_fp16_forward_through_the_one_launch_kernel(fixture, cfg_name):
             nonlocal calls
             for t in fx["ts"]:
                 p = f"t{int(t)}::"
-                s, a, g, sg = (G(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
+                s, a, g, sg = (to_dev(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
                 e1 = rel_err(m(s, a, g, sg).cpu().numpy(), fx[p + "denoised"])
                 e2 = rel_err(m(s, a, g, sg, uncond=True).cpu().numpy(), fx[p + "denoised_uncond"])
                 e3 = rel_err(m.inner_model(s, a, g, sg).cpu().numpy(), fx[p + "inner"])
@@ -189,7 +135,7 @@ def test_fp16_forward_through_the_one_launch_kernel(fixture, cfg_name):
                 calls += 3
 
         with torch.no_grad():
-            launches = count_fused_launches(run)
+            launches = count_site_launches("fused_layer", run)
         assert launches == calls
     print(f"[parity] {fixture}: fp16 {worst['fp16']:.3e}  (bf16 {worst['bf16']:.3e})")
     assert worst["fp16"] < TOL_FP16_FIXTURE[fixture]
@@ -205,7 +151,7 @@ def test_fp16_sampler_loops_and_rejections():
                               ("long_horizon_euler100.npz", "long_horizon")]:
         fx = load_golden(fixture)
         cfg = O.CONFIGS[cfg_name]
-        m = make_module(cfg, _weights(fx, cfg), "fp16")
+        m = make_denoiser(cfg, _weights(fx, cfg), "fp16")
         lam = float(fx["cond_lambda"])
         model = m if lam < 0 else ClassifierFreeSampleModel(m, lam)
         for key in sorted(k[:-5] for k in fx if k.endswith("::out")):
@@ -215,16 +161,16 @@ def test_fp16_sampler_loops_and_rejections():
                 continue
             out = {}
             with torch.no_grad():
-                launches = count_fused_launches(lambda: out.__setitem__(0, fns[sampler](
-                    model, G(fx["state"]), G(fx["x_t"]), G(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]), disable=True)))
+                launches = count_site_launches("fused_layer", lambda: out.__setitem__(0, fns[sampler](
+                    model, to_dev(fx["state"]), to_dev(fx["x_t"]), to_dev(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]), disable=True)))
             err = rel_err(out[0].cpu().numpy(), fx[key + "::out"])
             print(f"[parity] {fixture}:{key} fp16: {err:.3e} ({launches} launch)")
             assert launches == 1 and err < TOL["fp16"], key
     cfg = O.TINY
-    m = make_module(cfg, O.make_weights(cfg), "fp16")
-    s, g, a = (G(v) for v in O.make_inputs(cfg, 2, seed=0))
+    m = make_denoiser(cfg, O.make_weights(cfg), "fp16")
+    s, g, a = (to_dev(v) for v in O.make_inputs(cfg, 2, seed=0))
     with torch.no_grad(), pytest.raises(ValueError):
-        m(s, a, g, G(np.full(2, 0.5, np.float32)))
+        m(s, a, g, to_dev(np.full(2, 0.5, np.float32)))
 
 
 @pytest.mark.parametrize("fixture,cfg_name", [("kitchen_forward_std002.npz", "kitchen"), ("kitchen_forward_std008.npz", "kitchen"),
@@ -236,14 +182,14 @@ def test_bf16x3_forward_through_the_fused_kernel(fixture, cfg_name):
     one launch at the fused kernel's launch site (the mode has no per-op form to fall back to)."""
     fx = load_golden(fixture)
     cfg = O.CONFIGS[cfg_name]
-    m = make_module(cfg, _weights(fx, cfg), "bf16x3")
+    m = make_denoiser(cfg, _weights(fx, cfg), "bf16x3")
     worst, calls = 0.0, 0
 
     def run():
         nonlocal worst, calls
         for t in fx["ts"]:
             p = f"t{int(t)}::"
-            s, a, g, sg = (G(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
+            s, a, g, sg = (to_dev(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
             e1 = rel_err(m(s, a, g, sg).cpu().numpy(), fx[p + "denoised"])
             e2 = rel_err(m(s, a, g, sg, uncond=True).cpu().numpy(), fx[p + "denoised_uncond"])
             e3 = rel_err(m.inner_model(s, a, g, sg).cpu().numpy(), fx[p + "inner"])
@@ -251,7 +197,7 @@ def test_bf16x3_forward_through_the_fused_kernel(fixture, cfg_name):
             calls += 3
 
     with torch.no_grad():
-        launches = count_fused_launches(run)
+        launches = count_site_launches("fused_layer", run)
     print(f"[parity] {fixture} bf16x3 (layers_kernel, {launches} launches for {calls} calls): max rel err {worst:.3e}")
     assert launches == calls
     assert worst < TOL["bf16x3"]
@@ -267,14 +213,14 @@ def test_bf16x3_long_horizon_through_the_split_bf16_block_kernels():
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     cfg = O.CONFIGS["long_horizon"]
     fx = load_golden("long_horizon_forward.npz")
-    m = make_module(cfg, _weights(fx, cfg), "bf16x3")
+    m = make_denoiser(cfg, _weights(fx, cfg), "bf16x3")
     worst, calls = 0.0, 0
 
     def run():
         nonlocal worst, calls
         for t in fx["ts"]:
             p = f"t{int(t)}::"
-            s, a, g, sg = (G(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
+            s, a, g, sg = (to_dev(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
             e1 = rel_err(m(s, a, g, sg).cpu().numpy(), fx[p + "denoised"])
             e2 = rel_err(m(s, a, g, sg, uncond=True).cpu().numpy(), fx[p + "denoised_uncond"])
             e3 = rel_err(m.inner_model(s, a, g, sg).cpu().numpy(), fx[p + "inner"])
@@ -282,26 +228,26 @@ def test_bf16x3_long_horizon_through_the_split_bf16_block_kernels():
             calls += 3
 
     with torch.no_grad():
-        launches = count_fused_launches(run)
+        launches = count_site_launches("fused_layer", run)
     print(f"[parity] long_horizon_forward.npz bf16x3 (block kernels, {launches} launches for {calls} calls): {worst:.3e}")
     assert launches == calls * (cfg.n_layers + 1) and worst < TOL["bf16x3"]
     for fixture in ("long_horizon_euler.npz", "long_horizon_euler100.npz"):
         fe = load_golden(fixture)
-        me = make_module(cfg, _weights(fe, cfg), "bf16x3")
+        me = make_denoiser(cfg, _weights(fe, cfg), "bf16x3")
         for key in sorted(k[:-5] for k in fe if k.endswith("::out")):
             with torch.no_grad():
-                out = ks.sample_euler(me, G(fe["state"]), G(fe["x_t"]), G(fe["goal"]), torch.from_numpy(fe[key + "::sigmas"]), disable=True)
+                out = ks.sample_euler(me, to_dev(fe["state"]), to_dev(fe["x_t"]), to_dev(fe["goal"]), torch.from_numpy(fe[key + "::sigmas"]), disable=True)
             err = rel_err(out.cpu().numpy(), fe[key + "::out"])
             print(f"[parity] {fixture}:{key} bf16x3: {err:.3e}")
             assert err < TOL["bf16x3"], key
     # classifier-free pairs and a ragged batch against the oracle
     w = O.make_weights(cfg, seed=21, std=0.03)
-    mo = make_module(cfg, w, "bf16x3")
+    mo = make_denoiser(cfg, w, "bf16x3")
     with torch.no_grad():
         for B, t in [(1, cfg.obs_seq_len), (5, 3), (37, 16)]:
             s_np, g_np, a_np = O.make_inputs(cfg, B, seed=100 * B + t, t=t)
             sg_np = np.linspace(0.06, 1.0, B).astype(np.float32)
-            out = ClassifierFreeSampleModel(mo, 1.5)(G(s_np), G(a_np), G(g_np), G(sg_np))
+            out = ClassifierFreeSampleModel(mo, 1.5)(to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np))
             e = rel_err(out.cpu().numpy(), O.denoise_cfg(w, cfg, s_np, a_np, g_np, sg_np, 1.5))
             assert e < TOL["bf16x3"], (B, t, e)
 
@@ -317,11 +263,11 @@ def test_bf16x3_sampler_loops_and_cfg_through_the_fused_kernel():
                               ("block_push_cfg.npz", "block_push")]:
         fx = load_golden(fixture)
         cfg = O.CONFIGS[cfg_name]
-        m = make_module(cfg, _weights(fx, cfg), "bf16x3")
+        m = make_denoiser(cfg, _weights(fx, cfg), "bf16x3")
         if fixture == "block_push_cfg.npz":
             with torch.no_grad():
                 for lam in fx["lambdas"]:
-                    out = ClassifierFreeSampleModel(m, float(lam))(G(fx["state"]), G(fx["action"]), G(fx["goal"]), G(fx["sigma"]))
+                    out = ClassifierFreeSampleModel(m, float(lam))(to_dev(fx["state"]), to_dev(fx["action"]), to_dev(fx["goal"]), to_dev(fx["sigma"]))
                     err = rel_err(out.cpu().numpy(), fx[f"lam{float(lam)}"])
                     print(f"[parity] {fixture}:lambda={float(lam):g} bf16x3: {err:.3e}")
                     assert err < TOL["bf16x3"]
@@ -332,7 +278,7 @@ def test_bf16x3_sampler_loops_and_cfg_through_the_fused_kernel():
             n = int(key.split("_")[-2])
             sampler = key[: key.index(f"_{n}_")]
             with torch.no_grad():
-                out = fns[sampler](model, G(fx["state"]), G(fx["x_t"]), G(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]),
+                out = fns[sampler](model, to_dev(fx["state"]), to_dev(fx["x_t"]), to_dev(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]),
                                    disable=True)
             err = rel_err(out.cpu().numpy(), fx[key + "::out"])
             print(f"[parity] {fixture}:{key} bf16x3: {err:.3e}")
@@ -343,10 +289,10 @@ def test_bf16x3_rejects_shapes_without_a_fused_instance():
     """BF16X3 is an instance of the fused kernel only: shapes that kernel does not serve raise instead of silently
     running something else."""
     cfg = O.TINY
-    m = make_module(cfg, O.make_weights(cfg), "bf16x3")
-    s, g, a = (G(v) for v in O.make_inputs(cfg, 2, seed=0))
+    m = make_denoiser(cfg, O.make_weights(cfg), "bf16x3")
+    s, g, a = (to_dev(v) for v in O.make_inputs(cfg, 2, seed=0))
     with torch.no_grad(), pytest.raises(ValueError):
-        m(s, a, g, G(np.full(2, 0.5, np.float32)))
+        m(s, a, g, to_dev(np.full(2, 0.5, np.float32)))
 
 
 @pytest.mark.parametrize("cfg_name", ["kitchen", "block_push"])
@@ -362,17 +308,17 @@ def test_fused_bf16_kernel_against_the_per_op_bf16_kernels(cfg_name):
     cfg = O.CONFIGS[cfg_name]
     for std, bound in ((0.02, 2e-3), (0.08, 2e-2)):
         wts = O.make_weights(cfg, seed=3, std=std)
-        m = make_module(cfg, wts, "bf16")
+        m = make_denoiser(cfg, wts, "bf16")
         s_np, g_np, a_np = O.make_inputs(cfg, 256, seed=9)
         sg_np = np.linspace(0.05, 1.0, 256).astype(np.float32)
-        s, a, g, sg = G(s_np), G(a_np), G(g_np), G(sg_np)
+        s, a, g, sg = to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)
         ref = O.denoise(wts, cfg, s_np, a_np, g_np, sg_np)
         outs = {}
         try:
             with torch.no_grad():
                 for lvl in (2, 0):
                     set_level(lvl)
-                    n = count_fused_launches(lambda: outs.__setitem__(lvl, m(s, a, g, sg).cpu().numpy()))
+                    n = count_site_launches("fused_layer", lambda: outs.__setitem__(lvl, m(s, a, g, sg).cpu().numpy()))
                     assert n == (1 if lvl == 2 else 0)
         finally:
             set_level(2)
@@ -394,17 +340,17 @@ def test_long_sequence_layers_kernel_against_block_kernels_and_oracle(B, t):
     lib = _lib.load()
     cfg = O.CONFIGS["long_horizon"]
     wts = O.make_weights(cfg, seed=3, std=0.02)
-    m = make_module(cfg, wts, "bf16")
+    m = make_denoiser(cfg, wts, "bf16")
     s_np, g_np, a_np = O.make_inputs(cfg, B, seed=9 + t, t=t)
     sg_np = np.linspace(0.05, 1.0, B).astype(np.float32)
-    s, a, g, sg = G(s_np), G(a_np), G(g_np), G(sg_np)
+    s, a, g, sg = to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)
     ref = O.denoise(wts, cfg, s_np, a_np, g_np, sg_np)
     outs = {}
     try:
         with torch.no_grad():
             for lvl in (2, 1):
                 set_level(lvl)
-                n = count_fused_launches(lambda: outs.__setitem__(lvl, m(s, a, g, sg).cpu().numpy()))
+                n = count_site_launches("fused_layer", lambda: outs.__setitem__(lvl, m(s, a, g, sg).cpu().numpy()))
                 assert n == (1 if lvl == 2 else cfg.n_layers), (lvl, n)
     finally:
         set_level(2)
@@ -422,17 +368,17 @@ def test_long_sequence_classifier_free_pairs_are_one_launch_too():
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     cfg = O.CONFIGS["long_horizon"]
     wts = O.make_weights(cfg, seed=4, std=0.02)
-    m = make_module(cfg, wts, "bf16")
+    m = make_denoiser(cfg, wts, "bf16")
     s_np, g_np, a_np = O.make_inputs(cfg, 3, seed=2)
     sg_np = np.array([0.2, 0.5, 0.9], np.float32)
     lam = 1.5
     model = ClassifierFreeSampleModel(m, lam)
     out = {}
     with torch.no_grad():
-        n = count_fused_launches(lambda: out.__setitem__(0, model(G(s_np), G(a_np), G(g_np), G(sg_np)).cpu().numpy()))
+        n = count_site_launches("fused_layer", lambda: out.__setitem__(0, model(to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)).cpu().numpy()))
         set_level(1)
         try:
-            nb = count_fused_launches(lambda: out.__setitem__(1, model(G(s_np), G(a_np), G(g_np), G(sg_np)).cpu().numpy()))
+            nb = count_site_launches("fused_layer", lambda: out.__setitem__(1, model(to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)).cpu().numpy()))
         finally:
             set_level(2)
     assert (n, nb) == (1, cfg.n_layers), (n, nb)
@@ -443,8 +389,8 @@ def test_long_sequence_classifier_free_pairs_are_one_launch_too():
     # lambda = 1 / 0 short-circuit to the conditional / unconditional forward (no pair)
     with torch.no_grad():
         for lam1, un in ((1.0, False), (0.0, True)):
-            y = ClassifierFreeSampleModel(m, lam1)(G(s_np), G(a_np), G(g_np), G(sg_np))
-            assert torch.equal(y, m(G(s_np), G(a_np), G(g_np), G(sg_np), uncond=un))
+            y = ClassifierFreeSampleModel(m, lam1)(to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np))
+            assert torch.equal(y, m(to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np), uncond=un))
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
@@ -458,15 +404,15 @@ def test_fused_sampler_loops_vs_reference_vectors(precision):
                               ("long_horizon_euler.npz", "long_horizon"), ("long_horizon_euler100.npz", "long_horizon")]:
         fx = load_golden(fixture)
         cfg = O.CONFIGS[cfg_name]
-        m = make_module(cfg, _weights(fx, cfg), precision)
+        m = make_denoiser(cfg, _weights(fx, cfg), precision)
         lam = float(fx["cond_lambda"])
         model = m if lam < 0 else ClassifierFreeSampleModel(m, lam)
         for key in sorted(k[:-5] for k in fx if k.endswith("::out")):
             n = int(key.split("_")[-2])
             sampler = key[: key.index(f"_{n}_")]
-            x_t = G(fx["x_t"])
+            x_t = to_dev(fx["x_t"])
             keep = x_t.clone()
-            out = fns[sampler](model, G(fx["state"]), x_t, G(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]),
+            out = fns[sampler](model, to_dev(fx["state"]), x_t, to_dev(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]),
                                disable=True)
             assert torch.equal(x_t, keep), "sampler must not overwrite the caller's x_T"
             err = rel_err(out.cpu().numpy(), fx[key + "::out"])
@@ -489,19 +435,19 @@ def test_sampler_loop_is_one_launch_and_equals_the_stepwise_loop(cfg_name, preci
     evaluations are cut at step boundaries."""
     from beso_amd.agents.diffusion_agents.k_diffusion import gc_sampling as ks
     cfg = O.CONFIGS[cfg_name]
-    m = make_module(cfg, O.make_weights(cfg, seed=3, std=0.03), precision)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.03), precision)
     s_np, g_np, x_np = O.make_inputs(cfg, B, seed=11)
     with torch.no_grad():
         for t in sorted({cfg.obs_seq_len, max(1, cfg.obs_seq_len - 2)}):
-            s, g, x = G(s_np[:, :t]), G(g_np), G(x_np[:, :t])
+            s, g, x = to_dev(s_np[:, :t]), to_dev(g_np), to_dev(x_np[:, :t])
             for sampler, n_steps, n_evals in (("ddim", 3, 3), ("euler", 7, 7), ("heun", 4, 7), ("heun", 70, 139)):
                 if n_steps == 70 and (B > 200 or t != cfg.obs_seq_len):
                     continue
                 sig = ks.get_sigmas_exponential(n_steps, 0.05, 1.0)
                 out = {}
-                n_loop = count_fused_launches(lambda: out.__setitem__(
+                n_loop = count_site_launches("fused_layer", lambda: out.__setitem__(
                     "loop", m.fused_sampler(sampler, s, x, g, sig, cond_lambda=lam)))
-                n_step = count_fused_launches(lambda: out.__setitem__(
+                n_step = count_site_launches("fused_layer", lambda: out.__setitem__(
                     "step", m.fused_sampler(sampler, s, x, g, sig, cond_lambda=lam, stepwise=True)))
                 assert n_loop == (n_evals + 127) // 128, (sampler, n_steps, n_loop)
                 assert n_step == n_evals, (sampler, n_steps, n_step)
@@ -515,9 +461,9 @@ def test_sampler_loop_is_one_launch_and_equals_the_stepwise_loop(cfg_name, preci
                 sig = ks.get_sigmas_exponential(n_steps, 0.05, 1.0)
                 nz = torch.randn((n_steps,) + tuple(x.shape), device=DEV, generator=torch.Generator(DEV).manual_seed(5))
                 out = {}
-                n_loop = count_fused_launches(lambda: out.__setitem__(
+                n_loop = count_site_launches("fused_layer", lambda: out.__setitem__(
                     "loop", m.fused_sampler("euler_ancestral", s, x, g, sig, cond_lambda=lam, eta=eta, noise=nz)))
-                n_step = count_fused_launches(lambda: out.__setitem__(
+                n_step = count_site_launches("fused_layer", lambda: out.__setitem__(
                     "step", m.fused_sampler("euler_ancestral", s, x, g, sig, cond_lambda=lam, eta=eta, noise=nz, stepwise=True)))
                 assert (n_loop, n_step) == ((n_steps + 127) // 128, n_steps), (n_loop, n_step)
                 assert torch.isfinite(out["loop"]).all()
@@ -535,11 +481,11 @@ def test_stochastic_and_adaptive_samplers_on_gpu():
     from test_host_logic import _more_sampler_runs
     fx = load_golden("tiny_more_samplers.npz")
     cfg = O.TINY
-    m = make_module(cfg, O.make_weights(cfg, seed=int(fx["seed"]), std=float(fx["std"])), "fp32")
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=int(fx["seed"]), std=float(fx["std"])), "fp32")
     cpu_noise = lambda s, sn: torch.randn(fx["x_t"].shape).to(DEV)      # noqa: E731
-    runs = _more_sampler_runs(m, fx, lambda k: G(fx[k]), cpu_noise)
+    runs = _more_sampler_runs(m, fx, lambda k: to_dev(fx[k]), cpu_noise)
     sig = torch.from_numpy(fx["sigmas"])
-    runs["dpmpp_2s_ancestral"] = lambda: ks.sample_dpmpp_2s_ancestral(m, G(fx["state"]), G(fx["x_t"]), G(fx["goal"]), sig,
+    runs["dpmpp_2s_ancestral"] = lambda: ks.sample_dpmpp_2s_ancestral(m, to_dev(fx["state"]), to_dev(fx["x_t"]), to_dev(fx["goal"]), sig,
                                                                       disable=True, noise_sampler=cpu_noise)
     for key in ("ancestral", "dpm_fast_7_eta", "dpm_adaptive_3_eta"):    # these draw with randn_like on the device
         runs.pop(key)
@@ -559,8 +505,8 @@ def test_classifier_free_guidance(precision):
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     fx = load_golden("block_push_cfg.npz")
     cfg = O.BLOCK_PUSH
-    m = make_module(cfg, _weights(fx, cfg), precision)
-    s, a, g, sg = (G(fx[k]) for k in ("state", "action", "goal", "sigma"))
+    m = make_denoiser(cfg, _weights(fx, cfg), precision)
+    s, a, g, sg = (to_dev(fx[k]) for k in ("state", "action", "goal", "sigma"))
     with torch.no_grad():
         for lam in fx["lambdas"]:
             out = ClassifierFreeSampleModel(m, float(lam))(s, a, g, sg)
@@ -573,7 +519,7 @@ def test_agent_predict_trace_on_gpu():
     fx = load_golden("tiny_agent_trace.npz")
     cfg = O.TINY
     w = weights_from_fixture(fx)
-    agent = build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV)
     agent.ema_helper.load_shadow_params(agent.model.get_params())
     assert run_agent_trace(agent, fx, device=DEV) < 5e-5
     assert agent._ema_packed is not None, "the EMA packed image must have been used"
@@ -590,9 +536,9 @@ def test_agent_predict_trace_on_gpu():
 def test_repack_when_parameters_change():
     cfg = O.TINY
     w = O.make_weights(cfg, seed=5, std=0.05)
-    m = make_module(cfg, w, "fp32")
-    s, g, a = (G(v) for v in O.make_inputs(cfg, 4, seed=1))
-    sg = G(np.full(4, 0.3, np.float32))
+    m = make_denoiser(cfg, w, "fp32")
+    s, g, a = (to_dev(v) for v in O.make_inputs(cfg, 4, seed=1))
+    sg = to_dev(np.full(4, 0.3, np.float32))
     with torch.no_grad():
         y0 = m(s, a, g, sg).clone()
         m.inner_model.tok_emb.weight.mul_(1.5)              # in-place: version counter bumps
@@ -608,9 +554,9 @@ def test_autograd_comparator_equals_hip_forward():
     and the HIP forward agree: what the training-step tests compare against is the same function."""
     from autograd_reference import forward_autograd
     cfg = O.KITCHEN
-    m = make_module(cfg, O.make_weights(cfg, seed=3, std=0.04), "fp32")
-    s, g, a = (G(v) for v in O.make_inputs(cfg, 8, seed=2))
-    sg = G(np.exp(np.random.default_rng(0).uniform(np.log(0.005), 0, 8)).astype(np.float32))
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.04), "fp32")
+    s, g, a = (to_dev(v) for v in O.make_inputs(cfg, 8, seed=2))
+    sg = to_dev(np.exp(np.random.default_rng(0).uniform(np.log(0.005), 0, 8)).astype(np.float32))
     with torch.no_grad():
         hip = m.inner_model(s, a, g, sg)
     ref = forward_autograd(m.inner_model, s, a, g, sg, False)
@@ -628,11 +574,11 @@ def test_full_batch_properties_kitchen_4096(precision):
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     cfg = O.KITCHEN
     w = O.make_weights(cfg, seed=0, std=0.02)
-    m = make_module(cfg, w, precision)
+    m = make_denoiser(cfg, w, precision)
     B = 4096
     s_np, g_np, a_np = O.make_inputs(cfg, B, seed=0)
     sg_np = np.exp(np.random.default_rng(1).uniform(np.log(0.005), 0.0, B)).astype(np.float32)
-    s, g, a, sg = G(s_np), G(g_np), G(a_np), G(sg_np)
+    s, g, a, sg = to_dev(s_np), to_dev(g_np), to_dev(a_np), to_dev(sg_np)
     with torch.no_grad():
         full = m(s, a, g, sg)
         assert torch.isfinite(full).all()
@@ -661,10 +607,10 @@ def test_sampler_properties_block_push_2048():
     cfg = O.BLOCK_PUSH
     # fp32 mode: bf16 rounding makes the network discontinuous at the 1e-3 level, so "same loop, two
     # drivers" is only an equality at fp32 round-off in the exact mode
-    m = make_module(cfg, O.make_weights(cfg, seed=7, std=0.05), "fp32")
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=7, std=0.05), "fp32")
     model = ClassifierFreeSampleModel(m, 2.0)
     B = 2048
-    s, g, x = (G(v) for v in O.make_inputs(cfg, B, seed=3))
+    s, g, x = (to_dev(v) for v in O.make_inputs(cfg, B, seed=3))
     with torch.no_grad():
         one = ks.sample_ddim(model, s, x, g, torch.tensor([0.7, 0.0]), disable=True)
         den = model(s, x, g, torch.full((B,), 0.7, device=DEV))
@@ -687,13 +633,13 @@ def test_block_push_2048_heun50_cfg_bf16():
     w = O.make_weights(cfg, seed=7, std=0.05)
     B = 2048
     s_np, g_np, x_np = O.make_inputs(cfg, B, seed=3)
-    s, g, x = G(s_np), G(g_np), G(x_np)
+    s, g, x = to_dev(s_np), to_dev(g_np), to_dev(x_np)
     sig = ks.get_sigmas_exponential(50, 0.05, 1.0)
     outs = {}
     with torch.no_grad():
         for prec in ("bf16", "bf16x3"):
-            model = ClassifierFreeSampleModel(make_module(cfg, w, prec), 2.0)
-            n = count_fused_launches(lambda: outs.__setitem__(prec, ks.sample_heun(model, s, x, g, sig, disable=True)))
+            model = ClassifierFreeSampleModel(make_denoiser(cfg, w, prec), 2.0)
+            n = count_site_launches("fused_layer", lambda: outs.__setitem__(prec, ks.sample_heun(model, s, x, g, sig, disable=True)))
             assert n == 1, n                                               # 2 * 50 - 1 evaluations (cond + uncond inside) in ONE launch
             assert torch.isfinite(outs[prec]).all()
             if prec == "bf16":
@@ -719,17 +665,17 @@ def test_long_horizon_256_euler100_bf16():
     lib = _lib.load()
     cfg = O.CONFIGS["long_horizon"]
     w = O.make_weights(cfg, seed=7, std=0.03)
-    m = make_module(cfg, w, "bf16")
+    m = make_denoiser(cfg, w, "bf16")
     B = 256
     s_np, g_np, x_np = O.make_inputs(cfg, B, seed=3)
-    s, g, x = G(s_np), G(g_np), G(x_np)
+    s, g, x = to_dev(s_np), to_dev(g_np), to_dev(x_np)
     sig = ks.get_sigmas_exponential(100, 0.05, 1.0)
     outs = {}
     try:
         with torch.no_grad():
             for lvl in (2, 1):
                 set_level(lvl)
-                n = count_fused_launches(lambda: outs.__setitem__(lvl, ks.sample_euler(m, s, x, g, sig, disable=True)))
+                n = count_site_launches("fused_layer", lambda: outs.__setitem__(lvl, ks.sample_euler(m, s, x, g, sig, disable=True)))
                 assert n == (1 if lvl == 2 else 100 * cfg.n_layers), (lvl, n)       # the whole loop is one launch
                 assert torch.isfinite(outs[lvl]).all()
             set_level(2)
@@ -749,21 +695,21 @@ def test_ragged_and_edge_shapes():
     """B = 1 rollouts, t < W warm-up windows, a batch that is not a multiple of any tile, shared goal."""
     cfg = O.KITCHEN
     w = O.make_weights(cfg, seed=9, std=0.03)
-    m = make_module(cfg, w, "fp32")
+    m = make_denoiser(cfg, w, "fp32")
     with torch.no_grad():
         for B, t in [(1, 1), (1, 4), (3, 2), (37, 3), (129, 4)]:
             s_np, g_np, a_np = O.make_inputs(cfg, B, seed=B + t, t=t)
             sg_np = np.linspace(0.01, 1.0, B).astype(np.float32)
-            out = m(G(s_np), G(a_np), G(g_np), G(sg_np))
+            out = m(to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np))
             assert out.shape == (B, t, cfg.act_dim)
             assert rel_err(out.cpu().numpy(), O.denoise(w, cfg, s_np, a_np, g_np, sg_np)) < TOL["fp32"], (B, t)
         # goal given once for the whole batch ([G, obs]) as predict() does (beso_agent.py:328-329)
         s_np, g_np, a_np = O.make_inputs(cfg, 5, seed=77)
-        out = m(G(s_np), G(a_np), G(g_np[0]), G(np.full(5, 0.2, np.float32)))
+        out = m(to_dev(s_np), to_dev(a_np), to_dev(g_np[0]), to_dev(np.full(5, 0.2, np.float32)))
         ref = O.denoise(w, cfg, s_np, a_np, np.broadcast_to(g_np[0], g_np.shape), np.full(5, 0.2, np.float32))
         assert rel_err(out.cpu().numpy(), ref) < TOL["fp32"]
         with pytest.raises(ValueError):
-            m(G(np.zeros((2, 5, 30), np.float32)), G(np.zeros((2, 5, 9), np.float32)), G(g_np[:2]), G(np.ones(2, np.float32)))
+            m(to_dev(np.zeros((2, 5, 30), np.float32)), to_dev(np.zeros((2, 5, 9), np.float32)), to_dev(g_np[:2]), to_dev(np.ones(2, np.float32)))
 
 
 @pytest.mark.gpu
@@ -783,9 +729,9 @@ def test_generic_mfma_attention_matches_fp32_attention(T, H, hd):
     s, g, a = O.make_inputs(cfg, 5, seed=3)
     sg = np.linspace(0.1, 0.9, 5).astype(np.float32)
     ref = O.denoise(w, cfg, s, a, g, sg)
-    m = make_module(cfg, w, "bf16")
+    m = make_denoiser(cfg, w, "bf16")
     with torch.no_grad():
-        out = m(G(s), G(a), G(g), G(sg)).cpu().numpy()
+        out = m(to_dev(s), to_dev(a), to_dev(g), to_dev(sg)).cpu().numpy()
     err = rel_err(out, ref)
     print(f"[parity] generic MFMA attention T={T} H={H} hd={hd}: {err:.3e}")
     assert err < TOL["bf16"]
@@ -887,7 +833,7 @@ def test_train_step_with_fused_optimizer_matches_eager(monkeypatch):
     for mode in ("1", "0"):
         if mode == "0":                                   # the eager torch optimizer + EMA helper: keep what Hydra configured
             monkeypatch.setattr(agent_mod, "maybe_fuse", lambda opt: opt)
-        agent = build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV)
+        agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV)
         assert isinstance(agent.optimizer, FusedAdam) == (mode == "1")
         agent.get_scaler(Scaler(np.random.default_rng(0).standard_normal((64, cfg.obs_dim)).astype(np.float32),
                                 np.random.default_rng(1).standard_normal((64, cfg.act_dim)).astype(np.float32), True, DEV))
@@ -926,7 +872,7 @@ def test_graphed_train_step_matches_eager(monkeypatch):
     results = {}
     for mode in ("1", "0"):
         monkeypatch.setenv("BESO_AMD_TRAIN_GRAPH", mode)
-        agent = build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV)
+        agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV)
         agent.get_scaler(Scaler(np.random.default_rng(0).standard_normal((64, cfg.obs_dim)).astype(np.float32),
                                 np.random.default_rng(1).standard_normal((64, cfg.act_dim)).astype(np.float32), True, DEV))
         agent.set_bounds(agent.scaler)
@@ -962,13 +908,13 @@ def test_fused_path_ragged_shapes_and_cfg(cfg_name, fused_instance):
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     cfg = O.CONFIGS[cfg_name]
     w = O.make_weights(cfg, seed=21, std=0.03)
-    m = make_module(cfg, w, "bf16")
+    m = make_denoiser(cfg, w, "bf16")
     worst = 0.0
     with torch.no_grad():
         for B, t in [(1, 1), (1, cfg.obs_seq_len), (3, 2), (9, cfg.obs_seq_len - 1), (37, 3), (129, cfg.obs_seq_len)]:
             s_np, g_np, a_np = O.make_inputs(cfg, B, seed=100 * B + t, t=t)
             sg_np = np.linspace(0.06, 1.0, B).astype(np.float32)
-            s, a, g, sg = G(s_np), G(a_np), G(g_np), G(sg_np)
+            s, a, g, sg = to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)
             out = m(s, a, g, sg)
             assert out.shape == (B, t, cfg.act_dim)
             worst = max(worst, rel_err(out.cpu().numpy(), O.denoise(w, cfg, s_np, a_np, g_np, sg_np)))
@@ -988,13 +934,13 @@ def test_bf16x3_ragged_shapes_and_cfg(cfg_name):
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     cfg = O.CONFIGS[cfg_name]
     w = O.make_weights(cfg, seed=21, std=0.03)
-    m = make_module(cfg, w, "bf16x3")
+    m = make_denoiser(cfg, w, "bf16x3")
     worst = 0.0
     with torch.no_grad():
         for B, t in [(1, 1), (1, cfg.obs_seq_len), (3, 2), (9, cfg.obs_seq_len - 1), (37, 3), (129, cfg.obs_seq_len)]:
             s_np, g_np, a_np = O.make_inputs(cfg, B, seed=100 * B + t, t=t)
             sg_np = np.linspace(0.06, 1.0, B).astype(np.float32)
-            s, a, g, sg = G(s_np), G(a_np), G(g_np), G(sg_np)
+            s, a, g, sg = to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)
             out = m(s, a, g, sg)
             assert out.shape == (B, t, cfg.act_dim)
             worst = max(worst, rel_err(out.cpu().numpy(), O.denoise(w, cfg, s_np, a_np, g_np, sg_np)))
@@ -1017,15 +963,15 @@ def test_fused_instances_are_bit_identical(cfg_name):
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     lib = _lib.load()
     cfg = O.CONFIGS[cfg_name]
-    m = make_module(cfg, O.make_weights(cfg, seed=5, std=0.04), "bf16")
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=5, std=0.04), "bf16")
     cfgm = ClassifierFreeSampleModel(m, 1.5)
     sig = ks.get_sigmas_exponential(4, 0.05, 1.0)
     try:
         with torch.no_grad():
             for B, t in [(1, 1), (2, cfg.obs_seq_len), (5, 2), (64, cfg.obs_seq_len), (257, cfg.obs_seq_len - 1), (512, cfg.obs_seq_len),
                          (513, cfg.obs_seq_len), (771, 2), (1024, cfg.obs_seq_len)]:      # 2, then 4 samples per workgroup
-                s, g, a = (G(v) for v in O.make_inputs(cfg, B, seed=B + t, t=t))
-                sg = G(np.linspace(0.05, 1.0, B).astype(np.float32))
+                s, g, a = (to_dev(v) for v in O.make_inputs(cfg, B, seed=B + t, t=t))
+                sg = to_dev(np.linspace(0.05, 1.0, B).astype(np.float32))
                 outs = []
                 for limit in (0, 512):
                     set_instances(limit)
@@ -1048,14 +994,14 @@ def test_bf16x3_instances_are_bit_identical_and_stable_from_run_to_run(cfg_name)
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     lib = _lib.load()
     cfg = O.CONFIGS[cfg_name]
-    m = make_module(cfg, O.make_weights(cfg, seed=5, std=0.04), "bf16x3")
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=5, std=0.04), "bf16x3")
     cfgm = ClassifierFreeSampleModel(m, 1.5)
     sig = ks.get_sigmas_exponential(3, 0.05, 1.0)
     try:
         with torch.no_grad():
             for B, t in [(513, cfg.obs_seq_len), (771, 2), (1030, cfg.obs_seq_len - 1), (4096, cfg.obs_seq_len)]:
-                s, g, a = (G(v) for v in O.make_inputs(cfg, B, seed=B + t, t=t))
-                sg = G(np.linspace(0.05, 1.0, B).astype(np.float32))
+                s, g, a = (to_dev(v) for v in O.make_inputs(cfg, B, seed=B + t, t=t))
+                sg = to_dev(np.linspace(0.05, 1.0, B).astype(np.float32))
                 outs = []
                 for limit in (1 << 20, 512):          # two samples per workgroup at every size / four above 512
                     set_instances(limit)
@@ -1119,7 +1065,7 @@ def test_no_writes_outside_output_and_workspace(cfg_name, precision):
     import ctypes as C
     from beso_amd import _lib
     cfg = O.CONFIGS[cfg_name]
-    m = make_module(cfg, O.make_weights(cfg, seed=4, std=0.03), precision)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=4, std=0.03), precision)
     inner = m.inner_model
     rt, packed = inner.runtime(cfg.sigma_data), inner.packed_weights()
     lib = rt.lib
@@ -1128,8 +1074,8 @@ def test_no_writes_outside_output_and_workspace(cfg_name, precision):
     shapes = [(1, 1), (5, cfg.obs_seq_len), (67, cfg.obs_seq_len)] if cfg_name != "long_horizon" else [(2, cfg.obs_seq_len)]
     for B, t in shapes:
         s_np, g_np, a_np = O.make_inputs(cfg, B, seed=B + 3 * t, t=t)
-        s, g, a = G(s_np), G(g_np), G(a_np)
-        sg = G(np.linspace(0.1, 0.9, B).astype(np.float32))
+        s, g, a = to_dev(s_np), to_dev(g_np), to_dev(a_np)
+        sg = to_dev(np.linspace(0.1, 0.9, B).astype(np.float32))
         for lam in (1.0, 2.0):
             two = 1 if lam != 1.0 else 0
             ws_bytes = lib.beso_workspace_bytes(C.byref(rt.cfg), B, t, packed.precision, two)
@@ -1161,38 +1107,6 @@ def test_no_writes_outside_output_and_workspace(cfg_name, precision):
 # -------------------------------------------------------------------------------------------------
 # training step in HIP (beso_loss_grad): row f1
 # -------------------------------------------------------------------------------------------------
-def _train_module(cfg, w, precision, attn_pdrop=0.0, resid_pdrop=0.0, embed_pdrop=0.0, goal_drop=0.0):
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_gpts import DiffusionGPT
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_wrappers import GCDenoiser
-    inner = functools.partial(
-        DiffusionGPT, state_dim=cfg.obs_dim, device=DEV, goal_conditioned=cfg.goal_conditioned,
-        action_dim=cfg.act_dim, embed_dim=cfg.embed_dim, embed_pdrob=embed_pdrop, attn_pdrop=attn_pdrop,
-        resid_pdrop=resid_pdrop, n_layers=cfg.n_layers, n_heads=cfg.n_heads, goal_seq_len=cfg.goal_seq_len,
-        obs_seq_len=cfg.obs_seq_len, sigma_vocab_size=3, time_embedding_fn=None, goal_drop=goal_drop,
-        linear_output=cfg.linear_output, precision=precision)
-    m = GCDenoiser(inner, sigma_data=cfg.sigma_data)
-    sd = m.state_dict()
-    for k, v in w.items():
-        sd[k] = torch.from_numpy(v.copy())
-    m.load_state_dict(sd)
-    return m.to(DEV).train()
-
-
-def _train_inputs(cfg, B, seed=0):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    r = lambda *s: torch.randn(*s, generator=g).to(DEV)
-    return (r(B, cfg.obs_seq_len, cfg.obs_dim), r(B, cfg.obs_seq_len, cfg.act_dim), r(B, cfg.goal_seq_len, cfg.obs_dim),
-            r(B, cfg.obs_seq_len, cfg.act_dim), (torch.rand(B, generator=g) * 0.9 + 0.05).to(DEV))
-
-
-def _grad_errors(got, ref, floor=1e-4):
-    """per tensor ||got - ref|| / max(||ref||, floor): tensors whose exact gradient is zero (key.bias: softmax is
-    invariant to a shift of all scores of a row -- what is left is the rounding noise of the summands) are measured
-    against `floor` times the largest gradient entry"""
-    gmax = max(r.abs().max().item() for r in ref)
-    return [((g - r).norm() / max(r.norm().item(), floor * gmax * r.numel() ** 0.5)).item() for g, r in zip(got, ref)]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_training_gemm_operand_layouts(precision):
@@ -1257,10 +1171,10 @@ def test_hip_training_step_matches_reference_gradients(fixture, cfg_name, precis
     2.6e-2 per tensor (norms; the eight stored entries against the per-entry share of that bound) and 2e-3 on the loss."""
     fx = load_golden(fixture)
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, _weights(fx, cfg), precision)
-    T = lambda k: G(fx[k])
+    m = make_denoiser(cfg, _weights(fx, cfg), precision, train=True)
+    T = lambda k: to_dev(fx[k])
     box = [None]
-    n_fused = count_fused_launches(lambda: box.__setitem__(0, m.loss(T("state"), T("action"), T("goal"), T("noise"), T("sigma"))))
+    n_fused = count_site_launches("fused_layer", lambda: box.__setitem__(0, m.loss(T("state"), T("action"), T("goal"), T("noise"), T("sigma"))))
     loss = box[0]
     assert "ScoreMatchingLoss" in type(loss.grad_fn).__name__          # the HIP step, not the autograd evaluation
     if precision == "bf16":
@@ -1309,8 +1223,8 @@ def test_hip_loss_and_gradients_match_autograd(cfg_name, B, precision, monkeypat
     shapes measure on the MI355X (round 3: gradients 8.4e-3 .. 1.28e-2, loss 7.8e-5 .. 8.3e-4; fp32: 3e-6 .. 1.4e-5)."""
     cfg = {"tiny": O.TINY, "kitchen": O.KITCHEN, "block_push": O.BLOCK_PUSH, "long_window": _LONG_WINDOW,
            "tiny_mlp_head": O.TINY_MLP_HEAD}[cfg_name]         # (the last: Linear(D,100) - SiLU - Linear(100,act) action head)
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision)
-    state, action, goal, noise, sigma = _train_inputs(cfg, B, seed=1)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, train=True)
+    state, action, goal, noise, sigma = train_inputs(cfg, B, seed=1)
     from autograd_reference import loss_autograd
     ref_loss = loss_autograd(m, state, action, goal, noise.clone(), sigma)
     ref_loss.backward()
@@ -1323,7 +1237,7 @@ def test_hip_loss_and_gradients_match_autograd(cfg_name, B, precision, monkeypat
     got = [p.grad for p in m.parameters()]
     ltol, gtol = (2e-5, 1e-4) if precision == "fp32" else (2e-3, 2.6e-2)
     assert abs(loss.item() - ref_loss.item()) < ltol * abs(ref_loss.item())
-    errs = _grad_errors(got, ref, 1e-4 if precision == "fp32" else 2e-3)
+    errs = grad_errors(got, ref, 1e-4 if precision == "fp32" else 2e-3)
     worst = max(range(len(errs)), key=lambda i: errs[i])
     print(f"[parity] train grads {cfg_name} B={B} {precision}: loss {abs(loss.item() - ref_loss.item()) / abs(ref_loss.item()):.2e}, "
           f"worst gradient {errs[worst]:.2e} ({list(dict(m.named_parameters()))[worst]})")
@@ -1335,7 +1249,7 @@ def test_hip_loss_and_gradients_match_autograd(cfg_name, B, precision, monkeypat
         p.grad = None
     (3.0 * m.loss(state, action, goal, noise.clone(), sigma)).backward()
     if precision == "fp32":
-        errs3 = _grad_errors([p.grad / 3.0 for p in m.parameters()], got)
+        errs3 = grad_errors([p.grad / 3.0 for p in m.parameters()], got)
         assert max(errs3) < 1e-4, max(errs3)
 
 
@@ -1348,10 +1262,10 @@ def test_hip_training_dropout_masks():
     from beso_amd.training import HipTrainStep
     cfg = O.TINY
     w = O.make_weights(cfg, seed=4, std=0.08)
-    m = _train_module(cfg, w, "fp32", attn_pdrop=0.3, resid_pdrop=0.1, embed_pdrop=0.1)
+    m = make_denoiser(cfg, w, "fp32", attn_pdrop=0.3, resid_pdrop=0.1, embed_pdrop=0.1, train=True)
     inner = m.inner_model
     step = HipTrainStep(inner, cfg.sigma_data)
-    state, action, goal, noise, sigma = _train_inputs(cfg, 64, seed=2)
+    state, action, goal, noise, sigma = train_inputs(cfg, 64, seed=2)
     run = lambda seed: step.run(state, action, goal, noise, sigma, seed=seed, fresh_grads=True)
     l1, f1, _ = run(11)
     l2, f2, _ = run(11)
@@ -1362,7 +1276,7 @@ def test_hip_training_dropout_masks():
     # eval mode switches the dropouts off
     inner.eval()
     l_eval, _, _ = run(11)
-    m0 = _train_module(cfg, w, "fp32")
+    m0 = make_denoiser(cfg, w, "fp32", train=True)
     l_ref, _, _ = HipTrainStep(m0.inner_model, cfg.sigma_data).run(state, action, goal, noise, sigma, seed=1, fresh_grads=True)
     assert abs(l_eval.item() - l_ref.item()) < 1e-6 * abs(l_ref.item())
     inner.train()
@@ -1397,10 +1311,10 @@ def test_hip_training_goal_masking(cfg_name, B, precision):
     torch-autograd comparator: loss and every parameter gradient must agree (fp32 1e-4 / bf16 2.6e-2 per tensor: twice the 1.26e-2 measured)."""
     from autograd_reference import loss_autograd
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, goal_drop=0.1)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, goal_drop=0.1, train=True)
     inner = m.inner_model
     assert inner.cond_mask_prob == 0.1 and inner.training
-    state, action, goal, noise, sigma = _train_inputs(cfg, B, seed=4)
+    state, action, goal, noise, sigma = train_inputs(cfg, B, seed=4)
     step = m.hip_train_step(state, action, goal, noise, sigma)
     assert step is not None
     seed = 20240
@@ -1429,13 +1343,13 @@ def test_hip_training_goal_masking(cfg_name, B, precision):
             p.grad = None
     ltol, gtol, floor = (2e-5, 1e-4, 1e-4) if precision == "fp32" else (2e-3, 2.6e-2, 2e-3)
     assert abs(loss.item() - ref_loss.item()) < ltol * abs(ref_loss.item())
-    errs = _grad_errors(got, ref, floor)
+    errs = grad_errors(got, ref, floor)
     worst = max(range(len(errs)), key=lambda i: errs[i])
     print(f"[parity] goal masking {cfg_name} {precision}: masked fraction {frac:.4f}, loss rel err "
           f"{abs(loss.item() - ref_loss.item()) / abs(ref_loss.item()):.2e}, worst gradient {errs[worst]:.2e}")
     assert errs[worst] < gtol, (list(dict(m.named_parameters()))[worst], errs[worst])
     assert abs(loss0.item() - loss.item()) < 1e-6 * abs(loss.item())
-    assert max(_grad_errors([v for v in views0], got, floor)) < 1e-5
+    assert max(grad_errors([v for v in views0], got, floor)) < 1e-5
     # the unmasked step is a different one
     loss_plain, _, _ = step.run(state, action, goal, noise, sigma, seed=seed, fresh_grads=True, goal_drop=0.0)
     assert abs(loss_plain.item() - loss.item()) > 1e-6 * abs(loss.item())
@@ -1457,8 +1371,8 @@ def test_training_forward_tail_block_equals_the_per_op_forward(cfg_name, B, t):
     from beso_amd import _lib
     lib = _lib.load()
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), "bf16", attn_pdrop=0.3)
-    state, action, goal, noise, sigma = _train_inputs(cfg, B, seed=5)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), "bf16", attn_pdrop=0.3, train=True)
+    state, action, goal, noise, sigma = train_inputs(cfg, B, seed=5)
     if t is not None:
         state, action, noise = state[:, :t].contiguous(), action[:, :t].contiguous(), noise[:, :t].contiguous()
     step = m.hip_train_step(state, action, goal, noise, sigma)
@@ -1470,7 +1384,7 @@ def test_training_forward_tail_block_equals_the_per_op_forward(cfg_name, B, t):
             out[1 if on else 0] = (loss.item(), [v.clone() for v in views])
     finally:
         set_train_tail(1)
-    errs = _grad_errors(out[1][1], out[0][1], 2e-3)
+    errs = grad_errors(out[1][1], out[0][1], 2e-3)
     worst = max(range(len(errs)), key=lambda i: errs[i])
     print(f"[parity] tail-block vs per-op training forward {cfg_name} B={B}: loss {abs(out[1][0] - out[0][0]) / abs(out[0][0]):.2e}, "
           f"worst gradient {errs[worst]:.2e} ({list(dict(m.named_parameters()))[worst]})")
@@ -1491,8 +1405,8 @@ def test_training_forward_as_one_launch_equals_the_per_op_forward(cfg_name, B, t
     forms must agree inside the bf16 bound that holds them to autograd (2.6e-2): 2e-2 per tensor, loss 2e-3.  Both instances
     (four samples per workgroup up to 1024 samples, eight beyond), ragged last workgroups and short windows included."""
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), "bf16", attn_pdrop=0.3)
-    state, action, goal, noise, sigma = _train_inputs(cfg, B, seed=5)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), "bf16", attn_pdrop=0.3, train=True)
+    state, action, goal, noise, sigma = train_inputs(cfg, B, seed=5)
     if t is not None:
         state, action, noise = state[:, :t].contiguous(), action[:, :t].contiguous(), noise[:, :t].contiguous()
     step = m.hip_train_step(state, action, goal, noise, sigma)
@@ -1500,12 +1414,12 @@ def test_training_forward_as_one_launch_equals_the_per_op_forward(cfg_name, B, t
     try:
         for on in (1, 0):                                    # 1: the library's choice = one launch; 0: per-op kernels
             set_train_tail(on)
-            n = count_fused_launches(lambda: out.__setitem__(on, step.run(state, action, goal, noise, sigma, seed=77, fresh_grads=True)))
+            n = count_site_launches("fused_layer", lambda: out.__setitem__(on, step.run(state, action, goal, noise, sigma, seed=77, fresh_grads=True)))
             out[on] = (out[on][0].item(), [v.clone() for v in out[on][2]], n)
     finally:
         set_train_tail(1)
     assert (out[1][2], out[0][2]) == (1, 0), (out[1][2], out[0][2])      # launches at the fused kernel's site
-    errs = _grad_errors(out[1][1], out[0][1], 2e-3)
+    errs = grad_errors(out[1][1], out[0][1], 2e-3)
     worst = max(range(len(errs)), key=lambda i: errs[i])
     print(f"[parity] one-launch vs per-op training forward {cfg_name} B={B} t={t}: loss {abs(out[1][0] - out[0][0]) / abs(out[0][0]):.2e}, "
           f"worst gradient {errs[worst]:.2e} ({list(dict(m.named_parameters()))[worst]})")
@@ -1527,21 +1441,21 @@ def test_training_backward_kernels_with_residual_and_embedding_dropout_equal_the
     accumulated alone, masked with the per-op forward's hash, the residual added back from the kept x) -- one launch at the
     fused kernel's site is asserted, both instances (four / eight samples per workgroup) and a ragged three-sample batch."""
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), "bf16", attn_pdrop=0.3, resid_pdrop=resid_p, embed_pdrop=embed_p)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), "bf16", attn_pdrop=0.3, resid_pdrop=resid_p, embed_pdrop=embed_p, train=True)
     m.train()
-    state, action, goal, noise, sigma = _train_inputs(cfg, B, seed=5)
+    state, action, goal, noise, sigma = train_inputs(cfg, B, seed=5)
     step = m.hip_train_step(state, action, goal, noise, sigma)
     out = {}
     try:
         for on in (1, 0):
             set_train_tail(on)
-            n = count_fused_launches(lambda: out.__setitem__(on, step.run(state, action, goal, noise, sigma, seed=77, fresh_grads=True)))
+            n = count_site_launches("fused_layer", lambda: out.__setitem__(on, step.run(state, action, goal, noise, sigma, seed=77, fresh_grads=True)))
             r = out[on]
             out[on] = (r[0].item(), [v.clone() for v in r[2]], n)
     finally:
         set_train_tail(1)
     assert (out[1][2], out[0][2]) == (1, 0), (out[1][2], out[0][2])      # the forward: one launch / the per-op kernels
-    errs = _grad_errors(out[1][1], out[0][1], 2e-3)
+    errs = grad_errors(out[1][1], out[0][1], 2e-3)
     worst = max(range(len(errs)), key=lambda i: errs[i])
     print(f"[parity] library vs per-op training step {cfg_name} B={B} resid_p={resid_p} embed_p={embed_p}: "
           f"loss {abs(out[1][0] - out[0][0]) / abs(out[0][0]):.2e}, worst gradient {errs[worst]:.2e} "
@@ -1572,7 +1486,7 @@ def test_agent_train_step_with_goal_drop_runs_the_hip_step():
     from beso_amd.networks.scaler.scaler_class import Scaler
     cfg = O.KITCHEN
     w = O.make_weights(cfg, seed=5, std=0.02)
-    agent = build_agent(cfg, lambda: _train_module(cfg, w, "bf16", attn_pdrop=0.3, goal_drop=0.1), device=DEV, lr=1e-3)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "bf16", attn_pdrop=0.3, goal_drop=0.1, train=True), device=DEV, lr=1e-3)
     rng = np.random.default_rng(0)
     agent.get_scaler(Scaler(rng.standard_normal((64, cfg.obs_dim)).astype(np.float32),
                             rng.standard_normal((64, cfg.act_dim)).astype(np.float32), True, DEV))
@@ -1630,7 +1544,7 @@ def test_train_step_reads_the_loss_on_the_loss_stream(monkeypatch):
     for tag in ("1", "0", "1 again"):
         mode = tag[0]
         monkeypatch.setenv("BESO_AMD_ASYNC_LOSS", mode)
-        agent = build_agent(cfg, lambda: _train_module(cfg, w, "bf16", attn_pdrop=0.3, goal_drop=0.1), device=DEV, lr=1e-3)
+        agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "bf16", attn_pdrop=0.3, goal_drop=0.1, train=True), device=DEV, lr=1e-3)
         agent.get_scaler(Scaler(sc[0], sc[1], True, DEV))
         agent.set_bounds(agent.scaler)
         torch.manual_seed(11)
@@ -1657,8 +1571,8 @@ def test_training_step_kitchen_1024_is_the_mean_of_its_slices(precision):
     the first 48 samples' step against torch autograd."""
     from autograd_reference import loss_autograd
     cfg = O.KITCHEN
-    m = _train_module(cfg, O.make_weights(cfg, seed=8, std=0.04), precision)
-    state, action, goal, noise, sigma = _train_inputs(cfg, 1024, seed=2)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=8, std=0.04), precision, train=True)
+    state, action, goal, noise, sigma = train_inputs(cfg, 1024, seed=2)
     step = m.hip_train_step(state, action, goal, noise, sigma)
     loss, flat, _ = step.run(state, action, goal, noise, sigma, seed=1, fresh_grads=True)
     acc, lsum = torch.zeros_like(flat), 0.0
@@ -1680,7 +1594,7 @@ def test_training_step_kitchen_1024_is_the_mean_of_its_slices(precision):
         ref_loss.backward()
         ref = [p.grad.clone() for p in m.parameters()]
         assert abs(l_s.item() - ref_loss.item()) < 2e-5 * abs(ref_loss.item())
-        assert max(_grad_errors(got, ref)) < 2e-4
+        assert max(grad_errors(got, ref)) < 2e-4
 
 
 @pytest.mark.gpu
@@ -1693,7 +1607,7 @@ def test_inference_on_live_weights_follows_the_fused_optimizer():
     from beso_amd.networks.scaler.scaler_class import Scaler
     cfg = O.TINY
     w = O.make_weights(cfg, seed=2, std=0.05)
-    agent = build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV, lr=5e-3)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV, lr=5e-3)
     agent.use_ema = False
     assert isinstance(agent.optimizer, FusedAdam)
     rng = np.random.default_rng(0)
@@ -1704,7 +1618,7 @@ def test_inference_on_live_weights_follows_the_fused_optimizer():
     sg_np = np.linspace(0.1, 0.9, 8).astype(np.float32)
     agent.model.eval()
     with torch.no_grad():
-        y0 = agent.model(G(s_np), G(a_np), G(g_np), G(sg_np)).cpu().numpy()       # packs the initial weights
+        y0 = agent.model(to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)).cpu().numpy()       # packs the initial weights
     torch.manual_seed(7)
     batch = {"observation": torch.randn(16, cfg.obs_seq_len, cfg.obs_dim, device=DEV),
              "action": torch.randn(16, cfg.obs_seq_len, cfg.act_dim, device=DEV),
@@ -1714,7 +1628,7 @@ def test_inference_on_live_weights_follows_the_fused_optimizer():
     agent.model.eval()
     now = {k: v.detach().cpu().numpy() for k, v in agent.model.state_dict().items() if not k.endswith("attn.mask")}
     with torch.no_grad():
-        y1 = agent.model(G(s_np), G(a_np), G(g_np), G(sg_np)).cpu().numpy()
+        y1 = agent.model(to_dev(s_np), to_dev(a_np), to_dev(g_np), to_dev(sg_np)).cpu().numpy()
     assert rel_err(y1, O.denoise(now, cfg, s_np, a_np, g_np, sg_np)) < TOL["fp32"]
     assert rel_err(y1, y0) > 1e-3, "the forward still ran on the first-packed weights"
     mse0 = agent.evaluate(batch)
@@ -1731,21 +1645,21 @@ def test_schedules_with_interior_zeros_take_the_stepwise_loop():
     from beso_amd.agents.diffusion_agents.k_diffusion import gc_sampling as ks
     cfg = O.TINY
     w = O.make_weights(cfg, seed=2, std=0.05)
-    m = make_module(cfg, w, "fp32")
+    m = make_denoiser(cfg, w, "fp32")
     s_np, g_np, x_np = O.make_inputs(cfg, 4, seed=1)
     sig = ks.get_sigmas_linear(5, 0.0, 1.0)
     assert float(sig[-2]) == 0.0 and float(sig[-1]) == 0.0
     with torch.no_grad():
-        out = ks.sample_ddim(m, G(s_np), G(x_np), G(g_np), sig[:-1], disable=True)           # [1 .. 0]: plain fused call
+        out = ks.sample_ddim(m, to_dev(s_np), to_dev(x_np), to_dev(g_np), sig[:-1], disable=True)           # [1 .. 0]: plain fused call
         ref = O.sample_ddim(O.make_model(w, cfg), s_np, x_np, g_np, sig[:-1].numpy())
         assert rel_err(out.cpu().numpy(), ref) < TOL["fp32"]
         good = ks.get_sigmas_linear(5, 0.01, 1.0)
-        fused = ks.sample_euler(m, G(s_np), G(x_np), G(g_np), good, disable=True)
-        step = ks.sample_euler(m, G(s_np), G(x_np), G(g_np), good, disable=True, callback=lambda info: None)
+        fused = ks.sample_euler(m, to_dev(s_np), to_dev(x_np), to_dev(g_np), good, disable=True)
+        step = ks.sample_euler(m, to_dev(s_np), to_dev(x_np), to_dev(g_np), good, disable=True, callback=lambda info: None)
         assert rel_err(fused.cpu().numpy(), step.cpu().numpy()) < 1e-5
         # interior zero: the fused entry would raise ValueError; the sampler falls back to the loop, which (like the
         # reference's, gc_sampling.py:205-210) divides by sigma = 0 on the last step -- no exception either way
-        out0 = ks.sample_euler(m, G(s_np), G(x_np), G(g_np), sig, disable=True)
+        out0 = ks.sample_euler(m, to_dev(s_np), to_dev(x_np), to_dev(g_np), sig, disable=True)
         assert out0.shape == (4, cfg.obs_seq_len, cfg.act_dim)
 
 
@@ -1769,7 +1683,7 @@ def test_train_step_runs_on_the_hip_step_and_matches_autograd(monkeypatch):
     for mode in ("1", "0"):
         if mode == "0":
             use_autograd_training(monkeypatch)
-        agent = build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV)
+        agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV)
         agent.get_scaler(Scaler(np.random.default_rng(0).standard_normal((64, cfg.obs_dim)).astype(np.float32),
                                 np.random.default_rng(1).standard_normal((64, cfg.act_dim)).astype(np.float32), True, DEV))
         agent.set_bounds(agent.scaler)
@@ -1810,7 +1724,7 @@ def test_training_with_the_hip_step_converges_like_autograd(monkeypatch):
         if mode == "0":
             use_autograd_training(monkeypatch)
         torch.manual_seed(17)
-        agent = build_agent(cfg, lambda: _train_module(cfg, w, precision, attn_pdrop=0.3, resid_pdrop=0.05), device=DEV, lr=2e-3)
+        agent = build_agent(cfg, lambda: make_denoiser(cfg, w, precision, attn_pdrop=0.3, resid_pdrop=0.05, train=True), device=DEV, lr=2e-3)
         agent.get_scaler(Scaler(obs.reshape(-1, cfg.obs_dim).numpy(), act.reshape(-1, cfg.act_dim).numpy(), True, DEV))
         agent.set_bounds(agent.scaler)
         losses = []
@@ -1843,8 +1757,8 @@ def test_hip_loss_node_backward_twice():
     """The autograd node of the HIP training step keeps its gradients intact: two backward passes through a retained
     graph accumulate twice the gradient."""
     cfg = O.TINY
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32")
-    state, action, goal, noise, sigma = _train_inputs(cfg, 6, seed=4)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32", train=True)
+    state, action, goal, noise, sigma = train_inputs(cfg, 6, seed=4)
     loss = m.loss(state, action, goal, noise, sigma)
     loss.backward(retain_graph=True)
     g1 = [p.grad.clone() for p in m.parameters()]
@@ -1863,7 +1777,7 @@ def test_hip_train_steps_match_the_reference_agent_trace():
     fx = load_golden("tiny_train_trace.npz")
     cfg = O.TINY
     w = O.make_weights(cfg, seed=int(fx["seed"]), std=float(fx["std"]))
-    agent = build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV)
     agent.ema_helper.load_shadow_params(agent.model.get_params())
     assert isinstance(agent.optimizer, FusedAdam)
     loss_err, p_err, e_err = replay_train_trace(agent, fx, device=DEV)
@@ -1877,8 +1791,8 @@ def test_hip_loss_pred_last_action_only(monkeypatch):
     """GCDenoiser.loss(..., pred_last_action_only=True) (score_wrappers.py:59-63,76-77: the noise of all but the last
     step is zeroed in place and only the last step is scored) through the HIP step against autograd."""
     cfg = O.TINY
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32")
-    state, action, goal, noise, sigma = _train_inputs(cfg, 7, seed=6)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32", train=True)
+    state, action, goal, noise, sigma = train_inputs(cfg, 7, seed=6)
     out = {}
     from autograd_reference import loss_autograd
     for mode in ("0", "1"):
@@ -1894,7 +1808,7 @@ def test_hip_loss_pred_last_action_only(monkeypatch):
         loss.backward()
         out[mode] = (loss.item(), [p.grad.clone() for p in m.parameters()])
     assert abs(out["1"][0] - out["0"][0]) < 2e-5 * abs(out["0"][0])
-    assert max(_grad_errors(out["1"][1], out["0"][1])) < 2e-4
+    assert max(grad_errors(out["1"][1], out["0"][1])) < 2e-4
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2008,7 +1922,7 @@ def test_feed_from_sliced_and_train_step():
 
     feed = DeviceTrajectoryFeed.from_sliced(Sliced, 64, DEV, seed=1)
     assert feed.n_windows == len(table)
-    agent = build_agent(cfg, lambda: make_module(cfg, O.make_weights(cfg, seed=1, std=0.05), "fp32"), device=DEV)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, O.make_weights(cfg, seed=1, std=0.05), "fp32"), device=DEV)
     from beso_amd.networks.scaler.scaler_class import Scaler
     agent.get_scaler(Scaler(base.obs.reshape(-1, cfg.obs_dim), base.act.reshape(-1, cfg.act_dim), True, DEV))
     agent.set_bounds(agent.scaler)
@@ -2027,13 +1941,6 @@ def test_feed_from_sliced_and_train_step():
         DeviceTrajectoryFeed.from_sliced(Sliced, 64, DEV)
 
 
-def _free_port():
-    import socket
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        return str(sk.getsockname()[1])
-
-
 # ------------------------------------------------------------------------------------------------
 # overlapped gradient exchange (beso_loss_grad_overlap)
 # ------------------------------------------------------------------------------------------------
@@ -2044,9 +1951,9 @@ def test_early_gradient_range_is_final_when_the_early_stream_runs(cfg_name, prec
     their completion, not behind the whole backward)."""
     from beso_amd.training import HipTrainStep
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.05), precision)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.05), precision, train=True)
     B = 256 if cfg_name == "kitchen" else 9
-    state, action, goal, noise, sigma = _train_inputs(cfg, B, seed=4)
+    state, action, goal, noise, sigma = train_inputs(cfg, B, seed=4)
     step = HipTrainStep(m.inner_model, cfg.sigma_data)
     b, e = step.early_range()
     if cfg.n_layers < 2:
@@ -2075,7 +1982,7 @@ def test_overlapped_all_reduce_on_a_one_rank_group():
     from beso_amd import distributed as bdist
     from test_host_logic import build_agent
     from beso_amd.networks.scaler.scaler_class import Scaler
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=_free_port(), RANK="0", WORLD_SIZE="1")
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), RANK="0", WORLD_SIZE="1")
     dist.init_process_group("nccl", rank=0, world_size=1)
     real = bdist.is_distributed
     try:
@@ -2093,7 +2000,7 @@ def test_overlapped_all_reduce_on_a_one_rank_group():
             real_sum = bdist.all_reduce_sum_overlapped
             calls = []
             bdist.all_reduce_sum_overlapped = lambda f, r, st: (calls.append(r), real_sum(f, r, st, _single_rank_ok=True))
-            agent = build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV)
+            agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV)
             agent.get_scaler(Scaler(np.random.default_rng(0).standard_normal((64, cfg.obs_dim)).astype(np.float32),
                                     np.random.default_rng(1).standard_normal((64, cfg.act_dim)).astype(np.float32), True, DEV))
             agent.set_bounds(agent.scaler)
@@ -2132,15 +2039,15 @@ def test_fused_euler_ancestral_loop():
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     fx = load_golden("tiny_euler_ancestral.npz")
     cfg = O.TINY
-    m = make_module(cfg, O.make_weights(cfg, seed=int(fx["seed"]), std=0.02), "fp32")
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=int(fx["seed"]), std=0.02), "fp32")
     with torch.no_grad():
-        out = m.fused_sampler("euler_ancestral", G(fx["state"]), G(fx["x_t"]), G(fx["goal"]), fx["sigmas"], noise=G(fx["noise"]))
+        out = m.fused_sampler("euler_ancestral", to_dev(fx["state"]), to_dev(fx["x_t"]), to_dev(fx["goal"]), fx["sigmas"], noise=to_dev(fx["noise"]))
         assert out is not None and rel_err(out.cpu().numpy(), fx["out"]) < 2e-5
         for cfg_name, precision, wrap in (("tiny", "fp32", None), ("kitchen", "bf16", None), ("block_push", "fp32", 2.0)):
             c = O.CONFIGS[cfg_name]
-            mm = make_module(c, O.make_weights(c, seed=2, std=0.04), precision)
+            mm = make_denoiser(c, O.make_weights(c, seed=2, std=0.04), precision)
             model = mm if wrap is None else ClassifierFreeSampleModel(mm, wrap)
-            s, g, x = (G(v) for v in O.make_inputs(c, 6, seed=9))
+            s, g, x = (to_dev(v) for v in O.make_inputs(c, 6, seed=9))
             sig = ks.get_sigmas_exponential(5, 0.05, 1.0)
             keep = x.clone()
             torch.manual_seed(77)
@@ -2160,7 +2067,7 @@ def test_feed_takes_rank_and_seed_from_the_process_group():
     from beso_amd import distributed as bdist
     from beso_amd.data.trajectory_feed import DeviceTrajectoryFeed
     fx = load_golden("trajectory_windows.npz")
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=_free_port(), RANK="0", WORLD_SIZE="1")
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), RANK="0", WORLD_SIZE="1")
     dist.init_process_group("nccl", rank=0, world_size=1)
     real = bdist.is_distributed
     try:
@@ -2198,13 +2105,13 @@ def test_small_batch_path_vs_reference_vectors(fixture, cfg_name, precision):
     set_plan(forward=0 if own else _lib.PLAN_SMALL)
     fx = load_golden(fixture)
     cfg = O.CONFIGS[cfg_name]
-    m = make_module(cfg, _weights(fx, cfg), precision)
+    m = make_denoiser(cfg, _weights(fx, cfg), precision)
     worst, calls = [0.0], [0]
 
     def run():
         for t in fx["ts"]:
             p = f"t{int(t)}::"
-            s, a, g, sg = (G(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
+            s, a, g, sg = (to_dev(fx[p + k]) for k in ("state", "action", "goal", "sigma"))
             e1 = rel_err(m(s, a, g, sg).cpu().numpy(), fx[p + "denoised"])
             e2 = rel_err(m(s, a, g, sg, uncond=True).cpu().numpy(), fx[p + "denoised_uncond"])
             e3 = rel_err(m.inner_model(s, a, g, sg).cpu().numpy(), fx[p + "inner"])
@@ -2214,7 +2121,7 @@ def test_small_batch_path_vs_reference_vectors(fixture, cfg_name, precision):
     with torch.no_grad():
         n_small = count_site_launches("small", run)
         calls[0] = 0
-        n_fused = count_fused_launches(run)
+        n_fused = count_site_launches("fused_layer", run)
     print(f"[parity] small-batch path {fixture} {precision}: max rel err {worst[0]:.3e} ({calls[0]} calls)")
     assert n_small == calls[0] and n_fused == 0, (n_small, n_fused, calls[0])
     # bf16: this path rounds where the per-op bf16 kernels round (LayerNorm output, q | k | v, attention output, GELU(h) as bf16
@@ -2242,22 +2149,22 @@ def test_small_batch_path_samplers_cfg_and_hints(precision):
         set_plan(forward=0 if (precision == "fp32" or cfg_name == "kitchen") else _lib.PLAN_SMALL)      # (bf16 block-push: by hint)
         fx = load_golden(fixture)
         cfg = O.CONFIGS[cfg_name]
-        m = make_module(cfg, _weights(fx, cfg), precision)
+        m = make_denoiser(cfg, _weights(fx, cfg), precision)
         lam = float(fx["cond_lambda"])
         model = m if lam < 0 else ClassifierFreeSampleModel(m, lam)
         for key in sorted(k[:-5] for k in fx if k.endswith("::out")):
             n = int(key.split("_")[-2])
             sampler = key[: key.index(f"_{n}_")]
             out = [None]
-            nf = count_fused_launches(lambda: out.__setitem__(0, fns[sampler](
-                model, G(fx["state"]), G(fx["x_t"]), G(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]), disable=True)))
+            nf = count_site_launches("fused_layer", lambda: out.__setitem__(0, fns[sampler](
+                model, to_dev(fx["state"]), to_dev(fx["x_t"]), to_dev(fx["goal"]), torch.from_numpy(fx[key + "::sigmas"]), disable=True)))
             err = rel_err(out[0].cpu().numpy(), fx[key + "::out"])
             print(f"[parity] small-batch path {fixture}:{key} {precision}: {err:.3e}")
             assert nf == 0, (key, nf)
             assert err < (TOL[precision] * (1 if n <= 10 else 8) if precision == "fp32" else 2e-2), key
     fx = load_golden("block_push_cfg.npz")
-    m = make_module(O.BLOCK_PUSH, _weights(fx, O.BLOCK_PUSH), precision)
-    s, a, g, sg = (G(fx[k]) for k in ("state", "action", "goal", "sigma"))
+    m = make_denoiser(O.BLOCK_PUSH, _weights(fx, O.BLOCK_PUSH), precision)
+    s, a, g, sg = (to_dev(fx[k]) for k in ("state", "action", "goal", "sigma"))
     set_plan(forward=_lib.PLAN_SMALL)
     with torch.no_grad():
         for lam in fx["lambdas"]:
@@ -2266,9 +2173,9 @@ def test_small_batch_path_samplers_cfg_and_hints(precision):
             assert n == 1 and rel_err(box[0].cpu().numpy(), fx[f"lam{float(lam)}"]) < TOL[precision], lam
         # hints: 400 kitchen samples = 4400 token rows -- beyond the library's own thresholds
         cfg = O.KITCHEN
-        mk = make_module(cfg, O.make_weights(cfg, seed=4, std=0.04), precision)
-        s, g, a = (G(v) for v in O.make_inputs(cfg, 400, seed=3))
-        sg = G(np.linspace(0.05, 0.9, 400).astype(np.float32))
+        mk = make_denoiser(cfg, O.make_weights(cfg, seed=4, std=0.04), precision)
+        s, g, a = (to_dev(v) for v in O.make_inputs(cfg, 400, seed=3))
+        sg = to_dev(np.linspace(0.05, 0.9, 400).astype(np.float32))
         outs = {}
         for name, hint in (("own", 0), ("small", _lib.PLAN_SMALL), ("other", _lib.PLAN_FUSED if precision == "bf16" else _lib.PLAN_PER_OP)):
             set_plan(forward=hint)
@@ -2282,8 +2189,8 @@ def test_small_batch_path_samplers_cfg_and_hints(precision):
         # ragged: B = 1, 3, 33 (token rows not a multiple of the 32-row tile), short windows; B = 64 (BASELINE configs[0]) and 200:
         # the wide bf16 instances of round 6 (32 rows x 128 / 32 features, a head in twelve waves)
         for B, t in ((1, 1), (3, 2), (33, cfg.obs_seq_len), (64, cfg.obs_seq_len), (200, cfg.obs_seq_len), (93, 2)):
-            s, g, a = (G(v) for v in O.make_inputs(cfg, B, seed=B, t=t))
-            sg = G(np.linspace(0.1, 0.8, B).astype(np.float32))
+            s, g, a = (to_dev(v) for v in O.make_inputs(cfg, B, seed=B, t=t))
+            sg = to_dev(np.linspace(0.1, 0.8, B).astype(np.float32))
             set_plan(forward=_lib.PLAN_SMALL)
             o_small = mk(s, a, g, sg)
             set_plan(forward=_lib.PLAN_PER_OP)
@@ -2333,7 +2240,7 @@ def test_small_batch_path_serves_the_agent_rollout():
     fx = load_golden("tiny_agent_trace.npz")
     cfg = O.TINY
     w = weights_from_fixture(fx)
-    agent = build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV)
     agent.ema_helper.load_shadow_params(agent.model.get_params())
     err = [None]
     n = count_site_launches("small", lambda: err.__setitem__(0, run_agent_trace(agent, fx, device=DEV)))

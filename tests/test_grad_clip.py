@@ -11,6 +11,7 @@ import torch
 
 from oracle import beso_oracle as O
 from conftest import rel_err
+from support import build_agent, lib, make_denoiser  # noqa: F401
 
 DEV = "cuda:0"
 # a 1-element chunk, a chunk that is no multiple of 256, a full 4096 chunk + a 4-element tail, and 280 chunks in all:
@@ -318,22 +319,16 @@ def test_results_do_not_depend_on_the_scratch_contents(fill):
 
 
 @pytest.mark.gpu
-def test_agent_clips_and_guards_through_train_step(monkeypatch):
+def test_agent_clips_and_guards_through_train_step():
     """A TINY agent with max_grad_norm small enough to clip and skip_nonfinite_steps: two train_steps run, last_grad_norm()
     is finite and positive, nothing was skipped.  Then a batch with a NaN action -- a non-finite gradient through the
     ordinary path -- leaves the parameters and the EMA shadow bit-equal and the counter at 1 (the returned loss may be
     NaN: that is what the user sees)."""
-    import functools
-    import test_host_logic
-    from test_gpu_parity import make_module
-    from beso_amd.agents.diffusion_agents.beso_agent import BesoAgent
     from beso_amd.optim import FusedAdam
     from beso_amd.networks.scaler.scaler_class import Scaler
     cfg = O.TINY
     w = O.make_weights(cfg, seed=2, std=0.05)
-    monkeypatch.setattr(test_host_logic, "BesoAgent",
-                        functools.partial(BesoAgent, max_grad_norm=1e-3, skip_nonfinite_steps=True))
-    agent = test_host_logic.build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV, max_grad_norm=1e-3, skip_nonfinite_steps=True)
     assert isinstance(agent.optimizer, FusedAdam) and agent.max_grad_norm == 1e-3 and agent.skip_nonfinite_steps
     agent.get_scaler(Scaler(np.random.default_rng(0).standard_normal((64, cfg.obs_dim)).astype(np.float32),
                             np.random.default_rng(1).standard_normal((64, cfg.act_dim)).astype(np.float32), True, DEV))
@@ -360,14 +355,6 @@ def test_agent_clips_and_guards_through_train_step(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ CPU
-@pytest.fixture(scope="module")
-def lib():
-    from beso_amd import _lib
-    from beso_amd.build import build
-    build(verbose=False)
-    return _lib.load()
-
-
 def test_new_entry_points_reject_bad_arguments_without_touching_the_device(lib):
     """beso_grad_sumsq / beso_adam_step_clipped: null pointers with n_chunks > 0, a negative count, max_grad_norm <= 0 and
     NaN are the ABI's bad-argument status (-3) before anything is enqueued -- this test runs without a GPU.  An empty step
@@ -395,22 +382,12 @@ def test_new_entry_points_reject_bad_arguments_without_touching_the_device(lib):
         _lib.check(step(max_norm=0.0), "beso_adam_step_clipped")
 
 
-def cpu_agent(monkeypatch, **extra):
-    import functools
-    import test_host_logic
-    from beso_amd.agents.diffusion_agents.beso_agent import BesoAgent
+def cpu_agent(**extra):
+    from test_host_logic import make_module
     from beso_amd.networks.scaler.scaler_class import Scaler
     cfg = O.TINY
     w = O.make_weights(cfg, seed=2, std=0.05)
-    with monkeypatch.context() as mp:
-        mp.setattr(test_host_logic, "BesoAgent", functools.partial(BesoAgent, **extra))
-
-        def factory():
-            m = test_host_logic.make_module(cfg)
-            test_host_logic.load_weights(m, w)
-            return m
-
-        agent = test_host_logic.build_agent(cfg, factory)
+    agent = build_agent(cfg, lambda: make_module(cfg, w), **extra)
     rng = np.random.default_rng(0)
     agent.get_scaler(Scaler(rng.standard_normal((40, cfg.obs_dim)).astype(np.float32),
                             rng.uniform(-1, 1, (40, cfg.act_dim)).astype(np.float32), True, "cpu"))
@@ -442,7 +419,7 @@ def test_cpu_agent_clips_through_clip_grad_norm_(autograd_training):
              "action": torch.rand(8, cfg.obs_seq_len, cfg.act_dim) * 2 - 1}
     finals = {}
     for name, extra, clip in (("clipped", dict(max_grad_norm=m), m), ("default", {}, None)):
-        agent, twin = cpu_agent(autograd_training, **extra), cpu_agent(autograd_training)
+        agent, twin = cpu_agent(**extra), cpu_agent()
         assert type(agent.optimizer) is torch.optim.AdamW
         for _ in range(2):
             torch.manual_seed(11)
@@ -459,6 +436,6 @@ def test_cpu_agent_clips_through_clip_grad_norm_(autograd_training):
             assert float(agent.last_grad_norm()) > m                    # the step did clip
     assert any(not torch.equal(a, b) for a, b in zip(finals["clipped"], finals["default"]))
     with pytest.raises(ValueError):
-        cpu_agent(autograd_training, skip_nonfinite_steps=True)
+        cpu_agent(skip_nonfinite_steps=True)
     with pytest.raises(ValueError):
-        cpu_agent(autograd_training, max_grad_norm=0.0)
+        cpu_agent(max_grad_norm=0.0)

@@ -11,7 +11,6 @@ image of, so they are held to the parameter gradients' bounds; the input gradien
 entry, not against the (larger) parameter gradients'.  Every case prints what it measured."""
 import contextlib
 import ctypes as C
-import functools
 
 import pytest
 import torch
@@ -19,9 +18,9 @@ import torch
 from beso_amd import _lib
 from beso_amd.runtime import ScoreNetShape
 from oracle import beso_oracle as O
+from support import Scale, TRAIN_BOUNDS, grad_errors, lib, make_denoiser, train_inputs  # noqa: F401
 
 DEV = "cuda:0"
-BOUNDS = {"fp32": (2e-5, 1e-4, 1e-4), "bf16": (2e-3, 2.6e-2, 2e-3)}       # loss, per-tensor gradient, floor
 TOL_VJP = {"fp32": 2e-4, "bf16": 2.6e-2}                                  # tests/test_log_likelihood.py
 PLANS = {"default": 0, "tiles": _lib.TRAIN_PLAN_TILES, "per_op": _lib.TRAIN_PLAN_PER_OP}
 
@@ -29,13 +28,6 @@ PLANS = {"default": 0, "tiles": _lib.TRAIN_PLAN_TILES, "per_op": _lib.TRAIN_PLAN
 # -------------------------------------------------------------------------------------------------
 # CPU
 # -------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from beso_amd.build import build
-    build(verbose=False)
-    return _lib.load()
-
-
 def test_entry_points_are_exported_and_bound(lib):
     for name in ("beso_loss_grad_inputs", "beso_denoise_vjp_inputs"):
         assert name in _lib.EXPORTS
@@ -116,55 +108,6 @@ def test_backward_reduces_a_broadcast_goal_to_its_own_shape():
     assert asked[-1] is False
 
 
-# -------------------------------------------------------------------------------------------------
-# helpers (restated from test_dropout_parity.py: _train_module, _train_inputs, _grad_errors, _Scale, injected_masks)
-# -------------------------------------------------------------------------------------------------
-def _train_module(cfg, w, precision, embed_pdrop=0.0, goal_drop=0.0, train=True):
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_gpts import DiffusionGPT
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_wrappers import GCDenoiser
-    inner = functools.partial(
-        DiffusionGPT, state_dim=cfg.obs_dim, device=DEV, goal_conditioned=cfg.goal_conditioned,
-        action_dim=cfg.act_dim, embed_dim=cfg.embed_dim, embed_pdrob=embed_pdrop, attn_pdrop=0.0,
-        resid_pdrop=0.0, n_layers=cfg.n_layers, n_heads=cfg.n_heads, goal_seq_len=cfg.goal_seq_len,
-        obs_seq_len=cfg.obs_seq_len, sigma_vocab_size=3, time_embedding_fn=None, goal_drop=goal_drop,
-        linear_output=cfg.linear_output, precision=precision)
-    m = GCDenoiser(inner, sigma_data=cfg.sigma_data)
-    sd = m.state_dict()
-    for k, v in w.items():
-        sd[k] = torch.from_numpy(v.copy())
-    m.load_state_dict(sd)
-    m = m.to(DEV)
-    return m.train() if train else m.eval()
-
-
-def _train_inputs(cfg, B, t, seed=0):
-    """state, action, goal [B, G, obs], noise, sigma for a window of t steps"""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    r = lambda *s: torch.randn(*s, generator=g).to(DEV)                      # noqa: E731
-    return [r(B, t, cfg.obs_dim), r(B, t, cfg.act_dim), r(B, cfg.goal_seq_len, cfg.obs_dim), r(B, t, cfg.act_dim),
-            (torch.rand(B, generator=g) * 0.9 + 0.05).to(DEV)]
-
-
-def _grad_errors(got, ref, floor=1e-4):
-    """per tensor ||got - ref|| / max(||ref||, floor * largest gradient entry * sqrt(numel))"""
-    gmax = max(r.abs().max().item() for r in ref)
-    return [((g - r).norm() / max(r.norm().item(), floor * gmax * r.numel() ** 0.5)).item() for g, r in zip(got, ref)]
-
-
-class _Scale(torch.nn.Module):
-    """Stands in for an nn.Dropout: multiplies by preset keep-scales, one tensor per call, in call order."""
-
-    def __init__(self, *scales):
-        super().__init__()
-        self.scales, self.calls = scales, 0
-
-    def forward(self, x):
-        s = self.scales[self.calls % len(self.scales)]
-        self.calls += 1
-        assert s.shape == x.shape, (tuple(s.shape), tuple(x.shape))
-        return x * s
-
-
 @contextlib.contextmanager
 def _injected_embed_mask(inner, step, batch, t, seed):
     """inner.drop replaced by the library's embedding mask for (batch, t, seed): forward_autograd calls it for the states,
@@ -174,7 +117,7 @@ def _injected_embed_mask(inner, step, batch, t, seed):
     try:
         if inner._pdrops[0] > 0:
             e = step.dropout_mask("embed", 0, batch, t, seed)
-            inner._modules["drop"] = _Scale(e[:, G + 1::2], e[:, G + 2::2], e[:, 1:G + 1])
+            inner._modules["drop"] = Scale(e[:, G + 1::2], e[:, G + 2::2], e[:, 1:G + 1])
         yield
     finally:
         inner._modules["drop"] = old
@@ -209,11 +152,11 @@ def _reference(m, inputs, last_only=False, step=None, seed=None, goal_mask=True)
 def _report(tag, precision, m, got_loss, got_in, got_par, ref):
     """prints and returns (loss error, worst input-gradient error, worst parameter-gradient error)"""
     ref_loss, ref_s, ref_g, ref_par = ref
-    _, _, floor = BOUNDS[precision]
+    _, _, floor = TRAIN_BOUNDS[precision]
     lerr = abs(got_loss - ref_loss) / abs(ref_loss)
     pairs = [(g, r) for g, r in zip(got_in, (ref_s, ref_g)) if r is not None]
-    ierrs = _grad_errors([g for g, _ in pairs], [r for _, r in pairs], floor)
-    perrs = _grad_errors(got_par, ref_par, floor)
+    ierrs = grad_errors([g for g, _ in pairs], [r for _, r in pairs], floor)
+    perrs = grad_errors(got_par, ref_par, floor)
     worst = max(range(len(perrs)), key=lambda i: perrs[i])
     print(f"[parity] input grads {tag} {precision}: loss {lerr:.2e}, state_grad {ierrs[0]:.2e}, goal_grad "
           f"{ierrs[1] if len(ierrs) > 1 else float('nan'):.2e}, worst parameter gradient {perrs[worst]:.2e} "
@@ -250,11 +193,11 @@ def test_loss_backward_reaches_state_and_goal(cfg_name, precision, plan):
     pred_last_action_only.  B = 5: no multiple of a tile, and with the goals two partial row tiles of input_grad_kernel."""
     from beso_amd.runtime import plan as run_plan
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, train=True)
     W = cfg.obs_seq_len
-    ltol, gtol, _ = BOUNDS[precision]
+    ltol, gtol, _ = TRAIN_BOUNDS[precision]
     for t, last_only in [(t, False) for t in sorted({max(1, W - 1), W})] + [(W, True)]:
-        inputs = _train_inputs(cfg, 5, t, seed=4 + t)
+        inputs = train_inputs(cfg, 5, t, seed=4 + t)
         with run_plan(train=PLANS[plan]):
             loss, s_grad, g_grad, par = _through_autograd(m, inputs, last_only)
         ref = _reference(m, inputs, last_only)
@@ -274,8 +217,8 @@ def test_loss_backward_reaches_state_and_goal(cfg_name, precision, plan):
 @pytest.mark.gpu
 def test_broadcast_goal_gets_the_sum_over_samples():
     cfg = O.TINY
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32")
-    state, action, goal, noise, sigma = _train_inputs(cfg, 6, cfg.obs_seq_len, seed=9)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32", train=True)
+    state, action, goal, noise, sigma = train_inputs(cfg, 6, cfg.obs_seq_len, seed=9)
     shared = goal[0].contiguous()                                          # [G, obs]
     _, s_b, g_b, par_b = _through_autograd(m, [state, action, shared, noise, sigma])
     _, s_e, g_e, par_e = _through_autograd(m, [state, action, shared.unsqueeze(0).expand(6, -1, -1).contiguous(), noise, sigma])
@@ -286,7 +229,7 @@ def test_broadcast_goal_gets_the_sum_over_samples():
     assert ((s_b - s_e).norm() / s_e.norm()).item() < 1e-6
     ref = _reference(m, [state, action, shared, noise, sigma])
     assert ref[2].shape == shared.shape
-    assert _grad_errors([g_b], [ref[2]], 1e-4)[0] < 1e-4
+    assert grad_errors([g_b], [ref[2]], 1e-4)[0] < 1e-4
 
 
 # -------------------------------------------------------------------------------------------------
@@ -294,8 +237,8 @@ def test_broadcast_goal_gets_the_sum_over_samples():
 # -------------------------------------------------------------------------------------------------
 def _masked_case(cfg_name, precision, goal_drop, B=6, seed=20240):
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, embed_pdrop=0.1, goal_drop=goal_drop)
-    inputs = _train_inputs(cfg, B, cfg.obs_seq_len, seed=4)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, embed_pdrop=0.1, goal_drop=goal_drop, train=True)
+    inputs = train_inputs(cfg, B, cfg.obs_seq_len, seed=4)
     step = m.hip_train_step(*inputs)
     assert step is not None and m.inner_model.training
     loss, _, views, s_grad, g_grad = step.run(*inputs, seed=seed, fresh_grads=True, input_grads=True)
@@ -307,7 +250,7 @@ def _masked_case(cfg_name, precision, goal_drop, B=6, seed=20240):
 def test_masked_step_matches_autograd_with_the_librarys_masks(cfg_name, precision):
     """Training mode, embed_pdrop 0.1 and goal_drop 0.3, then goal_drop 1.0: parity with the library's masks injected; a goal
     element whose keep-mask is 0 has gradient exactly 0.0 -- with goal_drop 1.0 the whole goal gradient."""
-    ltol, gtol, _ = BOUNDS[precision]
+    ltol, gtol, _ = TRAIN_BOUNDS[precision]
     for goal_drop in (0.3, 1.0):
         m, inputs, step, seed, loss, got_in, par = _masked_case(cfg_name, precision, goal_drop)
         ref = _reference(m, inputs, step=step, seed=seed)
@@ -326,7 +269,7 @@ def test_masked_step_matches_autograd_with_the_librarys_masks(cfg_name, precisio
 def test_the_comparison_bites():
     """The same comparison with the goal mask left out of the comparator exceeds the bound (while the right one passes)."""
     m, inputs, step, seed, loss, got_in, par = _masked_case("kitchen", "fp32", 0.3)
-    _, gtol, _ = BOUNDS["fp32"]
+    _, gtol, _ = TRAIN_BOUNDS["fp32"]
     _, ierr, _ = _report("kitchen goal_drop=0.3 (right masks)", "fp32", m, loss, got_in, par, _reference(m, inputs, step=step, seed=seed))
     assert ierr < gtol
     _, ierr, _ = _report("kitchen goal_drop=0.3 (no goal mask in the comparator)", "fp32", m, loss, got_in, par,
@@ -341,8 +284,8 @@ def test_the_comparison_bites():
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_input_grads_are_reproducible_and_leave_the_step_alone(precision):
     cfg = O.KITCHEN
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, embed_pdrop=0.1, goal_drop=0.3)
-    inputs = _train_inputs(cfg, 6, cfg.obs_seq_len, seed=4)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, embed_pdrop=0.1, goal_drop=0.3, train=True)
+    inputs = train_inputs(cfg, 6, cfg.obs_seq_len, seed=4)
     step = m.hip_train_step(*inputs)
     a = step.run(*inputs, seed=7, fresh_grads=True, input_grads=True)
     b = step.run(*inputs, seed=7, fresh_grads=True, input_grads=True)
@@ -376,11 +319,11 @@ def test_denoise_vjp_input_grads_against_autograd(cfg_name, precision):
     first three outputs are the bits of the call without the option."""
     from autograd_reference import forward_autograd
     cfg = O.CONFIGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=0, std=0.02), precision, train=False)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=0, std=0.02), precision, train=False)
     G = m.inner_model.goal_seq_len
     W = cfg.obs_seq_len
     for t in sorted({max(1, W - 1), W}):
-        state, x, goal, cot, sigma = _train_inputs(cfg, 5, t, seed=t)
+        state, x, goal, cot, sigma = train_inputs(cfg, 5, t, seed=t)
         for uncond in (False, True):
             with torch.no_grad():
                 den, xg, dot, s_grad, g_grad = m.denoise_vjp(state, x, goal, sigma, cot, uncond=uncond, input_grads=True)
@@ -413,9 +356,9 @@ def test_denoise_vjp_input_grads_against_autograd(cfg_name, precision):
 @pytest.mark.gpu
 def test_action_noise_and_sigma_that_require_grad_are_refused():
     cfg = O.TINY
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32")
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), "fp32", train=True)
     for i in (1, 3, 4):                                                     # action, noise, sigma
-        inputs = _train_inputs(cfg, 5, cfg.obs_seq_len, seed=4)
+        inputs = train_inputs(cfg, 5, cfg.obs_seq_len, seed=4)
         inputs[i].requires_grad_()
         with pytest.raises(ValueError, match="gradients with respect to action, noise and sigma are not computed"):
             m.loss(*inputs)

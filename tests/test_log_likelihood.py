@@ -4,7 +4,6 @@ CPU: the private dopri5 integrator and the log-likelihood ODE driver on closed f
 GPU: denoise_vjp against torch autograd over the comparator of tests/autograd_reference.py (Karras preconditioning around
 forward_autograd), a finite difference, determinism, and log_likelihood against a closed form and a fixed-step fp64 RK4."""
 import ctypes as C
-import functools
 import math
 import os
 import subprocess
@@ -15,6 +14,7 @@ import torch
 
 from oracle import beso_oracle as O
 from conftest import rel_err
+from support import lib, make_denoiser  # noqa: F401
 from beso_amd import _lib
 from beso_amd.runtime import ScoreNetShape
 from beso_amd.agents.diffusion_agents.k_diffusion import gc_sampling as ks
@@ -67,13 +67,6 @@ def test_log_likelihood_rejects_models_without_the_hip_vjp():
         ks.log_likelihood(model, torch.zeros(2, 3, 5), x, None, 0.01, 1.0)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from beso_amd.build import build
-    build(verbose=False)
-    return _lib.load()
-
-
 def test_denoise_vjp_is_exported_and_checks_its_arguments(lib):
     from beso_amd.build import LIB
     out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
@@ -107,19 +100,7 @@ def test_denoise_vjp_is_exported_and_checks_its_arguments(lib):
 
 # ------------------------------------------------------------------------------------------------ GPU helpers
 def make_module(cfg, precision="fp32", seed=0, std=0.02, device=DEV):
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_gpts import DiffusionGPT
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_wrappers import GCDenoiser
-    inner = functools.partial(
-        DiffusionGPT, state_dim=cfg.obs_dim, device=device, goal_conditioned=cfg.goal_conditioned,
-        action_dim=cfg.act_dim, embed_dim=cfg.embed_dim, embed_pdrob=0.0, attn_pdrop=0.0, resid_pdrop=0.0,
-        n_layers=cfg.n_layers, n_heads=cfg.n_heads, goal_seq_len=cfg.goal_seq_len, obs_seq_len=cfg.obs_seq_len,
-        sigma_vocab_size=3, time_embedding_fn=None, goal_drop=0.0, linear_output=cfg.linear_output, precision=precision)
-    m = GCDenoiser(inner, sigma_data=cfg.sigma_data)
-    sd = m.state_dict()
-    for k, v in O.make_weights(cfg, seed=seed, std=std).items():
-        sd[k] = torch.from_numpy(v.copy())
-    m.load_state_dict(sd)
-    return m.to(device).eval()
+    return make_denoiser(cfg, O.make_weights(cfg, seed=seed, std=std), precision, device=device)
 
 
 def den_autograd(m, state, x, goal, sigma, uncond=False):

@@ -22,6 +22,7 @@ import torch
 
 from oracle import beso_oracle as O
 from conftest import load_golden, weights_from_fixture
+from support import bits, count_site_launches, lib, make_denoiser, to_dev  # noqa: F401
 from beso_amd import _lib
 
 gpu = pytest.mark.gpu
@@ -48,10 +49,6 @@ def _precisions(cfg_name):
 
 
 # ------------------------------------------------------------------------------------------------ helpers
-def G(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
 @functools.lru_cache(maxsize=None)
 def _weights(cfg_name, seed=0, std=0.02):
     return O.make_weights(O.CONFIGS[cfg_name], seed=seed, std=std)
@@ -59,8 +56,7 @@ def _weights(cfg_name, seed=0, std=0.02):
 
 @functools.lru_cache(maxsize=None)
 def _module(cfg_name, precision, seed=0, std=0.02):
-    from test_gpu_parity import make_module
-    return make_module(O.CONFIGS[cfg_name], _weights(cfg_name, seed, std), precision)
+    return make_denoiser(O.CONFIGS[cfg_name], _weights(cfg_name, seed, std), precision)
 
 
 @functools.lru_cache(maxsize=None)
@@ -104,13 +100,9 @@ def _rel_rows(got, ref):
     return float(np.abs(got.double().cpu().numpy() - ref).max() / ref.max())
 
 
-def _bits(x):
-    return x.contiguous().view(torch.int32)
-
-
 def _call(m, cfg_name, B, t=None, seed=0, last_only=False, uncond=False):
     """(loss, per_sample) of ONE runtime call on the module's weights"""
-    s, a, g, n, sg = (G(v) for v in _inputs(cfg_name, B, t, seed))
+    s, a, g, n, sg = (to_dev(v) for v in _inputs(cfg_name, B, t, seed))
     if last_only:
         n[:, :-1] = 0
     inner = m.inner_model
@@ -126,20 +118,19 @@ def test_loss_matches_the_reference_values(fixture, cfg_name, precision):
     """model.eval(); with torch.no_grad(): model.loss(...) against the value the REFERENCE's m.loss(...) returned, in every
     precision that has a kernel for the shape (bf16x3 and fp16: the two shipped shapes, as ONE launch at the fused site).
     MEASURED_BY_FIXTURE holds what an MI355X gave."""
-    from test_gpu_parity import count_fused_launches, make_module
     fx = load_golden(fixture)
     cfg = O.CONFIGS[cfg_name]
     w = weights_from_fixture(fx) or O.make_weights(cfg, seed=int(fx["seed"]), std=float(fx["std"]))
-    m = make_module(cfg, w, precision)
+    m = make_denoiser(cfg, w, precision)
     m.eval()
-    T = lambda k: G(fx[k])          # noqa: E731
+    T = lambda k: to_dev(fx[k])          # noqa: E731
     box = [None]
 
     def run():
         with torch.no_grad():
             box[0] = m.loss(T("state"), T("action"), T("goal"), T("noise"), T("sigma"))
 
-    n_fused = count_fused_launches(run)
+    n_fused = count_site_launches("fused_layer", run)
     loss = box[0]
     assert loss.grad_fn is None and not loss.requires_grad and loss.dim() == 0
     assert all(p.grad is None for p in m.parameters())
@@ -164,7 +155,7 @@ def test_per_sample_values_match_the_oracle(cfg_name, B, t):
     ref = _oracle(cfg_name, B, t)
     for precision in _precisions(cfg_name):
         m = _module(cfg_name, precision)
-        s, a, g, n, sg = (G(v) for v in _inputs(cfg_name, B, t))
+        s, a, g, n, sg = (to_dev(v) for v in _inputs(cfg_name, B, t))
         with torch.no_grad():
             rows = m.loss_per_sample(s, a, g, n, sg)
         assert rows.shape == (B,) and rows.grad_fn is None
@@ -173,7 +164,7 @@ def test_per_sample_values_match_the_oracle(cfg_name, B, t):
         mean_err = abs(rows2.double().mean().item() - loss.item()) / abs(loss.item())
         print(f"[loss_fwd] per-sample {cfg_name} B={B} t={t} {precision}: rel err {err:.3e} (largest value {ref.max():.4f}), "
               f"mean-vs-scalar {mean_err:.2e}")
-        assert torch.equal(_bits(rows), _bits(rows2))
+        assert torch.equal(bits(rows), bits(rows2))
         assert mean_err <= 1e-6
         assert err <= BAR[precision], (precision, err)
 
@@ -189,7 +180,7 @@ def test_pred_last_action_only_scores_the_last_step(cfg_name):
     ref = _oracle(cfg_name, B, None, last_only=True)
     for precision in _precisions(cfg_name):
         m = _module(cfg_name, precision)
-        s, a, g, n, sg = (G(v) for v in _inputs(cfg_name, B))
+        s, a, g, n, sg = (to_dev(v) for v in _inputs(cfg_name, B))
         with torch.no_grad():
             last = m.loss(s, a, g, n, sg, pred_last_action_only=True)
             assert float(n[:, :-1].abs().max()) == 0.0 and float(n[:, -1].abs().max()) > 0.0      # zeroed in place, like the reference
@@ -211,7 +202,7 @@ def test_pred_last_action_only_scores_the_last_step(cfg_name):
 def test_uncond_equals_zero_goals_bit_for_bit(cfg_name, precision):
     m = _module(cfg_name, precision)
     B = 5
-    s, a, g, n, sg = (G(v) for v in _inputs(cfg_name, B))
+    s, a, g, n, sg = (to_dev(v) for v in _inputs(cfg_name, B))
     inner = m.inner_model
     rt, packed = inner.runtime(m.sigma_data), inner.packed_weights()
     with torch.no_grad():
@@ -219,9 +210,9 @@ def test_uncond_equals_zero_goals_bit_for_bit(cfg_name, precision):
         lz, rz = rt.loss(packed, s, a, torch.zeros_like(g), n, sg, per_sample=True)
         lc, rc = rt.loss(packed, s, a, g, n, sg, per_sample=True)
         ru2 = m.loss_per_sample(s, a, g, n, sg, uncond=True)
-    assert torch.equal(_bits(lu), _bits(lz)) and torch.equal(_bits(ru), _bits(rz)) and torch.equal(_bits(ru), _bits(ru2))
+    assert torch.equal(bits(lu), bits(lz)) and torch.equal(bits(ru), bits(rz)) and torch.equal(bits(ru), bits(ru2))
     assert abs(lu.item() - lc.item()) > BAR[precision] * abs(lc.item())
-    assert not torch.equal(_bits(ru), _bits(rc))
+    assert not torch.equal(bits(ru), bits(rc))
     ref = oracle_rows(_weights(cfg_name), O.CONFIGS[cfg_name], *_inputs(cfg_name, B), uncond=True)
     assert _rel_rows(ru, ref) <= BAR[precision]
 
@@ -237,16 +228,16 @@ def test_per_sample_values_do_not_depend_on_the_batch(B):
     m = _module("kitchen", "bf16")
     inner = m.inner_model
     rt, packed = inner.runtime(m.sigma_data), inner.packed_weights()
-    s, a, g, n, sg = (G(v) for v in _inputs("kitchen", B))
+    s, a, g, n, sg = (to_dev(v) for v in _inputs("kitchen", B))
     with torch.no_grad(), plan(forward=_lib.PLAN_FUSED):
         loss, rows = rt.loss(packed, s, a, g, n, sg, per_sample=True)
         loss2, rows2 = rt.loss(packed, s, a, g, n, sg, per_sample=True)
         only = rt.loss(packed, s, a, g, n, sg)
         alone = torch.stack([rt.loss(packed, s[b:b + 1], a[b:b + 1], g[b:b + 1], n[b:b + 1], sg[b:b + 1], per_sample=True)[1][0]
                              for b in range(B)])
-    assert torch.equal(_bits(loss), _bits(loss2)) and torch.equal(_bits(rows), _bits(rows2)) and torch.equal(_bits(loss), _bits(only))
+    assert torch.equal(bits(loss), bits(loss2)) and torch.equal(bits(rows), bits(rows2)) and torch.equal(bits(loss), bits(only))
     assert torch.isfinite(rows).all()
-    mismatch = (_bits(rows) != _bits(alone)).nonzero().flatten().tolist()
+    mismatch = (bits(rows) != bits(alone)).nonzero().flatten().tolist()
     assert not mismatch, (B, mismatch[:8])
     assert abs(rows.double().mean().item() - loss.item()) <= 1e-6 * abs(loss.item())
 
@@ -255,7 +246,6 @@ def test_per_sample_values_do_not_depend_on_the_batch(B):
 @pytest.mark.parametrize("B", [1, 257])
 def test_library_plan_choice_matches_the_oracle(B):
     """No hint: B = 1 takes the chip-wide small-batch path, B = 257 the one-launch kernel; both within the bf16 bar."""
-    from test_gpu_parity import count_site_launches
     m = _module("kitchen", "bf16")
     box = [None]
     n_small = count_site_launches("small", lambda: box.__setitem__(0, _call(m, "kitchen", B)))
@@ -278,7 +268,7 @@ def test_results_do_not_depend_on_what_the_buffers_held(cfg_name, precision, B):
     inner = m.inner_model
     rt, packed = inner.runtime(m.sigma_data), inner.packed_weights()
     lib = rt.lib
-    s, a, g, n, sg = (G(v) for v in _inputs(cfg_name, B))
+    s, a, g, n, sg = (to_dev(v) for v in _inputs(cfg_name, B))
     t = s.shape[1]
     wsb = lib.beso_loss_fwd_workspace_bytes(C.byref(rt.cfg), B, t, packed.precision)
     assert wsb > lib.beso_workspace_bytes(C.byref(rt.cfg), B, t, packed.precision, 0) + 2 * a.numel() * 4
@@ -294,35 +284,28 @@ def test_results_do_not_depend_on_what_the_buffers_held(cfg_name, precision, B):
             ok = torch.stack([x.guards_ok() for x in [ws, out, rows] + ins]).all()
             assert bool(ok), f"{name}: a guard band was written"
             for x, src in zip(ins, (s, a, g, n, sg)):
-                assert torch.equal(_bits(x.f32()), _bits(src.reshape(-1))), f"{name}: an input was modified"
+                assert torch.equal(bits(x.f32()), bits(src.reshape(-1))), f"{name}: an input was modified"
             assert not bool(_carries_fill(out.f32(), byte)), name
             if with_rows:
                 assert not bool(_carries_fill(rows.f32(), byte)), name
                 got[name] = (out.f32().clone(), rows.f32().clone())
             else:
                 assert bool((rows.big == byte).all()), f"{name}: per_sample_out = NULL, yet the buffer was written"
-                assert torch.equal(_bits(out.f32()), _bits(got[name][0])), f"{name}: the scalar differs without per_sample_out"
+                assert torch.equal(bits(out.f32()), bits(got[name][0])), f"{name}: the scalar differs without per_sample_out"
     assert torch.isfinite(got["ZERO"][0]).all() and torch.isfinite(got["ZERO"][1]).all()
     for name in ("NAN", "HUGE"):
-        assert torch.equal(_bits(got[name][0]), _bits(got["ZERO"][0])), name
-        assert torch.equal(_bits(got[name][1]), _bits(got["ZERO"][1])), name
+        assert torch.equal(bits(got[name][0]), bits(got["ZERO"][0])), name
+        assert torch.equal(bits(got[name][1]), bits(got["ZERO"][1])), name
     # loss_out = NULL: the per-sample values alone, the same bits
     ws, rows = Guarded(wsb, 0xFF), Guarded(4 * B, 0xFF)
     st = lib.beso_loss_fwd(C.byref(rt.cfg), packed.buf.data_ptr(), packed.precision, s.data_ptr(), a.data_ptr(), g.data_ptr(),
                            n.data_ptr(), sg.data_ptr(), None, rows.ptr, B, t, 0, ws.ptr, wsb,
                            C.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert st == 0 and bool(ws.guards_ok() & rows.guards_ok())
-    assert torch.equal(_bits(rows.f32()), _bits(got["ZERO"][1]))
+    assert torch.equal(bits(rows.f32()), bits(got["ZERO"][1]))
 
 
 # ------------------------------------------------------------------------------------------------ 7. argument checking (no GPU)
-@pytest.fixture(scope="module")
-def lib():
-    from beso_amd.build import build
-    build(verbose=False)
-    return _lib.load()
-
-
 def test_argument_errors_do_not_touch_the_device(lib):
     """Every rejection happens before anything is enqueued (the pointers below are not memory): the documented status, and
     _lib.check turns it into the exception of that status -- ValueError for bad arguments / shapes, BesoHipError (the library's
@@ -414,11 +397,10 @@ def test_agent_validation_loss_is_the_ema_loss_of_the_scaled_batch(last_only):
     assert torch.equal(noise, noise_before)
     assert isinstance(got, float)
     # the same value from GCDenoiser.loss on a module that CARRIES the EMA weights, on the scaled batch
-    from test_gpu_parity import make_module
     state, action, goal = agent.process_batch(batch, predict=False)
     names = [k for k, _ in agent.model.named_parameters()]
-    ema = make_module(cfg, {k: v.detach().cpu().numpy() for k, v in zip(names, agent.ema_helper.shadow_params)}, "fp32")
-    raw = make_module(cfg, {k: v.detach().cpu().numpy() for k, v in agent.model.named_parameters()}, "fp32")
+    ema = make_denoiser(cfg, {k: v.detach().cpu().numpy() for k, v in zip(names, agent.ema_helper.shadow_params)}, "fp32")
+    raw = make_denoiser(cfg, {k: v.detach().cpu().numpy() for k, v in agent.model.named_parameters()}, "fp32")
     with torch.no_grad():
         want = ema.loss(state, action, goal, noise.clone(), sigma, pred_last_action_only=last_only).item()
         other = raw.loss(state, action, goal, noise.clone(), sigma, pred_last_action_only=last_only).item()
@@ -465,13 +447,13 @@ def test_agent_loss_by_sigma_is_one_call_over_all_levels(monkeypatch):
             agent.model.eval()
             for k, sg in enumerate(sigmas):
                 rows = den.loss_per_sample(state, action, goal, noise.clone(), torch.full((B,), sg, device=DEV))
-                assert torch.equal(_bits(rows), _bits(table[k])), k
+                assert torch.equal(bits(rows), bits(table[k])), k
         # a draw per level: [K, B, t, act]
         nk = torch.randn(3, B, cfg.obs_seq_len, cfg.act_dim, device=DEV, generator=torch.Generator(DEV).manual_seed(8))
         _, table_k = agent.loss_by_sigma(batch, sigmas, noise=nk)
         with agent._ema_scope(), torch.no_grad():
             rows = den.loss_per_sample(state, action, goal, nk[2].clone(), torch.full((B,), sigmas[2], device=DEV))
-        assert torch.equal(_bits(rows), _bits(table_k[2]))
+        assert torch.equal(bits(rows), bits(table_k[2]))
     assert table[0].mean() != table[2].mean()
     _same_state(before, _training_state(agent))
 

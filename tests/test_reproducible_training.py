@@ -6,14 +6,13 @@ written as partial sums into a slab of the workspace and added up by a second la
 ``HipTrainStep.run(deterministic=)``, ``BesoAgent(deterministic_training=)``, ``FusedAdam.export_state / import_state``,
 ``DeviceTrajectoryFeed.state_dict / load_state_dict`` and ``BesoAgent.store_training_state / load_training_state``.
 
-Bounds of the same-function test: ``test_dropout_parity.BOUNDS`` (imported) -- the importable form of the bounds that
+Bounds of the same-function test: ``support.TRAIN_BOUNDS`` (imported) -- the importable form of the bounds that
 ``test_gpu_parity.test_hip_loss_and_gradients_match_autograd`` applies to the same comparator (tests/autograd_reference.py):
 fp32 loss 2e-5, gradients 1e-4 per tensor; bf16 loss 2e-3, gradients 2.6e-2 per tensor.  Everything else here is bit equality.
 
 The feed: 7 trajectories of lengths 12, 15, ..., 30.  With a window of 5 that is 119 windows, eight batches of 16 with a
 short last one of 7 (a feed of 7 such trajectories cannot be as small as four batches: the shortest possible one has 74
 windows).  The agent test needs the kitchen model's window (4) and uses the same trajectories with it: 126 windows."""
-import functools
 
 import numpy as np
 import pytest
@@ -21,6 +20,7 @@ import torch
 
 from beso_amd import _lib
 from oracle import beso_oracle as O
+from support import TRAIN_BOUNDS, bits, build_agent, make_denoiser, train_inputs
 
 DEV = "cuda:0"
 SEED = 4242
@@ -68,11 +68,10 @@ IDS = ["-".join(str(v) for v in c[:4]) + ("-dropout" if any(c[4:]) else "") for 
 
 
 def _case(cfg_name, B, precision, attn_p, resid_p, embed_p, goal_p):
-    from test_dropout_parity import _train_inputs, _train_module
     cfg = _CFGS[cfg_name]
-    m = _train_module(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, attn_pdrop=attn_p, resid_pdrop=resid_p,
-                      embed_pdrop=embed_p, goal_drop=goal_p)
-    return m, _train_inputs(cfg, B, seed=4)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.06), precision, attn_pdrop=attn_p, resid_pdrop=resid_p,
+                      embed_pdrop=embed_p, goal_drop=goal_p, train=True)
+    return m, train_inputs(cfg, B, seed=4)
 
 
 def _run(step, inputs, plan, deterministic, **kw):
@@ -85,10 +84,6 @@ def _run(step, inputs, plan, deterministic, **kw):
         set_plan(train=0)
     torch.cuda.synchronize()
     return loss.clone(), flat.clone()
-
-
-def _bits(x):
-    return x.contiguous().view(torch.int32)
 
 
 # ------------------------------------------------------------------------------------------------ the step
@@ -107,8 +102,8 @@ def test_flagged_step_gives_equal_bits(cfg_name, B, precision, plan, attn_p, res
             step._ws.fill_(fill)
             step._flat_full.view(torch.uint8).fill_(fill)
         got = _run(step, inputs, plan, True)
-        assert torch.equal(_bits(got[0]), _bits(ref[0])), (fill, got[0].item(), ref[0].item())
-        assert torch.equal(_bits(got[1]), _bits(ref[1])), fill
+        assert torch.equal(bits(got[0]), bits(ref[0])), (fill, got[0].item(), ref[0].item())
+        assert torch.equal(bits(got[1]), bits(ref[1])), fill
 
 
 @pytest.mark.gpu
@@ -117,7 +112,7 @@ def test_flagged_step_is_the_same_function(cfg_name, B, precision, plan, attn_p,
     """The flagged step against torch autograd with the library's masks (the comparator and bounds of
     tests/test_dropout_parity.py), and against the unflagged step at the same seed: the six weight-matrix gradients of every
     block are plain stores of the grouped launch, which nothing of the three sites feeds -- bit-equal."""
-    from test_dropout_parity import BOUNDS, _autograd, _compare
+    from test_dropout_parity import _autograd, _compare
     m, inputs = _case(cfg_name, B, precision, attn_p, resid_p, embed_p, goal_p)
     step = m.hip_train_step(*inputs)
     loss_d, flat_d = _run(step, inputs, plan, True)
@@ -131,11 +126,11 @@ def test_flagged_step_is_the_same_function(cfg_name, B, precision, plan, attn_p,
     assert len(weights) == 6 * _CFGS[cfg_name].n_layers, weights
     for n in weights:
         a, b = views[n]
-        assert torch.equal(_bits(flat_d[a:b]), _bits(flat_u[a:b])), n
+        assert torch.equal(bits(flat_d[a:b]), bits(flat_u[a:b])), n
     got = [flat_d[a:b].view_as(p) for (a, b), p in zip(views.values(), m.parameters())]
     ref_loss, ref = _autograd(m, step, inputs, SEED)
     lerr, gerr = _compare(f"deterministic {cfg_name} B={B} {plan}", m, precision, loss_d.item(), got, ref_loss, ref)
-    ltol, gtol, _ = BOUNDS[precision]
+    ltol, gtol, _ = TRAIN_BOUNDS[precision]
     print(f"[reproducible] {cfg_name} {precision} {plan}: flagged loss {loss_d.item()!r}, unflagged {loss_u.item()!r}")
     assert lerr < ltol and gerr < gtol, (lerr, gerr)
 
@@ -243,7 +238,7 @@ def _small_feed(seed, window=5, obs_dim=30, act_dim=9, goal_len=2, batch_size=16
 
 
 def _same_batch(a, b):
-    return set(a) == set(b) and all(torch.equal(_bits(a[k]), _bits(b[k])) for k in a)
+    return set(a) == set(b) and all(torch.equal(bits(a[k]), bits(b[k])) for k in a)
 
 
 @pytest.mark.gpu
@@ -299,12 +294,10 @@ def test_feed_round_trip():
 # ------------------------------------------------------------------------------------------------ agent
 def _agent(weight_seed, torch_seed, **extra):
     from beso_amd.networks.scaler.scaler_class import Scaler
-    from test_gpu_parity import _train_module
-    from tools._agent import build_agent
     cfg = O.KITCHEN
     torch.manual_seed(torch_seed)
     w = O.make_weights(cfg, seed=weight_seed, std=0.05)
-    agent = build_agent(cfg, lambda: _train_module(cfg, w, "bf16", attn_pdrop=0.3), device=DEV, lr=1e-3, **extra)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "bf16", attn_pdrop=0.3, train=True), device=DEV, lr=1e-3, **extra)
     agent.lr_scheduler = torch.optim.lr_scheduler.StepLR(agent.optimizer, 1, 0.9)      # changes every step
     rng = np.random.default_rng(0)
     agent.get_scaler(Scaler(rng.standard_normal((64, cfg.obs_dim)).astype(np.float32),
@@ -380,8 +373,8 @@ def test_exact_resume(tmp_path):
     print(f"[reproducible] A {losses_a}, C {losses_c}")
     assert [np.float32(v).tobytes() for v in losses_c] == [np.float32(v).tobytes() for v in losses_a[3:]]
     for x, y in zip(_agent_state(a), _agent_state(c)):
-        assert torch.equal(_bits(x.float()) if x.dtype != torch.float64 else x.view(torch.int64),
-                           _bits(y.float()) if y.dtype != torch.float64 else y.view(torch.int64))
+        assert torch.equal(bits(x.float()) if x.dtype != torch.float64 else x.view(torch.int64),
+                           bits(y.float()) if y.dtype != torch.float64 else y.view(torch.int64))
     assert a.steps == c.steps == 6
     assert a.lr_scheduler.get_last_lr() == c.lr_scheduler.get_last_lr() != [1e-3]
     assert a.optimizer.param_groups[0]["lr"] == c.optimizer.param_groups[0]["lr"]

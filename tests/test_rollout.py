@@ -6,7 +6,7 @@ reference's recorded ``predict`` trace, one batched ``sample_loop`` call on wind
 every window is full), and the per-environment UNPADDED ``sample_loop`` call on the test's own deques (to the parity
 tolerances of tests/test_gpu_parity.py: padded and unpadded calls run different shapes, hence different kernels)."""
 import ctypes as C
-import functools
+import dataclasses
 from collections import deque
 
 import numpy as np
@@ -15,6 +15,7 @@ import torch
 
 from oracle import beso_oracle as O
 from conftest import load_golden, weights_from_fixture, rel_err
+from support import build_agent, count_site_launches, lib, make_denoiser  # noqa: F401
 from beso_amd import _lib
 from beso_amd.networks.scaler.scaler_class import Scaler
 
@@ -23,13 +24,6 @@ DEV = "cuda:0"
 
 
 # ------------------------------------------------------------------------------------------------ no GPU
-@pytest.fixture(scope="module")
-def lib():
-    from beso_amd.build import build
-    build(verbose=False)
-    return _lib.load()
-
-
 def test_rollout_argument_errors_do_not_touch_the_device(lib):
     """beso_rollout_begin / beso_rollout_end reject NULL required pointers, a statistics pair with one half missing, a window,
     obs_dim or act_dim below one and a negative n_envs before anything is enqueued (status -3); n_envs == 0 is a no-op."""
@@ -60,14 +54,8 @@ def test_rollout_argument_errors_do_not_touch_the_device(lib):
 
 def test_vector_rollout_has_no_cpu_path():
     """A model on the CPU raises when the rollout is made: there is no CPU path and no fallback to ``predict``."""
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_gpts import DiffusionGPT
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_wrappers import GCDenoiser
-    from test_host_logic import build_agent
-    cfg = O.TINY
-    inner = functools.partial(DiffusionGPT, state_dim=cfg.obs_dim, device="cpu", goal_conditioned=True, action_dim=cfg.act_dim,
-                              embed_dim=cfg.embed_dim, embed_pdrob=0.0, attn_pdrop=0.0, resid_pdrop=0.0, n_layers=cfg.n_layers,
-                              n_heads=cfg.n_heads, goal_seq_len=cfg.goal_seq_len, obs_seq_len=cfg.obs_seq_len)
-    agent = build_agent(cfg, lambda: GCDenoiser(inner, sigma_data=cfg.sigma_data))
+    cfg = dataclasses.replace(O.TINY, linear_output=False)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, precision=None, device="cpu", train=True))
     with pytest.raises(RuntimeError, match="no CPU path"):
         agent.vector_rollout(4)
 
@@ -75,10 +63,8 @@ def test_vector_rollout_has_no_cpu_path():
 # ------------------------------------------------------------------------------------------------ GPU
 def _agent(cfg, precision="fp32", sampler="ddim"):
     """An agent around the HIP module of `cfg` with seeded weights, the EMA shadow equal to them, and an fp32 scaler."""
-    from test_host_logic import build_agent
-    from test_gpu_parity import make_module
     w = O.make_weights(cfg, seed=3, std=0.05)
-    agent = build_agent(cfg, lambda: make_module(cfg, w, precision), device=DEV, sampler=sampler)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, w, precision), device=DEV, sampler=sampler)
     agent.ema_helper.load_shadow_params(agent.model.get_params())
     rng = np.random.default_rng(7)
     sc = Scaler(rng.standard_normal((64, cfg.obs_dim)).astype(np.float32) * 2 + 0.5,
@@ -168,12 +154,10 @@ def _staggered(agent, cfg, n_envs, n_steps_total, sampler, n_steps, tol, tag):
 def test_vector_rollout_replays_the_reference_trace():
     """N = 1 on tests/golden/tiny_agent_trace.npz with the fixture's draws injected: the reference's own predictions, within
     the bound test_agent_predict_trace_on_gpu holds predict to.  Its first W - 1 calls are short windows, run padded here."""
-    from test_host_logic import build_agent
-    from test_gpu_parity import make_module
     fx = load_golden("tiny_agent_trace.npz")
     cfg = O.TINY
     w = weights_from_fixture(fx)
-    agent = build_agent(cfg, lambda: make_module(cfg, w, "fp32"), device=DEV)
+    agent = build_agent(cfg, lambda: make_denoiser(cfg, w, "fp32"), device=DEV)
     agent.ema_helper.load_shadow_params(agent.model.get_params())
     agent.get_scaler(Scaler(fx["x_data"], fx["y_data"], True, DEV))
     agent.set_bounds(agent.scaler)
@@ -340,7 +324,7 @@ def test_kitchen_bf16_staggered_rollout_runs_the_one_launch_sampler():
     """KITCHEN shape, bf16, N = 8 with staggered resets, DDIM-3 and Heun against the unpadded per-environment calls; with the
     one-launch kernel asked for, a whole rollout step launches it once."""
     from beso_amd.runtime import set_plan
-    from test_gpu_parity import TOL, count_site_launches
+    from test_gpu_parity import TOL
     cfg = O.KITCHEN
     agent = _agent(cfg, "bf16")
     set_plan(forward=_lib.PLAN_FUSED)

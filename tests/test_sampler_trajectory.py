@@ -12,7 +12,8 @@ import torch
 
 from oracle import beso_oracle as O
 from conftest import load_golden, weights_from_fixture, rel_err
-from test_gpu_parity import make_module, G, count_fused_launches, TOL
+from support import build_agent, count_site_launches, make_denoiser, to_dev
+from test_gpu_parity import TOL
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -42,7 +43,7 @@ def test_trajectory_is_recorded_by_the_loop_itself_and_equals_the_stepwise_form(
     call step by step: kitchen bf16, 3 samples), x_0 is the plain call's, and xs / denoised equal those of the step-by-step
     form bit for bit; xs[0] is x_T, xs[-1] is x_0, the caller's x_T is untouched."""
     cfg = O.CONFIGS[cfg_name]
-    m = make_module(cfg, O.make_weights(cfg, seed=3, std=0.03), precision)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.03), precision)
     s_np, g_np, x_np = O.make_inputs(cfg, B, seed=11)
     from beso_amd import _lib
     from beso_amd.runtime import set_plan
@@ -57,7 +58,7 @@ def test_trajectory_is_recorded_by_the_loop_itself_and_equals_the_stepwise_form(
 def _loop_equals_stepwise(cfg, m, cfg_name, precision, B, lam, s_np, g_np, x_np, small_route):
     with torch.no_grad():
         for t in sorted({cfg.obs_seq_len, max(1, cfg.obs_seq_len - 2)}):
-            s, g, x = G(s_np[:, :t]), G(g_np), G(x_np[:, :t])
+            s, g, x = to_dev(s_np[:, :t]), to_dev(g_np), to_dev(x_np[:, :t])
             keep = x.clone()
             specs = list(SAMPLERS)
             if (cfg_name, precision, B) == ("kitchen", "bf16", 64) and t == cfg.obs_seq_len:
@@ -66,10 +67,10 @@ def _loop_equals_stepwise(cfg, m, cfg_name, precision, B, lam, s_np, g_np, x_np,
                 sig = _sigmas(n_steps)
                 kw = dict(kw, cond_lambda=lam, noise=_noise(sampler, n_steps, x))
                 out = {}
-                n_loop = count_fused_launches(lambda: out.__setitem__(
+                n_loop = count_site_launches("fused_layer", lambda: out.__setitem__(
                     "loop", m.fused_sampler(sampler, s, x, g, sig, trace=("x", "denoised"), **kw)))
                 out["step"] = m.fused_sampler(sampler, s, x, g, sig, trace=("x", "denoised"), stepwise=True, **kw)
-                n_plain = count_fused_launches(lambda: out.__setitem__("plain", m.fused_sampler(sampler, s, x, g, sig, **kw)))
+                n_plain = count_site_launches("fused_layer", lambda: out.__setitem__("plain", m.fused_sampler(sampler, s, x, g, sig, **kw)))
                 plain = out["plain"]
                 what = (cfg_name, precision, B, t, sampler, n_steps)
                 assert n_loop == n_plain == (0 if small_route else (n_evals + 127) // 128), what
@@ -103,9 +104,9 @@ def test_trajectory_is_the_chain_of_two_entry_schedules(cfg_name, B, lam):
     the model's own forward at (xs[i], sigmas[i]) -- equal bits."""
     from beso_amd.agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
     cfg = O.CONFIGS[cfg_name]
-    m = make_module(cfg, O.make_weights(cfg, seed=3, std=0.03), "bf16")
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.03), "bf16")
     model = m if lam == 1.0 else ClassifierFreeSampleModel(m, lam)
-    s, g, x = (G(v) for v in O.make_inputs(cfg, B, seed=11))
+    s, g, x = (to_dev(v) for v in O.make_inputs(cfg, B, seed=11))
     with torch.no_grad():
         for sampler, n_steps in (("ddim", 3), ("euler", 4), ("heun", 3), ("dpm_2", 3), ("dpmpp_2s", 3)):
             sig = _sigmas(n_steps)
@@ -125,13 +126,13 @@ def test_sample_trajectory_vs_reference_vectors(precision):
     from beso_amd.agents.diffusion_agents.k_diffusion import gc_sampling as ks
     fx = load_golden("tiny_trajectory.npz")
     cfg = O.TINY
-    m = make_module(cfg, O.make_weights(cfg, seed=int(fx["seed"]), std=float(fx["std"])), precision)
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=int(fx["seed"]), std=float(fx["std"])), precision)
     tol = TOL["fp32"] if precision == "fp32" else 2e-2
-    s, g, x_t = G(fx["state"]), G(fx["goal"]), G(fx["x_t"])
+    s, g, x_t = to_dev(fx["state"]), to_dev(fx["goal"]), to_dev(fx["x_t"])
     worst = {}
     with torch.no_grad():
         for name in ("euler", "heun", "dpmpp_2m", "euler_ancestral"):
-            nz = G(fx[name + "::noise"]) if name + "::noise" in fx else None
+            nz = to_dev(fx[name + "::noise"]) if name + "::noise" in fx else None
             x0, xs, den = ks.sample_trajectory(name, m, s, x_t, g, torch.from_numpy(fx[name + "::sigmas"]), noise=nz)
             n = len(fx[name + "::sigmas"]) - 1
             assert xs.shape[0] == n + 1 and den.shape[0] == n
@@ -143,9 +144,9 @@ def test_sample_trajectory_vs_reference_vectors(precision):
             worst[name] = max(ex + ed)
             assert torch.equal(xs[n], x0)
         k = int(fx["ode::get_mean"])
-        s2 = torch.repeat_interleave(G(fx["ode::state"]), repeats=k, dim=0)
-        g2 = torch.repeat_interleave(G(fx["ode::goal"]), repeats=k, dim=0)
-        _, xs, _ = ks.sample_trajectory("ddim", m, s2, G(fx["ode::actions"][0]), g2, torch.from_numpy(fx["ode::sigmas"]),
+        s2 = torch.repeat_interleave(to_dev(fx["ode::state"]), repeats=k, dim=0)
+        g2 = torch.repeat_interleave(to_dev(fx["ode::goal"]), repeats=k, dim=0)
+        _, xs, _ = ks.sample_trajectory("ddim", m, s2, to_dev(fx["ode::actions"][0]), g2, torch.from_numpy(fx["ode::sigmas"]),
                                         trace=("x",))
         eo = [rel_err(xs[i].cpu().numpy(), fx["ode::actions"][i]) for i in range(len(xs))]
         print(f"[trajectory] visualize_ode list {precision}: " + " ".join(f"{e:.2e}" for e in eo))
@@ -155,7 +156,6 @@ def test_sample_trajectory_vs_reference_vectors(precision):
 
 
 def _agent(cfg, module, x_data, y_data):
-    from test_host_logic import build_agent
     from beso_amd.networks.scaler.scaler_class import Scaler
     agent = build_agent(cfg, lambda: module, device=DEV)
     agent.ema_helper.load_shadow_params(agent.model.get_params())
@@ -174,11 +174,11 @@ def test_agent_visualize_ode(which):
     if which == "tiny":
         fx = load_golden("tiny_agent_trace.npz")
         cfg, get_mean, n_launch = O.TINY, 4, 0
-        agent = _agent(cfg, make_module(cfg, weights_from_fixture(fx), "fp32"), fx["x_data"], fx["y_data"])
+        agent = _agent(cfg, make_denoiser(cfg, weights_from_fixture(fx), "fp32"), fx["x_data"], fx["y_data"])
     else:
         cfg, get_mean, n_launch = O.KITCHEN, 100, 1
         rng = np.random.default_rng(2)
-        agent = _agent(cfg, make_module(cfg, O.make_weights(cfg, seed=3, std=0.03), "bf16"),
+        agent = _agent(cfg, make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.03), "bf16"),
                        rng.standard_normal((64, cfg.obs_dim)).astype(np.float32),
                        rng.standard_normal((64, cfg.act_dim)).astype(np.float32))
     from beso_amd.agents.diffusion_agents.k_diffusion import gc_sampling as ks
@@ -194,7 +194,7 @@ def test_agent_visualize_ode(which):
     for call in range(2):                         # the observation context grows: t = 1, then t = 2
         state = torch.from_numpy(rng.standard_normal((N, cfg.obs_dim)).astype(np.float32))
         out = {}
-        n = count_fused_launches(lambda: out.__setitem__(0, agent.visualize_ode(
+        n = count_site_launches("fused_layer", lambda: out.__setitem__(0, agent.visualize_ode(
             state, goal, get_mean=get_mean, new_sampling_steps=3, noise_scheduler="exponential")))
         acts = out[0]
         t = call + 1
@@ -236,9 +236,9 @@ def test_traced_entry_point_checks_its_arguments():
     """Capacities one float short -> BESO_ERR_WORKSPACE with x untouched; a trace buffer over x -> BESO_ERR_BAD_ARG; both
     pointers NULL -> beso_sample's result."""
     cfg = O.KITCHEN
-    m = make_module(cfg, O.make_weights(cfg, seed=3, std=0.03), "bf16")
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.03), "bf16")
     B, n_steps = 64, 3
-    s, g, x_t = (G(v) for v in O.make_inputs(cfg, B, seed=11))
+    s, g, x_t = (to_dev(v) for v in O.make_inputs(cfg, B, seed=11))
     sig = [float(v) for v in _sigmas(n_steps)]
     n = x_t.numel()
     tx = torch.zeros((n_steps + 1) * n, device=DEV)
@@ -265,9 +265,9 @@ def test_trace_buffers_are_written_not_read(B):
     """What the trace buffers hold before the call changes nothing (zeros, NaN bits, a large finite value): results and
     traces are identical, and the rows behind the stated capacity keep their fill."""
     cfg = O.KITCHEN
-    m = make_module(cfg, O.make_weights(cfg, seed=3, std=0.03), "bf16")
+    m = make_denoiser(cfg, O.make_weights(cfg, seed=3, std=0.03), "bf16")
     n_steps = 3
-    s, g, x_t = (G(v) for v in O.make_inputs(cfg, B, seed=11))
+    s, g, x_t = (to_dev(v) for v in O.make_inputs(cfg, B, seed=11))
     sig = [float(v) for v in _sigmas(n_steps)]
     n = x_t.numel()
     cap_x, cap_d, guard = (n_steps + 1) * n, n_steps * n, 2 * x_t.shape[1] * x_t.shape[2]

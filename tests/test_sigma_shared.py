@@ -8,7 +8,6 @@ instances, non-uniform batches (which must take the six-tile instance and leave 
 and its invalidation by a repack, and the launch-site count of a qualifying forward."""
 import ctypes as C
 import dataclasses
-import functools
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ import torch
 
 from oracle import beso_oracle as O
 from beso_amd import _lib
+from support import load_weights, make_denoiser, profile_site, to_dev
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -24,28 +24,8 @@ SIX = _lib.PLAN_FUSED | _lib.PLAN_SPW8 | _lib.PLAN_SIGMA_PRIVATE      # eight sa
 TWO = _lib.PLAN_FUSED | _lib.PLAN_SPW2 | _lib.PLAN_SIGMA_PRIVATE      # the two-sample latency instance
 
 
-def G(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
 def make_module(precision, seed=5, std=0.04, cfg=O.KITCHEN):
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_gpts import DiffusionGPT
-    from beso_amd.agents.diffusion_agents.k_diffusion.score_wrappers import GCDenoiser
-    inner = functools.partial(
-        DiffusionGPT, state_dim=cfg.obs_dim, device=DEV, goal_conditioned=cfg.goal_conditioned,
-        action_dim=cfg.act_dim, embed_dim=cfg.embed_dim, embed_pdrob=0.0, attn_pdrop=0.0, resid_pdrop=0.0,
-        n_layers=cfg.n_layers, n_heads=cfg.n_heads, goal_seq_len=cfg.goal_seq_len, obs_seq_len=cfg.obs_seq_len,
-        sigma_vocab_size=3, time_embedding_fn=None, goal_drop=0.0, linear_output=cfg.linear_output, precision=precision)
-    m = GCDenoiser(inner, sigma_data=cfg.sigma_data)
-    load_weights(m, seed, std, cfg)
-    return m.to(DEV).eval()
-
-
-def load_weights(m, seed, std=0.04, cfg=O.KITCHEN):
-    sd = m.state_dict()
-    for k, v in O.make_weights(cfg, seed=seed, std=std).items():
-        sd[k] = torch.from_numpy(v.copy())
-    m.load_state_dict(sd)
+    return make_denoiser(cfg, O.make_weights(cfg, seed=seed, std=std), precision)
 
 
 def entries(m):
@@ -78,7 +58,7 @@ def modes(m):
 def test_five_tile_equals_six_tile_and_two_sample_bit_for_bit(modules, precision, B):
     m = modules[precision]
     for t in (1, 2, 4):
-        s, g, a = (G(v) for v in O.make_inputs(O.KITCHEN, B, seed=B + t, t=t))
+        s, g, a = (to_dev(v) for v in O.make_inputs(O.KITCHEN, B, seed=B + t, t=t))
         for k, (name, fn) in enumerate(modes(m).items()):
             # a sigma no other case of this module uses: the first shared call must add exactly one entry (i.e. it DID take
             # the pre-pass and the five-tile instance), the second one none
@@ -100,7 +80,7 @@ def test_five_tile_equals_six_tile_and_two_sample_bit_for_bit(modules, precision
 def test_a_non_uniform_batch_takes_the_six_tile_instance_and_adds_no_entry(modules, precision):
     m = modules[precision]
     B = 21
-    s, g, a = (G(v) for v in O.make_inputs(O.KITCHEN, B, seed=77))
+    s, g, a = (to_dev(v) for v in O.make_inputs(O.KITCHEN, B, seed=77))
     for odd in (B - 1, 0):                              # one sample of the last workgroup, then of the first
         sg = torch.full((B,), 0.4171, device=DEV)
         sg[odd] = 0.77
@@ -126,7 +106,7 @@ def test_a_window_of_twelve_tokens_takes_the_six_tile_instance(G_len, W):
     B = 21
     for t, shares in ((W, False), (W - 1, True)):
         assert 1 + G_len + 2 * t == (12 if t == W else 10)
-        s, g, a = (G(v) for v in O.make_inputs(cfg, B, seed=40 + t, t=t))
+        s, g, a = (to_dev(v) for v in O.make_inputs(cfg, B, seed=40 + t, t=t))
         for k, (name, fn) in enumerate(modes(m).items()):
             sg = torch.full((B,), 0.2 + 0.1 * k + 0.03 * t, device=DEV)
             n0 = entries(m)
@@ -137,7 +117,7 @@ def test_a_window_of_twelve_tokens_takes_the_six_tile_instance(G_len, W):
             assert torch.equal(five, run(lambda: fn(s, a, g, sg), TWO)), (name, t)
     # ... and without a hint at a batch the eight-sample plan takes (the default dispatch of a large uniform-sigma batch)
     B = 1032
-    s, g, a = (G(v) for v in O.make_inputs(cfg, B, seed=50))
+    s, g, a = (to_dev(v) for v in O.make_inputs(cfg, B, seed=50))
     sg = torch.full((B,), 0.45, device=DEV)
     n0 = entries(m)
     own = run(lambda: m(s, a, g, sg), 0)
@@ -150,7 +130,7 @@ def test_cache_hits_replacement_and_fresh_modules():
     """sigma a, b, a on one module gives the bits of a fresh module (an empty cache) at each; 130 distinct sigmas in turn
     replace the first entries round-robin (128 entries), and the first sigma, computed again, gives the same bits."""
     B = 8
-    s, g, a = (G(v) for v in O.make_inputs(O.KITCHEN, B, seed=3))
+    s, g, a = (to_dev(v) for v in O.make_inputs(O.KITCHEN, B, seed=3))
     m = make_module("bf16")
     sig = lambda v: torch.full((B,), float(v), device=DEV)
     ref = {v: run(lambda: make_module("bf16")(s, a, g, sig(v)), FIVE) for v in (0.3, 0.7)}
@@ -175,12 +155,12 @@ def test_cache_hits_replacement_and_fresh_modules():
 def test_a_repack_invalidates_the_cache():
     """load_state_dict with other weights between two calls at the same sigma: the result follows the new weights."""
     B = 16
-    s, g, a = (G(v) for v in O.make_inputs(O.KITCHEN, B, seed=9))
+    s, g, a = (to_dev(v) for v in O.make_inputs(O.KITCHEN, B, seed=9))
     sg = torch.full((B,), 0.25, device=DEV)
     m = make_module("bf16", seed=5)
     old = run(lambda: m(s, a, g, sg), FIVE)
     assert entries(m) == 1
-    load_weights(m, seed=6)
+    load_weights(m, O.make_weights(O.KITCHEN, seed=6, std=0.04))
     assert entries(m) == 0                              # (the accessor packs the new image: its cache is empty)
     new = run(lambda: m(s, a, g, sg), FIVE)
     assert entries(m) == 1
@@ -192,16 +172,8 @@ def test_a_repack_invalidates_the_cache():
 def test_a_qualifying_forward_is_one_launch_at_the_fused_layer_site(modules):
     """The pre-pass and both instances are one group at the launch-site timer: one event pair per forward."""
     m = modules["bf16"]
-    lib = _lib.load()
     B = 24
-    s, g, a = (G(v) for v in O.make_inputs(O.KITCHEN, B, seed=1))
-    for sg in (torch.full((B,), 0.3, device=DEV), G(np.linspace(0.05, 1.0, B).astype(np.float32))):
-        lib.beso_profile_enable(_lib.SITES["fused_layer"])
-        try:
-            run(lambda: m(s, a, g, sg), FIVE)
-            torch.cuda.synchronize()
-            ms, n = C.c_double(0.0), C.c_int(0)
-            assert lib.beso_profile_read(C.byref(ms), C.byref(n)) == 0
-        finally:
-            lib.beso_profile_enable(0)
-        assert n.value == 1 and ms.value > 0.0
+    s, g, a = (to_dev(v) for v in O.make_inputs(O.KITCHEN, B, seed=1))
+    for sg in (torch.full((B,), 0.3, device=DEV), to_dev(np.linspace(0.05, 1.0, B).astype(np.float32))):
+        ms, n = profile_site("fused_layer", lambda: run(lambda: m(s, a, g, sg), FIVE))
+        assert n == 1 and ms > 0.0

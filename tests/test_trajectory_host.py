@@ -6,6 +6,7 @@ import torch
 
 from oracle import beso_oracle as O
 from conftest import load_golden, rel_err
+from support import load_lib
 
 TOL = 5e-5   # fp32 oracle vs fp32 reference over a loop of <= 10 steps (test_oracle_golden.test_samplers_match_reference)
 
@@ -81,10 +82,8 @@ def test_traced_entry_point_rejects_bad_arguments_before_touching_the_device():
     (BESO_ERR_WORKSPACE) and a trace buffer that overlaps x (BESO_ERR_BAD_ARG) -- nothing is enqueued (the pointers are fake)."""
     import ctypes as C
     from beso_amd import _lib
-    from beso_amd.build import build
     from beso_amd.runtime import ScoreNetShape
-    build(verbose=False)
-    lib = _lib.load()
+    lib = load_lib()
     cfg = ScoreNetShape(7, 3, 48, 2, 6, 2, 3, True, 0.5).c_struct()
     B, t, act, n_sig = 2, 2, 3, 3
     n = B * t * act

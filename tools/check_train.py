@@ -32,6 +32,7 @@ def gemm_case(lib, prec, aks, bks, M, N, K, splits):
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 from autograd_reference import loss_autograd  # noqa: E402   (the comparator lives with the tests)
+from support import grad_errors  # noqa: E402               (and so does the error measure)
 
 
 def main():
@@ -72,11 +73,7 @@ def main():
             torch.cuda.synchronize()
             print(f"{name} {prec}: loss hip {loss.item():.6f} ref {loss_ref.item():.6f}")
             worst_g = 0.0
-            gmax = max(r.abs().max().item() for r in ref)
-            for (n, p), r in zip(inner.named_parameters(), ref):
-                # per tensor, relative to its own norm; tensors whose gradient is identically zero in exact
-                # arithmetic (key.bias: softmax is shift invariant) are measured against the largest gradient entry
-                e = ((p.grad - r).norm() / max(r.norm().item(), 1e-4 * gmax * r.numel() ** 0.5)).item()
+            for (n, _), r, e in zip(inner.named_parameters(), ref, grad_errors([p.grad for p in inner.parameters()], ref, 1e-4)):
                 worst_g = max(worst_g, e)
                 if e > (1e-3 if prec == "fp32" else 5e-2):
                     print(f"   {n}: rel err {e:.3e}  |ref| {r.norm().item():.3e}")
