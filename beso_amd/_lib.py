@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # BESO_HIP_LIB points the binding at another build of the same library (kernel experiments: tools/variants.py)
 LIB_PATH = os.environ.get("BESO_HIP_LIB") or os.path.join(_HERE, "lib", "libbeso_hip.so")
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
+MLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_mlp.so")      # the MLP encoder (include/beso_mlp.h)
 
 # Every upper-case integer below is BESO_<name> of include/beso_hip.h, and every table one of its enums
 # (tests/test_cabi.py compares the values, and SIGNATURES with the prototypes, against the header's text).
@@ -109,6 +110,24 @@ DEV_SIGNATURES = {
 EXPORTS, DEV_EXPORTS = list(SIGNATURES), list(DEV_SIGNATURES)
 
 
+class MlpDims(C.Structure):
+    """struct beso_mlp_dims (include/beso_mlp.h)."""
+    _fields_ = [("in_dim", C.c_int32), ("hidden_dim", C.c_int32), ("n_hidden", C.c_int32), ("out_dim", C.c_int32),
+                ("activation", C.c_int32)]
+
+
+# include/beso_mlp.h (libbeso_mlp.so): BESO_MLP_ACT_* by the reference's activation names -- "tanh" IS the sigmoid there
+# (return_activiation_fcn, networks/utils.py:37-38) -- its flag, and every function it declares, in its order
+MLP_ACTIVATIONS = {"ReLU": 0, "Mish": 1, "sigmoid": 2, "tanh": 2}
+MLP_FLAGS = {"accumulate": 1}        # BESO_MLP_ACCUMULATE
+dimsp = C.POINTER(MlpDims)
+MLP_SIGNATURES = {
+    "beso_mlp_workspace_bytes": (sz, [dimsp, i64, i32]),
+    "beso_mlp_fwd": (i32, [vpp, i32, dimsp, vp, i64, vp, vp, vp]),
+    "beso_mlp_bwd": (i32, [vpp, i32, dimsp, vp, vp, i64, vp, vp, vp, sz, i32, vp]),
+}
+
+
 class BesoHipError(RuntimeError):
     pass
 
@@ -149,6 +168,21 @@ def load() -> C.CDLL:
         # predates some entry points: those are skipped, one by one.  The tree's own library must have them all.
         _lib = _bind(C.CDLL(LIB_PATH), SIGNATURES, tolerant=bool(os.environ.get("BESO_HIP_LIB")))
     return _lib
+
+
+_mlp = None
+
+
+def load_mlp() -> C.CDLL:
+    """The MLP encoder's library (include/beso_mlp.h), built with the product library.  No fallback either."""
+    global _mlp
+    if _mlp is None:
+        import torch  # noqa: F401      (the HIP runtime of the process: see load())
+        if not os.path.exists(MLP_LIB_PATH):
+            raise BesoHipError(f"{MLP_LIB_PATH} not found: build it with `python -m beso_amd.build` (hipcc, gfx950). "
+                               "beso_amd has no CPU or eager fallback for the encoder.")
+        _mlp = _bind(C.CDLL(MLP_LIB_PATH), MLP_SIGNATURES, tolerant=False)
+    return _mlp
 
 
 _dev = None

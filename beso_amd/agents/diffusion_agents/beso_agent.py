@@ -12,6 +12,10 @@ attributes (``model``, ``sigma_min/max``, ``use_kde`` ...).  What changes undern
   * two optional constructor arguments the reference does not have, ``max_grad_norm`` and ``skip_nonfinite_steps``
     (after ``patience``, both off by default): global gradient-norm clipping and a guard that drops a step whose
     gradient is not finite, both inside the fused optimizer launch (``FusedAdam.step``);
+  * a trainable ``input_encoder`` (``MLPEncoder``: an ``MLPNetwork`` on HIP kernels, forward and backward) is trained by the
+    same step from the loss's gradient with respect to ``state`` and ``goal``; the agent SCALES FIRST AND ENCODES SECOND (the
+    scaler's statistics are those of the raw observations, the denoiser's ``obs_dim`` is the encoder's ``output_dim``) -- a
+    deliberate choice: the reference has no trainable encoder that would define the order.  With ``NoEncoder`` nothing changes;
   * ``deterministic_training`` (off by default): every HIP training step runs with ``BESO_TRAIN_DETERMINISTIC`` -- the loss
     and all gradients are summed in a fixed order, so a re-run gives the same bits -- and ``store_training_state`` /
     ``load_training_state`` save and restore everything a step reads, so that a resumed run continues bit for bit.
@@ -85,6 +89,18 @@ class BesoAgent(BaseAgent):
         # hands it to every HipTrainStep it gives out: the eager step and the one behind `model.loss()` in the captured graph
         self.deterministic_training = bool(deterministic_training)
         self.lr_scheduler = instantiate(lr_scheduler, optimizer=self.optimizer)
+        # a trainable input encoder gets its own optimizer instance from the same config (with FusedAdam: its own one-group
+        # instance, so fused EMA and clipping keep their one-group precondition -- the gradient norm of max_grad_norm is then
+        # PER OPTIMIZER: the denoiser and the encoder are clipped separately), its own EMA with the agent's decay and update
+        # period, and the same LR schedule
+        self.encoder_optimizer = self.encoder_ema = self.encoder_lr_scheduler = None
+        self._enc_flat = None
+        if self._trainable_encoder() is not None:
+            enc = self.input_encoder
+            enc.to(device)
+            self.encoder_optimizer = maybe_fuse(instantiate(optimization, params=enc.get_params()))
+            self.encoder_ema = ExponentialMovingAverage(enc.get_params(), decay, self.device)
+            self.encoder_lr_scheduler = instantiate(lr_scheduler, optimizer=self.encoder_optimizer)
         self.gc = goal_conditioned
         self.train_method = train_method
         self.epochs = max_epochs
@@ -134,6 +150,108 @@ class BesoAgent(BaseAgent):
                 raise ValueError("deterministic_training needs the beso_amd GCDenoiser / DiffusionGPT (the HIP training step)")
             return
         den.deterministic_training = bool(on)
+
+    # ------------------------------------------------------------------ trainable input encoder
+    def _trainable_encoder(self):
+        """``self.input_encoder`` if it has parameters (``MLPEncoder``), else None: every code path of a ``NoEncoder`` agent is
+        the one without an encoder."""
+        enc = self.input_encoder
+        if isinstance(enc, nn.Module) and hasattr(enc, "encode") and next(iter(enc.parameters()), None) is not None:
+            return enc
+        return None
+
+    def _refuse_with_encoder(self, what: str):
+        if self._trainable_encoder() is not None:
+            raise NotImplementedError(f"{what} with a trainable input encoder ({type(self.input_encoder).__name__}) is not "
+                                      "supported")
+
+    def _encode_eval(self, state, goal):
+        """Inference: (state, goal) through the trainable encoder under no_grad -- on its EMA weights with ``use_ema`` -- or
+        unchanged without one."""
+        enc = self._trainable_encoder()
+        if enc is None:
+            return state, goal
+        net = enc.network
+        params = tuple(self.encoder_ema.shadow_params) if self.use_ema else None
+
+        def run(x):
+            net._check_input(x)
+            rows = x.reshape(-1, net.input_dim).to(torch.float32).contiguous()
+            return net.run_forward(rows, keep=False, params=params)[0].view(*x.shape[:-1], net.output_dim)
+
+        with torch.no_grad():
+            return run(state), (run(goal) if goal is not None and enc.encode_goal else goal)
+
+    def _encoder_grad_buffer(self, net):
+        """The flat gradient buffer of the encoder; its views are the parameters' ``.grad`` (as for the denoiser)."""
+        params = list(net.get_params())
+        if self._enc_flat is None or self._enc_flat.device != params[0].device:
+            self._enc_flat = torch.empty(net.num_param_floats(), dtype=torch.float32, device=params[0].device)
+            off = 0
+            for p in params:
+                p.grad = self._enc_flat[off:off + p.numel()].view_as(p)
+                off += p.numel()
+        return self._enc_flat
+
+    def _encoded_loss_backward(self, enc, state, action, goal):
+        """``_loss_backward`` behind the encoder: encode keeping what the backward needs, the HIP step with
+        ``input_grads=True``, then ``beso_mlp_bwd`` on (state_grad, goal_grad) -- enqueued on the compute stream behind the
+        step's last launch; the early-released loss stream is not touched."""
+        if bdist.is_distributed() and bdist.world_size() > 1:
+            raise NotImplementedError("data-parallel training (world_size > 1) with a trainable input encoder "
+                                      f"({type(enc).__name__}) is not supported: its gradients are not exchanged")
+        if os.environ.get("BESO_AMD_TRAIN_GRAPH", "0") == "1" and not getattr(self, "_enc_graph_logged", False):
+            self._enc_graph_logged = True
+            log.info("BESO_AMD_TRAIN_GRAPH=1 ignored: the agent has a trainable input encoder")
+        net = enc.network
+
+        def encode(x):
+            net._check_input(x)
+            rows = x.reshape(-1, net.input_dim).to(torch.float32).contiguous()
+            y, keep = net.run_forward(rows, keep=True)
+            return y.view(*x.shape[:-1], net.output_dim), keep
+
+        state_e, state_keep = encode(state)
+        goal_e, goal_keep = encode(goal) if goal is not None and enc.encode_goal else (goal, None)
+        noise = torch.randn_like(action)
+        sigma = self.make_sample_density()(shape=(len(action),), device=self.device)
+        step = self.model.hip_train_step(state_e, action, goal_e, noise, sigma) if hasattr(self.model, "hip_train_step") else None
+        if step is None:
+            raise NotImplementedError("a trainable input encoder needs the HIP training step (the beso_amd GCDenoiser / "
+                                      "DiffusionGPT on the GPU)")
+        self.optimizer.zero_grad(set_to_none=True)
+        self._hip_step = step
+        self._c1_early = None
+        self._loss_ready = None
+        if os.environ.get("BESO_AMD_ASYNC_LOSS", "1") != "0":
+            if getattr(self, "_loss_stream", None) is None:
+                self._loss_stream = torch.cuda.Stream(state.device)
+            self._loss_ready = self._loss_stream
+        loss, state_grad, goal_grad = step.loss_backward(state_e, action, goal_e, noise, sigma, grad_scale=1.0,
+                                                         loss_stream=self._loss_ready, input_grads=True)
+        flat = self._encoder_grad_buffer(net)
+        net.run_backward(state_keep, state_grad, flat)
+        if goal_keep is not None and goal_grad is not None:
+            if goal_grad.numel() != goal_e.numel():
+                goal_grad = goal_grad.sum(dim=0, keepdim=True)      # one goal for the whole batch: its gradient is the sum
+            net.run_backward(goal_keep, goal_grad, flat, accumulate=True)
+        return loss
+
+    def _encoder_optimizer_step(self, enc, do_ema: bool):
+        opt = self.encoder_optimizer
+        if isinstance(opt, FusedAdam):
+            if self.max_grad_norm is None and not self.skip_nonfinite_steps:
+                opt.step(ema=self.encoder_ema if do_ema else None)
+            else:
+                opt.step(ema=self.encoder_ema if do_ema else None, max_grad_norm=self.max_grad_norm,
+                         skip_nonfinite=self.skip_nonfinite_steps)
+        else:
+            if self.max_grad_norm is not None:
+                torch.nn.utils.clip_grad_norm_(list(enc.get_params()), self.max_grad_norm)
+            opt.step()
+            if do_ema:
+                self.encoder_ema.update(enc.get_params())
+        self.encoder_lr_scheduler.step()
 
     # ------------------------------------------------------------------ scaler / bounds
     def get_scaler(self, scaler):
@@ -430,7 +548,10 @@ class BesoAgent(BaseAgent):
         self.model.training = True
         self._c1_early = None
         self._loss_ready = None
-        if self._use_train_graph(state):
+        enc = self._trainable_encoder()
+        if enc is not None:
+            loss = self._encoded_loss_backward(enc, state, action, goal)
+        elif self._use_train_graph(state):
             loss = self._graphed_loss_backward(state, action, goal)
         else:
             loss = self._loss_backward(state, action, goal)
@@ -481,6 +602,8 @@ class BesoAgent(BaseAgent):
             self.lr_scheduler.step()
             if do_ema:
                 self.ema_helper.update(self.model.parameters())
+        if enc is not None:
+            self._encoder_optimizer_step(enc, do_ema)
         if loss_stream is not None:
             with torch.cuda.stream(loss_stream):
                 return loss.item()
@@ -511,6 +634,7 @@ class BesoAgent(BaseAgent):
         """MSE between sampled and ground-truth action windows; always the exponential schedule
         (beso_agent.py:250-289)."""
         state, action, goal = self.process_batch(batch, predict=True)
+        state, goal = self._encode_eval(state, goal)
         with self._ema_scope():
             self.model.eval()
             self.model.training = False
@@ -564,6 +688,7 @@ class BesoAgent(BaseAgent):
         reductions: the same inputs give the same bits."""
         den = self._held_out_model()
         state, action, goal = self.process_batch(batch, predict=False)
+        state, goal = self._encode_eval(state, goal)
         sigma, noise = self._held_out_draws(action, len(action), sigma, noise, generator)
         with self._ema_scope():
             if self.model.training:
@@ -581,6 +706,7 @@ class BesoAgent(BaseAgent):
         ``validation_loss``."""
         den = self._held_out_model()
         state, action, goal = self.process_batch(batch, predict=False)
+        state, goal = self._encode_eval(state, goal)
         B = len(action)
         sigmas = torch.as_tensor(sigmas, dtype=torch.float32, device=action.device).reshape(-1)
         K = sigmas.numel()
@@ -618,6 +744,7 @@ class BesoAgent(BaseAgent):
         noise), keep the last action, clip, un-scale, remember it."""
         noise_scheduler = self.noise_scheduler if noise_scheduler is None else noise_scheduler
         state, goal, _ = self.process_batch(batch, predict=True)
+        state, goal = self._encode_eval(state, goal)
         if state.dim() == 2 and self.window_size > 1:
             self.obs_context.append(state)
             input_state = torch.stack(tuple(self.obs_context), dim=1)
@@ -653,6 +780,7 @@ class BesoAgent(BaseAgent):
         """A ``VectorRollout`` over ``n_envs`` environments that finish and reset independently: one sampler call per
         environment step for all of them, the windows kept per environment on the device (beso_amd/rollout.py).  ``predict``
         and ``reset`` keep serving the reference's single set of environments; the two share nothing but the agent."""
+        self._refuse_with_encoder("vector_rollout")
         from ...rollout import VectorRollout
         return VectorRollout(self, n_envs)
 
@@ -677,6 +805,7 @@ class BesoAgent(BaseAgent):
         noise_scheduler = self.noise_scheduler if noise_scheduler is None else noise_scheduler
         state = self.scaler.scale_input(state)
         goal = self.scaler.scale_input(goal)
+        state, goal = self._encode_eval(state, goal)
         if self.window_size > 1 and state.dim() == 2:
             self.obs_context.append(state)
             input_state = torch.stack(tuple(self.obs_context), dim=1)
@@ -746,7 +875,21 @@ class BesoAgent(BaseAgent):
         self.model.load_state_dict(state)
         self.ema_helper = ExponentialMovingAverage(self.model.get_params(), self.decay, self.device)
         self._ema_packed_key = None
+        self._load_encoder_weights(weights_path)
         log.info('Loaded pre-trained model parameters')
+
+    def _load_encoder_weights(self, weights_path: str) -> None:
+        """``encoder_state_dict.pth`` (the EMA weights) into a trainable encoder, its EMA shadow re-seeded from them.  A
+        directory without the file loads into a ``NoEncoder`` agent as before; into an agent with an encoder it raises."""
+        enc = self._trainable_encoder()
+        if enc is None:
+            return
+        path = os.path.join(weights_path, "encoder_state_dict.pth")
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{path}: the agent has a trainable input encoder ({type(enc).__name__}) but the "
+                                    "checkpoint directory holds no encoder weights")
+        enc.network.load_state_dict(torch.load(path, map_location=self.device))
+        self.encoder_ema = ExponentialMovingAverage(enc.get_params(), self.decay, self.device)
 
     def store_model_weights(self, store_path: str) -> None:
         """EMA weights -> model_state_dict.pth, raw weights -> non_ema_model_state_dict.pth
@@ -762,9 +905,21 @@ class BesoAgent(BaseAgent):
                 ema[n] = s.detach().clone()
         torch.save(ema, os.path.join(store_path, "model_state_dict.pth"))
         torch.save(raw, os.path.join(store_path, "non_ema_model_state_dict.pth"))
+        enc = self._trainable_encoder()
+        if enc is not None:
+            # the encoder beside them: encoder_state_dict.pth (EMA) and non_ema_encoder_state_dict.pth
+            raw = {k: v.detach().clone() for k, v in enc.network.state_dict().items()}
+            ema = dict(raw)
+            if self.use_ema:
+                names = [n for n, p in enc.network.named_parameters() if p.requires_grad]
+                for n, s in zip(names, self.encoder_ema.shadow_params):
+                    ema[n] = s.detach().clone()
+            torch.save(ema, os.path.join(store_path, "encoder_state_dict.pth"))
+            torch.save(raw, os.path.join(store_path, "non_ema_encoder_state_dict.pth"))
 
     # ------------------------------------------------------------------ exact resume
     def _training_state_guard(self):
+        self._refuse_with_encoder("store_training_state / load_training_state")
         if bdist.is_distributed() and bdist.world_size() > 1:
             raise NotImplementedError("store_training_state / load_training_state: single process only (sharded EMA shadows and "
                                       "per-rank generators are not saved)")

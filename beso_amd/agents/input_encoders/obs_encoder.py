@@ -26,3 +26,30 @@ class NoEncoder(nn.Module):
         if state is None:
             raise KeyError(self.state_modality)
         return state, self._fetch(batch, self.goal_modality)
+
+
+class MLPEncoder(NoEncoder):
+    """A trainable ``MLPNetwork`` (beso_amd/networks/mlps/mlps.py: HIP kernels, forward and backward) in front of the score
+    network, for observations that are not the denoiser's ``obs_dim`` features.  The reference ships no trainable encoder;
+    its ``MLPNetwork`` (networks/mlps/mlps.py:11-73) is the only small network it has for the role.
+
+    ``network`` is a config for ``MLPNetwork`` (``_target_`` + kwargs) or a factory.  ``forward(batch)`` fetches exactly as
+    ``NoEncoder.forward`` does -- ``BaseAgent.process_batch`` and the scaler see the RAW observations; the agent scales
+    first and encodes second -- and ``encode(state, goal)`` maps the last dimension of both through the ONE shared network,
+    keeping the leading dimensions.  With ``encode_goal=False`` the goal passes through."""
+
+    def __init__(self, device: str, state_modality: str, goal_modality: str, network, encode_goal: bool = True):
+        super().__init__(device, state_modality, goal_modality)
+        from ..._instantiate import instantiate
+        self.network = instantiate(network)
+        self.network.get_device(device)
+        self.encode_goal = bool(encode_goal)
+
+    def get_params(self):
+        return self.network.get_params()
+
+    def encode(self, state: Tensor, goal: Optional[Tensor]) -> Tuple[Tensor, Optional[Tensor]]:
+        state_e = self.network(state)
+        if goal is None or not self.encode_goal:
+            return state_e, goal
+        return state_e, self.network(goal)

@@ -22,6 +22,10 @@ STAMP = os.path.join(LIBDIR, "libbeso_hip.sha256")        # source hash the .so 
 DEV_LIB = os.path.join(LIBDIR, "libbeso_hip_dev.so")
 DEV_STAMP = os.path.join(LIBDIR, "libbeso_hip_dev.sha256")
 UNITS = ["api", "elementwise", "attention", "gemm", "fused", "fused_f16", "optim", "train", "feed", "small", "rollout", "lossfwd"]
+# the MLP observation / goal encoder (include/beso_mlp.h) is a library of its own, built with the product library and under
+# the same stamp: libbeso_hip.so's dynamic symbol table stays exactly include/beso_hip.h
+MLP_LIB = os.path.join(LIBDIR, "libbeso_mlp.so")
+MLP_UNITS = ["encoder"]
 ARCH = "gfx950"
 # -fvisibility=hidden: the dynamic symbol table is exactly include/beso_hip.h (its declarations carry default visibility)
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
@@ -42,10 +46,11 @@ def _source_hash() -> str:
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC))
     files.append(os.path.join(os.path.dirname(PKG), "include", "beso_hip.h"))
     files.append(os.path.join(os.path.dirname(PKG), "include", "beso_hip_debug.h"))
+    files.append(os.path.join(os.path.dirname(PKG), "include", "beso_mlp.h"))
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         h.update(open(f, "rb").read())
-    h.update(" ".join(FLAGS + os.environ.get("BESO_EXTRA_HIPCC_FLAGS", "").split() + UNITS).encode())
+    h.update(" ".join(FLAGS + os.environ.get("BESO_EXTRA_HIPCC_FLAGS", "").split() + UNITS + MLP_UNITS).encode())
     return h.hexdigest()
 
 
@@ -72,7 +77,8 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
         have = open(STAMP).read().strip()
     except OSError:
         have = ""
-    if not force and os.path.exists(LIB) and have == want:
+    libs = [(LIB, UNITS)] + ([] if dev else [(MLP_LIB, MLP_UNITS)])
+    if not force and all(os.path.exists(path) for path, _ in libs) and have == want:
         return LIB
     try:
         _hipcc()
@@ -83,12 +89,14 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
                              f"{have[:12] if have else 'unknown: no stamp file'}, tree is {want[:12]})\n")
             return LIB
         raise
-    with cf.ThreadPoolExecutor(max_workers=len(UNITS)) as ex:
-        objs = list(ex.map(lambda u: _compile(u, dev), UNITS))
-    cmd = [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB, *objs]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    units = [u for _, us in libs for u in us]
+    with cf.ThreadPoolExecutor(max_workers=len(units)) as ex:
+        objs = dict(zip(units, ex.map(lambda u: _compile(u, dev), units)))
+    for path, us in libs:
+        cmd = [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", path, *[objs[u] for u in us]]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
     with open(STAMP, "w") as f:
         f.write(want + "\n")
     if verbose:
@@ -99,7 +107,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
 def is_current() -> bool:
     """True when the library in lib/ was built from exactly the sources in the tree."""
     try:
-        return os.path.exists(LIB) and open(STAMP).read().strip() == _source_hash()
+        return os.path.exists(LIB) and os.path.exists(MLP_LIB) and open(STAMP).read().strip() == _source_hash()
     except OSError:
         return False
 

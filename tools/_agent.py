@@ -9,9 +9,12 @@ from beso_amd.agents.input_encoders.obs_encoder import NoEncoder
 
 
 def build_agent(shape, model_factory, device="cuda:0", sampler="ddim", lr=1e-4, **extra):
+    # (`input_encoder` in `extra`: a factory for another encoder, e.g. an MLPEncoder)
+    encoder = extra.pop("input_encoder", None) or functools.partial(NoEncoder, device=device, state_modality="observation",
+                                                                    goal_modality="goal_observation")
     return BesoAgent(
         model=model_factory,
-        input_encoder=functools.partial(NoEncoder, device=device, state_modality="observation", goal_modality="goal_observation"),
+        input_encoder=encoder,
         optimization=lambda params: torch.optim.AdamW(params, lr=lr),
         device=device, obs_modalities=["observation"], goal_modalities=["goal_observation"], target_modality="action",
         max_train_steps=10, max_epochs=1, train_method="steps", eval_every_n_steps=5, use_ema=True, goal_conditioned=True,

@@ -5,9 +5,11 @@ Adam(W) + EMA launch; `--autograd` times the tests' torch-autograd comparator of
 `--max-grad-norm X` / `--skip-nonfinite` turn on gradient clipping / the non-finite guard of the fused step;
 `--deterministic` times the step with BESO_TRAIN_DETERMINISTIC (BesoAgent(deterministic_training=True));
 `--input-grads` makes every step also compute the gradients with respect to state and goal (beso_loss_grad_inputs: one more
-launch and two output tensors per step; the agent itself does not use them).
+launch and two output tensors per step; the agent itself does not use them);
+`--encoder IN,HIDDEN,LAYERS` times the step with and without a trainable MLPEncoder (IN raw features -> HIDDEN x LAYERS -> obs_dim,
+ReLU) in front of the denoiser: two agents in ONE process, alternating in rounds of ten steps, median and spread per agent.
     python tools/bench_train.py [batch] [kitchen|block_push] [--autograd] [--max-grad-norm X] [--skip-nonfinite] [--deterministic]
-                                [--input-grads]"""
+                                [--input-grads] [--encoder IN,HIDDEN,LAYERS]"""
 import json
 import os
 import sys
@@ -24,6 +26,47 @@ from bench import build_model  # noqa: E402
 from beso_amd import synthetic as O  # noqa: E402
 from _agent import build_agent  # noqa: E402
 from beso_amd.networks.scaler.scaler_class import Scaler  # noqa: E402
+
+
+def encoder_ab(cfg, model, dev, B, encoder, det, clip, rounds=7, steps=10):
+    """The same step with and without an MLPEncoder, alternating in one process: per agent the median seconds per step over
+    `rounds` rounds of `steps` steps (each round synchronised and timed on its own), and the rounds' minimum and maximum."""
+    import functools
+    from beso_amd.agents.input_encoders.obs_encoder import MLPEncoder
+    from beso_amd.networks.mlps.mlps import MLPNetwork
+    n_in, hidden, layers = encoder
+    net = functools.partial(MLPNetwork, n_in, hidden, layers, cfg.obs_dim, device=dev)
+    enc = functools.partial(MLPEncoder, device=dev, state_modality="observation", goal_modality="goal_observation", network=net)
+    agents, batches = {}, {}
+    for name, raw, extra in (("no_encoder", cfg.obs_dim, {}), ("encoder", n_in, {"input_encoder": enc})):
+        agent = build_agent(cfg, model, device=dev, deterministic_training=det, **clip, **extra)
+        rng = np.random.default_rng(0)
+        agent.get_scaler(Scaler(rng.standard_normal((256, raw)).astype(np.float32),
+                                rng.standard_normal((256, cfg.act_dim)).astype(np.float32), True, dev))
+        agent.set_bounds(agent.scaler)
+        torch.manual_seed(1234)
+        batches[name] = {"observation": torch.randn(B, cfg.obs_seq_len, raw, device=dev),
+                         "action": torch.randn(B, cfg.obs_seq_len, cfg.act_dim, device=dev),
+                         "goal_observation": torch.randn(B, cfg.goal_seq_len, raw, device=dev)}
+        agents[name] = agent
+        for _ in range(3):
+            agent.train_step(batches[name])
+    torch.cuda.synchronize()
+    times = {name: [] for name in agents}
+    for _ in range(rounds):
+        for name, agent in agents.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                loss = agent.train_step(batches[name])
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / steps)
+    out = {"config": f"{B}-sample train_step, MLPEncoder {n_in}->{hidden}x{layers}->{cfg.obs_dim} against NoEncoder", "batch": B,
+           "rounds": rounds, "steps_per_round": steps, "deterministic": det, "loss": loss}
+    for name, ts in times.items():
+        out[name] = {"median_ms": 1e3 * float(np.median(ts)), "min_ms": 1e3 * min(ts), "max_ms": 1e3 * max(ts)}
+    out["encoder_cost_ms"] = out["encoder"]["median_ms"] - out["no_encoder"]["median_ms"]
+    print(json.dumps(out))
 
 
 def main():
@@ -62,6 +105,11 @@ def main():
             taken[0] += 1
             return loss
         HipTrainStep.loss_backward = with_input_grads
+    encoder = None
+    if "--encoder" in sys.argv:
+        i = sys.argv.index("--encoder")
+        encoder = tuple(int(v) for v in sys.argv[i + 1].split(","))
+        del sys.argv[i:i + 2]
     if "--autograd" in sys.argv:
         sys.argv.remove("--autograd")
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -96,6 +144,8 @@ def main():
                     mod.p = resid_p
         return m
 
+    if encoder is not None:
+        return encoder_ab(cfg, model, dev, B, encoder, det, clip)
     agent = build_agent(cfg, model, device=dev, deterministic_training=det, **clip)
     rng = np.random.default_rng(0)
     agent.get_scaler(Scaler(rng.standard_normal((256, cfg.obs_dim)).astype(np.float32),
