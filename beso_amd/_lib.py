@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BESO_HIP_LIB") or os.path.join(_HERE, "lib", "libbeso_hip.so")
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
 MLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_mlp.so")      # the MLP encoder (include/beso_mlp.h)
+RESMLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_resmlp.so")   # the residual MLP encoder (include/beso_resmlp.h)
 
 # Every upper-case integer below is BESO_<name> of include/beso_hip.h, and every table one of its enums
 # (tests/test_cabi.py compares the values, and SIGNATURES with the prototypes, against the header's text).
@@ -128,6 +129,23 @@ MLP_SIGNATURES = {
 }
 
 
+class ResMlpDims(C.Structure):
+    """struct beso_resmlp_dims (include/beso_resmlp.h)."""
+    _fields_ = [("in_dim", C.c_int32), ("hidden_dim", C.c_int32), ("n_blocks", C.c_int32), ("out_dim", C.c_int32),
+                ("activation", C.c_int32), ("norm", C.c_int32)]
+
+
+# include/beso_resmlp.h (libbeso_resmlp.so): BESO_RESMLP_NORM_* and every function it declares, in its order; the activations
+# and the accumulate flag are include/beso_mlp.h's
+RESMLP_NORMS = {"none": 0, "LayerNorm": 1}
+rdimsp = C.POINTER(ResMlpDims)
+RESMLP_SIGNATURES = {
+    "beso_resmlp_workspace_bytes": (sz, [rdimsp, i64, i32]),
+    "beso_resmlp_fwd": (i32, [vpp, i32, rdimsp, vp, i64, vp, vp, vp]),
+    "beso_resmlp_bwd": (i32, [vpp, i32, rdimsp, vp, vp, i64, vp, vp, vp, sz, i32, vp]),
+}
+
+
 class BesoHipError(RuntimeError):
     pass
 
@@ -183,6 +201,21 @@ def load_mlp() -> C.CDLL:
                                "beso_amd has no CPU or eager fallback for the encoder.")
         _mlp = _bind(C.CDLL(MLP_LIB_PATH), MLP_SIGNATURES, tolerant=False)
     return _mlp
+
+
+_resmlp = None
+
+
+def load_resmlp() -> C.CDLL:
+    """The residual MLP encoder's library (include/beso_resmlp.h), built with the product library.  No fallback either."""
+    global _resmlp
+    if _resmlp is None:
+        import torch  # noqa: F401      (the HIP runtime of the process: see load())
+        if not os.path.exists(RESMLP_LIB_PATH):
+            raise BesoHipError(f"{RESMLP_LIB_PATH} not found: build it with `python -m beso_amd.build` (hipcc, gfx950). "
+                               "beso_amd has no CPU or eager fallback for the encoder.")
+        _resmlp = _bind(C.CDLL(RESMLP_LIB_PATH), RESMLP_SIGNATURES, tolerant=False)
+    return _resmlp
 
 
 _dev = None

@@ -26,6 +26,9 @@ UNITS = ["api", "elementwise", "attention", "gemm", "fused", "fused_f16", "optim
 # the same stamp: libbeso_hip.so's dynamic symbol table stays exactly include/beso_hip.h
 MLP_LIB = os.path.join(LIBDIR, "libbeso_mlp.so")
 MLP_UNITS = ["encoder"]
+# ... and so is the residual MLP encoder (include/beso_resmlp.h); the two share csrc/mlp_tile.h
+RESMLP_LIB = os.path.join(LIBDIR, "libbeso_resmlp.so")
+RESMLP_UNITS = ["resmlp"]
 ARCH = "gfx950"
 # -fvisibility=hidden: the dynamic symbol table is exactly include/beso_hip.h (its declarations carry default visibility)
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
@@ -47,10 +50,11 @@ def _source_hash() -> str:
     files.append(os.path.join(os.path.dirname(PKG), "include", "beso_hip.h"))
     files.append(os.path.join(os.path.dirname(PKG), "include", "beso_hip_debug.h"))
     files.append(os.path.join(os.path.dirname(PKG), "include", "beso_mlp.h"))
+    files.append(os.path.join(os.path.dirname(PKG), "include", "beso_resmlp.h"))
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         h.update(open(f, "rb").read())
-    h.update(" ".join(FLAGS + os.environ.get("BESO_EXTRA_HIPCC_FLAGS", "").split() + UNITS + MLP_UNITS).encode())
+    h.update(" ".join(FLAGS + os.environ.get("BESO_EXTRA_HIPCC_FLAGS", "").split() + UNITS + MLP_UNITS + RESMLP_UNITS).encode())
     return h.hexdigest()
 
 
@@ -77,7 +81,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
         have = open(STAMP).read().strip()
     except OSError:
         have = ""
-    libs = [(LIB, UNITS)] + ([] if dev else [(MLP_LIB, MLP_UNITS)])
+    libs = [(LIB, UNITS)] + ([] if dev else [(MLP_LIB, MLP_UNITS), (RESMLP_LIB, RESMLP_UNITS)])
     if not force and all(os.path.exists(path) for path, _ in libs) and have == want:
         return LIB
     try:
@@ -107,7 +111,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
 def is_current() -> bool:
     """True when the library in lib/ was built from exactly the sources in the tree."""
     try:
-        return os.path.exists(LIB) and os.path.exists(MLP_LIB) and open(STAMP).read().strip() == _source_hash()
+        return all(os.path.exists(p) for p in (LIB, MLP_LIB, RESMLP_LIB)) and open(STAMP).read().strip() == _source_hash()
     except OSError:
         return False
 

@@ -6,10 +6,12 @@ Adam(W) + EMA launch; `--autograd` times the tests' torch-autograd comparator of
 `--deterministic` times the step with BESO_TRAIN_DETERMINISTIC (BesoAgent(deterministic_training=True));
 `--input-grads` makes every step also compute the gradients with respect to state and goal (beso_loss_grad_inputs: one more
 launch and two output tensors per step; the agent itself does not use them);
-`--encoder IN,HIDDEN,LAYERS` times the step with and without a trainable MLPEncoder (IN raw features -> HIDDEN x LAYERS -> obs_dim,
-ReLU) in front of the denoiser: two agents in ONE process, alternating in rounds of ten steps, median and spread per agent.
+`--encoder IN,HIDDEN,LAYERS[,KIND]` times the step with and without a trainable MLPEncoder (IN raw features -> HIDDEN x LAYERS ->
+obs_dim) in front of the denoiser: the agents in ONE process, alternating in rounds of ten steps, median and spread per agent.
+KIND: `mlp` (default: MLPNetwork, ReLU), `res` (ResidualMLPNetwork, Mish, no norm) or `resln` (... with LayerNorm); the flag may
+be given more than once, one agent per encoder.
     python tools/bench_train.py [batch] [kitchen|block_push] [--autograd] [--max-grad-norm X] [--skip-nonfinite] [--deterministic]
-                                [--input-grads] [--encoder IN,HIDDEN,LAYERS]"""
+                                [--input-grads] [--encoder IN,HIDDEN,LAYERS[,KIND]]..."""
 import json
 import os
 import sys
@@ -28,17 +30,27 @@ from _agent import build_agent  # noqa: E402
 from beso_amd.networks.scaler.scaler_class import Scaler  # noqa: E402
 
 
-def encoder_ab(cfg, model, dev, B, encoder, det, clip, rounds=7, steps=10):
-    """The same step with and without an MLPEncoder, alternating in one process: per agent the median seconds per step over
-    `rounds` rounds of `steps` steps (each round synchronised and timed on its own), and the rounds' minimum and maximum."""
+ENCODER_KINDS = {"mlp": "encoder", "res": "residual_encoder", "resln": "residual_layernorm_encoder"}      # KIND -> the agent's name
+
+
+def encoder_ab(cfg, model, dev, B, encoders, det, clip, rounds=7, steps=10):
+    """The same step without an encoder and with each MLPEncoder of `encoders` [(IN, HIDDEN, LAYERS, KIND)], alternating in one
+    process: per agent the median seconds per step over `rounds` rounds of `steps` steps (each round synchronised and timed on
+    its own), and the rounds' minimum and maximum."""
     import functools
     from beso_amd.agents.input_encoders.obs_encoder import MLPEncoder
-    from beso_amd.networks.mlps.mlps import MLPNetwork
-    n_in, hidden, layers = encoder
-    net = functools.partial(MLPNetwork, n_in, hidden, layers, cfg.obs_dim, device=dev)
-    enc = functools.partial(MLPEncoder, device=dev, state_modality="observation", goal_modality="goal_observation", network=net)
+    from beso_amd.networks.mlps.mlps import MLPNetwork, ResidualMLPNetwork
+    specs = [("no_encoder", cfg.obs_dim, {})]
+    for n_in, hidden, layers, kind in encoders:
+        if kind == "mlp":
+            net = functools.partial(MLPNetwork, n_in, hidden, layers, cfg.obs_dim, device=dev)
+        else:
+            net = functools.partial(ResidualMLPNetwork, n_in, hidden, layers, cfg.obs_dim, use_norm=kind == "resln",
+                                    norm_style="LayerNorm", device=dev)
+        enc = functools.partial(MLPEncoder, device=dev, state_modality="observation", goal_modality="goal_observation", network=net)
+        specs.append((ENCODER_KINDS[kind], n_in, {"input_encoder": enc}))
     agents, batches = {}, {}
-    for name, raw, extra in (("no_encoder", cfg.obs_dim, {}), ("encoder", n_in, {"input_encoder": enc})):
+    for name, raw, extra in specs:
         agent = build_agent(cfg, model, device=dev, deterministic_training=det, **clip, **extra)
         rng = np.random.default_rng(0)
         agent.get_scaler(Scaler(rng.standard_normal((256, raw)).astype(np.float32),
@@ -61,11 +73,13 @@ def encoder_ab(cfg, model, dev, B, encoder, det, clip, rounds=7, steps=10):
                 loss = agent.train_step(batches[name])
             torch.cuda.synchronize()
             times[name].append((time.perf_counter() - t0) / steps)
-    out = {"config": f"{B}-sample train_step, MLPEncoder {n_in}->{hidden}x{layers}->{cfg.obs_dim} against NoEncoder", "batch": B,
+    shapes = ", ".join(f"{ENCODER_KINDS[k]} {i}->{h}x{n}->{cfg.obs_dim}" for i, h, n, k in encoders)
+    out = {"config": f"{B}-sample train_step, MLPEncoder ({shapes}) against NoEncoder", "batch": B,
            "rounds": rounds, "steps_per_round": steps, "deterministic": det, "loss": loss}
     for name, ts in times.items():
         out[name] = {"median_ms": 1e3 * float(np.median(ts)), "min_ms": 1e3 * min(ts), "max_ms": 1e3 * max(ts)}
-    out["encoder_cost_ms"] = out["encoder"]["median_ms"] - out["no_encoder"]["median_ms"]
+    for name in list(times)[1:]:
+        out[name + "_cost_ms"] = out[name]["median_ms"] - out["no_encoder"]["median_ms"]
     print(json.dumps(out))
 
 
@@ -105,10 +119,14 @@ def main():
             taken[0] += 1
             return loss
         HipTrainStep.loss_backward = with_input_grads
-    encoder = None
-    if "--encoder" in sys.argv:
+    encoders = []
+    while "--encoder" in sys.argv:
         i = sys.argv.index("--encoder")
-        encoder = tuple(int(v) for v in sys.argv[i + 1].split(","))
+        parts = sys.argv[i + 1].split(",")
+        kind = parts[3] if len(parts) > 3 else "mlp"
+        if len(parts) not in (3, 4) or kind not in ENCODER_KINDS:
+            raise SystemExit(f"--encoder IN,HIDDEN,LAYERS[,{'|'.join(ENCODER_KINDS)}]: got {sys.argv[i + 1]!r}")
+        encoders.append((int(parts[0]), int(parts[1]), int(parts[2]), kind))
         del sys.argv[i:i + 2]
     if "--autograd" in sys.argv:
         sys.argv.remove("--autograd")
@@ -144,8 +162,8 @@ def main():
                     mod.p = resid_p
         return m
 
-    if encoder is not None:
-        return encoder_ab(cfg, model, dev, B, encoder, det, clip)
+    if encoders:
+        return encoder_ab(cfg, model, dev, B, encoders, det, clip)
     agent = build_agent(cfg, model, device=dev, deterministic_training=det, **clip)
     rng = np.random.default_rng(0)
     agent.get_scaler(Scaler(rng.standard_normal((256, cfg.obs_dim)).astype(np.float32),
