@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("BESO_HIP_LIB") or os.path.join(_HERE, "lib", "libbeso
 DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
 MLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_mlp.so")      # the MLP encoder (include/beso_mlp.h)
 RESMLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_resmlp.so")   # the residual MLP encoder (include/beso_resmlp.h)
+GUIDE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_guide.so")     # the guide gradient of guided sampling (include/beso_guide.h)
 
 # Every upper-case integer below is BESO_<name> of include/beso_hip.h, and every table one of its enums
 # (tests/test_cabi.py compares the values, and SIGNATURES with the prototypes, against the header's text).
@@ -145,6 +146,14 @@ RESMLP_SIGNATURES = {
     "beso_resmlp_bwd": (i32, [vpp, i32, rdimsp, vp, vp, i64, vp, vp, vp, sz, i32, vp]),
 }
 
+# include/beso_guide.h (libbeso_guide.so): every function it declares, in its order; the dims struct and the activations are
+# include/beso_mlp.h's
+GUIDE_SIGNATURES = {
+    "beso_guide_supported": (i32, [dimsp, i32, i32, i32]),
+    "beso_guide_apply": (i32, [vpp, i32, dimsp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]),
+}
+GUIDE_EXPORTS = list(GUIDE_SIGNATURES)
+
 
 class BesoHipError(RuntimeError):
     pass
@@ -216,6 +225,22 @@ def load_resmlp() -> C.CDLL:
                                "beso_amd has no CPU or eager fallback for the encoder.")
         _resmlp = _bind(C.CDLL(RESMLP_LIB_PATH), RESMLP_SIGNATURES, tolerant=False)
     return _resmlp
+
+
+_guide = None
+
+
+def load_guide() -> C.CDLL:
+    """The guide-gradient library of classifier-guided sampling (include/beso_guide.h), built with the product library.  No
+    fallback either: a guide it does not serve takes autograd over the guide's own HIP kernels, decided once per guide."""
+    global _guide
+    if _guide is None:
+        import torch  # noqa: F401      (the HIP runtime of the process: see load())
+        if not os.path.exists(GUIDE_LIB_PATH):
+            raise BesoHipError(f"{GUIDE_LIB_PATH} not found: build it with `python -m beso_amd.build` (hipcc, gfx950). "
+                               "beso_amd has no CPU or eager fallback for the fused guide gradient.")
+        _guide = _bind(C.CDLL(GUIDE_LIB_PATH), GUIDE_SIGNATURES, tolerant=False)
+    return _guide
 
 
 _dev = None

@@ -39,7 +39,7 @@ from ...data.prefetch import DevicePrefetcher
 from ..base_agent import BaseAgent
 from .k_diffusion import gc_sampling as ks
 from .k_diffusion import utils
-from .k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel
+from .k_diffusion.classifier_free_sampler import ClassifierFreeSampleModel, ClassifierGuidedSampleModel
 from .k_diffusion.score_gpts import DiffusionGPT
 from .k_diffusion.score_wrappers import GCDenoiser
 
@@ -264,8 +264,11 @@ class BesoAgent(BaseAgent):
     # ------------------------------------------------------------------ EMA evaluation scope
     def _hip_denoiser(self):
         """The beso_amd GCDenoiser behind ``self.model`` (which scripts may wrap in
-        ClassifierFreeSampleModel: scripts/training.py:54-55), or None."""
+        ClassifierFreeSampleModel: scripts/training.py:54-55, in ClassifierGuidedSampleModel, or in the latter around the
+        former), or None."""
         m = self.model
+        if isinstance(m, ClassifierGuidedSampleModel):
+            m = m.model
         if isinstance(m, ClassifierFreeSampleModel):
             m = m.model
         if isinstance(m, GCDenoiser) and isinstance(m.inner_model, DiffusionGPT):
@@ -837,6 +840,10 @@ class BesoAgent(BaseAgent):
         reduced = {k: extra_args[k] for k in ('s_churn', 'keep_last_actions')} if extra_args else {}
         scaler = self.scaler if extra_args.get('use_scaler', False) else None
         m = self.model
+        if isinstance(m, ClassifierGuidedSampleModel) and m.cond_lambda == 0:
+            # a guidance scale of zero is no guidance (as ClassifierFreeSampleModel takes cond_lambda 0 and 1 as the plain
+            # calls): the wrapped model, and with it the one-enqueue sampler loops an agent without the wrapper runs
+            m = m.model
         if sampler_type == 'lms':
             return ks.sample_lms(m, state, x_t, goal, sigmas, scaler=scaler, disable=True, extra_args=reduced)
         if sampler_type == 'heun':

@@ -29,6 +29,9 @@ MLP_UNITS = ["encoder"]
 # ... and so is the residual MLP encoder (include/beso_resmlp.h); the two share csrc/mlp_tile.h
 RESMLP_LIB = os.path.join(LIBDIR, "libbeso_resmlp.so")
 RESMLP_UNITS = ["resmlp"]
+# ... and the guide gradient of classifier-guided sampling (include/beso_guide.h), on the same tile GEMMs
+GUIDE_LIB = os.path.join(LIBDIR, "libbeso_guide.so")
+GUIDE_UNITS = ["guide"]
 ARCH = "gfx950"
 # -fvisibility=hidden: the dynamic symbol table is exactly include/beso_hip.h (its declarations carry default visibility)
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
@@ -51,10 +54,11 @@ def _source_hash() -> str:
     files.append(os.path.join(os.path.dirname(PKG), "include", "beso_hip_debug.h"))
     files.append(os.path.join(os.path.dirname(PKG), "include", "beso_mlp.h"))
     files.append(os.path.join(os.path.dirname(PKG), "include", "beso_resmlp.h"))
+    files.append(os.path.join(os.path.dirname(PKG), "include", "beso_guide.h"))
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         h.update(open(f, "rb").read())
-    h.update(" ".join(FLAGS + os.environ.get("BESO_EXTRA_HIPCC_FLAGS", "").split() + UNITS + MLP_UNITS + RESMLP_UNITS).encode())
+    h.update(" ".join(FLAGS + os.environ.get("BESO_EXTRA_HIPCC_FLAGS", "").split() + UNITS + MLP_UNITS + RESMLP_UNITS + GUIDE_UNITS).encode())
     return h.hexdigest()
 
 
@@ -81,7 +85,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
         have = open(STAMP).read().strip()
     except OSError:
         have = ""
-    libs = [(LIB, UNITS)] + ([] if dev else [(MLP_LIB, MLP_UNITS), (RESMLP_LIB, RESMLP_UNITS)])
+    libs = [(LIB, UNITS)] + ([] if dev else [(MLP_LIB, MLP_UNITS), (RESMLP_LIB, RESMLP_UNITS), (GUIDE_LIB, GUIDE_UNITS)])
     if not force and all(os.path.exists(path) for path, _ in libs) and have == want:
         return LIB
     try:
@@ -111,7 +115,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
 def is_current() -> bool:
     """True when the library in lib/ was built from exactly the sources in the tree."""
     try:
-        return all(os.path.exists(p) for p in (LIB, MLP_LIB, RESMLP_LIB)) and open(STAMP).read().strip() == _source_hash()
+        return all(os.path.exists(p) for p in (LIB, MLP_LIB, RESMLP_LIB, GUIDE_LIB)) and open(STAMP).read().strip() == _source_hash()
     except OSError:
         return False
 
