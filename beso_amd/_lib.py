@@ -197,50 +197,41 @@ def load() -> C.CDLL:
     return _lib
 
 
-_mlp = None
+# the libraries beside the product library, built with it: name -> (path, signatures, header, what has no fallback)
+_SIDE = {"mlp": (MLP_LIB_PATH, MLP_SIGNATURES, "beso_mlp.h", "the encoder"),
+         "resmlp": (RESMLP_LIB_PATH, RESMLP_SIGNATURES, "beso_resmlp.h", "the encoder"),
+         "guide": (GUIDE_LIB_PATH, GUIDE_SIGNATURES, "beso_guide.h", "the fused guide gradient")}
+_side = {}
+
+
+def _load_side(name: str) -> C.CDLL:
+    """Load one library of _SIDE (once), as load() does the product library.  No fallback either."""
+    if name not in _side:
+        with _lock:
+            if name not in _side:
+                import torch  # noqa: F401      (the HIP runtime of the process: see load())
+                path, table, header, what = _SIDE[name]
+                if not os.path.exists(path):
+                    raise BesoHipError(f"{path} (include/{header}) not found: build it with `python -m beso_amd.build` (hipcc, "
+                                       f"gfx950). beso_amd has no CPU or eager fallback for {what}.")
+                _side[name] = _bind(C.CDLL(path), table, tolerant=False)
+    return _side[name]
 
 
 def load_mlp() -> C.CDLL:
-    """The MLP encoder's library (include/beso_mlp.h), built with the product library.  No fallback either."""
-    global _mlp
-    if _mlp is None:
-        import torch  # noqa: F401      (the HIP runtime of the process: see load())
-        if not os.path.exists(MLP_LIB_PATH):
-            raise BesoHipError(f"{MLP_LIB_PATH} not found: build it with `python -m beso_amd.build` (hipcc, gfx950). "
-                               "beso_amd has no CPU or eager fallback for the encoder.")
-        _mlp = _bind(C.CDLL(MLP_LIB_PATH), MLP_SIGNATURES, tolerant=False)
-    return _mlp
-
-
-_resmlp = None
+    """The MLP encoder's library (include/beso_mlp.h)."""
+    return _load_side("mlp")
 
 
 def load_resmlp() -> C.CDLL:
-    """The residual MLP encoder's library (include/beso_resmlp.h), built with the product library.  No fallback either."""
-    global _resmlp
-    if _resmlp is None:
-        import torch  # noqa: F401      (the HIP runtime of the process: see load())
-        if not os.path.exists(RESMLP_LIB_PATH):
-            raise BesoHipError(f"{RESMLP_LIB_PATH} not found: build it with `python -m beso_amd.build` (hipcc, gfx950). "
-                               "beso_amd has no CPU or eager fallback for the encoder.")
-        _resmlp = _bind(C.CDLL(RESMLP_LIB_PATH), RESMLP_SIGNATURES, tolerant=False)
-    return _resmlp
-
-
-_guide = None
+    """The residual MLP encoder's library (include/beso_resmlp.h)."""
+    return _load_side("resmlp")
 
 
 def load_guide() -> C.CDLL:
-    """The guide-gradient library of classifier-guided sampling (include/beso_guide.h), built with the product library.  No
-    fallback either: a guide it does not serve takes autograd over the guide's own HIP kernels, decided once per guide."""
-    global _guide
-    if _guide is None:
-        import torch  # noqa: F401      (the HIP runtime of the process: see load())
-        if not os.path.exists(GUIDE_LIB_PATH):
-            raise BesoHipError(f"{GUIDE_LIB_PATH} not found: build it with `python -m beso_amd.build` (hipcc, gfx950). "
-                               "beso_amd has no CPU or eager fallback for the fused guide gradient.")
-        _guide = _bind(C.CDLL(GUIDE_LIB_PATH), GUIDE_SIGNATURES, tolerant=False)
-    return _guide
+    """The guide-gradient library of classifier-guided sampling (include/beso_guide.h).  A guide it does not serve takes
+    autograd over the guide's own HIP kernels, decided once per guide."""
+    return _load_side("guide")
 
 
 _dev = None

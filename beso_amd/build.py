@@ -22,16 +22,15 @@ STAMP = os.path.join(LIBDIR, "libbeso_hip.sha256")        # source hash the .so 
 DEV_LIB = os.path.join(LIBDIR, "libbeso_hip_dev.so")
 DEV_STAMP = os.path.join(LIBDIR, "libbeso_hip_dev.sha256")
 UNITS = ["api", "elementwise", "attention", "gemm", "fused", "fused_f16", "optim", "train", "feed", "small", "rollout", "lossfwd"]
-# the MLP observation / goal encoder (include/beso_mlp.h) is a library of its own, built with the product library and under
-# the same stamp: libbeso_hip.so's dynamic symbol table stays exactly include/beso_hip.h
-MLP_LIB = os.path.join(LIBDIR, "libbeso_mlp.so")
-MLP_UNITS = ["encoder"]
-# ... and so is the residual MLP encoder (include/beso_resmlp.h); the two share csrc/mlp_tile.h
-RESMLP_LIB = os.path.join(LIBDIR, "libbeso_resmlp.so")
-RESMLP_UNITS = ["resmlp"]
-# ... and the guide gradient of classifier-guided sampling (include/beso_guide.h), on the same tile GEMMs
-GUIDE_LIB = os.path.join(LIBDIR, "libbeso_guide.so")
-GUIDE_UNITS = ["guide"]
+# Every library: (path, units, public header under include/).  The MLP observation / goal encoder, the residual MLP encoder and
+# the guide gradient of classifier-guided sampling (they share csrc/mlp_tile.h) are libraries of their own, built with the
+# product library and under the same stamp: libbeso_hip.so's dynamic symbol table stays exactly include/beso_hip.h
+LIBS = [(LIB, UNITS, "beso_hip.h"),
+        (DEV_LIB, UNITS, "beso_hip_debug.h"),
+        (os.path.join(LIBDIR, "libbeso_mlp.so"), ["encoder"], "beso_mlp.h"),
+        (os.path.join(LIBDIR, "libbeso_resmlp.so"), ["resmlp"], "beso_resmlp.h"),
+        (os.path.join(LIBDIR, "libbeso_guide.so"), ["guide"], "beso_guide.h")]
+PRODUCT_LIBS = [lib for lib in LIBS if lib[0] != DEV_LIB]     # what a plain build makes and is_current() asks for
 ARCH = "gfx950"
 # -fvisibility=hidden: the dynamic symbol table is exactly include/beso_hip.h (its declarations carry default visibility)
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
@@ -45,20 +44,16 @@ def _hipcc() -> str:
 
 
 def _source_hash() -> str:
-    """sha256 over every file the library is built from (csrc/*, include/beso_hip.h), the flags and the compiler path:
+    """sha256 over every file the libraries are built from (csrc/*, every public header of LIBS), the flags and the unit names:
     the key that decides whether the prebuilt .so is current.  (Modification times are not: the .so is git-ignored but
     travels with the tree, and a checkout or copy can make a stale binary look newer than its sources.)"""
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC))
-    files.append(os.path.join(os.path.dirname(PKG), "include", "beso_hip.h"))
-    files.append(os.path.join(os.path.dirname(PKG), "include", "beso_hip_debug.h"))
-    files.append(os.path.join(os.path.dirname(PKG), "include", "beso_mlp.h"))
-    files.append(os.path.join(os.path.dirname(PKG), "include", "beso_resmlp.h"))
-    files.append(os.path.join(os.path.dirname(PKG), "include", "beso_guide.h"))
+    files += [os.path.join(os.path.dirname(PKG), "include", header) for _, _, header in LIBS]
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
         h.update(open(f, "rb").read())
-    h.update(" ".join(FLAGS + os.environ.get("BESO_EXTRA_HIPCC_FLAGS", "").split() + UNITS + MLP_UNITS + RESMLP_UNITS + GUIDE_UNITS).encode())
+    h.update(" ".join(FLAGS + os.environ.get("BESO_EXTRA_HIPCC_FLAGS", "").split() + [u for _, us, _ in PRODUCT_LIBS for u in us]).encode())
     return h.hexdigest()
 
 
@@ -85,7 +80,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
         have = open(STAMP).read().strip()
     except OSError:
         have = ""
-    libs = [(LIB, UNITS)] + ([] if dev else [(MLP_LIB, MLP_UNITS), (RESMLP_LIB, RESMLP_UNITS), (GUIDE_LIB, GUIDE_UNITS)])
+    libs = [lib[:2] for lib in LIBS if (lib[0] == DEV_LIB) == dev]
     if not force and all(os.path.exists(path) for path, _ in libs) and have == want:
         return LIB
     try:
@@ -115,7 +110,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False) -> str:
 def is_current() -> bool:
     """True when the library in lib/ was built from exactly the sources in the tree."""
     try:
-        return all(os.path.exists(p) for p in (LIB, MLP_LIB, RESMLP_LIB, GUIDE_LIB)) and open(STAMP).read().strip() == _source_hash()
+        return all(os.path.exists(path) for path, _, _ in PRODUCT_LIBS) and open(STAMP).read().strip() == _source_hash()
     except OSError:
         return False
 

@@ -4,8 +4,6 @@
 //                        layers (every pre-activation tile stays in LDS), runs the data-gradient chain of sum(q) backward and
 //                        writes out = pred + lam sigma^2 dq/da for the action columns
 // Nothing leaves the workgroup but `out`: no keep buffer, no workspace, no weight gradient.
-#include <atomic>
-
 #include "mlp_tile.h"
 #include "../../include/beso_guide.h"
 
@@ -26,31 +24,6 @@ struct Guide {
     long long goal_stride, goal_off;           // floats between two samples' goals (0: one shared goal) and to step G - 1
     float lam;
 };
-
-// The last step of the chain: out[16, [k_lo, k_lo + n_cols)] = in[16, N] W[N, ldw] for those columns of W alone, handed to
-// `epi(row, column - k_lo, value)`.  tile_xw's loop and summation order over a column window.
-template <typename Epi>
-__device__ __forceinline__ void tile_xw_window(const float* in, int pitch, const float* __restrict__ W, int N, int ldw,
-                                               int k_lo, int n_cols, Epi epi) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, lr = lane & 15, g = lane >> 4;
-    const int Np = round16(N);
-    for (int c0 = wid * 16; c0 < n_cols; c0 += kWaves * 16) {
-        const int c = c0 + lr;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int n0 = 0; n0 < Np; n0 += 16) {
-            const int n = n0 + 4 * g;
-            const f32x4 a = *(const f32x4*)(in + lr * pitch + n);
-            f32x4 b;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = (c < n_cols && n + j < N) ? W[(size_t)(n + j) * ldw + k_lo + c] : 0.f;
-            acc = mfma4(acc, a, b);
-        }
-        if (c < n_cols) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) epi(4 * g + r, c, acc[r]);
-        }
-    }
-}
 
 __global__ __launch_bounds__(kThreads) void guide_apply_kernel(Guide gd, long long M, int pitch) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -118,7 +91,7 @@ __global__ __launch_bounds__(kThreads) void guide_apply_kernel(Guide gd, long lo
     // dx = dz_0 W_0 for the action columns only, and the guided prediction.  A thread reads pred[e] before it writes out[e],
     // and no other thread touches element e: pred == out is safe.
     const float lam = gd.lam;
-    tile_xw_window(cur, pitch, gd.w[0], H, I, obs, adim, [&](int r, int c, float v) {
+    tile_xw(cur, pitch, gd.w[0], H, I, obs, adim, [&](int r, int c, float v) {
         const long long m = m0 + r;
         if (m < M) {
             const float s = gd.sigma[m / gd.T];
@@ -129,37 +102,21 @@ __global__ __launch_bounds__(kThreads) void guide_apply_kernel(Guide gd, long lo
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-static int tile_pitch(const beso_mlp_dims* d) {
-    return round16(d->in_dim > d->hidden_dim ? d->in_dim : d->hidden_dim) + kLdsPad;
-}
+static int pitch_of(const beso_mlp_dims* d) { return tile_pitch(std::max(d->in_dim, d->hidden_dim)); }
 
 static size_t lds_bytes(const beso_mlp_dims* d) {
-    return (size_t)(d->n_hidden + 2) * kRows * tile_pitch(d) * sizeof(float);
+    return (size_t)(d->n_hidden + 2) * kRows * pitch_of(d) * sizeof(float);
 }
 
 static int check_guide(const beso_mlp_dims* d, int obs, int adim, int use_goal) {
     if (!d) return BESO_ERR_BAD_ARG;
-    if (d->in_dim < 1 || d->in_dim > kMaxDim || d->out_dim != 1) return BESO_ERR_BAD_SHAPE;
-    if (d->hidden_dim < 16 || d->hidden_dim > kMaxDim || d->hidden_dim % 16) return BESO_ERR_BAD_SHAPE;
-    if (d->n_hidden < 1 || d->n_hidden > kMaxLinear - 1) return BESO_ERR_BAD_SHAPE;
+    if (d->out_dim != 1 || d->n_hidden < 1 || d->n_hidden > kMaxLinear - 1) return BESO_ERR_BAD_SHAPE;
     if (obs < 1 || adim < 1 || obs > kMaxDim || adim > kMaxDim) return BESO_ERR_BAD_SHAPE;
     if (d->in_dim != obs + adim + (use_goal ? obs : 0)) return BESO_ERR_BAD_SHAPE;
-    if (lds_bytes(d) > kMaxLds) return BESO_ERR_BAD_SHAPE;
-    if (d->activation < BESO_MLP_ACT_RELU || d->activation > BESO_MLP_ACT_SIGMOID) return BESO_ERR_BAD_ARG;
-    return BESO_OK;
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize = the ceiling, once per device (the bit of a device is set after it succeeded)
-static hipError_t allow_max_lds() {
-    static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (dev < 64 && (done.load(std::memory_order_relaxed) & bit)) return hipSuccess;
-    e = hipFuncSetAttribute((const void*)guide_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (e == hipSuccess && dev < 64) done.fetch_or(bit, std::memory_order_relaxed);
-    return e;
+    const int st = check_common(d->in_dim, d->hidden_dim, 1, d->activation, 1);       // M is beso_guide_apply's to check
+    // the LDS ceiling is a shape error, and like every shape error it ranks above a bad activation
+    if (st == BESO_ERR_BAD_SHAPE || lds_bytes(d) > kMaxLds) return BESO_ERR_BAD_SHAPE;
+    return st;
 }
 
 }  // namespace beso_guide
@@ -179,9 +136,7 @@ extern "C" int beso_guide_apply(const float* const* params, int n_params, const 
     const long long M = (long long)B * T;
     if (M > 0x7fffffffLL) return BESO_ERR_BAD_SHAPE;
     if (goal ? (goal_steps < 1 || (goal_rows != B && goal_rows != 1)) : (goal_steps != 0 || goal_rows != 0)) return BESO_ERR_BAD_SHAPE;
-    if (!params || n_params != 2 * (dims->n_hidden + 1)) return BESO_ERR_BAD_ARG;
-    for (int i = 0; i < n_params; ++i)
-        if (!params[i] || ((uintptr_t)params[i] & 3)) return BESO_ERR_BAD_ARG;
+    if (check_params(params, n_params, 2 * (dims->n_hidden + 1)) != BESO_OK) return BESO_ERR_BAD_ARG;
     if (!state || !pred || !sigma || !out || ((uintptr_t)state & 3) || ((uintptr_t)goal & 3) || ((uintptr_t)pred & 3) ||
         ((uintptr_t)sigma & 3) || ((uintptr_t)out & 3))
         return BESO_ERR_BAD_ARG;
@@ -208,10 +163,6 @@ extern "C" int beso_guide_apply(const float* const* params, int n_params, const 
     gd.goal_off = goal ? (long long)(goal_steps - 1) * obs_dim : 0;
     gd.lam = lam;
 
-    const size_t lds = lds_bytes(dims);
-    (void)hipGetLastError();
-    if (lds > 64 * 1024 && allow_max_lds() != hipSuccess) return BESO_ERR_HIP;
-    const unsigned grid = (unsigned)((M + kRows - 1) / kRows);
-    hipLaunchKernelGGL(guide_apply_kernel, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, gd, M, tile_pitch(dims));
-    return hipGetLastError() == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    return to_status(launch_lds_attr<guide_apply_kernel>(kMaxLds, dim3(tile_grid(M)), dim3(kThreads), lds_bytes(dims), (hipStream_t)stream,
+                                                         gd, M, pitch_of(dims)));
 }

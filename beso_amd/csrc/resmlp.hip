@@ -1,9 +1,8 @@
 // The residual MLP encoder (include/beso_resmlp.h; reference networks/mlps/mlps.py:76-133 over res_layers.py): libbeso_resmlp.so.
-// fp32 on v_mfma_f32_16x16x4_f32 through the tile GEMMs of mlp_tile.h (operand layout there).  Four kernels:
+// fp32 on v_mfma_f32_16x16x4_f32 through the tile GEMMs of mlp_tile.h (operand layout there).  Two kernels of its own:
 //   resmlp_fwd_kernel     a workgroup carries 16 rows through every layer: the residual stream and two ping-pong tiles in LDS
 //   resmlp_bwd_kernel     the data-gradient chain of the same 16 rows in reverse order, LayerNorm backward at both uses
-//   resmlp_wgrad_kernel   dW / db (and dgamma / dbeta as bias-only "layers") partial sums per (layer, 16 input columns, row range)
-//   resmlp_reduce_kernel  adds the partial sums in row-range order
+// and mlp_tile.h's wgrad_kernel<kWgChunk> (dW / db, and dgamma / dbeta as bias-only "layers", summed in chunks) and reduce_kernel.
 // The element-wise passes between the GEMMs give a row to 16 lanes (thread t: row t >> 4, columns (t & 15) + 16 i), so a
 // LayerNorm statistic is a fixed-order sum per lane and a four-step butterfly over those 16 lanes.
 #include "mlp_tile.h"
@@ -14,8 +13,9 @@ namespace beso_resmlp {
 using namespace beso_mlp;
 
 constexpr int kMaxBlocks = 4;
-constexpr int kMaxWgLayers = 2 + 4 * kMaxBlocks;      // two outer Linears; per block l1, l2, gamma, beta
+static_assert(2 + 4 * kMaxBlocks <= kMaxWgLayers, "two outer Linears; per block l1, l2, gamma, beta");
 constexpr float kLnEps = 1e-6f;
+constexpr size_t kLdsMax = 3 * kTileBytes;            // the two tile kernels' LDS, three [16][pitch] buffers, at the widest: 99072
 constexpr int kWgChunk = 2;                           // 16-row steps of the weight gradient summed before they join the total
 
 struct Net {
@@ -134,12 +134,7 @@ __global__ __launch_bounds__(kThreads) void resmlp_fwd_kernel(Net net, const flo
     const long long m0 = (long long)blockIdx.x * kRows;
     const int H = net.hidden, B = net.n_blocks, act = net.act;
     load_tile(T1, pitch, x, net.in_dim, m0, M);
-    if (keep) {                                                       // keep[0 : M in] = x
-        for (int i = threadIdx.x; i < kRows * net.in_dim; i += kThreads) {
-            const int r = i / net.in_dim, c = i - r * net.in_dim;
-            if (m0 + r < M) keep[(size_t)(m0 + r) * net.in_dim + c] = x[(size_t)(m0 + r) * net.in_dim + c];
-        }
-    }
+    if (keep) keep_x(keep, x, net.in_dim, m0, M);
     __syncthreads();
     const size_t MH = (size_t)M * H;
     float* keep_u = keep ? keep + (size_t)M * net.in_dim : nullptr;   // u_0 .. u_B
@@ -232,113 +227,13 @@ __global__ __launch_bounds__(kThreads) void resmlp_bwd_kernel(Net net, const flo
     }
 }
 
-// What one "layer" of the weight gradient reads and where its partial sums go.  K == 0: only the bias column (dgamma, dbeta).
-struct WgLayer {
-    const float* dz;      // [M, N]
-    const float* a;       // [M, K]: the layer's input as it entered the GEMM
-    int N, K;
-    int block0;           // first workgroup of the layer: ceil((K + 1) / 16) column tiles x n_splits row ranges
-    long long w_off, b_off;   // offsets into one slab row (= into grads_flat)
-};
-struct WgPlan {
-    WgLayer layer[kMaxWgLayers];
-    int n_layers, n_splits;
-    long long rows_per_split, M, P;
-};
-
-// slab[split][w_off + n K + k] = sum over the split's rows of dz[m][n] a[m][k];  column k == K is the bias (a = 1).
-__global__ __launch_bounds__(kThreads) void resmlp_wgrad_kernel(WgPlan plan, float* __restrict__ slab) {
-    int li = 0;
-    while (li + 1 < plan.n_layers && (int)blockIdx.x >= plan.layer[li + 1].block0) ++li;
-    const WgLayer L = plan.layer[li];
-    const int local = blockIdx.x - L.block0;
-    const int split = local % plan.n_splits, ktile = local / plan.n_splits;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, lr = lane & 15, g = lane >> 4;
-    const long long r0 = (long long)split * plan.rows_per_split;
-    const long long r1 = r0 + plan.rows_per_split < plan.M ? r0 + plan.rows_per_split : plan.M;
-    const int k = ktile * 16 + lr;
-    const int n_tiles = (L.N + 15) / 16;
-
-    // blocked summation over the rows: `acc` takes kWgChunk 16-row steps, then joins `total` -- the rounding error of a
-    // 256-row range grows like that of a 32-term sum, and the order stays a function of (dims, M)
-    f32x4 acc[kWgTiles], total[kWgTiles];
-#pragma unroll
-    for (int i = 0; i < kWgTiles; ++i) acc[i] = total[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    int in_chunk = 0;
-    for (long long m0 = r0; m0 < r1; m0 += 16) {
-        f32x4 b;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const long long m = m0 + 4 * g + j;
-            float v = 0.f;
-            if (m < r1) {
-                if (k < L.K) v = L.a[(size_t)m * L.K + k];
-                else if (k == L.K) v = 1.f;
-            }
-            b[j] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < kWgTiles; ++i) {
-            const int tile = wid + kWaves * i;
-            if (tile < n_tiles) {
-                const int n = tile * 16 + lr;
-                f32x4 a;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const long long m = m0 + 4 * g + j;
-                    a[j] = (m < r1 && n < L.N) ? L.dz[(size_t)m * L.N + n] : 0.f;
-                }
-                acc[i] = mfma4(acc[i], a, b);
-            }
-        }
-        if (++in_chunk == kWgChunk) {
-            in_chunk = 0;
-#pragma unroll
-            for (int i = 0; i < kWgTiles; ++i) {
-                total[i] += acc[i];
-                acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < kWgTiles; ++i) total[i] += acc[i];             // the last, partial chunk (zeros if there is none)
-    float* out = slab + (size_t)split * (size_t)plan.P;
-#pragma unroll
-    for (int i = 0; i < kWgTiles; ++i) {
-        const int tile = wid + kWaves * i;
-        if (tile < n_tiles) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = tile * 16 + 4 * g + r;
-                if (n < L.N) {
-                    if (k < L.K) out[L.w_off + (size_t)n * L.K + k] = total[i][r];
-                    else if (k == L.K) out[L.b_off + n] = total[i][r];
-                }
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void resmlp_reduce_kernel(const float* __restrict__ slab, float* __restrict__ grads,
-                                                                 long long P, int n_splits, int accumulate) {
-    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
-    if (e >= P) return;
-    float s = slab[e];
-    for (int i = 1; i < n_splits; ++i) s += slab[(size_t)i * (size_t)P + e];
-    grads[e] = accumulate ? grads[e] + s : s;
-}
-
 // ------------------------------------------------------------------------------------------------------------ host
 static int check_dims(const beso_resmlp_dims* d, long long M) {
     if (!d) return BESO_ERR_BAD_ARG;
-    if (d->in_dim < 1 || d->in_dim > kMaxDim || d->out_dim < 1 || d->out_dim > kMaxDim) return BESO_ERR_BAD_SHAPE;
-    if (d->hidden_dim < 16 || d->hidden_dim > kMaxDim || d->hidden_dim % 16) return BESO_ERR_BAD_SHAPE;
     if (d->n_blocks < 1 || d->n_blocks > kMaxBlocks) return BESO_ERR_BAD_SHAPE;
-    if (M < 1 || M > 0x7fffffffLL) return BESO_ERR_BAD_SHAPE;
-    if (d->activation < BESO_MLP_ACT_RELU || d->activation > BESO_MLP_ACT_SIGMOID) return BESO_ERR_BAD_ARG;
-    if (d->norm != BESO_RESMLP_NORM_NONE && d->norm != BESO_RESMLP_NORM_LAYER) return BESO_ERR_BAD_ARG;
-    return BESO_OK;
+    const int st = check_common(d->in_dim, d->hidden_dim, d->out_dim, d->activation, M);
+    if (st != BESO_OK) return st;
+    return d->norm == BESO_RESMLP_NORM_NONE || d->norm == BESO_RESMLP_NORM_LAYER ? BESO_OK : BESO_ERR_BAD_ARG;
 }
 
 static long long param_count(const beso_resmlp_dims* d) {
@@ -355,9 +250,7 @@ static size_t chain_bytes(const beso_resmlp_dims* d, long long M) {
 
 static int fill_net(Net* net, const float* const* params, int n_params, const beso_resmlp_dims* d) {
     const int per_block = d->norm ? 6 : 4;
-    if (!params || n_params != 4 + per_block * d->n_blocks) return BESO_ERR_BAD_ARG;
-    for (int i = 0; i < n_params; ++i)
-        if (!params[i] || ((uintptr_t)params[i] & 3)) return BESO_ERR_BAD_ARG;
+    if (check_params(params, n_params, 4 + per_block * d->n_blocks) != BESO_OK) return BESO_ERR_BAD_ARG;
     *net = Net{};
     net->w0 = params[0];
     net->b0 = params[1];
@@ -382,12 +275,7 @@ static int fill_net(Net* net, const float* const* params, int n_params, const be
     return BESO_OK;
 }
 
-// LDS of the two tile kernels: three [16][pitch] buffers, 99072 bytes at the widest
-static int tile_pitch(const beso_resmlp_dims* d) {
-    int w = d->in_dim > d->out_dim ? d->in_dim : d->out_dim;
-    if (d->hidden_dim > w) w = d->hidden_dim;
-    return round16(w) + kLdsPad;
-}
+static int pitch_of(const beso_resmlp_dims* d) { return tile_pitch(std::max({d->in_dim, d->hidden_dim, d->out_dim})); }
 
 }  // namespace beso_resmlp
 
@@ -395,8 +283,7 @@ using namespace beso_resmlp;
 
 extern "C" size_t beso_resmlp_workspace_bytes(const beso_resmlp_dims* dims, long long M, int training) {
     if (check_dims(dims, M) != BESO_OK || !training) return 0;
-    const long long R = rows_per_split(M), S = (M + R - 1) / R;
-    return chain_bytes(dims, M) + align256((size_t)S * (size_t)param_count(dims) * sizeof(float));
+    return chain_bytes(dims, M) + slab_bytes(M, param_count(dims));
 }
 
 extern "C" int beso_resmlp_fwd(const float* const* params, int n_params, const beso_resmlp_dims* dims, const float* x,
@@ -406,13 +293,9 @@ extern "C" int beso_resmlp_fwd(const float* const* params, int n_params, const b
     Net net;
     if ((st = fill_net(&net, params, n_params, dims)) != BESO_OK) return st;
     if (!x || !y || ((uintptr_t)x & 3) || ((uintptr_t)y & 3) || ((uintptr_t)keep & 3)) return BESO_ERR_BAD_ARG;
-    const int pitch = tile_pitch(dims);
-    const size_t lds = 3 * (size_t)kRows * pitch * sizeof(float);
-    (void)hipGetLastError();
-    if (allow_lds(resmlp_fwd_kernel, lds) != hipSuccess) return BESO_ERR_HIP;
-    const unsigned grid = (unsigned)((M + kRows - 1) / kRows);
-    hipLaunchKernelGGL(resmlp_fwd_kernel, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, net, x, M, y, keep, pitch);
-    return hipGetLastError() == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    const int pitch = pitch_of(dims);
+    return to_status(launch_lds_attr<resmlp_fwd_kernel>(kLdsMax, dim3(tile_grid(M)), dim3(kThreads), 3 * (size_t)kRows * pitch * sizeof(float),
+                                                        (hipStream_t)stream, net, x, M, y, keep, pitch));
 }
 
 extern "C" int beso_resmlp_bwd(const float* const* params, int n_params, const beso_resmlp_dims* dims, const float* keep,
@@ -435,50 +318,21 @@ extern "C" int beso_resmlp_bwd(const float* const* params, int n_params, const b
     const float* keep_u = keep + (size_t)M * dims->in_dim;
     const float* norm_ws = ws + (size_t)(1 + 4 * B) * MH;
 
-    WgPlan plan;
-    plan.M = M;
-    plan.P = param_count(dims);
-    plan.rows_per_split = rows_per_split(M);
-    plan.n_splits = (int)((M + plan.rows_per_split - 1) / plan.rows_per_split);
-    long long off = 0;
-    int blocks = 0, nl = 0;
-    auto add = [&](const float* dz, const float* a, int N, int K) {     // the next parameter pair (weight [N, K], bias [N])
-        WgLayer& L = plan.layer[nl++];
-        L.dz = dz;
-        L.a = a;
-        L.N = N;
-        L.K = K;
-        L.block0 = blocks;
-        L.w_off = off;
-        L.b_off = off + (long long)N * K;
-        off = L.b_off + N;
-        blocks += (K + 1 + 15) / 16 * plan.n_splits;
-    };
-    add(ws, keep, H, dims->in_dim);
+    WgPlan plan(M, param_count(dims), dims->activation);              // apply_act 0: every input is stored as it entered its GEMM
+    plan.add(ws, keep, H, dims->in_dim, 0);
     for (int b = 0; b < B; ++b) {
         const float* blk = ws + (size_t)(1 + 4 * b) * MH;
-        add(blk, blk + 2 * MH, H, H);                                   // l1: dV_b, A1_b
-        add(blk + MH, blk + 3 * MH, H, H);                              // l2: dU_{b+1}, A2_b
-        if (dims->norm) {                                               // gamma, beta: two bias-only layers, back to back
+        plan.add(blk, blk + 2 * MH, H, H, 0);                         // l1: dV_b, A1_b
+        plan.add(blk + MH, blk + 3 * MH, H, H, 0);                    // l2: dU_{b+1}, A2_b
+        if (dims->norm) {                                             // gamma, beta: two bias-only layers, back to back
             const float* gp = norm_ws + (size_t)(2 * b) * MH;
-            add(gp, nullptr, H, 0);
-            add(gp + MH, nullptr, H, 0);
+            plan.add(gp, nullptr, H, 0, 0);
+            plan.add(gp + MH, nullptr, H, 0, 0);
         }
     }
-    add(dy, keep_u + (size_t)B * MH, dims->out_dim, H);
-    plan.n_layers = nl;
+    plan.add(dy, keep_u + (size_t)B * MH, dims->out_dim, H, 0);
 
-    const int pitch = tile_pitch(dims);
-    const size_t lds = 3 * (size_t)kRows * pitch * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    if (allow_lds(resmlp_bwd_kernel, lds) != hipSuccess) return BESO_ERR_HIP;
-    const unsigned grid = (unsigned)((M + kRows - 1) / kRows);
-    hipLaunchKernelGGL(resmlp_bwd_kernel, dim3(grid), dim3(kThreads), lds, s, net, keep, dy, M, ws, dx, pitch);
-    if (hipGetLastError() != hipSuccess) return BESO_ERR_HIP;
-    hipLaunchKernelGGL(resmlp_wgrad_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, plan, slab);
-    if (hipGetLastError() != hipSuccess) return BESO_ERR_HIP;
-    hipLaunchKernelGGL(resmlp_reduce_kernel, dim3((unsigned)((plan.P + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       (const float*)slab, grads_flat, plan.P, plan.n_splits, flags & BESO_MLP_ACCUMULATE);
-    return hipGetLastError() == hipSuccess ? BESO_OK : BESO_ERR_HIP;
+    const int pitch = pitch_of(dims);
+    return launch_bwd<resmlp_bwd_kernel, kWgChunk>(kLdsMax, 3 * (size_t)kRows * pitch * sizeof(float), (hipStream_t)stream, plan, slab,
+                                                   grads_flat, flags & BESO_MLP_ACCUMULATE, net, keep, dy, M, ws, dx, pitch);
 }

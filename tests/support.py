@@ -85,6 +85,71 @@ def bits(x):
     return x.contiguous().view(torch.int32)
 
 
+def check_side_library(header, prefix, signatures, lib_path, loader, n_functions, min_kernels, min_mfma=21):
+    """A library beside the product library exports the `n_functions` symbols ``<prefix>*`` its header under include/ declares,
+    no more; the binding table `signatures` has the header's argument counts, and so has what `loader()` bound; the matrix-pipe
+    hazard check of DESIGN.md 4.1c passes on it.  -> the header's text without its comments."""
+    import os
+    import re
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(root, "include", header)).read(), flags=re.S)
+    protos = {fn: args.split(",") for fn, args in re.findall(r"\b(%s[a-z_]+)\s*\(([^()]*)\)\s*;" % prefix, text)}
+    assert sorted(protos) == sorted(signatures) and len(protos) == n_functions
+    out = subprocess.run(["nm", "-D", "--defined-only", lib_path], capture_output=True, text=True, check=True).stdout
+    assert sorted(ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("beso_")) == sorted(protos)
+    bound = loader()
+    for fn, args in protos.items():
+        assert len(signatures[fn][1]) == len(args) == len(getattr(bound, fn).argtypes), fn
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import check_mfma_chains as chk
+    if os.path.exists(os.path.join(chk.LLVM, "llvm-objdump")):
+        bad, n_fn, n_mfma = chk.check_library(lib_path)
+        assert n_fn >= min_kernels and n_mfma >= min_mfma and not bad, (n_fn, n_mfma, bad[:5])
+    return text
+
+
+def raw_fwd_bwd(net, x, dy, fill=None):
+    """One ``<net._entry>_fwd`` (with keep) + ``_bwd`` (with dx, accumulate = 0) through the raw entry points on banded buffers
+    -> the result bytes.  `fill`: the byte every output, keep, workspace and gradient buffer holds on entry."""
+    fwd, bwd = (getattr(net._library(), f"{net._entry}_{what}") for what in ("fwd", "bwd"))
+    M = x.shape[0]
+    dims = net.dims()
+    ptrs, n = net._pointers(None)
+    band = 256
+    sizes = dict(y=4 * M * net.output_dim, keep=4 * net.keep_floats(M), ws=net.workspace_bytes(M),
+                 grads=4 * net.num_param_floats(), dx=4 * M * net.input_dim)
+    bufs = {k: torch.full((v + 2 * band,), 0xA5 if fill is None else fill, dtype=torch.uint8, device=DEV) for k, v in sizes.items()}
+    for b in bufs.values():
+        b[:band] = 0x5C
+        b[-band:] = 0x5C
+    p = {k: b.data_ptr() + band for k, b in bufs.items()}
+    s = torch.cuda.current_stream().cuda_stream
+    assert fwd(ptrs, n, C.byref(dims), x.data_ptr(), M, p["y"], p["keep"], s) == 0
+    assert bwd(ptrs, n, C.byref(dims), p["keep"], dy.data_ptr(), M, p["dx"], p["grads"], p["ws"], sizes["ws"], 0, s) == 0
+    torch.cuda.synchronize()
+    for k, b in bufs.items():
+        assert bool((b[:band] == 0x5C).all()) and bool((b[-band:] == 0x5C).all()), f"{k}: a sentinel band was written"
+    return {k: bufs[k][band:band + sizes[k]].clone() for k in ("y", "keep", "grads", "dx")}
+
+
+def check_row_ranges_add_up(net, x, dy, cut=256):
+    """The flat gradient of a raw fwd + bwd over all M rows is, bit for bit, the single fp32 addition of the flat gradients
+    over rows [0, cut) and [cut, M), each from a call of its own; y and dx are the two calls' concatenated.  Exact for
+    M = 300, cut = 256: the weight-gradient slabs' row ranges hold 256 rows up to M = 16384, so range 0 is the 256-row call's
+    only range; range 1 starts on a 16-row tile boundary and takes the 44-row call's steps, 16 + 16 + 12 rows (for the chunked
+    kernel one full chunk and a partial one); rows padded with zeros add exact zeros; the reduce is one addition."""
+    M = x.shape[0]
+    whole = raw_fwd_bwd(net, x, dy)
+    head, tail = (raw_fwd_bwd(net, x[a:b].contiguous(), dy[a:b].contiguous()) for a, b in ((0, cut), (cut, M)))
+    g = lambda r: r["grads"].view(torch.float32)                             # noqa: E731
+    assert bool(torch.isfinite(g(whole)).all()) and g(head).abs().max() > 0 and g(tail).abs().max() > 0
+    assert torch.equal(bits(g(whole)), bits(g(head) + g(tail)))
+    for k in ("y", "dx"):
+        assert torch.equal(whole[k], torch.cat([head[k], tail[k]])), k
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))

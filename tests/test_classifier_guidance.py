@@ -8,10 +8,6 @@ values, torch's error taken as at least one fp32 rounding (``compare_grads``'s r
 it measured."""
 import copy
 import ctypes as C
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -25,10 +21,9 @@ from beso_amd.agents.diffusion_agents.k_diffusion.guides import MLPGuide
 from beso_amd.networks.mlps.mlps import MLPNetwork
 from beso_amd.networks.scaler.scaler_class import Scaler
 from oracle import beso_oracle as O
-from support import TRAIN_BOUNDS, bits, build_agent, grad_errors, lib, make_denoiser  # noqa: F401
+from support import TRAIN_BOUNDS, bits, build_agent, check_side_library, grad_errors, lib, make_denoiser  # noqa: F401
 
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ACTS = {"ReLU": nn.ReLU, "Mish": nn.Mish, "sigmoid": nn.Sigmoid}
 FP32_BAR = 2e-5
 EPS = 2.0 ** -24        # one fp32 rounding
@@ -74,19 +69,9 @@ def test_the_class_imports_and_has_the_references_surface():
 def test_library_exports_what_its_header_declares(lib):
     """libbeso_guide.so: the two symbols of include/beso_guide.h, no more; the binding table has the header's argument counts;
     the matrix-pipe hazard check of DESIGN.md 4.1c passes on it."""
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "beso_guide.h")).read(), flags=re.S)
-    protos = {fn: args.split(",") for fn, args in re.findall(r"\b(beso_guide_[a-z_]+)\s*\(([^()]*)\)\s*;", text)}
-    assert sorted(protos) == sorted(_lib.GUIDE_SIGNATURES) == sorted(_lib.GUIDE_EXPORTS) and len(protos) == 2
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.GUIDE_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("beso_")) == sorted(protos)
-    g = _lib.load_guide()
-    for fn, args in protos.items():
-        assert len(_lib.GUIDE_SIGNATURES[fn][1]) == len(args) == len(getattr(g, fn).argtypes), fn
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import check_mfma_chains as chk
-    if os.path.exists(os.path.join(chk.LLVM, "llvm-objdump")):
-        bad, n_fn, n_mfma = chk.check_library(_lib.GUIDE_LIB_PATH)
-        assert n_fn >= 1 and n_mfma >= 12 and not bad, (n_fn, n_mfma, bad[:5])
+    check_side_library("beso_guide.h", "beso_guide_", _lib.GUIDE_SIGNATURES, _lib.GUIDE_LIB_PATH, _lib.load_guide, 2, min_kernels=1,
+                       min_mfma=12)
+    assert sorted(_lib.GUIDE_SIGNATURES) == sorted(_lib.GUIDE_EXPORTS)
 
 
 def test_argument_errors_do_not_touch_the_device(lib):

@@ -14,7 +14,8 @@ import torch.nn as nn
 from beso_amd import _lib
 from beso_amd.networks.mlps.mlps import MLPNetwork
 from oracle import beso_oracle as O
-from support import TRAIN_BOUNDS, bits, grad_errors, lib, make_denoiser  # noqa: F401
+from support import (TRAIN_BOUNDS, bits, check_row_ranges_add_up, check_side_library, grad_errors, lib, make_denoiser,  # noqa: F401
+                     raw_fwd_bwd)
 
 DEV = "cuda:0"
 # (in, hidden, hidden layers, out, M): M = 1, one below a multiple of the 16-row tile, one above one, a partial last tile
@@ -52,19 +53,8 @@ def rows(shape, seed=1, extra=0):
 def test_library_exports_what_its_header_declares(lib):
     """libbeso_mlp.so: the symbols of include/beso_mlp.h, no more; the binding table has the header's argument counts; the
     struct has the header's fields; the matrix-pipe hazard check of DESIGN.md 4.1c passes on it."""
-    import os
     import re
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(root, "include", "beso_mlp.h")).read(), flags=re.S)
-    protos = {fn: args.split(",") for fn, args in re.findall(r"\b(beso_mlp_[a-z_]+)\s*\(([^()]*)\)\s*;", text)}
-    assert sorted(protos) == sorted(_lib.MLP_SIGNATURES) and len(protos) == 3
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.MLP_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("beso_")) == sorted(protos)
-    mlp = _lib.load_mlp()
-    for fn, args in protos.items():
-        assert len(_lib.MLP_SIGNATURES[fn][1]) == len(args) == len(getattr(mlp, fn).argtypes), fn
+    text = check_side_library("beso_mlp.h", "beso_mlp_", _lib.MLP_SIGNATURES, _lib.MLP_LIB_PATH, _lib.load_mlp, 3, min_kernels=4)
     body = re.search(r"typedef\s+struct\s+beso_mlp_dims\s*\{(.*?)\}", text, flags=re.S).group(1)
     assert [f.split()[1] for f in body.split(";") if f.strip()] == [n for n, _ in _lib.MlpDims._fields_]
     consts = dict(re.findall(r"\b(BESO_MLP_[A-Z_]+)\s*=\s*(\d+)", text))
@@ -72,11 +62,6 @@ def test_library_exports_what_its_header_declares(lib):
         {k: _lib.MLP_ACTIVATIONS[k] for k in ("ReLU", "Mish", "sigmoid")}
     assert _lib.MLP_ACTIVATIONS["tanh"] == _lib.MLP_ACTIVATIONS["sigmoid"]
     assert int(consts["BESO_MLP_ACCUMULATE"]) == _lib.MLP_FLAGS["accumulate"]
-    sys.path.insert(0, os.path.join(root, "tools"))
-    import check_mfma_chains as chk
-    if os.path.exists(os.path.join(chk.LLVM, "llvm-objdump")):
-        bad, n_fn, n_mfma = chk.check_library(_lib.MLP_LIB_PATH)
-        assert n_fn >= 4 and n_mfma > 20 and not bad, (n_fn, n_mfma, bad[:5])
 
 
 def test_argument_errors_do_not_touch_the_device(lib):
@@ -180,37 +165,13 @@ def test_backward_matches_fp64_autograd_as_closely_as_torch_fp32_does(shape, act
     assert all(torch.equal(bits(p.grad), bits(b)) for p, b in zip(net.parameters(), before))
 
 
-def _raw_run(net, x, dy, fill=None, accumulate_into=None):
-    """One beso_mlp_fwd (with keep) + beso_mlp_bwd (with dx) through the raw entry points on banded buffers -> the result
-    tensors.  `fill`: the byte every output, keep, workspace and gradient buffer holds on entry."""
-    mlp = _lib.load_mlp()
-    M = x.shape[0]
-    dims = net.dims()
-    ptrs, n = net._pointers(None)
-    band = 256
-    sizes = dict(y=4 * M * net.output_dim, keep=4 * net.keep_floats(M), ws=net.workspace_bytes(M),
-                 grads=4 * net.num_param_floats(), dx=4 * M * net.input_dim)
-    bufs = {k: torch.full((v + 2 * band,), 0xA5 if fill is None else fill, dtype=torch.uint8, device=DEV) for k, v in sizes.items()}
-    for b in bufs.values():
-        b[:band] = 0x5C
-        b[-band:] = 0x5C
-    p = {k: b.data_ptr() + band for k, b in bufs.items()}
-    s = torch.cuda.current_stream().cuda_stream
-    assert mlp.beso_mlp_fwd(ptrs, n, C.byref(dims), x.data_ptr(), M, p["y"], p["keep"], s) == 0
-    assert mlp.beso_mlp_bwd(ptrs, n, C.byref(dims), p["keep"], dy.data_ptr(), M, p["dx"], p["grads"], p["ws"], sizes["ws"], 0, s) == 0
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert bool((b[:band] == 0x5C).all()) and bool((b[-band:] == 0x5C).all()), f"{k}: a sentinel band was written"
-    return {k: bufs[k][band:band + sizes[k]].clone() for k in ("y", "keep", "grads", "dx")}
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", SHAPES + [(5, 16, 1, 3, 300)], ids=lambda s: "x".join(map(str, s)))
 def test_equal_bits_from_run_to_run_and_rows_are_independent(shape):
     net = make_net(shape, "Mish")
     x, dy = rows(shape, extra=17).to(DEV), torch.randn(shape[4], shape[3], generator=torch.Generator().manual_seed(2)).to(DEV)
     M = shape[4]
-    a, b = _raw_run(net, x[:M].contiguous(), dy), _raw_run(net, x[:M].contiguous(), dy)
+    a, b = raw_fwd_bwd(net, x[:M].contiguous(), dy), raw_fwd_bwd(net, x[:M].contiguous(), dy)
     for k in a:
         assert torch.equal(a[k], b[k]), k
     with torch.no_grad():
@@ -219,16 +180,25 @@ def test_equal_bits_from_run_to_run_and_rows_are_independent(shape):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(5, 16, 1, 3, 300), (11, 48, 2, 7, 300)], ids=lambda s: "x".join(map(str, s)))
+def test_row_ranges_add_up(shape):
+    """M = 300 is two row ranges of the weight-gradient slabs with a partial last 16-row step (support.check_row_ranges_add_up);
+    the second shape has hidden-to-hidden layers, whose input is the activation applied on load."""
+    net = make_net(shape, "Mish")
+    check_row_ranges_add_up(net, rows(shape).to(DEV), torch.randn(shape[4], shape[3], generator=torch.Generator().manual_seed(2)).to(DEV))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("shape", [SHAPES[1], SHAPES[3]], ids=lambda s: "x".join(map(str, s)))
 def test_results_do_not_depend_on_what_the_buffers_held(shape):
     """0xFF (NaN) and 0x7B (~1.3e36) fills of the output, keep, workspace and gradient buffers change no result bit; the
-    sentinel bands around every buffer stay as they were (checked inside _raw_run); BESO_MLP_ACCUMULATE adds to what the
+    sentinel bands around every buffer stay as they were (checked inside raw_fwd_bwd); BESO_MLP_ACCUMULATE adds to what the
     gradient buffer holds, in one addition per element."""
     net = make_net(shape, "sigmoid")
     x, dy = rows(shape).to(DEV), torch.randn(shape[4], shape[3], generator=torch.Generator().manual_seed(2)).to(DEV)
-    base = _raw_run(net, x, dy)
+    base = raw_fwd_bwd(net, x, dy)
     for fill in (0xFF, 0x7B):
-        got = _raw_run(net, x, dy, fill=fill)
+        got = raw_fwd_bwd(net, x, dy, fill=fill)
         for k in base:
             assert torch.equal(base[k], got[k]), (k, hex(fill))
     grads = base["grads"].view(torch.float32)

@@ -10,8 +10,6 @@ import copy
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,7 +18,7 @@ import torch.nn as nn
 
 from beso_amd import _lib
 from beso_amd.networks.mlps.mlps import ResidualMLPNetwork
-from support import TRAIN_BOUNDS, bits, grad_errors, lib  # noqa: F401
+from support import TRAIN_BOUNDS, bits, check_row_ranges_add_up, check_side_library, grad_errors, lib, raw_fwd_bwd  # noqa: F401
 
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,23 +98,12 @@ def compare_grads(tag, got, t32, ref):
 def test_library_exports_what_its_header_declares(lib):
     """libbeso_resmlp.so: the three symbols of include/beso_resmlp.h, no more; the binding table has the header's argument
     counts; the struct has the header's fields; the matrix-pipe hazard check of DESIGN.md 4.1c passes on it."""
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "beso_resmlp.h")).read(), flags=re.S)
-    protos = {fn: args.split(",") for fn, args in re.findall(r"\b(beso_resmlp_[a-z_]+)\s*\(([^()]*)\)\s*;", text)}
-    assert sorted(protos) == sorted(_lib.RESMLP_SIGNATURES) and len(protos) == 3
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.RESMLP_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("beso_")) == sorted(protos)
-    res = _lib.load_resmlp()
-    for fn, args in protos.items():
-        assert len(_lib.RESMLP_SIGNATURES[fn][1]) == len(args) == len(getattr(res, fn).argtypes), fn
+    text = check_side_library("beso_resmlp.h", "beso_resmlp_", _lib.RESMLP_SIGNATURES, _lib.RESMLP_LIB_PATH, _lib.load_resmlp, 3,
+                              min_kernels=4)
     body = re.search(r"typedef\s+struct\s+beso_resmlp_dims\s*\{(.*?)\}", text, flags=re.S).group(1)
     assert [f.split()[1] for f in body.split(";") if f.strip()] == [n for n, _ in _lib.ResMlpDims._fields_]
     consts = dict(re.findall(r"\b(BESO_RESMLP_[A-Z_]+)\s*=\s*(\d+)", text))
     assert {"none": int(consts["BESO_RESMLP_NORM_NONE"]), "LayerNorm": int(consts["BESO_RESMLP_NORM_LAYER"])} == _lib.RESMLP_NORMS
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import check_mfma_chains as chk
-    if os.path.exists(os.path.join(chk.LLVM, "llvm-objdump")):
-        bad, n_fn, n_mfma = chk.check_library(_lib.RESMLP_LIB_PATH)
-        assert n_fn >= 4 and n_mfma > 20 and not bad, (n_fn, n_mfma, bad[:5])
 
 
 def test_argument_errors_do_not_touch_the_device(lib):
@@ -294,30 +281,6 @@ def test_shared_normalizer_gradient_is_the_sum_of_both_uses(case):
     compare_grads(f"resmlp shared normalizer {case}", got, t32, ref)
 
 
-def _raw_run(net, x, dy, fill=None):
-    """One beso_resmlp_fwd (with keep) + beso_resmlp_bwd (with dx) through the raw entry points on banded buffers -> the
-    result tensors.  `fill`: the byte every output, keep, workspace and gradient buffer holds on entry."""
-    res = _lib.load_resmlp()
-    M = x.shape[0]
-    dims = net.dims()
-    ptrs, n = net._pointers(None)
-    band = 256
-    sizes = dict(y=4 * M * net.output_dim, keep=4 * net.keep_floats(M), ws=net.workspace_bytes(M),
-                 grads=4 * net.num_param_floats(), dx=4 * M * net.input_dim)
-    bufs = {k: torch.full((v + 2 * band,), 0xA5 if fill is None else fill, dtype=torch.uint8, device=DEV) for k, v in sizes.items()}
-    for b in bufs.values():
-        b[:band] = 0x5C
-        b[-band:] = 0x5C
-    p = {k: b.data_ptr() + band for k, b in bufs.items()}
-    s = torch.cuda.current_stream().cuda_stream
-    assert res.beso_resmlp_fwd(ptrs, n, C.byref(dims), x.data_ptr(), M, p["y"], p["keep"], s) == 0
-    assert res.beso_resmlp_bwd(ptrs, n, C.byref(dims), p["keep"], dy.data_ptr(), M, p["dx"], p["grads"], p["ws"], sizes["ws"], 0, s) == 0
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        assert bool((b[:band] == 0x5C).all()) and bool((b[-band:] == 0x5C).all()), f"{k}: a sentinel band was written"
-    return {k: bufs[k][band:band + sizes[k]].clone() for k in ("y", "keep", "grads", "dx")}
-
-
 BIT_CASES = [(11, 48, 4, 7, 33, "Mish", True), (5, 16, 2, 3, 300, "ReLU", False), (60, 512, 8, 30, 65, "sigmoid", True)]
 
 
@@ -327,10 +290,10 @@ def test_equal_bits_from_run_to_run_and_rows_are_independent(case):
     net = make_net(case)
     M = case[4]
     x, dy = rows(case, extra=17).to(DEV), cotangent(case, extra=17).to(DEV)
-    a, b = _raw_run(net, x[:M].contiguous(), dy[:M].contiguous()), _raw_run(net, x[:M].contiguous(), dy[:M].contiguous())
+    a, b = raw_fwd_bwd(net, x[:M].contiguous(), dy[:M].contiguous()), raw_fwd_bwd(net, x[:M].contiguous(), dy[:M].contiguous())
     for k in a:
         assert torch.equal(a[k], b[k]), k
-    longer = _raw_run(net, x, dy)                                     # M + 17 rows: y and dx of the first M are the same bits
+    longer = raw_fwd_bwd(net, x, dy)                                  # M + 17 rows: y and dx of the first M are the same bits
     for k, width in (("y", net.output_dim), ("dx", net.input_dim)):
         assert torch.equal(longer[k][:4 * M * width], a[k]), k
     with torch.no_grad():
@@ -339,16 +302,24 @@ def test_equal_bits_from_run_to_run_and_rows_are_independent(case):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("case", [(5, 16, 2, 3, 300, "ReLU", False), (11, 48, 4, 7, 300, "Mish", True)], ids=case_id)
+def test_row_ranges_add_up(case):
+    """M = 300 is two row ranges of the weight-gradient slabs, the second one full chunk of 32 rows and a partial one
+    (support.check_row_ranges_add_up); the second case has the bias-only gamma / beta layers."""
+    check_row_ranges_add_up(make_net(case), rows(case).to(DEV), cotangent(case).to(DEV))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("case", BIT_CASES[:2], ids=case_id)
 def test_results_do_not_depend_on_what_the_buffers_held(case):
     """0x00, 0xFF (NaN) and 0x7B (~1.3e36) fills of the output, keep, workspace and gradient buffers change no result bit; the
-    sentinel bands around every buffer stay as they were (checked inside _raw_run); BESO_MLP_ACCUMULATE adds to what the
+    sentinel bands around every buffer stay as they were (checked inside raw_fwd_bwd); BESO_MLP_ACCUMULATE adds to what the
     gradient buffer holds, in one addition per element."""
     net = make_net(case)
     x, dy = rows(case).to(DEV), cotangent(case).to(DEV)
-    base = _raw_run(net, x, dy)
+    base = raw_fwd_bwd(net, x, dy)
     for fill in (0x00, 0xFF, 0x7B):
-        got = _raw_run(net, x, dy, fill=fill)
+        got = raw_fwd_bwd(net, x, dy, fill=fill)
         for k in base:
             assert torch.equal(base[k], got[k]), (k, hex(fill))
     grads = base["grads"].view(torch.float32)

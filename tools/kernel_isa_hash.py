@@ -32,8 +32,9 @@ def main(lib):
             out[cur] = body
         for k in sorted(out):
             # the padding behind a kernel's last instruction (s_nop / s_code_end up to the next symbol or the end of the code
-            # object) is no part of it: a kernel that stops being the last one of its unit would otherwise change its hash
-            while out[k] and out[k][-1] in ("", "s_nop 0", "s_code_end"):
+            # object, which objdump may abbreviate to "...") is no part of it: a kernel that stops being the last one of its unit
+            # would otherwise change its hash
+            while out[k] and out[k][-1] in ("", "s_nop 0", "s_code_end", "..."):
                 out[k].pop()
             if k.startswith("_Z"):
                 h = hashlib.sha1("\n".join(out[k]).encode()).hexdigest()[:12]
