@@ -175,6 +175,18 @@ def count_site_launches(site, fn):
     return profile_site(site, fn)[1]
 
 
+def kernel_names(fn):
+    """Runs fn() under the torch profiler; returns the names of the GPU kernels it launched, the library's own among them (the
+    profiler records every kernel of the process), in the order they started."""
+    from torch.autograd import DeviceType
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    ev = [e for e in prof.events() if e.device_type == DeviceType.CUDA]
+    return [e.name for e in sorted(ev, key=lambda e: e.time_range.start)]
+
+
 class Scale(torch.nn.Module):
     """Stands in for an nn.Dropout: multiplies by preset keep-scales, one tensor per call, in call order."""
 
