@@ -13,6 +13,7 @@ DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
 MLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_mlp.so")      # the MLP encoder (include/beso_mlp.h)
 RESMLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_resmlp.so")   # the residual MLP encoder (include/beso_resmlp.h)
 GUIDE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_guide.so")     # the guide gradient of guided sampling (include/beso_guide.h)
+SELECT_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_select.so")   # best-of-K action selection (include/beso_select.h)
 
 # Every upper-case integer below is BESO_<name> of include/beso_hip.h, and every table one of its enums
 # (tests/test_cabi.py compares the values, and SIGNATURES with the prototypes, against the header's text).
@@ -154,6 +155,17 @@ GUIDE_SIGNATURES = {
 }
 GUIDE_EXPORTS = list(GUIDE_SIGNATURES)
 
+# include/beso_select.h (libbeso_select.so): BESO_SELECT_* by the rollout's names, its limits, and every function it declares,
+# in its order
+SELECT_MODES = {"mean": 0, "kde": 1}
+SELECT_LIMITS = {"max_k": 256, "max_act": 64}        # BESO_SELECT_MAX_K, BESO_SELECT_MAX_ACT
+SELECT_SIGNATURES = {
+    "beso_candidates_last_error": (cstr, []),
+    "beso_candidates_expand": (i32, [vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "beso_candidates_select": (i32, [vp, vp, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp]),
+}
+SELECT_EXPORTS = list(SELECT_SIGNATURES)
+
 
 class BesoHipError(RuntimeError):
     pass
@@ -200,7 +212,8 @@ def load() -> C.CDLL:
 # the libraries beside the product library, built with it: name -> (path, signatures, header, what has no fallback)
 _SIDE = {"mlp": (MLP_LIB_PATH, MLP_SIGNATURES, "beso_mlp.h", "the encoder"),
          "resmlp": (RESMLP_LIB_PATH, RESMLP_SIGNATURES, "beso_resmlp.h", "the encoder"),
-         "guide": (GUIDE_LIB_PATH, GUIDE_SIGNATURES, "beso_guide.h", "the fused guide gradient")}
+         "guide": (GUIDE_LIB_PATH, GUIDE_SIGNATURES, "beso_guide.h", "the fused guide gradient"),
+         "select": (SELECT_LIB_PATH, SELECT_SIGNATURES, "beso_select.h", "best-of-K action selection")}
 _side = {}
 
 
@@ -232,6 +245,21 @@ def load_guide() -> C.CDLL:
     """The guide-gradient library of classifier-guided sampling (include/beso_guide.h).  A guide it does not serve takes
     autograd over the guide's own HIP kernels, decided once per guide."""
     return _load_side("guide")
+
+
+def load_select() -> C.CDLL:
+    """The best-of-K action selection library of the rollout (include/beso_select.h)."""
+    return _load_side("select")
+
+
+def check_select(status: int, what: str) -> None:
+    """check() for libbeso_select.so: its own message (beso_candidates_last_error) names what was refused."""
+    if status == OK:
+        return
+    text = f"beso_select: {what}: {load_select().beso_candidates_last_error().decode()} (status {status})"
+    if status in (ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
+        raise ValueError(text)
+    raise BesoHipError(text)
 
 
 _dev = None

@@ -779,6 +779,68 @@ class BesoAgent(BaseAgent):
         self.action_context.append(x_0)
         return model_pred
 
+    @torch.no_grad()
+    def predict_best_of(self, batch: dict, k: int, select=None, bandwidth=None, new_sampler_type=None, new_sampling_steps=None,
+                        noise_scheduler=None, extra_args=None, noise=None) -> torch.Tensor:
+        """``predict`` with ``k`` action candidates per environment, reduced to ONE action each: ``select='mean'`` acts on the
+        candidates' sample mean, ``'kde'`` on the candidate of the highest diagonal Gaussian kernel density among its
+        siblings (``bandwidth=None``: Scott's rule); the default is 'kde' with ``use_kde``, else 'mean'.  The window
+        bookkeeping on ``obs_context`` / ``action_context``, the EMA scope, the schedule, the clip and the inverse scale are
+        ``predict``'s; the k draws go through one sampler call on ``len(state) * k`` rows between the two launches of
+        beso_amd/candidates.py (include/beso_select.h), and the selected, clipped action is what ``action_context`` remembers.
+        ``noise`` [B, k, act] is the x_T draw of the newest action (None: ``torch.randn``); with k = 1 the call returns
+        ``predict``'s bits for the same draw, in ``predict``'s shape (a one-slot window gives [B, 1, act], as there).
+        ``last_best_of`` holds the call's ``candidates`` [B, k, act], ``scores`` and ``index``.  ``predict(get_mean=...)`` is
+        the reference's call and stays what it is: it draws the extra rows and reduces nothing.  Needs the GPU."""
+        from ... import candidates as best_of
+        k, select, bandwidth = best_of.check_arguments(k, select, bandwidth, bool(self.use_kde))
+        noise_scheduler = self.noise_scheduler if noise_scheduler is None else noise_scheduler
+        state, goal, _ = self.process_batch(batch, predict=True)
+        state, goal = self._encode_eval(state, goal)
+        act_dim = self.scaler.y_bounds.shape[1]
+        noise = best_of.check_noise(noise, len(state), k, act_dim, self.device)
+        windowed = state.dim() == 2 and self.window_size > 1
+        if windowed:
+            self.obs_context.append(state)
+            input_state = torch.stack(tuple(self.obs_context), dim=1)
+        else:
+            input_state = state
+        if goal.dim() == 2 and self.window_size > 1:
+            goal = goal.unsqueeze(0)                                       # 'b d -> 1 b d'
+        sampler_type = self.sampler_type if new_sampler_type is None else new_sampler_type
+        n_steps = self.num_sampling_steps if new_sampling_steps is None else new_sampling_steps
+        B = len(input_state)
+        state3 = (input_state if input_state.dim() == 3 else input_state.unsqueeze(1)).to(torch.float32).contiguous()
+        t = state3.shape[1]
+        with self._ema_scope():
+            if self.model.training:
+                self.model.eval()
+            sigmas = self.get_noise_schedule(n_steps, noise_scheduler)
+            # the window as predict lays it out: the remembered actions, then the newest slot (expand fills it per candidate)
+            x = torch.zeros((B, 1, act_dim), dtype=torch.float32, device=state3.device)
+            if windowed and len(self.action_context) > 0:
+                x = torch.cat((*self.action_context, x), dim=1)
+            if x.shape[1] != t:
+                raise ValueError(f"predict_best_of: {x.shape[1]} action slots beside {t} observation slots")
+            lengths = torch.full((B,), t, dtype=torch.int32, device=state3.device)
+            state_k, x_k = best_of.expand(state3, x.contiguous(), lengths, noise, self.sigma_max)
+            if input_state.dim() == 2:
+                state_k = state_k[:, 0].contiguous()
+            if goal.dim() == 3 and goal.shape[0] == B and B > 1:
+                goal = torch.repeat_interleave(goal, k, dim=0)
+            x0_k = self.sample_loop(sigmas, x_k, state_k, goal, sampler_type, extra_args)
+            x0_k = x0_k.reshape(B * k, t, act_dim).to(torch.float32).contiguous()
+            x_0, index, scores = best_of.select(x0_k, lengths, k, select, bandwidth)
+            if t > 1:
+                x_0 = x_0[:, -1, :]
+            x_0 = self.scaler.clip_action(x_0)
+        model_pred = self.scaler.inverse_scale_output(x_0)
+        if model_pred.dim() == 2:
+            x_0 = x_0.unsqueeze(1)
+        self.action_context.append(x_0)
+        self.last_best_of = {"candidates": x0_k.view(B, k, t, act_dim)[:, :, -1], "scores": scores, "index": index}
+        return model_pred
+
     def vector_rollout(self, n_envs: int):
         """A ``VectorRollout`` over ``n_envs`` environments that finish and reset independently: one sampler call per
         environment step for all of them, the windows kept per environment on the device (beso_amd/rollout.py).  ``predict``

@@ -17,6 +17,21 @@ from . import _lib
 from .runtime import stream_ptr
 
 
+class _Last(dict):
+    """``VectorRollout.last``.  ``candidates`` [N, K, act] -- the newest-slot actions of the N K sampled rows ``x0_k`` -- is an
+    audit value no step needs: it is gathered on first access (small launches the step does not pay), from the live
+    ``lengths``, so ask for it before the next step."""
+
+    def __missing__(self, key):
+        if key != "candidates" or "x0_k" not in self:
+            raise KeyError(key)
+        x0_k, lengths = self["x0_k"], self["lengths"]
+        N = lengths.numel()
+        rows = torch.arange(N, device=x0_k.device)
+        self[key] = x0_k.view(N, -1, *x0_k.shape[1:])[rows, :, (lengths - 1).long()]
+        return self[key]
+
+
 class VectorRollout:
     """``agent.vector_rollout(n_envs)``.  ``step(obs)`` returns the actions ``[N, act]`` of one environment step; ``reset`` /
     ``set_goal`` act on all environments or on the listed ones.  The rollout reads the agent's scaler, sampler settings and
@@ -24,7 +39,7 @@ class VectorRollout:
 
     ``lengths`` [N] int32, ``obs_ctx`` [N, W, obs] and ``act_ctx`` [N, W, act] are the device-resident state (slots at or
     behind an environment's length are dead); ``last`` holds the latest step's ``state`` / ``x`` (the sampler's inputs),
-    ``x0`` (its result) and ``lengths`` (the live tensor), for audit."""
+    ``x0`` (its result; with ``candidates`` the selected windows) and ``lengths`` (the live tensor), for audit."""
 
     def __init__(self, agent, n_envs: int):
         n_envs = int(n_envs)
@@ -132,10 +147,30 @@ class VectorRollout:
 
     # ------------------------------------------------------------------ one environment step
     @torch.no_grad()
-    def step(self, obs, new_sampler_type=None, new_sampling_steps=None, noise_scheduler=None, noise=None) -> torch.Tensor:
+    def step(self, obs, new_sampler_type=None, new_sampling_steps=None, noise_scheduler=None, noise=None, candidates=None,
+             select=None, bandwidth=None) -> torch.Tensor:
         """Raw observations ``[N, obs]`` (device or host) -> actions ``[N, act]``.  ``noise`` ``[N, 1, act]`` is the x_T draw
-        of the newest action; None draws ``torch.randn((N, 1, act), device=...)``, the draw ``predict`` makes."""
+        of the newest action; None draws ``torch.randn((N, 1, act), device=...)``, the draw ``predict`` makes.
+
+        ``candidates=K`` draws K actions per environment in ONE sampler call on N K rows and acts on one action per
+        environment (beso_amd/candidates.py, include/beso_select.h): ``select='mean'`` on the candidates' sample mean,
+        ``'kde'`` on the candidate of the highest kernel density among its siblings (``bandwidth=None``: Scott's rule); the
+        default is 'kde' with ``agent.use_kde``, else 'mean'.  ``noise`` is then ``[N, K, act]``.  Two launches more than a
+        plain step.  Clip, un-scale and the remembered context take the selected action only; ``last`` gains ``candidates``
+        ``[N, K, act]`` (the newest-slot actions before the clip), ``scores`` ``[N, K]`` and ``index`` ``[N]``, and the
+        sampler call's ``state_k`` / ``x_k`` / ``x0_k`` on N K rows."""
         agent, dev, N, W = self.agent, self.device, self.n_envs, self.window
+        K = None
+        if candidates is not None:
+            from . import candidates as best_of
+            K, select, bandwidth = best_of.check_arguments(candidates, select, bandwidth, bool(getattr(agent, "use_kde", False)))
+            max_act = _lib.SELECT_LIMITS["max_act"]
+            if self.act_dim > max_act:
+                raise ValueError(f"candidates: act_dim {self.act_dim} exceeds the {max_act} components the selection takes")
+            noise_k = best_of.check_noise(noise, N, K, self.act_dim, dev)
+            noise = noise_k[:, :1].contiguous()                  # begin's newest slot: expand overwrites it in every row
+        elif select is not None or bandwidth is not None:
+            raise ValueError("select and bandwidth belong to candidates=K")
         xs, ys = self._scaler_plan()
         obs = torch.as_tensor(obs)
         if xs is None:
@@ -143,7 +178,9 @@ class VectorRollout:
         obs = obs.to(device=dev, dtype=torch.float32).contiguous()
         if tuple(obs.shape) != (N, self.obs_dim):
             raise ValueError(f"obs must be [{N}, {self.obs_dim}], got {tuple(obs.shape)}")
-        if noise is None:
+        if K is not None:
+            pass                                                 # (checked with the other best-of-K arguments)
+        elif noise is None:
             noise = torch.randn((N, 1, self.act_dim), device=dev)
         else:
             noise = torch.as_tensor(noise).to(device=dev, dtype=torch.float32).contiguous()
@@ -170,11 +207,21 @@ class VectorRollout:
             if agent.model.training:
                 agent.model.eval()
             sigmas = agent.get_noise_schedule(n_steps, noise_scheduler)
-            x0 = agent.sample_loop(sigmas, x, state, self.goal, sampler_type)
+            if K is None:
+                x0 = agent.sample_loop(sigmas, x, state, self.goal, sampler_type)
+            else:
+                state_k, x_k = best_of.expand(state, x, self.lengths, noise_k, agent.sigma_max)
+                goal_k = None if self.goal is None else torch.repeat_interleave(self.goal, K, dim=0)
+                x0 = agent.sample_loop(sigmas, x_k, state_k, goal_k, sampler_type)
         if x0.dtype != torch.float32 or not x0.is_contiguous():
             x0 = x0.to(torch.float32).contiguous()
-        if tuple(x0.shape) != (N, W, self.act_dim):
-            raise RuntimeError(f"the sampler returned {tuple(x0.shape)}, expected {(N, W, self.act_dim)}")
+        if tuple(x0.shape) != (N * (K or 1), W, self.act_dim):
+            raise RuntimeError(f"the sampler returned {tuple(x0.shape)}, expected {(N * (K or 1), W, self.act_dim)}")
+        picked = {}
+        if K is not None:
+            x0_k = x0
+            x0, index, scores = best_of.select(x0_k, self.lengths, K, select, bandwidth)
+            picked = {"scores": scores, "index": index, "state_k": state_k, "x_k": x_k, "x0_k": x0_k}
         if ys is not None:
             pred = torch.empty((N, self.act_dim), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
@@ -188,5 +235,5 @@ class VectorRollout:
             clipped = agent.scaler.clip_action(x0[self._rows, slot])
             self.act_ctx[self._rows, slot] = clipped
             pred = agent.scaler.inverse_scale_output(clipped)
-        self.last = {"state": state, "x": x, "lengths": self.lengths, "x0": x0}
+        self.last = _Last({"state": state, "x": x, "lengths": self.lengths, "x0": x0, **picked})
         return pred
