@@ -14,6 +14,7 @@ MLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_mlp.so")      # the MLP encod
 RESMLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_resmlp.so")   # the residual MLP encoder (include/beso_resmlp.h)
 GUIDE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_guide.so")     # the guide gradient of guided sampling (include/beso_guide.h)
 SELECT_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_select.so")   # best-of-K action selection (include/beso_select.h)
+SCALE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_scale.so")     # MinMaxScaler's scalings (include/beso_scale.h)
 
 # Every upper-case integer below is BESO_<name> of include/beso_hip.h, and every table one of its enums
 # (tests/test_cabi.py compares the values, and SIGNATURES with the prototypes, against the header's text).
@@ -166,6 +167,17 @@ SELECT_SIGNATURES = {
 }
 SELECT_EXPORTS = list(SELECT_SIGNATURES)
 
+# include/beso_scale.h (libbeso_scale.so): BESO_SCALE_* by what MinMaxScaler.scale_many calls them, its limit, and every function
+# it declares, in its order
+SCALE_KINDS = {"zscore": 0, "minmax": 1}
+SCALE_LIMITS = {"max_items": 4}                      # BESO_SCALE_MAX_ITEMS
+SCALE_SIGNATURES = {
+    "beso_scale_last_error": (cstr, []),
+    "beso_scale_rows_mixed": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "beso_rollout_end_minmax": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+}
+SCALE_EXPORTS = list(SCALE_SIGNATURES)
+
 
 class BesoHipError(RuntimeError):
     pass
@@ -213,7 +225,8 @@ def load() -> C.CDLL:
 _SIDE = {"mlp": (MLP_LIB_PATH, MLP_SIGNATURES, "beso_mlp.h", "the encoder"),
          "resmlp": (RESMLP_LIB_PATH, RESMLP_SIGNATURES, "beso_resmlp.h", "the encoder"),
          "guide": (GUIDE_LIB_PATH, GUIDE_SIGNATURES, "beso_guide.h", "the fused guide gradient"),
-         "select": (SELECT_LIB_PATH, SELECT_SIGNATURES, "beso_select.h", "best-of-K action selection")}
+         "select": (SELECT_LIB_PATH, SELECT_SIGNATURES, "beso_select.h", "best-of-K action selection"),
+         "scale": (SCALE_LIB_PATH, SCALE_SIGNATURES, "beso_scale.h", "MinMaxScaler's one-launch scalings")}
 _side = {}
 
 
@@ -257,6 +270,21 @@ def check_select(status: int, what: str) -> None:
     if status == OK:
         return
     text = f"beso_select: {what}: {load_select().beso_candidates_last_error().decode()} (status {status})"
+    if status in (ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
+        raise ValueError(text)
+    raise BesoHipError(text)
+
+
+def load_scale() -> C.CDLL:
+    """The library of MinMaxScaler's scalings (include/beso_scale.h)."""
+    return _load_side("scale")
+
+
+def check_scale(status: int, what: str) -> None:
+    """check() for libbeso_scale.so: its own message (beso_scale_last_error) names what was refused."""
+    if status == OK:
+        return
+    text = f"beso_scale: {what}: {load_scale().beso_scale_last_error().decode()} (status {status})"
     if status in (ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
         raise ValueError(text)
     raise BesoHipError(text)

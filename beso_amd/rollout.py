@@ -114,12 +114,15 @@ class VectorRollout:
 
     # ------------------------------------------------------------------ what of the scaler the two launches can take over
     def _scaler_plan(self):
-        """(x statistics for beso_rollout_begin or None, (lo, hi, den_y, mean_y) for beso_rollout_end or None), rebuilt when
-        the scaler, one of its tensors or a tensor's version changes.  The launches take fp32 statistics and float64 bounds
-        of the package's Scaler; anything else is served by the scaler's own methods."""
-        from .networks.scaler.scaler_class import Scaler
+        """(x statistics for beso_rollout_begin or None, the tail's arguments or None), rebuilt when the scaler, one of its
+        tensors or a tensor's version changes.  The tail is (lo, hi, den_y, mean_y) for beso_rollout_end (the package's Scaler)
+        or ("minmax", lo, hi, new_lo, span, range, lo_y) for beso_rollout_end_minmax (its MinMaxScaler, whose scale_input is
+        Scaler's arithmetic: the same begin launch serves it).  The launches take fp32 statistics and float64 bounds of the
+        package's two scalers; anything else is served by the scaler's own methods."""
+        from .networks.scaler.scaler_class import MinMaxScaler, Scaler
         sc = self.agent.scaler
-        parts = tuple(getattr(sc, k, None) for k in ("x_mean", "x_std", "y_mean", "y_std", "y_bounds_tensor"))
+        parts = tuple(getattr(sc, k, None) for k in ("x_mean", "x_std", "y_mean", "y_std", "y_bounds_tensor", "y_min", "y_max",
+                                                     "new_min_y", "new_max_y"))
         key = (sc, getattr(sc, "scale_data", None)) + tuple((p, getattr(p, "_version", None)) for p in parts)
         old = self._plan_key
         if old is not None and len(old) == len(key) and all(
@@ -130,15 +133,21 @@ class VectorRollout:
                             and v.dim() == 1 and v.numel() == n and v.is_contiguous())
         ours = isinstance(sc, Scaler) and all(getattr(type(sc), m) is getattr(Scaler, m)
                                               for m in ("scale_input", "clip_action", "inverse_scale_output", "_den"))
+        minmax = isinstance(sc, MinMaxScaler) and all(getattr(type(sc), m) is getattr(MinMaxScaler, m) for m in (
+            "scale_input", "clip_action", "inverse_scale_output", "_den", "_y_range", "_y_span"))
         xs = ys = None
-        if ours and sc.scale_data and not (self.obs_dim == 7 and len(sc.x_mean) == 30):
-            mean, den = sc.x_mean, sc._den("x")
+        if (ours or minmax) and sc.scale_data and not (self.obs_dim == 7 and len(sc.x_mean) == 30):
+            mean, den = sc.x_mean, sc._den("x") if ours else sc._den()
             if f32(mean, self.obs_dim) and f32(den, self.obs_dim):
                 xs = (mean, den)
         b = parts[4]
-        if ours and isinstance(b, torch.Tensor) and b.device == dev and b.dtype == torch.float64 and tuple(b.shape) == (2, self.act_dim):
+        if (ours or minmax) and isinstance(b, torch.Tensor) and b.device == dev and b.dtype == torch.float64 and tuple(b.shape) == (2, self.act_dim):
             lo, hi = (b[0] * 1.1).contiguous(), (b[1] * 1.1).contiguous()        # clip_action's bounds, in float64
-            if not sc.scale_data:
+            if minmax:
+                stats = (sc.new_min_y, sc._y_span(), sc._y_range(), sc.y_min) if sc.scale_data else (None,) * 4
+                if not sc.scale_data or all(f32(s, self.act_dim) for s in stats):
+                    ys = ("minmax", lo, hi) + stats
+            elif not sc.scale_data:
                 ys = (lo, hi, None, None)
             elif f32(sc.y_mean, self.act_dim) and f32(sc._den("y"), self.act_dim):
                 ys = (lo, hi, sc._den("y"), sc.y_mean)
@@ -222,7 +231,13 @@ class VectorRollout:
             x0_k = x0
             x0, index, scores = best_of.select(x0_k, self.lengths, K, select, bandwidth)
             picked = {"scores": scores, "index": index, "state_k": state_k, "x_k": x_k, "x0_k": x0_k}
-        if ys is not None:
+        if ys is not None and isinstance(ys[0], str):              # MinMaxScaler's tail (include/beso_scale.h)
+            pred = torch.empty((N, self.act_dim), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check_scale(_lib.load_scale().beso_rollout_end_minmax(
+                    x0.data_ptr(), self.lengths.data_ptr(), *[ptr(v) for v in ys[1:]], self.act_ctx.data_ptr(), pred.data_ptr(),
+                    N, W, self.act_dim, stream_ptr(dev)), "rollout_end_minmax")
+        elif ys is not None:
             pred = torch.empty((N, self.act_dim), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
                 stream = stream_ptr(dev)

@@ -12,7 +12,12 @@ Both are divided by `steps`; the record holds the median over the repetitions an
 host, as a simulator hands them over; windows are full and no environment resets inside the timed steps, except in the
 `reset_every_step` figure, where one environment is reset in front of every step (two small fill launches more).
 ``predict`` runs one set of environments per agent, so N sequential calls are timed as `steps` calls of one B = 1 agent and
-multiplied by N (`predict_n_ms`).  One JSON line per N is appended to --out."""
+multiplied by N (`predict_n_ms`).  One JSON line per N is appended to --out.
+
+    python tools/bench_rollout.py --scaler minmax [--envs 1,16,100] [--steps 100] [--reps 5] [--out profiles/minmax_scaler_bench.jsonl]
+
+measures something else: block-push shape, ``MinMaxScaler`` on the rollout's two launches against the same scaler on the torch-op
+fallback of the step (minmax_ab below)."""
 import argparse
 import json
 import os
@@ -52,15 +57,82 @@ def stats(v):
     return {"median": round(float(np.median(v)), 4), "min": round(float(np.min(v)), 4), "max": round(float(np.max(v)), 4)}
 
 
+def minmax_ab(a):
+    """--scaler minmax: the block-push shape with the block-push workspace's MinMaxScaler.  Per N, `reps` x `steps` environment
+    steps of each of two rollouts, alternating: `launches` -- the scaler on beso_rollout_begin + beso_rollout_end_minmax -- and
+    `fallback` -- the same scaler as a trivial subclass that overrides one method, which VectorRollout._scaler_plan declines, so
+    that the step scales, gathers, clamps, index-writes and un-scales with torch ops.  Same weights, observations and draws."""
+    from beso_amd.networks.scaler.scaler_class import MinMaxScaler
+
+    class Declined(MinMaxScaler):
+        def clip_action(self, y):
+            return super().clip_action(y)
+
+    cfg = O.SHAPES["block_push"]
+    w = O.make_weights(cfg, seed=0, std=0.02)
+    rng = np.random.default_rng(0)
+    x_data = rng.standard_normal((256, cfg.obs_dim)).astype(np.float32)
+    y_data = rng.standard_normal((256, cfg.act_dim)).astype(np.float32)
+    agents = {}
+    for name, cls in (("launches", MinMaxScaler), ("fallback", Declined)):
+        agent = build_agent(cfg, lambda: build_model(cfg, w, "bf16", DEV), device=DEV, sampler="ddim")
+        agent.get_scaler(cls(x_data, y_data, True, DEV))
+        agent.set_bounds(agent.scaler)
+        agents[name] = agent
+    box = {"device": torch.cuda.get_device_name(0), "hip": torch.version.hip, "torch": torch.__version__}
+    goal = torch.randn(cfg.goal_seq_len, cfg.obs_dim)
+    warm = max(20, 3 * cfg.obs_seq_len)
+    for N in [int(v) for v in a.envs.split(",")]:
+        obs = [torch.randn(N, cfg.obs_dim) for _ in range(a.steps)]
+        noise = torch.randn(N, 1, cfg.act_dim, device=DEV)
+        rolls = {name: agent.vector_rollout(N) for name, agent in agents.items()}
+        plans = {name: tuple(p is not None for p in r._scaler_plan()) for name, r in rolls.items()}
+        assert plans == {"launches": (True, True), "fallback": (False, False)}, plans
+        for r in rolls.values():
+            r.set_goal(goal)
+        last = {}
+        for i in range(warm):
+            for name, r in rolls.items():
+                last[name] = r.step(obs[i % a.steps], noise=noise)
+        agree = bool(torch.equal(last["launches"], last["fallback"]))       # (the same bits: tests/test_minmax_scaler_gpu.py)
+        t = {name: [] for name in rolls}
+        for _ in range(a.reps):
+            for name, r in rolls.items():
+                t[name].append(timed(lambda i: r.step(obs[i], noise=noise), a.steps))
+        rec = {"bench": "rollout_minmax_scaler", "config": "block_push", "precision": "bf16", "sampler": "ddim", "sampling_steps": 3,
+               "n_envs": N, "steps_per_rep": a.steps, "reps": a.reps, "paths_agree": agree}
+        for name in rolls:
+            rec[name + "_wall_ms"] = stats([v[0] for v in t[name]])
+            rec[name + "_event_ms"] = stats([v[1] for v in t[name]])
+        rec["fallback_over_launches_wall"] = round(rec["fallback_wall_ms"]["median"] / rec["launches_wall_ms"]["median"], 3)
+        rec["saved_wall_ms"] = round(rec["fallback_wall_ms"]["median"] - rec["launches_wall_ms"]["median"], 4)
+        rec.update(box)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", default="1,16,100,256")
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rollout_bench.jsonl"))
+    ap.add_argument("--envs", default=None)
+    ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--reps", type=int, default=None)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--scaler", choices=("zscore", "minmax"), default="zscore",
+                    help="minmax: block-push shape, MinMaxScaler on the two launches against its torch-op fallback (5 x 100 steps, "
+                         "N = 1, 16, 100, profiles/minmax_scaler_bench.jsonl)")
     a = ap.parse_args()
+    mm = a.scaler == "minmax"
+    a.envs = a.envs or ("1,16,100" if mm else "1,16,100,256")
+    a.steps = a.steps or (100 if mm else 200)
+    a.reps = a.reps or (5 if mm else 7)
+    a.out = a.out or os.path.join(ROOT, "profiles", "minmax_scaler_bench.jsonl" if mm else "rollout_bench.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("bench_rollout.py measures on the GPU; none found")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if mm:
+        return minmax_ab(a)
     cfg = O.SHAPES["kitchen"]
     w = O.make_weights(cfg, seed=0, std=0.02)
     agent = build_agent(cfg, lambda: build_model(cfg, w, "bf16", DEV), device=DEV, sampler="ddim")

@@ -9,9 +9,11 @@ launch and two output tensors per step; the agent itself does not use them);
 `--encoder IN,HIDDEN,LAYERS[,KIND]` times the step with and without a trainable MLPEncoder (IN raw features -> HIDDEN x LAYERS ->
 obs_dim) in front of the denoiser: the agents in ONE process, alternating in rounds of ten steps, median and spread per agent.
 KIND: `mlp` (default: MLPNetwork, ReLU), `res` (ResidualMLPNetwork, Mish, no norm) or `resln` (... with LayerNorm); the flag may
-be given more than once, one agent per encoder.
+be given more than once, one agent per encoder;
+`--scaler minmax` times the step with a MinMaxScaler, its one-launch scale_many against the three per-tensor calls, in ONE process
+(5 x 100 steps per agent, alternating; the record is appended to profiles/minmax_scaler_bench.jsonl).
     python tools/bench_train.py [batch] [kitchen|block_push] [--autograd] [--max-grad-norm X] [--skip-nonfinite] [--deterministic]
-                                [--input-grads] [--encoder IN,HIDDEN,LAYERS[,KIND]]..."""
+                                [--input-grads] [--encoder IN,HIDDEN,LAYERS[,KIND]]... [--scaler minmax]"""
 import json
 import os
 import sys
@@ -83,7 +85,64 @@ def encoder_ab(cfg, model, dev, B, encoders, det, clip, rounds=7, steps=10):
     print(json.dumps(out))
 
 
+def minmax_ab(cfg, name, model, dev, B, det, clip, rounds=5, steps=100):
+    """--scaler minmax: train_step with the block-push workspace's MinMaxScaler, its scale_many (one beso_scale_rows_mixed launch for
+    state, goal and action) against the same scaler with scale_many restated as the three per-tensor calls, alternating in one
+    process: per agent the median milliseconds per step over `rounds` rounds of `steps` steps.  Appends the record to
+    profiles/minmax_scaler_bench.jsonl."""
+    from beso_amd.networks.scaler.scaler_class import MinMaxScaler
+
+    class PerTensor(MinMaxScaler):
+        def scale_many(self, items):
+            return [self.scale_input(x) if which == "x" else self.scale_output(x) for x, which in items]
+
+    rng = np.random.default_rng(0)
+    x_data = rng.standard_normal((256, cfg.obs_dim)).astype(np.float32)
+    y_data = rng.standard_normal((256, cfg.act_dim)).astype(np.float32)
+    torch.manual_seed(1234)
+    batch = {"observation": torch.randn(B, cfg.obs_seq_len, cfg.obs_dim, device=dev),
+             "action": torch.randn(B, cfg.obs_seq_len, cfg.act_dim, device=dev),
+             "goal_observation": torch.randn(B, cfg.goal_seq_len, cfg.obs_dim, device=dev)}
+    agents = {}
+    for key, cls in (("scale_many", MinMaxScaler), ("per_tensor", PerTensor)):
+        agent = build_agent(cfg, model, device=dev, deterministic_training=det, **clip)
+        agent.get_scaler(cls(x_data, y_data, True, dev))
+        agent.set_bounds(agent.scaler)
+        agents[key] = agent
+        for _ in range(5):
+            agent.train_step(batch)
+    torch.cuda.synchronize()
+    times = {key: [] for key in agents}
+    for _ in range(rounds):
+        for key, agent in agents.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                loss = agent.train_step(batch)
+            torch.cuda.synchronize()
+            times[key].append((time.perf_counter() - t0) / steps)
+    out = {"bench": "train_minmax_scaler", "config": name, "precision": "bf16", "batch": B, "rounds": rounds, "steps_per_round": steps,
+           "deterministic": det, "loss": loss, "device": torch.cuda.get_device_name(0), "hip": torch.version.hip,
+           "torch": torch.__version__}
+    for key, ts in times.items():
+        out[key + "_ms"] = {"median": round(1e3 * float(np.median(ts)), 4), "min": round(1e3 * min(ts), 4), "max": round(1e3 * max(ts), 4)}
+    out["saved_ms"] = round(out["per_tensor_ms"]["median"] - out["scale_many_ms"]["median"], 4)
+    line = json.dumps(out)
+    print(line)
+    path = os.path.join(ROOT, "profiles", "minmax_scaler_bench.jsonl")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "a") as f:
+        f.write(line + "\n")
+
+
 def main():
+    scaler_kind = "zscore"
+    if "--scaler" in sys.argv:                  # minmax: MinMaxScaler.scale_many against its three per-tensor calls (minmax_ab)
+        i = sys.argv.index("--scaler")
+        scaler_kind = sys.argv[i + 1]
+        if scaler_kind not in ("zscore", "minmax"):
+            raise SystemExit(f"--scaler zscore|minmax: got {scaler_kind!r}")
+        del sys.argv[i:i + 2]
     if "--per-op-forward" in sys.argv:          # A/B: every layer of the training forward through the per-op kernels
         sys.argv.remove("--per-op-forward")
         from beso_amd import _lib
@@ -164,6 +223,8 @@ def main():
 
     if encoders:
         return encoder_ab(cfg, model, dev, B, encoders, det, clip)
+    if scaler_kind == "minmax":
+        return minmax_ab(cfg, name, model, dev, B, det, clip)
     agent = build_agent(cfg, model, device=dev, deterministic_training=det, **clip)
     rng = np.random.default_rng(0)
     agent.get_scaler(Scaler(rng.standard_normal((256, cfg.obs_dim)).astype(np.float32),
