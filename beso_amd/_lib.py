@@ -15,6 +15,7 @@ RESMLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_resmlp.so")   # the residu
 GUIDE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_guide.so")     # the guide gradient of guided sampling (include/beso_guide.h)
 SELECT_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_select.so")   # best-of-K action selection (include/beso_select.h)
 SCALE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_scale.so")     # MinMaxScaler's scalings (include/beso_scale.h)
+NOISE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_noise.so")     # the rollout's keyed noise (include/beso_noise.h)
 
 # Every upper-case integer below is BESO_<name> of include/beso_hip.h, and every table one of its enums
 # (tests/test_cabi.py compares the values, and SIGNATURES with the prototypes, against the header's text).
@@ -178,6 +179,18 @@ SCALE_SIGNATURES = {
 }
 SCALE_EXPORTS = list(SCALE_SIGNATURES)
 
+# include/beso_noise.h (libbeso_noise.so): BESO_NOISE_* by what the rollout draws, its limit, and every function it declares, in
+# its order
+NOISE_PURPOSES = {"x_t": 0, "candidate": 1, "step": 2}
+NOISE_LIMITS = {"max_purpose": 15}                   # BESO_NOISE_MAX_PURPOSE
+NOISE_SIGNATURES = {
+    "beso_noise_last_error": (cstr, []),
+    "beso_noise_words": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "beso_noise_normal": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
+    "beso_noise_rollout": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+}
+NOISE_EXPORTS = list(NOISE_SIGNATURES)
+
 
 class BesoHipError(RuntimeError):
     pass
@@ -226,7 +239,8 @@ _SIDE = {"mlp": (MLP_LIB_PATH, MLP_SIGNATURES, "beso_mlp.h", "the encoder"),
          "resmlp": (RESMLP_LIB_PATH, RESMLP_SIGNATURES, "beso_resmlp.h", "the encoder"),
          "guide": (GUIDE_LIB_PATH, GUIDE_SIGNATURES, "beso_guide.h", "the fused guide gradient"),
          "select": (SELECT_LIB_PATH, SELECT_SIGNATURES, "beso_select.h", "best-of-K action selection"),
-         "scale": (SCALE_LIB_PATH, SCALE_SIGNATURES, "beso_scale.h", "MinMaxScaler's one-launch scalings")}
+         "scale": (SCALE_LIB_PATH, SCALE_SIGNATURES, "beso_scale.h", "MinMaxScaler's one-launch scalings"),
+         "noise": (NOISE_LIB_PATH, NOISE_SIGNATURES, "beso_noise.h", "the rollout's keyed noise")}
 _side = {}
 
 
@@ -285,6 +299,21 @@ def check_scale(status: int, what: str) -> None:
     if status == OK:
         return
     text = f"beso_scale: {what}: {load_scale().beso_scale_last_error().decode()} (status {status})"
+    if status in (ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
+        raise ValueError(text)
+    raise BesoHipError(text)
+
+
+def load_noise() -> C.CDLL:
+    """The library of the rollout's keyed noise (include/beso_noise.h)."""
+    return _load_side("noise")
+
+
+def check_noise_status(status: int, what: str) -> None:
+    """check() for libbeso_noise.so: its own message (beso_noise_last_error) names what was refused."""
+    if status == OK:
+        return
+    text = f"beso_noise: {what}: {load_noise().beso_noise_last_error().decode()} (status {status})"
     if status in (ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
         raise ValueError(text)
     raise BesoHipError(text)

@@ -156,10 +156,59 @@ def _fused_call(model, state, action, goal, sigmas, scaler, extra_args, callback
     return den, lam, sig
 
 
-def predraw_noise(sampler, sig, action, eta, noise_sampler=None):
+class keyed_step_noise:
+    """``with keyed_step_noise(noise):`` -- the sampler calls inside draw nothing from the global generator: an ancestral sampler
+    on its one-enqueue path takes `noise` [n_steps, *action.shape] (the rollout's keyed draws, beso_amd/noise.py; None: the
+    step drew none) as its step noise, and a call that would draw inside a Python loop raises ValueError naming the sampler.
+    One context per thread of control; only the branches below consult it, and without one everything draws as it always has."""
+    active = None
+
+    def __init__(self, noise):
+        self.noise = noise
+
+    def __enter__(self):
+        if keyed_step_noise.active is not None:
+            raise RuntimeError("keyed_step_noise contexts do not nest")
+        keyed_step_noise.active = self
+        return self
+
+    def __exit__(self, *exc):
+        keyed_step_noise.active = None
+        return False
+
+
+def _keyed_noise(sampler):
+    """The active keyed context's step noise for the one-enqueue path of `sampler`, None without a context."""
+    ctx = keyed_step_noise.active
+    if ctx is None:
+        return None
+    if ctx.noise is None:
+        raise ValueError(f"keyed noise: sampler {sampler!r} needs step noise and the keyed step drew none")
+    return ctx.noise
+
+
+_OFF_FUSED = 'is off its one-enqueue path (a scaler, callback, extra_args, eta < 0, or inputs the fused loop does not run)'
+
+
+def _refuse_keyed(sampler, why):
+    """ValueError inside a keyed context for a call that is about to draw from the global generator; nothing otherwise."""
+    if keyed_step_noise.active is not None:
+        raise ValueError(f"keyed noise: sampler {sampler!r} {why}: it would draw from the global generator inside a Python "
+                         "loop, and a seeded rollout makes no unkeyed draws")
+
+
+def predraw_noise(sampler, sig, action, eta, noise_sampler=None, noise=None):
     """The draws of an ancestral sampler's loop made up front for its one enqueue, in the loop's order and number:
     [len(sig) - 1, *action.shape], zero where a step draws nothing.  dpmpp_2s_ancestral draws on every step (through
-    ``noise_sampler``), euler_ancestral and dpm_2_ancestral on the steps whose sigma_down != 0 (``get_ancestral_step``)."""
+    ``noise_sampler``), euler_ancestral and dpm_2_ancestral on the steps whose sigma_down != 0 (``get_ancestral_step``).
+    ``noise``: draws made elsewhere, of that shape; they are returned as they are and nothing is drawn here (the entries of
+    steps that draw nothing are not read by the enqueue: include/beso_hip.h)."""
+    if noise is not None:
+        want = (len(sig) - 1,) + tuple(action.shape)
+        if tuple(noise.shape) != want or noise.dtype != torch.float32 or noise.device != action.device:
+            raise ValueError(f"predraw_noise: noise must be float32 {want} on {action.device}, got {noise.dtype} "
+                             f"{tuple(noise.shape)} on {noise.device}")
+        return noise
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
     noise = torch.zeros((len(sig) - 1,) + tuple(action.shape), dtype=torch.float32, device=action.device)
     for i in range(len(sig) - 1):
@@ -187,6 +236,8 @@ def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('euler', state, action, goal, sig, cond_lambda=lam)
+    if s_churn:
+        _refuse_keyed('euler', 'with s_churn > 0')
     sig = _host_sigmas(sigmas)
     n = len(sig) - 1
     for i in range(n):
@@ -214,7 +265,8 @@ def sample_euler_ancestral(model, state, action, goal, sigmas, scaler=None, extr
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('euler_ancestral', state, action, goal, sig, cond_lambda=lam, eta=eta,
-                                 noise=predraw_noise('euler_ancestral', sig, action, eta))
+                                 noise=predraw_noise('euler_ancestral', sig, action, eta, noise=_keyed_noise('euler_ancestral')))
+    _refuse_keyed('euler_ancestral', _OFF_FUSED)
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)
@@ -240,6 +292,8 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('heun', state, action, goal, sig, cond_lambda=lam)
+    if s_churn:
+        _refuse_keyed('heun', 'with s_churn > 0')
     sig = _host_sigmas(sigmas)
     n = len(sig) - 1
     for i in range(n):
@@ -279,6 +333,8 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('dpm_2', state, action, goal, sig, cond_lambda=lam)
+    if s_churn:
+        _refuse_keyed('dpm_2', 'with s_churn > 0')
     sig = _host_sigmas(sigmas)
     n = len(sig) - 1
     for i in range(n):
@@ -313,7 +369,8 @@ def sample_dpm_2_ancestral(model, state, action, goal, sigmas, scaler=None, extr
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('dpm_2_ancestral', state, action, goal, sig, cond_lambda=lam, eta=eta,
-                                 noise=predraw_noise('dpm_2_ancestral', sig, action, eta))
+                                 noise=predraw_noise('dpm_2_ancestral', sig, action, eta, noise=_keyed_noise('dpm_2_ancestral')))
+    _refuse_keyed('dpm_2_ancestral', _OFF_FUSED)
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)
@@ -473,7 +530,8 @@ def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, e
     if tgt is not None:
         den, lam, sig = tgt
         return den.fused_sampler('dpmpp_2s_ancestral', state, action, goal, sig, cond_lambda=lam, eta=eta, s_noise=s_noise,
-                                 noise=predraw_noise('dpmpp_2s_ancestral', sig, action, eta, noise_sampler))
+                                 noise=predraw_noise('dpmpp_2s_ancestral', sig, action, eta, noise_sampler, noise=_keyed_noise('dpmpp_2s_ancestral')))
+    _refuse_keyed('dpmpp_2s_ancestral', _OFF_FUSED)
     sig = _host_sigmas(sigmas)
     for i in range(len(sig) - 1):
         denoised = model(state, action, goal, _sig_vec(action, sig[i]), **extra_args)
@@ -704,6 +762,8 @@ def sample_dpm_fast(model, state, action, goal, sigma_min, sigma_max, n, scaler=
     log sigma from sigma_max to sigma_min (:675-699)."""
     if sigma_min <= 0 or sigma_max <= 0:
         raise ValueError('sigma_min and sigma_max must not be 0')
+    if eta:
+        _refuse_keyed('dpm_fast', 'with eta > 0')
     return _solver(model, extra_args, callback).dpm_solver_fast(
         state, action, goal, _neg_log(sigma_max), _neg_log(sigma_min), n, eta, s_noise, noise_sampler)
 
@@ -715,6 +775,8 @@ def sample_dpm_adaptive(model, state, action, goal, sigma_min, sigma_max, extra_
     """DPM-Solver-12 / -23 with adaptive step size (:855-892)."""
     if sigma_min <= 0 or sigma_max <= 0:
         raise ValueError('sigma_min and sigma_max must not be 0')
+    if eta:
+        _refuse_keyed('dpm_adaptive', 'with eta > 0')
     action, info = _solver(model, extra_args, callback).dpm_solver_adaptive(
         state, action, goal, _neg_log(sigma_max), _neg_log(sigma_min), order, rtol, atol, h_init, pcoeff, icoeff,
         dcoeff, accept_safety, eta, s_noise)
@@ -728,6 +790,7 @@ def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callba
     ancestral sigma_down of its sub-interval followed by the matching amount of Brownian noise.  This is what
     ``sampler_type='dpmpp_2m_sde'`` runs (beso_agent.py:452-453)."""
     extra_args = {} if extra_args is None else extra_args
+    _refuse_keyed('dpmpp_2m_sde', '(sample_dpmpp_sde) draws Brownian-path noise per step')
     sig = _host_sigmas(sigmas)
     if noise_sampler is None:
         noise_sampler = BrownianTreeNoiseSampler(action, sig[sig > 0].min(), sig.max())

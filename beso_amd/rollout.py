@@ -39,7 +39,14 @@ class VectorRollout:
 
     ``lengths`` [N] int32, ``obs_ctx`` [N, W, obs] and ``act_ctx`` [N, W, act] are the device-resident state (slots at or
     behind an environment's length are dead); ``last`` holds the latest step's ``state`` / ``x`` (the sampler's inputs),
-    ``x0`` (its result; with ``candidates`` the selected windows) and ``lengths`` (the live tensor), for audit."""
+    ``x0`` (its result; with ``candidates`` the selected windows) and ``lengths`` (the live tensor), for audit.
+
+    ``seed(seeds)`` turns keyed noise on (beso_amd/noise.py, include/beso_noise.h): every draw of an environment -- its x_T, its
+    K candidates, an ancestral sampler's step noise -- then depends on the environment's seed, episode and step alone, not on
+    ``n_envs``, its row or the global generator, and comes from ONE launch in front of the step's.  ``last`` gains
+    ``noise_episode`` / ``noise_step`` [N] int32, the counters the step used (read them before the step after next)."""
+
+    _keyed = None        # the KeyedNoise of a seeded rollout (seed / unseed)
 
     def __init__(self, agent, n_envs: int):
         n_envs = int(n_envs)
@@ -86,6 +93,59 @@ class VectorRollout:
         else:
             self._reset.index_fill_(0, self._ids(env_ids), 1)
         self._reset_pending = True
+        if self._keyed is not None:
+            self._keyed.mark_reset(None if env_ids is None else self._ids(env_ids))
+
+    # ------------------------------------------------------------------ keyed noise
+    def seed(self, seeds, env_ids=None) -> None:
+        """Turn keyed noise on.  ``seeds``: an int (environment i takes ``seeds + i`` modulo 2^64) or one int in [0, 2^64) per
+        listed environment (default: all).  The listed environments start at noise episode 0, and their step counter restarts
+        with their next step; every ``reset`` of an environment then begins its next episode.  Their windows are not touched.
+        The first call seeds all environments; later calls may re-seed some.  Equal seeds give equal draws: distinct
+        environments want distinct seeds."""
+        from .noise import KeyedNoise, check_seeds
+        if env_ids is None:
+            self._keyed = KeyedNoise(check_seeds(seeds, list(range(self.n_envs))), self.device)
+            return
+        ids = self._ids(env_ids).tolist()
+        if self._keyed is None:
+            raise ValueError("seed(): the first call seeds every environment (env_ids=None); later calls may re-seed some")
+        self._keyed.set_seeds(seeds, ids)
+
+    def unseed(self) -> None:
+        """Back to the global generator: ``noise=None`` draws ``torch.randn`` again, as a rollout that was never seeded."""
+        self._keyed = None
+
+    # what a seeded step can serve: the samplers whose one-enqueue path takes its step noise as an argument, and the ones that
+    # draw nothing that enters their result (agent.sample_loop's names)
+    _KEYED_STEP_SAMPLERS = ("euler_ancestral", "ancestral", "dpmpp_2s_ancestral")
+    _DETERMINISTIC_SAMPLERS = ("ddim", "euler", "heun", "dpm", "dpmpp_2m", "dpmpp_2s", "lms", "dpm_fast", "dpm_adaptive")
+
+    def _keyed_step_slabs(self, sampler_type, sigmas, rows: int) -> int:
+        """How many slabs of step noise the sampler call of a seeded step takes (0: a deterministic sampler), or ValueError for a
+        sampler that would draw from the global generator inside a Python loop.  Decided before anything is enqueued."""
+        from .agents.diffusion_agents.k_diffusion import gc_sampling as ks
+        from .agents.diffusion_agents.k_diffusion.classifier_free_sampler import ClassifierGuidedSampleModel
+        if sampler_type in self._DETERMINISTIC_SAMPLERS:
+            return 0
+        if sampler_type not in self._KEYED_STEP_SAMPLERS:
+            raise ValueError(f"seeded rollout: sampler {sampler_type!r} draws its noise from the global generator inside a Python "
+                             f"loop, which keyed noise does not serve (no silent unkeyed draws); keyed step noise serves "
+                             f"{self._KEYED_STEP_SAMPLERS}, and {self._DETERMINISTIC_SAMPLERS} need none")
+        agent, dev = self.agent, self.device
+        m = agent.model
+        if m.training:
+            m.eval()
+        if isinstance(m, ClassifierGuidedSampleModel) and m.cond_lambda == 0:
+            m = m.model                                          # (as sample_loop)
+        probe = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731  (shapes only: nothing reads them)
+        goal = None if self.goal is None else probe(rows, *self.goal.shape[1:])
+        if ks._fused_call(m, probe(rows, self.window, self.obs_dim), probe(rows, self.window, self.act_dim), goal, sigmas,
+                          None, {}, None) is None:
+            raise ValueError(f"seeded rollout: sampler {sampler_type!r} is forced off its one-launch path here (the model, its "
+                             "precision or shape, or the schedule), where it would draw its step noise from the global "
+                             "generator inside a Python loop (no silent unkeyed draws)")
+        return len(sigmas) - 1
 
     @torch.no_grad()
     def set_goal(self, goal, env_ids=None) -> None:
@@ -167,8 +227,13 @@ class VectorRollout:
         default is 'kde' with ``agent.use_kde``, else 'mean'.  ``noise`` is then ``[N, K, act]``.  Two launches more than a
         plain step.  Clip, un-scale and the remembered context take the selected action only; ``last`` gains ``candidates``
         ``[N, K, act]`` (the newest-slot actions before the clip), ``scores`` ``[N, K]`` and ``index`` ``[N]``, and the
-        sampler call's ``state_k`` / ``x_k`` / ``x0_k`` on N K rows."""
+        sampler call's ``state_k`` / ``x_k`` / ``x0_k`` on N K rows.
+
+        Seeded (``seed``): ``noise=None`` is the keyed draw -- x_T, the K candidates and the step noise of 'euler_ancestral',
+        'ancestral' and 'dpmpp_2s_ancestral' on their one-launch path, all from one launch -- and a sampler that would draw
+        from the global generator inside a Python loop is a ValueError.  An explicit ``noise`` still wins."""
         agent, dev, N, W = self.agent, self.device, self.n_envs, self.window
+        keyed, given = self._keyed, noise is not None
         K = None
         if candidates is not None:
             from . import candidates as best_of
@@ -176,8 +241,9 @@ class VectorRollout:
             max_act = _lib.SELECT_LIMITS["max_act"]
             if self.act_dim > max_act:
                 raise ValueError(f"candidates: act_dim {self.act_dim} exceeds the {max_act} components the selection takes")
-            noise_k = best_of.check_noise(noise, N, K, self.act_dim, dev)
-            noise = noise_k[:, :1].contiguous()                  # begin's newest slot: expand overwrites it in every row
+            if keyed is None or given:
+                noise_k = best_of.check_noise(noise, N, K, self.act_dim, dev)
+                noise = noise_k[:, :1].contiguous()              # begin's newest slot: expand overwrites it in every row
         elif select is not None or bandwidth is not None:
             raise ValueError("select and bandwidth belong to candidates=K")
         xs, ys = self._scaler_plan()
@@ -189,6 +255,8 @@ class VectorRollout:
             raise ValueError(f"obs must be [{N}, {self.obs_dim}], got {tuple(obs.shape)}")
         if K is not None:
             pass                                                 # (checked with the other best-of-K arguments)
+        elif keyed is not None and not given:
+            pass                                                 # (the keyed launch below draws it)
         elif noise is None:
             noise = torch.randn((N, 1, self.act_dim), device=dev)
         else:
@@ -200,6 +268,17 @@ class VectorRollout:
         sampler_type = agent.sampler_type if new_sampler_type is None else new_sampler_type
         n_steps = agent.num_sampling_steps if new_sampling_steps is None else new_sampling_steps
         noise_scheduler = agent.noise_scheduler if noise_scheduler is None else noise_scheduler
+        step_noise = sigmas = None
+        if keyed is not None:
+            # ONE launch: the counters advance and every draw of this step is made (include/beso_noise.h)
+            sigmas = agent.get_noise_schedule(n_steps, noise_scheduler)
+            rows = K or 1
+            slabs = self._keyed_step_slabs(sampler_type, sigmas, N * rows)
+            x_t, cand, step_noise = keyed.rollout(self.act_dim, 0 if K is None or given else K, slabs, rows * W * self.act_dim)
+            if not given:
+                noise, noise_k = x_t, cand
+            if step_noise is not None:
+                step_noise = step_noise.view(slabs, N * rows, W, self.act_dim)
         state = torch.empty((N, W, self.obs_dim), dtype=torch.float32, device=dev)
         x = torch.empty((N, W, self.act_dim), dtype=torch.float32, device=dev)
         ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
@@ -215,13 +294,18 @@ class VectorRollout:
         with agent._ema_scope():
             if agent.model.training:
                 agent.model.eval()
-            sigmas = agent.get_noise_schedule(n_steps, noise_scheduler)
-            if K is None:
-                x0 = agent.sample_loop(sigmas, x, state, self.goal, sampler_type)
-            else:
+            if sigmas is None:
+                sigmas = agent.get_noise_schedule(n_steps, noise_scheduler)
+            if K is not None:
                 state_k, x_k = best_of.expand(state, x, self.lengths, noise_k, agent.sigma_max)
                 goal_k = None if self.goal is None else torch.repeat_interleave(self.goal, K, dim=0)
-                x0 = agent.sample_loop(sigmas, x_k, state_k, goal_k, sampler_type)
+            args = (sigmas, x, state, self.goal, sampler_type) if K is None else (sigmas, x_k, state_k, goal_k, sampler_type)
+            if keyed is None:
+                x0 = agent.sample_loop(*args)
+            else:
+                from .agents.diffusion_agents.k_diffusion.gc_sampling import keyed_step_noise
+                with keyed_step_noise(step_noise):
+                    x0 = agent.sample_loop(*args)
         if x0.dtype != torch.float32 or not x0.is_contiguous():
             x0 = x0.to(torch.float32).contiguous()
         if tuple(x0.shape) != (N * (K or 1), W, self.act_dim):
@@ -250,5 +334,9 @@ class VectorRollout:
             clipped = agent.scaler.clip_action(x0[self._rows, slot])
             self.act_ctx[self._rows, slot] = clipped
             pred = agent.scaler.inverse_scale_output(clipped)
+        if keyed is not None:
+            picked.update(noise_episode=keyed.episodes, noise_step=keyed.steps)
+            if step_noise is not None:
+                picked["step_noise"] = step_noise
         self.last = _Last({"state": state, "x": x, "lengths": self.lengths, "x0": x0, **picked})
         return pred

@@ -17,7 +17,13 @@ multiplied by N (`predict_n_ms`).  One JSON line per N is appended to --out.
     python tools/bench_rollout.py --scaler minmax [--envs 1,16,100] [--steps 100] [--reps 5] [--out profiles/minmax_scaler_bench.jsonl]
 
 measures something else: block-push shape, ``MinMaxScaler`` on the rollout's two launches against the same scaler on the torch-op
-fallback of the step (minmax_ab below)."""
+fallback of the step (minmax_ab below).
+
+    python tools/bench_rollout.py --seeded [--envs 1,16,100] [--steps 100] [--reps 5] [--out profiles/keyed_noise_bench.jsonl]
+
+measures the seeded step (``VectorRollout.seed``: every draw from one beso_noise_rollout launch) against the unseeded step of
+the same process, for DDIM-3 and euler_ancestral at the agent's step count, with the GPU launches per step of both (seeded_ab
+below)."""
 import argparse
 import json
 import os
@@ -113,6 +119,65 @@ def minmax_ab(a):
             f.write(line + "\n")
 
 
+def launches_per_step(fn, steps=8):
+    """GPU kernels and copies per call of fn(i), counted by the torch profiler over `steps` calls."""
+    from torch.autograd import DeviceType
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        for i in range(steps):
+            fn(i)
+        torch.cuda.synchronize()
+    return round(sum(1 for e in prof.events() if e.device_type == DeviceType.CUDA) / steps, 2)
+
+
+def seeded_ab(a):
+    """--seeded: kitchen bf16, EMA image.  Per N and per sampler (DDIM-3; euler_ancestral with the agent's step count), `reps` x
+    `steps` environment steps of two rollouts of one agent, alternating: `unseeded` draws from the global generator (torch.randn
+    for x_T; for euler_ancestral also predraw_noise's zeros + per step one randn and one slice copy), `seeded` takes every draw
+    from the one beso_noise_rollout launch.  Same weights, observations (from the host) and windows; no resets inside the timed
+    steps.  The record states both step times as measured and the launches per step of both."""
+    cfg = O.SHAPES["kitchen"]
+    w = O.make_weights(cfg, seed=0, std=0.02)
+    agent = build_agent(cfg, lambda: build_model(cfg, w, "bf16", DEV), device=DEV, sampler="ddim")
+    rng = np.random.default_rng(0)
+    agent.get_scaler(Scaler(rng.standard_normal((256, cfg.obs_dim)).astype(np.float32),
+                            rng.standard_normal((256, cfg.act_dim)).astype(np.float32), True, DEV))
+    agent.set_bounds(agent.scaler)
+    box = {"device": torch.cuda.get_device_name(0), "hip": torch.version.hip, "torch": torch.__version__}
+    goal = torch.randn(cfg.goal_seq_len, cfg.obs_dim)
+    warm = max(20, 3 * cfg.obs_seq_len)
+    for N in [int(v) for v in a.envs.split(",")]:
+        obs = [torch.randn(N, cfg.obs_dim) for _ in range(a.steps)]
+        rolls = {"unseeded": agent.vector_rollout(N), "seeded": agent.vector_rollout(N)}
+        rolls["seeded"].seed(1000)
+        for r in rolls.values():
+            r.set_goal(goal)
+        for sampler, n_steps in (("ddim", 3), ("euler_ancestral", int(agent.num_sampling_steps))):
+            step = {name: (lambda i, r=r: r.step(obs[i % a.steps], new_sampler_type=sampler, new_sampling_steps=n_steps))
+                    for name, r in rolls.items()}
+            for i in range(warm):
+                for fn in step.values():
+                    fn(i)
+            t = {name: [] for name in rolls}
+            for _ in range(a.reps):
+                for name, fn in step.items():
+                    t[name].append(timed(fn, a.steps))
+            rec = {"bench": "rollout_keyed_noise", "config": "kitchen", "precision": "bf16", "sampler": sampler,
+                   "sampling_steps": n_steps, "n_envs": N, "steps_per_rep": a.steps, "reps": a.reps}
+            for name, fn in step.items():
+                rec[name + "_wall_ms"] = stats([v[0] for v in t[name]])
+                rec[name + "_event_ms"] = stats([v[1] for v in t[name]])
+                rec[name + "_launches_per_step"] = launches_per_step(fn)
+            rec["seeded_over_unseeded_wall"] = round(rec["seeded_wall_ms"]["median"] / rec["unseeded_wall_ms"]["median"], 3)
+            rec["seeded_minus_unseeded_wall_ms"] = round(rec["seeded_wall_ms"]["median"] - rec["unseeded_wall_ms"]["median"], 4)
+            rec.update(box)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", default=None)
@@ -122,15 +187,22 @@ def main():
     ap.add_argument("--scaler", choices=("zscore", "minmax"), default="zscore",
                     help="minmax: block-push shape, MinMaxScaler on the two launches against its torch-op fallback (5 x 100 steps, "
                          "N = 1, 16, 100, profiles/minmax_scaler_bench.jsonl)")
+    ap.add_argument("--seeded", action="store_true",
+                    help="the seeded step (keyed noise, one launch) against the unseeded step: kitchen bf16, DDIM-3 and "
+                         "euler_ancestral, 5 x 100 steps, N = 1, 16, 100, profiles/keyed_noise_bench.jsonl")
     a = ap.parse_args()
     mm = a.scaler == "minmax"
-    a.envs = a.envs or ("1,16,100" if mm else "1,16,100,256")
-    a.steps = a.steps or (100 if mm else 200)
-    a.reps = a.reps or (5 if mm else 7)
-    a.out = a.out or os.path.join(ROOT, "profiles", "minmax_scaler_bench.jsonl" if mm else "rollout_bench.jsonl")
+    short = mm or a.seeded
+    a.envs = a.envs or ("1,16,100" if short else "1,16,100,256")
+    a.steps = a.steps or (100 if short else 200)
+    a.reps = a.reps or (5 if short else 7)
+    a.out = a.out or os.path.join(ROOT, "profiles", "keyed_noise_bench.jsonl" if a.seeded else
+                                  "minmax_scaler_bench.jsonl" if mm else "rollout_bench.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("bench_rollout.py measures on the GPU; none found")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.seeded:
+        return seeded_ab(a)
     if mm:
         return minmax_ab(a)
     cfg = O.SHAPES["kitchen"]
