@@ -3,6 +3,7 @@ if the library is missing or fails to load, importing callers get a RuntimeError
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import threading
 
@@ -234,13 +235,17 @@ def load() -> C.CDLL:
     return _lib
 
 
-# the libraries beside the product library, built with it: name -> (path, signatures, header, what has no fallback)
-_SIDE = {"mlp": (MLP_LIB_PATH, MLP_SIGNATURES, "beso_mlp.h", "the encoder"),
-         "resmlp": (RESMLP_LIB_PATH, RESMLP_SIGNATURES, "beso_resmlp.h", "the encoder"),
-         "guide": (GUIDE_LIB_PATH, GUIDE_SIGNATURES, "beso_guide.h", "the fused guide gradient"),
-         "select": (SELECT_LIB_PATH, SELECT_SIGNATURES, "beso_select.h", "best-of-K action selection"),
-         "scale": (SCALE_LIB_PATH, SCALE_SIGNATURES, "beso_scale.h", "MinMaxScaler's one-launch scalings"),
-         "noise": (NOISE_LIB_PATH, NOISE_SIGNATURES, "beso_noise.h", "the rollout's keyed noise")}
+# the libraries beside the product library, built with it: name -> (path, signatures, header, what has no fallback, the symbol
+# of its own last-error message and the prefix of the exceptions check_side raises with it: None where it keeps no message)
+_SIDE = {"mlp": (MLP_LIB_PATH, MLP_SIGNATURES, "beso_mlp.h", "the encoder", None, None),
+         "resmlp": (RESMLP_LIB_PATH, RESMLP_SIGNATURES, "beso_resmlp.h", "the encoder", None, None),
+         "guide": (GUIDE_LIB_PATH, GUIDE_SIGNATURES, "beso_guide.h", "the fused guide gradient", None, None),
+         "select": (SELECT_LIB_PATH, SELECT_SIGNATURES, "beso_select.h", "best-of-K action selection",
+                    "beso_candidates_last_error", "beso_select"),
+         "scale": (SCALE_LIB_PATH, SCALE_SIGNATURES, "beso_scale.h", "MinMaxScaler's one-launch scalings",
+                   "beso_scale_last_error", "beso_scale"),
+         "noise": (NOISE_LIB_PATH, NOISE_SIGNATURES, "beso_noise.h", "the rollout's keyed noise",
+                   "beso_noise_last_error", "beso_noise")}
 _side = {}
 
 
@@ -250,12 +255,28 @@ def _load_side(name: str) -> C.CDLL:
         with _lock:
             if name not in _side:
                 import torch  # noqa: F401      (the HIP runtime of the process: see load())
-                path, table, header, what = _SIDE[name]
+                path, table, header, what = _SIDE[name][:4]
                 if not os.path.exists(path):
                     raise BesoHipError(f"{path} (include/{header}) not found: build it with `python -m beso_amd.build` (hipcc, "
                                        f"gfx950). beso_amd has no CPU or eager fallback for {what}.")
                 _side[name] = _bind(C.CDLL(path), table, tolerant=False)
     return _side[name]
+
+
+def check_side(name: str, status: int, what: str) -> None:
+    """check() for a library of _SIDE that keeps its own message (select, scale, noise): the message names what was refused."""
+    if status == OK:
+        return
+    last_error, prefix = _SIDE[name][4:]
+    text = f"{prefix}: {what}: {getattr(_load_side(name), last_error)().decode()} (status {status})"
+    if status in (ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
+        raise ValueError(text)
+    raise BesoHipError(text)
+
+
+check_select = functools.partial(check_side, "select")
+check_scale = functools.partial(check_side, "scale")
+check_noise_status = functools.partial(check_side, "noise")
 
 
 def load_mlp() -> C.CDLL:
@@ -279,44 +300,14 @@ def load_select() -> C.CDLL:
     return _load_side("select")
 
 
-def check_select(status: int, what: str) -> None:
-    """check() for libbeso_select.so: its own message (beso_candidates_last_error) names what was refused."""
-    if status == OK:
-        return
-    text = f"beso_select: {what}: {load_select().beso_candidates_last_error().decode()} (status {status})"
-    if status in (ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
-        raise ValueError(text)
-    raise BesoHipError(text)
-
-
 def load_scale() -> C.CDLL:
     """The library of MinMaxScaler's scalings (include/beso_scale.h)."""
     return _load_side("scale")
 
 
-def check_scale(status: int, what: str) -> None:
-    """check() for libbeso_scale.so: its own message (beso_scale_last_error) names what was refused."""
-    if status == OK:
-        return
-    text = f"beso_scale: {what}: {load_scale().beso_scale_last_error().decode()} (status {status})"
-    if status in (ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
-        raise ValueError(text)
-    raise BesoHipError(text)
-
-
 def load_noise() -> C.CDLL:
     """The library of the rollout's keyed noise (include/beso_noise.h)."""
     return _load_side("noise")
-
-
-def check_noise_status(status: int, what: str) -> None:
-    """check() for libbeso_noise.so: its own message (beso_noise_last_error) names what was refused."""
-    if status == OK:
-        return
-    text = f"beso_noise: {what}: {load_noise().beso_noise_last_error().decode()} (status {status})"
-    if status in (ERR_BAD_SHAPE, ERR_BAD_ARG, ERR_UNSUPPORTED):
-        raise ValueError(text)
-    raise BesoHipError(text)
 
 
 _dev = None
@@ -347,3 +338,17 @@ def check(status: int, what: str = "") -> None:
     if status == ERR_HIP:
         text += ": " + load().beso_last_error().decode()
     raise BesoHipError(text)
+
+
+def launch(name: str, entry: str, dev, *args) -> None:
+    """Enqueue `entry` of the product library (`name` "hip") or of the library `name` of _SIDE on the current stream of `dev`,
+    which is appended to `args`, and raise on a non-zero status with that library's checker ("beso_rollout_end" is reported as
+    "rollout_end").  The entry point is looked up on the library object at every call, so that a test which replaces it there
+    sees the call."""
+    import torch
+    from .runtime import stream_ptr
+    side = name != "hip"
+    lib = _load_side(name) if side else load()
+    with torch.cuda.device(dev):
+        status = getattr(lib, entry)(*args, stream_ptr(dev))
+    (functools.partial(check_side, name) if side else check)(status, entry[len("beso_"):])

@@ -8,7 +8,6 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .runtime import stream_ptr
 
 SELECT_MODES = tuple(_lib.SELECT_MODES)
 
@@ -61,10 +60,8 @@ def expand(state: torch.Tensor, x: torch.Tensor, lengths: torch.Tensor, noise: t
     dev = state.device
     state_k = torch.empty((N * K, W, obs), dtype=torch.float32, device=dev)
     x_k = torch.empty((N * K, W, act), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check_select(_lib.load_select().beso_candidates_expand(
-            state.data_ptr(), x.data_ptr(), lengths.contiguous().data_ptr(), noise.data_ptr(), float(sigma_max), N, W, obs, act, K,
-            state_k.data_ptr(), x_k.data_ptr(), stream_ptr(dev)), "candidates_expand")
+    _lib.launch("select", "beso_candidates_expand", dev, state.data_ptr(), x.data_ptr(), lengths.contiguous().data_ptr(),
+                noise.data_ptr(), float(sigma_max), N, W, obs, act, K, state_k.data_ptr(), x_k.data_ptr())
     return state_k, x_k
 
 
@@ -82,8 +79,6 @@ def select(x0_k: torch.Tensor, lengths: torch.Tensor, k: int, mode: str, bandwid
     x0 = torch.empty((N, W, act), dtype=torch.float32, device=dev)
     index = torch.empty(N, dtype=torch.int32, device=dev)
     scores = torch.empty((N, k), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check_select(_lib.load_select().beso_candidates_select(
-            x0_k.data_ptr(), lengths.contiguous().data_ptr(), _lib.SELECT_MODES[mode], float(bandwidth), N, W, act, k,
-            x0.data_ptr(), index.data_ptr(), scores.data_ptr(), stream_ptr(dev)), "candidates_select")
+    _lib.launch("select", "beso_candidates_select", dev, x0_k.data_ptr(), lengths.contiguous().data_ptr(), _lib.SELECT_MODES[mode],
+                float(bandwidth), N, W, act, k, x0.data_ptr(), index.data_ptr(), scores.data_ptr())
     return x0, index, scores

@@ -2,10 +2,13 @@
 clips to (reference: beso/networks/scaler/scaler_class.py:11-166), and MinMaxScaler, the block-push workspace's scaler
 (:169-338): observations z-scored, actions mapped onto [-1, 1].  Elementwise host-side torch;
 the workspace normally builds the reference's own Scaler -- any object with this surface works."""
+import ctypes as C
+
 import numpy as np
 import torch
 
 _GOAL_4_OF_16 = [0, 1, 3, 4]        # the block positions a 4-wide block-push goal holds, among the 16 observation features
+_MAX_ITEMS = 4                      # tensors per scale_many launch: beso_scale_rows' limit and BESO_SCALE_MAX_ITEMS
 
 
 def _scale_block_push_goal(sc, x):
@@ -28,17 +31,60 @@ def _cached(sc, slot: str, sources, make):
     return hit[1]
 
 
+def _data_rows(x_data, y_data):
+    """The data both constructors fit on, as numpy arrays: tensors converted, [episodes, steps, features] flattened to rows."""
+    if isinstance(x_data, torch.Tensor):
+        x_data, y_data = x_data.detach().cpu().numpy(), y_data.detach().cpu().numpy()
+    if x_data.ndim == 3:
+        x_data = x_data.reshape(-1, x_data.shape[-1])
+        y_data = y_data.reshape(-1, y_data.shape[-1])
+    elif x_data.ndim not in (2, 4):
+        raise ValueError('not implemented yet!')
+    return x_data, y_data
+
+
+def _clip_action(sc, y):
+    """clip_action of both scalers: clamp to 1.1 x y_bounds_tensor (scaler_class.py:162-166, :334-338).  The two scaled bound
+    rows are the same tensors every call: computed once per bounds tensor (two elementwise launches less per environment step)."""
+    b = sc.y_bounds_tensor
+    lo, hi = _cached(sc, "_clip_cache", (b,), lambda: (b[0] * 1.1, b[1] * 1.1))
+    return torch.clamp(y, lo, hi).to(sc.device).to(torch.float32)
+
+
+def _scale_many(sc, items, stats_of, available, launch):
+    """scale_many of both scalers: [(tensor, 'x' | 'y'), ...] -> the scaled tensors, as ONE HIP launch where every tensor is a
+    non-empty contiguous fp32 CUDA tensor and every statistic of its kind (``stats_of(which)``) an fp32 row beside it.  Anything
+    else -- CPU tensors, other dtypes, one-hot or 4-of-16 goals, scale_data off, more than _MAX_ITEMS items, or a library that
+    cannot (``available()``, asked last) -- takes the per-tensor methods.  ``launch(dev, src, dst, stat, rows, cols, n)`` enqueues
+    the class's entry point on the host tables of n entries; ``stat(j)`` is the table of every item's statistic j (NULL where an
+    item has fewer)."""
+    plan, ok = [], bool(sc.scale_data) and 0 < len(items) <= _MAX_ITEMS
+    for x, which in items:
+        if not ok:
+            break
+        stats = stats_of(which)
+        ok = (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0
+              and all(isinstance(s, torch.Tensor) and s.device == x.device and s.dtype == torch.float32 and s.dim() == 1
+                      and s.numel() == x.shape[-1] and s.is_contiguous() for s in stats)
+              and not (which == "x" and x.shape[-1] == 7 and len(sc.x_mean) == 30)
+              and not (which == "x" and x.shape[-1] == 4 and len(sc.x_mean) == 16))
+        plan.append((x, stats))
+    if not (ok and available()):
+        return [sc.scale_input(x) if which == "x" else sc.scale_output(x) for x, which in items]
+    n = len(plan)
+    outs = [torch.empty_like(x) for x, _ in plan]
+    vp = C.c_void_p * n
+    stat = lambda j: vp(*[s[j].data_ptr() if j < len(s) else None for _, s in plan])      # noqa: E731
+    launch(plan[0][0].device, vp(*[x.data_ptr() for x, _ in plan]), vp(*[o.data_ptr() for o in outs]), stat,
+           (C.c_longlong * n)(*[x.numel() // x.shape[-1] for x, _ in plan]), (C.c_int * n)(*[x.shape[-1] for x, _ in plan]), n)
+    return outs
+
+
 class Scaler:
     def __init__(self, x_data, y_data, scale_data: bool, device: str):
         self.scale_data = scale_data
         self.device = device
-        if isinstance(x_data, torch.Tensor):
-            x_data, y_data = x_data.detach().cpu().numpy(), y_data.detach().cpu().numpy()
-        if x_data.ndim == 3:
-            x_data = x_data.reshape(-1, x_data.shape[-1])
-            y_data = y_data.reshape(-1, y_data.shape[-1])
-        elif x_data.ndim not in (2, 4):
-            raise ValueError('not implemented yet!')
+        x_data, y_data = _data_rows(x_data, y_data)
         dev = lambda a: torch.from_numpy(a).to(device)       # noqa: E731
         self.x_mean, self.x_std = dev(x_data.mean(0)), dev(x_data.std(0))
         self.y_mean, self.y_std = dev(y_data.mean(0)), dev(y_data.std(0))
@@ -79,54 +125,21 @@ class Scaler:
     @torch.no_grad()
     def scale_many(self, items):
         """[(tensor, 'x' | 'y'), ...] -> the scaled tensors: scale_input / scale_output of every item (scaler_class.py:95-117) as
-        ONE HIP launch (beso_scale_rows: the same subtraction and correctly rounded division per element) where every tensor
-        is a contiguous fp32 CUDA tensor with fp32 statistics -- a training batch is three tensors, i.e. six elementwise launches
-        of ~6 us each in front of the forward.  Anything else (CPU tensors, other dtypes, one-hot goals, scale_data off, a
-        library without the entry point): the per-tensor methods."""
-        plan, ok = [], self.scale_data and 0 < len(items) <= 4
-        for x, which in items:
-            mean = self.x_mean if which == "x" else self.y_mean
-            den = self._den(which) if self.scale_data else None
-            good = (ok and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0
-                    and isinstance(mean, torch.Tensor) and mean.is_cuda and mean.device == x.device and mean.dtype == torch.float32
-                    and den.dtype == torch.float32 and mean.dim() == 1 and mean.numel() == x.shape[-1] and mean.is_contiguous()
-                    and den.is_contiguous() and not (which == "x" and x.shape[-1] == 7 and len(self.x_mean) == 30)
-                    and not (which == "x" and x.shape[-1] == 4 and len(self.x_mean) == 16))
-            ok = ok and good
-            plan.append((x, mean, den))
-        lib = None
-        if ok:
-            from ... import _lib
-            lib = _lib.load()
-            ok = hasattr(lib, "beso_scale_rows")
-        if not ok:
-            return [self.scale_input(x) if which == "x" else self.scale_output(x) for x, which in items]
-        import ctypes as C
+        ONE HIP launch (beso_scale_rows: the same subtraction and correctly rounded division per element) -- a training batch is
+        three tensors, i.e. six elementwise launches of ~6 us each in front of the forward.  What the launch does not take, a
+        product library without the entry point included: the per-tensor methods (_scale_many)."""
         from ... import _lib
-        from ...runtime import stream_ptr
-        n = len(plan)
-        outs = [torch.empty_like(x) for x, _, _ in plan]
-        vp = C.c_void_p * n
-        src = vp(*[x.data_ptr() for x, _, _ in plan]); dst = vp(*[o.data_ptr() for o in outs])
-        mean = vp(*[m.data_ptr() for _, m, _ in plan]); den = vp(*[d.data_ptr() for _, _, d in plan])
-        rows = (C.c_longlong * n)(*[x.numel() // x.shape[-1] for x, _, _ in plan])
-        cols = (C.c_int * n)(*[x.shape[-1] for x, _, _ in plan])
-        dev = plan[0][0].device
-        with torch.cuda.device(dev):
-            _lib.check(lib.beso_scale_rows(src, dst, mean, den, rows, cols, n, stream_ptr(dev)),
-                       "scale_rows")
-        return outs
+        return _scale_many(
+            self, items, lambda which: (self.x_mean if which == "x" else self.y_mean, self._den(which)),
+            lambda: hasattr(_lib.load(), "beso_scale_rows"),
+            lambda dev, src, dst, stat, rows, cols, n: _lib.launch("hip", "beso_scale_rows", dev, src, dst, stat(0), stat(1), rows,
+                                                                   cols, n))
 
     def _den(self, which: str):
         """std + 1e-12 (scaler_class.py:129,139): the same tensor every call -- computed once per std tensor instead of one
         more elementwise launch per scaled batch (three per training step)."""
         std = self.x_std if which == "x" else self.y_std
-        cache = self.__dict__.setdefault("_den_cache", {})
-        hit = cache.get(which)
-        if hit is None or hit[0] is not std or hit[1] != std._version:
-            hit = (std, std._version, std + 1e-12)
-            cache[which] = hit
-        return hit[2]
+        return _cached(self, "_den_cache_" + which, (std,), lambda: std + 1e-12)
 
     @torch.no_grad()
     def inverse_scale_input(self, x):
@@ -143,14 +156,7 @@ class Scaler:
 
     @torch.no_grad()
     def clip_action(self, y):
-        """Clamp to 1.1 x the data bounds (scaler_class.py:162-166).  The two scaled bound rows are the same tensors every
-        call: computed once per bounds tensor (two elementwise launches less per environment step)."""
-        b = self.y_bounds_tensor
-        hit = self.__dict__.get("_clip_cache")
-        if hit is None or hit[0] is not b or hit[1] != b._version:
-            hit = (b, b._version, b[0] * 1.1, b[1] * 1.1)
-            self._clip_cache = hit
-        return torch.clamp(y, hit[2], hit[3]).to(self.device).to(torch.float32)
+        return _clip_action(self, y)
 
 
 class MinMaxScaler:
@@ -163,13 +169,7 @@ class MinMaxScaler:
     def __init__(self, x_data, y_data, scale_data: bool, device: str):
         self.scale_data = scale_data
         self.device = device
-        if isinstance(x_data, torch.Tensor):
-            x_data, y_data = x_data.detach().cpu().numpy(), y_data.detach().cpu().numpy()
-        if x_data.ndim == 3:
-            x_data = x_data.reshape(-1, x_data.shape[-1])
-            y_data = y_data.reshape(-1, y_data.shape[-1])
-        elif x_data.ndim not in (2, 4):
-            raise ValueError('not implemented yet!')
+        x_data, y_data = _data_rows(x_data, y_data)
         dev = lambda a: torch.from_numpy(a).to(device)       # noqa: E731
         with torch.no_grad():
             self.x_max, self.x_min = dev(x_data.max(0)), dev(x_data.min(0))
@@ -246,51 +246,27 @@ class MinMaxScaler:
 
     @torch.no_grad()
     def clip_action(self, y):
-        """Clamp to 1.1 x y_bounds_tensor (:334-338); the two scaled rows are computed once per bounds tensor."""
-        b = self.y_bounds_tensor
-        lo, hi = _cached(self, "_clip_cache", (b,), lambda: (b[0] * 1.1, b[1] * 1.1))
-        return torch.clamp(y, lo, hi).to(self.device).to(torch.float32)
+        return _clip_action(self, y)
 
     # ------------------------------------------------------------------ a batch's scalings as one launch
     @torch.no_grad()
     def scale_many(self, items):
-        """Scaler.scale_many's contract: [(tensor, 'x' | 'y'), ...] -> the scaled tensors, 'x' items z-scored as scale_input
-        does and 'y' items min-max scaled as scale_output does, as ONE HIP launch (beso_scale_rows_mixed, include/beso_scale.h:
-        the same individually rounded operations in the same order) where every tensor is a contiguous fp32 CUDA tensor with
-        fp32 statistics.  Anything else (CPU tensors, other dtypes, one-hot or 4-of-16 goals, scale_data off, a missing
-        library): the per-tensor methods."""
+        """Scaler.scale_many's contract: 'x' items z-scored as scale_input does and 'y' items min-max scaled as scale_output
+        does, as ONE HIP launch (beso_scale_rows_mixed, include/beso_scale.h: the same individually rounded operations in the
+        same order).  What the launch does not take, a missing libbeso_scale.so included: the per-tensor methods (_scale_many)."""
         from ... import _lib
-        plan, ok = [], bool(self.scale_data) and 0 < len(items) <= _lib.SCALE_LIMITS["max_items"]
-        for x, which in items:
-            if not ok:
-                break
-            stats = (self.x_mean, self._den()) if which == "x" else (self.y_min, self._y_range(), self._y_span(), self.new_min_y)
-            ok = (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0
-                  and all(isinstance(s, torch.Tensor) and s.device == x.device and s.dtype == torch.float32 and s.dim() == 1
-                          and s.numel() == x.shape[-1] and s.is_contiguous() for s in stats)
-                  and not (which == "x" and x.shape[-1] == 7 and len(self.x_mean) == 30)
-                  and not (which == "x" and x.shape[-1] == 4 and len(self.x_mean) == 16))
-            plan.append((x, _lib.SCALE_KINDS["zscore" if which == "x" else "minmax"], stats))
-        lib = None
-        if ok:
+
+        def available():
             try:
-                lib = _lib.load_scale()
+                _lib.load_scale()
             except _lib.BesoHipError:
-                lib = None
-        if lib is None:
-            return [self.scale_input(x) if which == "x" else self.scale_output(x) for x, which in items]
-        import ctypes as C
-        from ...runtime import stream_ptr
-        n = len(plan)
-        outs = [torch.empty_like(x) for x, _, _ in plan]
-        vp = C.c_void_p * n
-        stat = lambda j: vp(*[s[j].data_ptr() if j < len(s) else None for _, _, s in plan])      # noqa: E731
-        src, dst = vp(*[x.data_ptr() for x, _, _ in plan]), vp(*[o.data_ptr() for o in outs])
-        kind = (C.c_int * n)(*[k for _, k, _ in plan])
-        rows = (C.c_longlong * n)(*[x.numel() // x.shape[-1] for x, _, _ in plan])
-        cols = (C.c_int * n)(*[x.shape[-1] for x, _, _ in plan])
-        dev = plan[0][0].device
-        with torch.cuda.device(dev):
-            _lib.check_scale(lib.beso_scale_rows_mixed(src, dst, kind, stat(0), stat(1), stat(2), stat(3), rows, cols, n,
-                                                       stream_ptr(dev)), "scale_rows_mixed")
-        return outs
+                return False
+            return True
+
+        def launch(dev, src, dst, stat, rows, cols, n):
+            kind = (C.c_int * n)(*[_lib.SCALE_KINDS["zscore" if which == "x" else "minmax"] for _, which in items])
+            _lib.launch("scale", "beso_scale_rows_mixed", dev, src, dst, kind, stat(0), stat(1), stat(2), stat(3), rows, cols, n)
+
+        return _scale_many(
+            self, items, lambda which: ((self.x_mean, self._den()) if which == "x" else
+                                        (self.y_min, self._y_range(), self._y_span(), self.new_min_y)), available, launch)

@@ -10,7 +10,6 @@ import numbers
 import torch
 
 from . import _lib
-from .runtime import stream_ptr
 
 PURPOSES = tuple(_lib.NOISE_PURPOSES)
 _FRESH = -1         # episode 0xffffffff: with the reset flag set, the next step is episode 0, step 0
@@ -98,10 +97,8 @@ class KeyedNoise:
             out = torch.empty((int(S), self.n, int(E)), dtype=dtype, device=self.device)
         elif out.dtype != dtype or out.device != self.device or not out.is_contiguous() or out.numel() != int(S) * self.n * int(E):
             raise ValueError(f"out must be a contiguous {dtype} tensor of {int(S) * self.n * int(E)} elements on {self.device}")
-        with torch.cuda.device(self.device):
-            _lib.check_noise_status(getattr(self.lib, fn)(
-                self.keys.data_ptr(), self.episodes.data_ptr(), self.steps.data_ptr(), self.n, _lib.NOISE_PURPOSES[purpose], int(S),
-                int(E), *scale, out.data_ptr(), stream_ptr(self.device)), fn[len("beso_"):])
+        _lib.launch("noise", fn, self.device, self.keys.data_ptr(), self.episodes.data_ptr(), self.steps.data_ptr(), self.n,
+                    _lib.NOISE_PURPOSES[purpose], int(S), int(E), *scale, out.data_ptr())
         return out
 
     def words(self, purpose: str, S: int, E: int, out=None) -> torch.Tensor:
@@ -126,11 +123,9 @@ class KeyedNoise:
                 raise ValueError(f"{name} must be a contiguous float32 tensor of {count} elements on {dev}")
         src, dst = self._counters[self._cur], self._counters[1 - self._cur]
         ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
-        with torch.cuda.device(dev):
-            _lib.check_noise_status(self.lib.beso_noise_rollout(
-                self.keys.data_ptr(), self.reset.data_ptr() if self._reset_pending else None, src[0].data_ptr(), src[1].data_ptr(),
-                dst[0].data_ptr(), dst[1].data_ptr(), N, int(act_dim), K, n_steps, int(step_elems), ptr(x_t), ptr(cand),
-                ptr(step_noise), stream_ptr(dev)), "noise_rollout")
+        _lib.launch("noise", "beso_noise_rollout", dev, self.keys.data_ptr(), self.reset.data_ptr() if self._reset_pending else None,
+                    src[0].data_ptr(), src[1].data_ptr(), dst[0].data_ptr(), dst[1].data_ptr(), N, int(act_dim), K, n_steps,
+                    int(step_elems), ptr(x_t), ptr(cand), ptr(step_noise))
         self._cur = 1 - self._cur
         if self._reset_pending:
             self.reset.zero_()

@@ -11,10 +11,26 @@ through a sampler loop without anything reading them.  No denoiser o
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 
 from . import _lib
-from .runtime import stream_ptr
+from . import candidates as best_of
+
+# What ``_scaler_plan`` hands the launch behind the sampler: ``kind`` names the entry point (_TAIL_ENTRY), ``lo`` / ``hi`` are
+# clip_action's float64 bounds, ``stats`` the fp32 statistics in the entry point's argument order -- (den_y, mean_y) for 'zscore',
+# (new_lo, span, range, lo_y) for 'minmax' -- or as many None with ``scale_data`` off.
+_Tail = namedtuple("_Tail", "kind lo hi stats")
+# kind -> (library, entry point): the package's Scaler and its MinMaxScaler (include/beso_scale.h)
+_TAIL_ENTRY = {"zscore": ("hip", "beso_rollout_end"), "minmax": ("scale", "beso_rollout_end_minmax")}
+# A step's checked arguments (``VectorRollout._arguments``).  ``K`` is None without candidates; ``sigmas`` is the host-side schedule
+# of the sampler settings; ``slabs`` counts the step-noise slabs a seeded step draws (0: none).
+_StepArgs = namedtuple("_StepArgs", "obs K select bandwidth sampler_type sigmas slabs")
+
+
+def _ptr(v):
+    return None if v is None else v.data_ptr()
 
 
 class _Last(dict):
@@ -174,11 +190,10 @@ class VectorRollout:
 
     # ------------------------------------------------------------------ what of the scaler the two launches can take over
     def _scaler_plan(self):
-        """(x statistics for beso_rollout_begin or None, the tail's arguments or None), rebuilt when the scaler, one of its
-        tensors or a tensor's version changes.  The tail is (lo, hi, den_y, mean_y) for beso_rollout_end (the package's Scaler)
-        or ("minmax", lo, hi, new_lo, span, range, lo_y) for beso_rollout_end_minmax (its MinMaxScaler, whose scale_input is
-        Scaler's arithmetic: the same begin launch serves it).  The launches take fp32 statistics and float64 bounds of the
-        package's two scalers; anything else is served by the scaler's own methods."""
+        """(x statistics for beso_rollout_begin or None, the _Tail of the launch behind the sampler or None), rebuilt when the
+        scaler, one of its tensors or a tensor's version changes.  The tail is 'zscore' for the package's Scaler and 'minmax' for
+        its MinMaxScaler (whose scale_input is Scaler's arithmetic: the same begin launch serves it).  The launches take fp32
+        statistics and float64 bounds of the package's two scalers; anything else is served by the scaler's own methods."""
         from .networks.scaler.scaler_class import MinMaxScaler, Scaler
         sc = self.agent.scaler
         parts = tuple(getattr(sc, k, None) for k in ("x_mean", "x_std", "y_mean", "y_std", "y_bounds_tensor", "y_min", "y_max",
@@ -203,14 +218,13 @@ class VectorRollout:
         b = parts[4]
         if (ours or minmax) and isinstance(b, torch.Tensor) and b.device == dev and b.dtype == torch.float64 and tuple(b.shape) == (2, self.act_dim):
             lo, hi = (b[0] * 1.1).contiguous(), (b[1] * 1.1).contiguous()        # clip_action's bounds, in float64
-            if minmax:
-                stats = (sc.new_min_y, sc._y_span(), sc._y_range(), sc.y_min) if sc.scale_data else (None,) * 4
-                if not sc.scale_data or all(f32(s, self.act_dim) for s in stats):
-                    ys = ("minmax", lo, hi) + stats
-            elif not sc.scale_data:
-                ys = (lo, hi, None, None)
-            elif f32(sc.y_mean, self.act_dim) and f32(sc._den("y"), self.act_dim):
-                ys = (lo, hi, sc._den("y"), sc.y_mean)
+            kind = "minmax" if minmax else "zscore"
+            if not sc.scale_data:
+                ys = _Tail(kind, lo, hi, (None,) * (4 if minmax else 2))
+            else:
+                stats = (sc.new_min_y, sc._y_span(), sc._y_range(), sc.y_min) if minmax else (sc._den("y"), sc.y_mean)
+                if all(f32(s, self.act_dim) for s in stats):
+                    ys = _Tail(kind, lo, hi, stats)
         self._plan_key, self._plan = key, (xs, ys)
         return self._plan
 
@@ -232,111 +246,125 @@ class VectorRollout:
         Seeded (``seed``): ``noise=None`` is the keyed draw -- x_T, the K candidates and the step noise of 'euler_ancestral',
         'ancestral' and 'dpmpp_2s_ancestral' on their one-launch path, all from one launch -- and a sampler that would draw
         from the global generator inside a Python loop is a ValueError.  An explicit ``noise`` still wins."""
-        agent, dev, N, W = self.agent, self.device, self.n_envs, self.window
-        keyed, given = self._keyed, noise is not None
+        a = self._arguments(obs, noise, new_sampler_type, new_sampling_steps, noise_scheduler, candidates, select, bandwidth)
+        xs, ys = self._scaler_plan()
+        noise, noise_k, step_noise = self._draws(a, noise)
+        state, x = self._begin(a.obs, noise, xs)
+        x0, picked = self._sample(a, state, x, noise_k, step_noise)
+        pred = self._end(x0, ys)
+        if self._keyed is not None:
+            picked.update(noise_episode=self._keyed.episodes, noise_step=self._keyed.steps)
+            if step_noise is not None:
+                picked["step_noise"] = step_noise
+        self.last = _Last({"state": state, "x": x, "lengths": self.lengths, "x0": x0, **picked})
+        return pred
+
+    def _arguments(self, obs, noise, new_sampler_type, new_sampling_steps, noise_scheduler, candidates, select, bandwidth):
+        """Phase 1: every refusal of a step -- the best-of-K arguments, the shapes of ``obs`` and of an explicit ``noise``, the
+        goal, the schedule, what a seeded step can serve (_keyed_step_slabs) -- as a ValueError, and the sampler settings
+        resolved.  Touches no device state and enqueues nothing: after a refusal no window, counter or reset flag has changed."""
+        agent, N = self.agent, self.n_envs
         K = None
         if candidates is not None:
-            from . import candidates as best_of
             K, select, bandwidth = best_of.check_arguments(candidates, select, bandwidth, bool(getattr(agent, "use_kde", False)))
             max_act = _lib.SELECT_LIMITS["max_act"]
             if self.act_dim > max_act:
                 raise ValueError(f"candidates: act_dim {self.act_dim} exceeds the {max_act} components the selection takes")
-            if keyed is None or given:
-                noise_k = best_of.check_noise(noise, N, K, self.act_dim, dev)
-                noise = noise_k[:, :1].contiguous()              # begin's newest slot: expand overwrites it in every row
         elif select is not None or bandwidth is not None:
             raise ValueError("select and bandwidth belong to candidates=K")
-        xs, ys = self._scaler_plan()
-        obs = torch.as_tensor(obs)
-        if xs is None:
-            obs = agent.scaler.scale_input(obs)
-        obs = obs.to(device=dev, dtype=torch.float32).contiguous()
-        if tuple(obs.shape) != (N, self.obs_dim):
-            raise ValueError(f"obs must be [{N}, {self.obs_dim}], got {tuple(obs.shape)}")
-        if K is not None:
-            pass                                                 # (checked with the other best-of-K arguments)
-        elif keyed is not None and not given:
-            pass                                                 # (the keyed launch below draws it)
-        elif noise is None:
-            noise = torch.randn((N, 1, self.act_dim), device=dev)
-        else:
-            noise = torch.as_tensor(noise).to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(noise.shape) != (N, 1, self.act_dim):
-                raise ValueError(f"noise must be [{N}, 1, {self.act_dim}], got {tuple(noise.shape)}")
+        if noise is not None and tuple(torch.as_tensor(noise).shape) != (N, K or 1, self.act_dim):
+            raise ValueError(f"noise must be [{N}, {K or 1}, {self.act_dim}], got {tuple(torch.as_tensor(noise).shape)}")
         if self.goal_len and self.goal is None:
             raise ValueError("set_goal() must be called before the first step of a goal-conditioned model")
+        obs = torch.as_tensor(obs)
+        if tuple(obs.shape) != (N, self.obs_dim):
+            raise ValueError(f"obs must be [{N}, {self.obs_dim}], got {tuple(obs.shape)}")
         sampler_type = agent.sampler_type if new_sampler_type is None else new_sampler_type
         n_steps = agent.num_sampling_steps if new_sampling_steps is None else new_sampling_steps
-        noise_scheduler = agent.noise_scheduler if noise_scheduler is None else noise_scheduler
-        step_noise = sigmas = None
+        sigmas = agent.get_noise_schedule(n_steps, agent.noise_scheduler if noise_scheduler is None else noise_scheduler)
+        slabs = 0 if self._keyed is None else self._keyed_step_slabs(sampler_type, sigmas, N * (K or 1))
+        return _StepArgs(obs, K, select, bandwidth, sampler_type, sigmas, slabs)
+
+    def _draws(self, a, noise):
+        """Phase 2, the one place that says where a step's draws come from -> (noise [N, 1, act] for begin's newest slot, noise_k
+        [N, K, act] or None, step_noise [slabs, N K, W, act] or None).  An explicit ``noise`` wins; without one a seeded rollout
+        takes every draw from its ONE keyed launch (include/beso_noise.h) and an unseeded one makes its one global-generator
+        draw.  A seeded step runs the keyed launch in either case: its counters advance, and its step noise is keyed."""
+        N, W, K, keyed, given = self.n_envs, self.window, a.K, self._keyed, noise is not None
+        rows = K or 1
+        noise_k = step_noise = None
+        if given:
+            noise = torch.as_tensor(noise).to(device=self.device, dtype=torch.float32).contiguous()
+        elif keyed is None:
+            noise = torch.randn((N, rows, self.act_dim), device=self.device)
+        if K is not None and noise is not None:
+            noise_k, noise = noise, noise[:, :1].contiguous()            # begin's newest slot: expand overwrites it in every row
         if keyed is not None:
-            # ONE launch: the counters advance and every draw of this step is made (include/beso_noise.h)
-            sigmas = agent.get_noise_schedule(n_steps, noise_scheduler)
-            rows = K or 1
-            slabs = self._keyed_step_slabs(sampler_type, sigmas, N * rows)
-            x_t, cand, step_noise = keyed.rollout(self.act_dim, 0 if K is None or given else K, slabs, rows * W * self.act_dim)
+            x_t, cand, step_noise = keyed.rollout(self.act_dim, 0 if K is None or given else K, a.slabs, rows * W * self.act_dim)
             if not given:
                 noise, noise_k = x_t, cand
             if step_noise is not None:
-                step_noise = step_noise.view(slabs, N * rows, W, self.act_dim)
+                step_noise = step_noise.view(a.slabs, N * rows, W, self.act_dim)
+        return noise, noise_k, step_noise
+
+    def _begin(self, obs, noise, xs):
+        """Phase 3: beso_rollout_begin -- the marked environments start empty, the observation joins every window, the sampler's
+        inputs (state [N, W, obs], x [N, W, act]) are written -- then the reset flags are cleared."""
+        agent, dev, N, W = self.agent, self.device, self.n_envs, self.window
+        if xs is None:                                           # a scaler the launch cannot serve: its own method
+            obs = agent.scaler.scale_input(obs)
+            if tuple(obs.shape) != (N, self.obs_dim):
+                raise RuntimeError(f"the scaler returned {tuple(obs.shape)}, expected {(N, self.obs_dim)}")
+        obs = obs.to(device=dev, dtype=torch.float32).contiguous()
+        mean, den = xs or (None, None)
         state = torch.empty((N, W, self.obs_dim), dtype=torch.float32, device=dev)
         x = torch.empty((N, W, self.act_dim), dtype=torch.float32, device=dev)
-        ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
-        with torch.cuda.device(dev):
-            stream = stream_ptr(dev)
-            _lib.check(self.lib.beso_rollout_begin(
-                obs.data_ptr(), self._reset.data_ptr() if self._reset_pending else None, noise.data_ptr(),
-                ptr(xs and xs[0]), ptr(xs and xs[1]), float(agent.sigma_max), self.lengths.data_ptr(), self.obs_ctx.data_ptr(),
-                self.act_ctx.data_ptr(), state.data_ptr(), x.data_ptr(), N, W, self.obs_dim, self.act_dim, stream), "rollout_begin")
+        _lib.launch("hip", "beso_rollout_begin", dev, obs.data_ptr(), self._reset.data_ptr() if self._reset_pending else None,
+                    noise.data_ptr(), _ptr(mean), _ptr(den), float(agent.sigma_max), self.lengths.data_ptr(),
+                    self.obs_ctx.data_ptr(), self.act_ctx.data_ptr(), state.data_ptr(), x.data_ptr(), N, W, self.obs_dim, self.act_dim)
         if self._reset_pending:
             self._reset.zero_()
             self._reset_pending = False
+        return state, x
+
+    def _sample(self, a, state, x, noise_k, step_noise):
+        """Phase 4: ONE sampler call on the EMA weights in eval mode -> (x0 [N, W, act], the best-of-K entries of ``last``).
+        With candidates the N windows are expanded to N K rows in front of it and the selection picks N of them behind it; a
+        seeded step hands its keyed step noise to the sampler (gc_sampling.keyed_step_noise)."""
+        agent, N, W, K = self.agent, self.n_envs, self.window, a.K
         with agent._ema_scope():
             if agent.model.training:
                 agent.model.eval()
-            if sigmas is None:
-                sigmas = agent.get_noise_schedule(n_steps, noise_scheduler)
-            if K is not None:
-                state_k, x_k = best_of.expand(state, x, self.lengths, noise_k, agent.sigma_max)
-                goal_k = None if self.goal is None else torch.repeat_interleave(self.goal, K, dim=0)
-            args = (sigmas, x, state, self.goal, sampler_type) if K is None else (sigmas, x_k, state_k, goal_k, sampler_type)
-            if keyed is None:
-                x0 = agent.sample_loop(*args)
+            goal = self.goal
+            if K is not None:                                    # from here on N K rows
+                state, x = best_of.expand(state, x, self.lengths, noise_k, agent.sigma_max)
+                goal = None if goal is None else torch.repeat_interleave(goal, K, dim=0)
+            if self._keyed is None:
+                x0 = agent.sample_loop(a.sigmas, x, state, goal, a.sampler_type)
             else:
                 from .agents.diffusion_agents.k_diffusion.gc_sampling import keyed_step_noise
                 with keyed_step_noise(step_noise):
-                    x0 = agent.sample_loop(*args)
+                    x0 = agent.sample_loop(a.sigmas, x, state, goal, a.sampler_type)
         if x0.dtype != torch.float32 or not x0.is_contiguous():
             x0 = x0.to(torch.float32).contiguous()
         if tuple(x0.shape) != (N * (K or 1), W, self.act_dim):
             raise RuntimeError(f"the sampler returned {tuple(x0.shape)}, expected {(N * (K or 1), W, self.act_dim)}")
-        picked = {}
-        if K is not None:
-            x0_k = x0
-            x0, index, scores = best_of.select(x0_k, self.lengths, K, select, bandwidth)
-            picked = {"scores": scores, "index": index, "state_k": state_k, "x_k": x_k, "x0_k": x0_k}
-        if ys is not None and isinstance(ys[0], str):              # MinMaxScaler's tail (include/beso_scale.h)
-            pred = torch.empty((N, self.act_dim), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check_scale(_lib.load_scale().beso_rollout_end_minmax(
-                    x0.data_ptr(), self.lengths.data_ptr(), *[ptr(v) for v in ys[1:]], self.act_ctx.data_ptr(), pred.data_ptr(),
-                    N, W, self.act_dim, stream_ptr(dev)), "rollout_end_minmax")
-        elif ys is not None:
-            pred = torch.empty((N, self.act_dim), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                stream = stream_ptr(dev)
-                _lib.check(self.lib.beso_rollout_end(
-                    x0.data_ptr(), self.lengths.data_ptr(), ys[0].data_ptr(), ys[1].data_ptr(), ptr(ys[2]), ptr(ys[3]),
-                    self.act_ctx.data_ptr(), pred.data_ptr(), N, W, self.act_dim, stream), "rollout_end")
-        else:
-            # a scaler the launch cannot serve (other dtypes, another class): its own methods on the gathered rows
-            slot = (self.lengths - 1).long()
-            clipped = agent.scaler.clip_action(x0[self._rows, slot])
+        if K is None:
+            return x0, {}
+        x0_k = x0
+        x0, index, scores = best_of.select(x0_k, self.lengths, K, a.select, a.bandwidth)
+        return x0, {"scores": scores, "index": index, "state_k": state, "x_k": x, "x0_k": x0_k}
+
+    def _end(self, x0, ys):
+        """Phase 5: the newest action of every window is clipped, remembered in ``act_ctx`` and un-scaled -> pred [N, act].  One
+        launch (_TAIL_ENTRY) where the plan has a tail; else the scaler's own methods on the gathered rows."""
+        if ys is None:                                           # (other dtypes, another class)
+            scaler, slot = self.agent.scaler, (self.lengths - 1).long()
+            clipped = scaler.clip_action(x0[self._rows, slot])
             self.act_ctx[self._rows, slot] = clipped
-            pred = agent.scaler.inverse_scale_output(clipped)
-        if keyed is not None:
-            picked.update(noise_episode=keyed.episodes, noise_step=keyed.steps)
-            if step_noise is not None:
-                picked["step_noise"] = step_noise
-        self.last = _Last({"state": state, "x": x, "lengths": self.lengths, "x0": x0, **picked})
+            return scaler.inverse_scale_output(clipped)
+        pred = torch.empty((self.n_envs, self.act_dim), dtype=torch.float32, device=self.device)
+        _lib.launch(*_TAIL_ENTRY[ys.kind], self.device, x0.data_ptr(), self.lengths.data_ptr(), ys.lo.data_ptr(), ys.hi.data_ptr(),
+                    *[_ptr(s) for s in ys.stats], self.act_ctx.data_ptr(), pred.data_ptr(), self.n_envs, self.window,
+                    self.act_dim)
         return pred

@@ -617,3 +617,38 @@ def test_numa_pinning_reads_the_topology_and_is_best_effort(tmp_path, monkeypatc
     assert bdist.pin_to_gpu_numa_node(0, sysfs=str(sysfs)) == 1
     assert pinned == [sorted({have[0], have[-1]})]
     assert bdist.pin_to_gpu_numa_node(0, sysfs=str(tmp_path / "nothing")) is None and len(pinned) == 1
+
+
+def test_side_library_checkers_raise_one_text_under_both_names():
+    """One refused call per library that keeps its own message (the argument checks return before any launch): check_side(name,
+    ...) and the library's old checker raise the same exception class with the same text."""
+    import ctypes as C
+    from beso_amd import _lib
+    from beso_amd.build import build
+    build(verbose=False)
+    one = C.c_void_p(0x1000)
+    cases = {
+        "select": (lambda: _lib.load_select().beso_candidates_select(one, one, 1, 0.0, 2, 3, 4, 0, one, one, one, None),
+                   _lib.check_select, "candidates_select",
+                   "beso_select: candidates_select: beso_candidates_select: K = 0 candidates per environment, supported: 1 ... 256 "
+                   "(status -5)"),
+        "scale": (lambda: _lib.load_scale().beso_rollout_end_minmax(one, one, one, one, one, one, one, one, one, one, 4, 3, 0, None),
+                  _lib.check_scale, "rollout_end_minmax",
+                  "beso_scale: rollout_end_minmax: beso_rollout_end_minmax: act_dim = 0 and window = 3 must be at least 1, n_envs = 4 "
+                  "at least 0 (status -2)"),
+        "noise": (lambda: _lib.load_noise().beso_noise_words(one, one, one, 0, 0, 1, 4, one, None),
+                  _lib.check_noise_status, "noise_words",
+                  "beso_noise: noise_words: beso_noise_words: N = 0, S = 1, E = 4 must all be at least 1 (status -2)"),
+    }
+    for name, (refused, old, what, text) in cases.items():
+        for check in (lambda status: _lib.check_side(name, status, what), lambda status: old(status, what)):
+            with pytest.raises(ValueError) as e:
+                check(refused())
+            assert type(e.value) is ValueError and str(e.value) == text, name
+        _lib.check_side(name, _lib.OK, what)
+    # a status outside the three argument classes is the library's runtime error
+    _lib.load_select().beso_candidates_select(one, one, 1, 0.0, 2, 3, 4, 0, one, one, one, None)
+    for check in (lambda: _lib.check_side("select", _lib.ERR_HIP, "x"), lambda: _lib.check_select(_lib.ERR_HIP, "x")):
+        with pytest.raises(_lib.BesoHipError) as e:
+            check()
+        assert str(e.value) == "beso_select: x: beso_candidates_select: K = 0 candidates per environment, supported: 1 ... 256 (status -6)"

@@ -221,7 +221,8 @@ def test_rollout_with_minmax_scaler_takes_both_launches_and_keeps_the_scalers_bi
     agent.get_scaler(sc)
     xs, ys = agent.vector_rollout(3)._scaler_plan()
     assert xs is not None and xs[0] is sc.x_mean and xs[1] is sc._den()
-    assert ys is not None and ys[0] == "minmax" and len(ys) == 7 and ys[1].dtype == torch.float64
+    assert ys is not None and ys.kind == "minmax" and len(ys.stats) == 4 and ys.lo.dtype == ys.hi.dtype == torch.float64
+    assert all(s is not None for s in ys.stats)
     launches, calls, n_clipped, n_seen, plain = _run_rollout(agent, sc, monkeypatch)
     assert (launches, calls) == (5, 0)
     print(f"[minmax] rollout, data bounds: {n_clipped} of {n_seen} components clipped")
@@ -261,7 +262,7 @@ def test_rollout_declines_the_scalers_the_launches_do_not_serve(monkeypatch):
     raw.y_bounds_tensor = raw.y_bounds_tensor * 0.05
     agent.get_scaler(raw)
     xs, ys = agent.vector_rollout(3)._scaler_plan()
-    assert xs is None and ys[0] == "minmax" and ys[3:] == (None,) * 4
+    assert xs is None and ys.kind == "minmax" and ys.stats == (None,) * 4
     launches, calls, n_clipped, n_seen, _ = _run_rollout(agent, raw, monkeypatch)
     assert launches == 5 and calls == 5 and n_clipped > 0           # (scale_input: a .to() per step)
 
