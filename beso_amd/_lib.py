@@ -14,6 +14,7 @@ DEV_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_hip_dev.so")
 MLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_mlp.so")      # the MLP encoder (include/beso_mlp.h)
 RESMLP_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_resmlp.so")   # the residual MLP encoder (include/beso_resmlp.h)
 GUIDE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_guide.so")     # the guide gradient of guided sampling (include/beso_guide.h)
+GUIDEFIT_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_guidefit.so")   # the guide's fit step (include/beso_guide_fit.h)
 SELECT_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_select.so")   # best-of-K action selection (include/beso_select.h)
 SCALE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_scale.so")     # MinMaxScaler's scalings (include/beso_scale.h)
 NOISE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_noise.so")     # the rollout's keyed noise (include/beso_noise.h)
@@ -158,6 +159,17 @@ GUIDE_SIGNATURES = {
 }
 GUIDE_EXPORTS = list(GUIDE_SIGNATURES)
 
+# include/beso_guide_fit.h (libbeso_guidefit.so): BESO_GUIDE_FIT_* by GuideTrainer's loss names, and every function it declares,
+# in its order; beso_guide_apply_sigma is beso_guide_apply with c_noise behind sigma
+GUIDEFIT_LOSSES = {"mse": 0, "bce": 1}
+GUIDEFIT_SIGNATURES = {
+    "beso_guide_fit_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "beso_guide_fit_loss": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, vp]),
+    "beso_guide_supported_sigma": (i32, [dimsp, i32, i32, i32]),
+    "beso_guide_apply_sigma": (i32, [vpp, i32, dimsp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp]),
+}
+GUIDEFIT_EXPORTS = list(GUIDEFIT_SIGNATURES)
+
 # include/beso_select.h (libbeso_select.so): BESO_SELECT_* by the rollout's names, its limits, and every function it declares,
 # in its order
 SELECT_MODES = {"mean": 0, "kde": 1}
@@ -240,6 +252,7 @@ def load() -> C.CDLL:
 _SIDE = {"mlp": (MLP_LIB_PATH, MLP_SIGNATURES, "beso_mlp.h", "the encoder", None, None),
          "resmlp": (RESMLP_LIB_PATH, RESMLP_SIGNATURES, "beso_resmlp.h", "the encoder", None, None),
          "guide": (GUIDE_LIB_PATH, GUIDE_SIGNATURES, "beso_guide.h", "the fused guide gradient", None, None),
+         "guidefit": (GUIDEFIT_LIB_PATH, GUIDEFIT_SIGNATURES, "beso_guide_fit.h", "the guide's fit step", None, None),
          "select": (SELECT_LIB_PATH, SELECT_SIGNATURES, "beso_select.h", "best-of-K action selection",
                     "beso_candidates_last_error", "beso_select"),
          "scale": (SCALE_LIB_PATH, SCALE_SIGNATURES, "beso_scale.h", "MinMaxScaler's one-launch scalings",
@@ -293,6 +306,12 @@ def load_guide() -> C.CDLL:
     """The guide-gradient library of classifier-guided sampling (include/beso_guide.h).  A guide it does not serve takes
     autograd over the guide's own HIP kernels, decided once per guide."""
     return _load_side("guide")
+
+
+def load_guidefit() -> C.CDLL:
+    """The library of the guide's fit step and of the guide gradient over rows with the noise-level column
+    (include/beso_guide_fit.h)."""
+    return _load_side("guidefit")
 
 
 def load_select() -> C.CDLL:

@@ -57,7 +57,9 @@ class ClassifierGuidedSampleModel(nn.Module):
     is kept (``create_graph=True`` at :85 is detached on the same line).
 
     Two paths, decided once per guide and row layout (``MLPGuide.fused_supported``), never by catching an error per call:
-      * ``cond_func`` an ``MLPGuide`` the library serves, on GPU tensors: ``beso_guide_apply`` -- one launch behind the denoiser;
+      * ``cond_func`` an ``MLPGuide`` the library serves, on GPU tensors: ``beso_guide_apply`` -- one launch behind the denoiser
+        (an ``MLPGuide(use_sigma=True)``, a classifier of the noised action trained by ``guide_fit.GuideTrainer``, is handed
+        ``sigma`` on either path; its launch is ``beso_guide_apply_sigma``);
       * any other callable (a torch-op function, a ``ResidualMLPNetwork`` behind a lambda, an ``MLPGuide`` beyond the launch's
         shapes): ``torch.enable_grad()`` and ``autograd.grad`` over the guide alone.  This is also what runs on CPU tensors.
 
@@ -86,7 +88,9 @@ class ClassifierGuidedSampleModel(nn.Module):
             return self.guide.apply(state, pred, goal, sigma, float(cond_lambda))
         with torch.enable_grad():
             a = pred.detach().clone().requires_grad_(True)
-            q_value = self.guide(state, a, goal)
+            # a noise-aware MLPGuide reads the noise level; every other guide keeps the reference's three arguments
+            takes_sigma = isinstance(self.guide, MLPGuide) and self.guide.use_sigma
+            q_value = self.guide(state, a, goal, sigma) if takes_sigma else self.guide(state, a, goal)
             grads = torch.autograd.grad(outputs=q_value.sum(), inputs=a, only_inputs=True)[0].detach()
         return pred + cond_lambda * grads * append_dims(sigma ** 2, action.ndim)
 

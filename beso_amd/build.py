@@ -23,7 +23,8 @@ DEV_LIB = os.path.join(LIBDIR, "libbeso_hip_dev.so")
 DEV_STAMP = os.path.join(LIBDIR, "libbeso_hip_dev.sha256")
 UNITS = ["api", "elementwise", "attention", "gemm", "fused", "fused_f16", "optim", "train", "feed", "small", "rollout", "lossfwd"]
 # Every library: (path, units, public header under include/).  The MLP observation / goal encoder, the residual MLP encoder and
-# the guide gradient of classifier-guided sampling (they share csrc/mlp_tile.h), the best-of-K action selection of the
+# the guide gradient of classifier-guided sampling (they share csrc/mlp_tile.h), the guide's fit step (it shares
+# csrc/guide_tile.h with the guide gradient), the best-of-K action selection of the
 # rollout, MinMaxScaler's scalings, and the rollout's keyed noise, are libraries of their own, built with the product library and
 # under the same stamp: libbeso_hip.so's dynamic symbol table stays exactly include/beso_hip.h
 LIBS = [(LIB, UNITS, "beso_hip.h"),
@@ -31,6 +32,7 @@ LIBS = [(LIB, UNITS, "beso_hip.h"),
         (os.path.join(LIBDIR, "libbeso_mlp.so"), ["encoder"], "beso_mlp.h"),
         (os.path.join(LIBDIR, "libbeso_resmlp.so"), ["resmlp"], "beso_resmlp.h"),
         (os.path.join(LIBDIR, "libbeso_guide.so"), ["guide"], "beso_guide.h"),
+        (os.path.join(LIBDIR, "libbeso_guidefit.so"), ["guide_fit"], "beso_guide_fit.h"),
         (os.path.join(LIBDIR, "libbeso_select.so"), ["select"], "beso_select.h"),
         (os.path.join(LIBDIR, "libbeso_scale.so"), ["scale"], "beso_scale.h"),
         (os.path.join(LIBDIR, "libbeso_noise.so"), ["noise"], "beso_noise.h")]
