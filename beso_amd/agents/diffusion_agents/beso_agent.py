@@ -134,6 +134,11 @@ class BesoAgent(BaseAgent):
         self._ema_partial = False        # sharded exchange: the EMA shadow is current for the owned range only
         self._train_graphs = {}          # batch shape -> captured forward+backward (train_step)
         self._train_graph_ok = True
+        self._enc_graph_logged = False   # "BESO_AMD_TRAIN_GRAPH=1 ignored" is logged once
+        self._replicas_synced = False    # data parallel: rank 0's weights were broadcast (C2)
+        self._loss_stream = self._c1_stream = None           # the step's side streams, created on first use (_side_stream)
+        # _hip_loss_backward leaves these: the HipTrainStep that ran (None: autograd), the early C1 stream, the early loss stream
+        self._hip_step = self._c1_early = self._loss_ready = None
 
     # ------------------------------------------------------------------ reproducibility
     @property
@@ -171,16 +176,18 @@ class BesoAgent(BaseAgent):
         enc = self._trainable_encoder()
         if enc is None:
             return state, goal
-        net = enc.network
         params = tuple(self.encoder_ema.shadow_params) if self.use_ema else None
-
-        def run(x):
-            net._check_input(x)
-            rows = x.reshape(-1, net.input_dim).to(torch.float32).contiguous()
-            return net.run_forward(rows, keep=False, params=params)[0].view(*x.shape[:-1], net.output_dim)
-
+        run = partial(self._encode_rows, enc.network, keep=False, params=params)
         with torch.no_grad():
-            return run(state), (run(goal) if goal is not None and enc.encode_goal else goal)
+            return run(state)[0], (run(goal)[0] if goal is not None and enc.encode_goal else goal)
+
+    @staticmethod
+    def _encode_rows(net, x, *, keep, params=None):
+        """``x`` [..., input_dim] through ``net`` (on ``params``: the EMA shadow) -> (y [..., output_dim], the kept rows or None)."""
+        net._check_input(x)
+        rows = x.reshape(-1, net.input_dim).to(torch.float32).contiguous()
+        y, kept = net.run_forward(rows, keep=keep, params=params)
+        return y.view(*x.shape[:-1], net.output_dim), kept
 
     def _encoder_grad_buffer(self, net):
         """The flat gradient buffer of the encoder; its views are the parameters' ``.grad`` (as for the denoiser)."""
@@ -200,35 +207,13 @@ class BesoAgent(BaseAgent):
         if bdist.is_distributed() and bdist.world_size() > 1:
             raise NotImplementedError("data-parallel training (world_size > 1) with a trainable input encoder "
                                       f"({type(enc).__name__}) is not supported: its gradients are not exchanged")
-        if os.environ.get("BESO_AMD_TRAIN_GRAPH", "0") == "1" and not getattr(self, "_enc_graph_logged", False):
+        if os.environ.get("BESO_AMD_TRAIN_GRAPH", "0") == "1" and not self._enc_graph_logged:
             self._enc_graph_logged = True
             log.info("BESO_AMD_TRAIN_GRAPH=1 ignored: the agent has a trainable input encoder")
         net = enc.network
-
-        def encode(x):
-            net._check_input(x)
-            rows = x.reshape(-1, net.input_dim).to(torch.float32).contiguous()
-            y, keep = net.run_forward(rows, keep=True)
-            return y.view(*x.shape[:-1], net.output_dim), keep
-
-        state_e, state_keep = encode(state)
-        goal_e, goal_keep = encode(goal) if goal is not None and enc.encode_goal else (goal, None)
-        noise = torch.randn_like(action)
-        sigma = self.make_sample_density()(shape=(len(action),), device=self.device)
-        step = self.model.hip_train_step(state_e, action, goal_e, noise, sigma) if hasattr(self.model, "hip_train_step") else None
-        if step is None:
-            raise NotImplementedError("a trainable input encoder needs the HIP training step (the beso_amd GCDenoiser / "
-                                      "DiffusionGPT on the GPU)")
-        self.optimizer.zero_grad(set_to_none=True)
-        self._hip_step = step
-        self._c1_early = None
-        self._loss_ready = None
-        if os.environ.get("BESO_AMD_ASYNC_LOSS", "1") != "0":
-            if getattr(self, "_loss_stream", None) is None:
-                self._loss_stream = torch.cuda.Stream(state.device)
-            self._loss_ready = self._loss_stream
-        loss, state_grad, goal_grad = step.loss_backward(state_e, action, goal_e, noise, sigma, grad_scale=1.0,
-                                                         loss_stream=self._loss_ready, input_grads=True)
+        state_e, state_keep = self._encode_rows(net, state, keep=True)
+        goal_e, goal_keep = self._encode_rows(net, goal, keep=True) if goal is not None and enc.encode_goal else (goal, None)
+        loss, state_grad, goal_grad = self._hip_loss_backward(state_e, action, goal_e, input_grads=True, exchange=False)   # (world 1)
         flat = self._encoder_grad_buffer(net)
         net.run_backward(state_keep, state_grad, flat)
         if goal_keep is not None and goal_grad is not None:
@@ -236,22 +221,6 @@ class BesoAgent(BaseAgent):
                 goal_grad = goal_grad.sum(dim=0, keepdim=True)      # one goal for the whole batch: its gradient is the sum
             net.run_backward(goal_keep, goal_grad, flat, accumulate=True)
         return loss
-
-    def _encoder_optimizer_step(self, enc, do_ema: bool):
-        opt = self.encoder_optimizer
-        if isinstance(opt, FusedAdam):
-            if self.max_grad_norm is None and not self.skip_nonfinite_steps:
-                opt.step(ema=self.encoder_ema if do_ema else None)
-            else:
-                opt.step(ema=self.encoder_ema if do_ema else None, max_grad_norm=self.max_grad_norm,
-                         skip_nonfinite=self.skip_nonfinite_steps)
-        else:
-            if self.max_grad_norm is not None:
-                torch.nn.utils.clip_grad_norm_(list(enc.get_params()), self.max_grad_norm)
-            opt.step()
-            if do_ema:
-                self.encoder_ema.update(enc.get_params())
-        self.encoder_lr_scheduler.step()
 
     # ------------------------------------------------------------------ scaler / bounds
     def get_scaler(self, scaler):
@@ -311,7 +280,7 @@ class BesoAgent(BaseAgent):
     def _sync_replicas(self):
         """Data parallel: every replica starts from rank 0's weights (C2, one flat broadcast), and the EMA shadow is
         re-seeded from them (a shadow built from the pre-broadcast init would make the ranks' EMA weights differ)."""
-        if bdist.is_distributed() and not getattr(self, "_replicas_synced", False):
+        if bdist.is_distributed() and not self._replicas_synced:
             bdist.broadcast_parameters(self.model.get_params(), src=0)
             den = self._hip_denoiser()
             if den is not None:
@@ -336,14 +305,14 @@ class BesoAgent(BaseAgent):
         return mode
 
     def _sharded(self):
-        if getattr(self, "_sharded_ex", None) is None:
+        if self._sharded_ex is None:
             self._sharded_ex = bdist.ShardedExchange(self.model.get_params())
         return self._sharded_ex
 
     def _complete_ema(self):
         """Sharded C1 updates the EMA shadow of the owned parameter range only; before the shadow is read (evaluation,
         checkpoint) the ranges are gathered -- a collective: every rank gets here at the same step."""
-        if getattr(self, "_ema_partial", False) and bdist.is_distributed():
+        if self._ema_partial and bdist.is_distributed():
             self._sharded().all_gather_flat_state(self.ema_helper._flat)
             self.ema_helper.version += 1
         self._ema_partial = False
@@ -429,45 +398,51 @@ class BesoAgent(BaseAgent):
         log.info("Training done!")
 
     # ------------------------------------------------------------------ training step internals
+    def _side_stream(self, attr: str, device):
+        """The step's side stream kept in ``self.<attr>``, created on first use."""
+        if getattr(self, attr) is None:
+            setattr(self, attr, torch.cuda.Stream(device))
+        return getattr(self, attr)
+
     def _loss_backward(self, state, action, goal):
         """noise ~ N(0, I), sigma ~ the configured density, score-matching loss, backward (beso_agent.py:226-235)."""
-        noise = torch.randn_like(action)
+        return self._hip_loss_backward(state, action, goal, input_grads=False, exchange=True)
+
+    def _hip_loss_backward(self, state, action, goal, *, input_grads: bool, exchange: bool):
+        """The one HIP forward + backward call (beso_loss_grad) -> what ``step.loss_backward`` returns: the loss, with
+        ``input_grads`` (the encoder's caller) also (state_grad, goal_grad); the gradients land in views of one flat buffer.
+        ``exchange``: they go to the data-parallel exchange next -- pre-divided by the world size, padded for the sharded mode,
+        the early C1 stream opened in overlap mode.  The only place that sets ``_hip_step``, ``_c1_early`` and ``_loss_ready``
+        (a graph replay clears the two streams).  Without a HIP step the plain caller gets ``model.loss`` + autograd."""
+        noise = torch.randn_like(action)                           # (the draws keep this order, in front of zero_grad)
         sigma = self.make_sample_density()(shape=(len(action),), device=self.device)
         step = self.model.hip_train_step(state, action, goal, noise, sigma) if hasattr(self.model, "hip_train_step") else None
-        if step is not None:
-            # HIP forward + backward (beso_loss_grad): gradients land in views of one flat buffer, already
-            # divided by the world size for the data-parallel mean
-            self.optimizer.zero_grad(set_to_none=True)
-            self._hip_step = step
-            # under data parallelism the all-reduce of the upper layers' gradients starts under the backward of the lower
-            # ones: the call orders self._c1_stream behind the completion of that range (BESO_AMD_C1_OVERLAP=0: one flat
-            # all-reduce after the backward)
-            early = None
-            if bdist.is_distributed() and self._c1_mode() == "sharded":
-                step.pad_to = self._sharded().padded
-            if bdist.is_distributed() and state.is_cuda and self._c1_mode() == "overlap" \
-                    and not torch.cuda.is_current_stream_capturing():
-                if getattr(self, "_c1_stream", None) is None:
-                    self._c1_stream = torch.cuda.Stream(state.device)
-                early = self._c1_stream
-            self._c1_early = early
-            # the loss value is final a third of the way into the step: a side stream is released at that point, and
-            # train_step reads the loss there -- its `loss.item()` (beso_agent.py:248) then returns while the backward pass
-            # and the optimizer are still running, and the host prepares the next step under them (BESO_AMD_ASYNC_LOSS=0:
-            # the read waits for the whole step, as a plain .item() on the compute stream does)
-            self._loss_ready = None
-            if state.is_cuda and os.environ.get("BESO_AMD_ASYNC_LOSS", "1") != "0" and not torch.cuda.is_current_stream_capturing():
-                if getattr(self, "_loss_stream", None) is None:
-                    self._loss_stream = torch.cuda.Stream(state.device)
-                self._loss_ready = self._loss_stream
-            # (goal masking for classifier-free guidance, mask_cond, is applied by the kernel from cond_mask_prob)
-            return step.loss_backward(state, action, goal, noise, sigma, grad_scale=1.0 / bdist.world_size(),
-                                      early_stream=early, loss_stream=self._loss_ready)
-        self._hip_step = None
-        loss = self.model.loss(state, action, goal, noise, sigma)
-        self.optimizer.zero_grad()
-        loss.backward()
-        return loss
+        if step is None and input_grads:
+            raise NotImplementedError("a trainable input encoder needs the HIP training step (the beso_amd GCDenoiser / "
+                                      "DiffusionGPT on the GPU)")
+        self._hip_step, self._c1_early, self._loss_ready = step, None, None
+        if step is None:
+            loss = self.model.loss(state, action, goal, noise, sigma)
+            self.optimizer.zero_grad()
+            loss.backward()
+            return loss
+        self.optimizer.zero_grad(set_to_none=True)
+        # side streams: on the GPU, outside a graph capture (the encoder's caller is not asked: it has its HIP step and no graph)
+        streams = input_grads or (state.is_cuda and not torch.cuda.is_current_stream_capturing())
+        if exchange and bdist.is_distributed() and self._c1_mode() == "sharded":
+            step.pad_to = self._sharded().padded
+        # under data parallelism the all-reduce of the upper layers' gradients starts under the backward of the lower ones: the
+        # call orders self._c1_stream behind the completion of that range (BESO_AMD_C1_OVERLAP=0: one flat all-reduce afterwards)
+        if exchange and streams and bdist.is_distributed() and self._c1_mode() == "overlap":
+            self._c1_early = self._side_stream("_c1_stream", state.device)
+        # the loss value is final a third of the way into the step: a side stream is released at that point, and train_step reads
+        # the loss there -- its `loss.item()` (beso_agent.py:248) then returns while the backward pass and the optimizer are still
+        # running, and the host prepares the next step under them (BESO_AMD_ASYNC_LOSS=0: the read waits for the whole step)
+        if streams and os.environ.get("BESO_AMD_ASYNC_LOSS", "1") != "0":
+            self._loss_ready = self._side_stream("_loss_stream", state.device)
+        # (goal masking for classifier-free guidance, mask_cond, is applied by the kernel from cond_mask_prob)
+        return step.loss_backward(state, action, goal, noise, sigma, grad_scale=1.0 / bdist.world_size() if exchange else 1.0,
+                                  early_stream=self._c1_early, loss_stream=self._loss_ready, input_grads=input_grads)
 
     def _use_train_graph(self, state) -> bool:
         # opt-in: measured 16.6 vs 17.4 ms per 1024-sample step -- the eager step is bound by its fp32 kernels,
@@ -486,11 +461,11 @@ class BesoAgent(BaseAgent):
         return True
 
     def _graphed_loss_backward(self, state, action, goal):
-        """The same forward + backward replayed as ONE HIP graph per batch shape.  The eager training step
-        issues several thousand small kernels; the graph removes the launch gaps and changes no arithmetic
-        (opt-in, BESO_AMD_TRAIN_GRAPH=1: the measured gain is 5 %).  Inputs are copied into static
-        buffers, noise / sigma / dropout masks are drawn inside the graph from torch's graph-safe generator,
-        gradients land in static .grad tensors that the (fused) optimizer reads afterwards."""
+        """The same forward + backward replayed as ONE HIP graph per batch shape.  The eager training step issues several thousand
+        small kernels; the graph removes the launch gaps and changes no arithmetic (opt-in, BESO_AMD_TRAIN_GRAPH=1: the measured
+        gain is 5 %).  Inputs are copied into static buffers, noise / sigma / dropout masks are drawn inside the graph from torch's
+        graph-safe generator, gradients land in static .grad tensors that the (fused) optimizer reads afterwards."""
+        self._c1_early = self._loss_ready = None             # a replay releases no side stream (`_hip_step` stays what it was)
         key = (tuple(state.shape), tuple(action.shape), None if goal is None else tuple(goal.shape))
         g = self._train_graphs.get(key)
         if g is None:
@@ -532,10 +507,102 @@ class BesoAgent(BaseAgent):
             g["graph"].replay()
         return g["loss"]
 
+    def _prepare_step(self, batch):
+        """Phase 1, prepare: the batch as scaled (state, action, goal) and the model in training mode."""
+        state, action, goal = self.process_batch(batch, predict=False)
+        if not self.model.training:          # (.train() / .eval() set the whole tree: the root's flag tells; walking the 69 modules
+            self.model.train()               #  costs 0.1 ms per step)
+        self.model.training = True
+        return state, action, goal
+
+    def _forward_backward(self, state, action, goal):
+        """Phase 2, forward/backward -> the loss (0-d tensor), the gradients in ``.grad``: behind the trainable encoder if there
+        is one, else as a replayed graph (BESO_AMD_TRAIN_GRAPH=1), else the plain call.  Each sets what phases 3 and 5 read."""
+        enc = self._trainable_encoder()
+        if enc is not None:
+            return self._encoded_loss_backward(enc, state, action, goal)
+        if self._use_train_graph(state):
+            return self._graphed_loss_backward(state, action, goal)
+        return self._loss_backward(state, action, goal)
+
+    def _exchange(self, loss):
+        """Phase 3, exchange (data parallel only) -> (loss, shard).  C3 first, where the loss has its own stream: its mean over
+        the global batch is exchanged there, in front of C1 (every rank issues its collectives in this order), so that it waits
+        for the forward half only.  Then C1 as ``_c1_mode`` says; ``shard``: the range a reduce-scatter left this rank, or None."""
+        if not bdist.is_distributed():
+            return loss, None
+        if self._loss_ready is not None:
+            with torch.cuda.stream(self._loss_ready):
+                loss = bdist.all_reduce_mean(loss.detach().clone())
+        flat = self._hip_step.flat_grads() if self._hip_step is not None else None
+        sharded = self._c1_mode() == "sharded"
+        if flat is not None and sharded and isinstance(self.optimizer, FusedAdam):
+            # reduce-scatter: this rank ends up with the summed gradient of the parameter range it owns
+            ex = self._sharded()
+            ex.reduce_scatter_grads(self._hip_step.flat_grads_padded())
+            return loss, (ex.lo, ex.hi)
+        if flat is not None and self._c1_early is not None:
+            bdist.all_reduce_sum_overlapped(flat, self._hip_step.early_range(), self._c1_early)
+        elif flat is not None:
+            bdist.all_reduce_sum(flat)                    # C1 on the flat buffer the kernels wrote (pre-scaled)
+        else:
+            if self._grad_bucket is None:
+                self._grad_bucket = bdist.GradientBucket(self.model.get_params())
+            self._grad_bucket.sync(decomposed=sharded)   # (eager optimizer: the same exchange as its two halves)
+        return loss, None
+
+    def _update(self, shard):
+        """Phase 4, update: count the step, then ``_optimizer_step`` of the denoiser -- over ``shard`` only after a reduce-scatter,
+        which leaves the EMA shadow partial -- and of the trainable encoder.  ``last_grad_norm()`` is the denoiser's alone."""
+        self.steps += 1
+        do_ema = self.steps % self.update_ema_every_n_steps == 0
+        norm = self._optimizer_step(self.optimizer, self.model.get_params, self.ema_helper, self.lr_scheduler, do_ema, shard,
+                                    ema_params=self.model.parameters)
+        if norm is not None:
+            self._eager_grad_norm = norm
+        if shard is not None:
+            self._ema_partial = self._ema_partial or do_ema
+        enc = self._trainable_encoder()
+        if enc is not None:
+            self._optimizer_step(self.encoder_optimizer, enc.get_params, self.encoder_ema, self.encoder_lr_scheduler, do_ema)
+
+    def _optimizer_step(self, optimizer, params, ema, scheduler, do_ema, shard=None, ema_params=None):
+        """Optimizer + LR scheduler + (with ``do_ema``) EMA, clipped / guarded as the agent was built -> the norm
+        ``clip_grad_norm_`` measured, else None.  The eager path clips ``params()`` and updates the EMA from ``ema_params()``
+        (default ``params``; the denoiser's walks ``model.parameters()``, as the reference's).  ``shard``: the denoiser's only."""
+        if not isinstance(optimizer, FusedAdam):
+            norm = torch.nn.utils.clip_grad_norm_(list(params()), self.max_grad_norm) if self.max_grad_norm is not None else None
+            optimizer.step()
+            scheduler.step()
+            if do_ema:
+                ema.update((ema_params or params)())
+            return norm
+        # Adam(W) over all tensors and the EMA of the updated parameters in ONE HIP launch -- over the owned range only in the
+        # sharded exchange, followed by the all-gather of the updated parameters
+        if self.max_grad_norm is None and not self.skip_nonfinite_steps:
+            optimizer.step(ema=ema if do_ema else None, shard=shard)
+        else:
+            # (sharded exchange: each rank reduces the squared norm of its own range; the sum over the ranks is the whole
+            # gradient's.  flat / overlap: every rank holds the full reduced gradient and computes the same norm)
+            optimizer.step(ema=ema if do_ema else None, shard=shard, max_grad_norm=self.max_grad_norm,
+                           skip_nonfinite=self.skip_nonfinite_steps, reduce_sumsq=bdist.all_reduce_sum if shard is not None else None)
+        if shard is not None:
+            self._sharded().all_gather_params()
+        scheduler.step()
+
+    def _read_loss(self, loss) -> float:
+        """Phase 5, read the loss: on the loss stream where the step has one -- the read then returns behind the forward
+        half -- else on the compute stream, behind the whole step and, data parallel, behind the late C3."""
+        if self._loss_ready is not None:
+            with torch.cuda.stream(self._loss_ready):
+                return loss.item()
+        if bdist.is_distributed():
+            loss = bdist.all_reduce_mean(loss.detach().clone())      # C3: the logged loss is the global-batch mean
+        return loss.item()
+
     def train_step(self, batch: dict):
-        """One score-matching step (beso_agent.py:215-248): noise ~ N(0, I), sigma ~ the configured
-        density, loss = GCDenoiser.loss, optimizer + LR scheduler + EMA.  Under data parallelism the
-        gradients are averaged over the ranks first.
+        """One score-matching step (beso_agent.py:215-248) in five phases: noise ~ N(0, I), sigma ~ the configured density, loss =
+        GCDenoiser.loss, optimizer + LR scheduler + EMA.  Under data parallelism the gradients are averaged over the ranks first.
 
         Completion semantics (BESO_AMD_ASYNC_LOSS=1, the default): the returned float is this step's loss, but the call
         returns when the FORWARD half is done -- the backward pass and the optimizer of this step are still queued on the
@@ -545,74 +612,11 @@ class BesoAgent(BaseAgent):
         to the step (the library also runs the next step's weight copies on it): nothing else may be queued there.
         Everything later on the compute stream is ordered behind the update as usual; BESO_AMD_ASYNC_LOSS=0 restores the
         reference's full synchronisation per step."""
-        state, action, goal = self.process_batch(batch, predict=False)
-        if not self.model.training:          # (.train() / .eval() set the whole tree: the root's flag tells; walking the 69 modules
-            self.model.train()               #  costs 0.1 ms per step)
-        self.model.training = True
-        self._c1_early = None
-        self._loss_ready = None
-        enc = self._trainable_encoder()
-        if enc is not None:
-            loss = self._encoded_loss_backward(enc, state, action, goal)
-        elif self._use_train_graph(state):
-            loss = self._graphed_loss_backward(state, action, goal)
-        else:
-            loss = self._loss_backward(state, action, goal)
-        shard = None
-        loss_stream = getattr(self, "_loss_ready", None)
-        if bdist.is_distributed() and loss_stream is not None:
-            # C3 first: the global-batch mean of the loss is exchanged on the loss stream, in front of the gradients' exchange
-            # (every rank issues its collectives in this order), so that it waits for the forward half only
-            with torch.cuda.stream(loss_stream):
-                loss = bdist.all_reduce_mean(loss.detach().clone())
-        if bdist.is_distributed():
-            flat = self._hip_step.flat_grads() if getattr(self, "_hip_step", None) is not None else None
-            sharded = self._c1_mode() == "sharded"
-            if flat is not None and sharded and isinstance(self.optimizer, FusedAdam):
-                # reduce-scatter: this rank ends up with the summed gradient of the parameter range it owns
-                ex = self._sharded()
-                ex.reduce_scatter_grads(self._hip_step.flat_grads_padded())
-                shard = (ex.lo, ex.hi)
-            elif flat is not None and getattr(self, "_c1_early", None) is not None:
-                bdist.all_reduce_sum_overlapped(flat, self._hip_step.early_range(), self._c1_early)
-            elif flat is not None:
-                bdist.all_reduce_sum(flat)                    # C1 on the flat buffer the kernels wrote (pre-scaled)
-            else:
-                if self._grad_bucket is None:
-                    self._grad_bucket = bdist.GradientBucket(self.model.get_params())
-                self._grad_bucket.sync(decomposed=sharded)   # (eager optimizer: the same exchange as its two halves)
-        self.steps += 1
-        do_ema = self.steps % self.update_ema_every_n_steps == 0
-        if isinstance(self.optimizer, FusedAdam):
-            # Adam(W) over all tensors and the EMA of the updated parameters in ONE HIP launch -- over the owned range
-            # only in the sharded exchange, followed by the all-gather of the updated parameters
-            if self.max_grad_norm is None and not self.skip_nonfinite_steps:
-                self.optimizer.step(ema=self.ema_helper if do_ema else None, shard=shard)
-            else:
-                # (sharded exchange: each rank reduces the squared norm of its own range; the sum over the ranks is the whole
-                # gradient's.  flat / overlap: every rank holds the full reduced gradient and computes the same norm)
-                self.optimizer.step(ema=self.ema_helper if do_ema else None, shard=shard, max_grad_norm=self.max_grad_norm,
-                                    skip_nonfinite=self.skip_nonfinite_steps,
-                                    reduce_sumsq=bdist.all_reduce_sum if shard is not None else None)
-            if shard is not None:
-                self._sharded().all_gather_params()
-                self._ema_partial = getattr(self, "_ema_partial", False) or do_ema
-            self.lr_scheduler.step()
-        else:
-            if self.max_grad_norm is not None:
-                self._eager_grad_norm = torch.nn.utils.clip_grad_norm_(self.model.get_params(), self.max_grad_norm)
-            self.optimizer.step()
-            self.lr_scheduler.step()
-            if do_ema:
-                self.ema_helper.update(self.model.parameters())
-        if enc is not None:
-            self._encoder_optimizer_step(enc, do_ema)
-        if loss_stream is not None:
-            with torch.cuda.stream(loss_stream):
-                return loss.item()
-        if bdist.is_distributed():
-            loss = bdist.all_reduce_mean(loss.detach().clone())      # C3: the logged loss is the global-batch mean
-        return loss.item()
+        state, action, goal = self._prepare_step(batch)
+        loss = self._forward_backward(state, action, goal)
+        loss, shard = self._exchange(loss)
+        self._update(shard)
+        return self._read_loss(loss)
 
     def last_grad_norm(self) -> torch.Tensor:
         """The global L2 norm of the last training step's gradient, before clipping (``max_grad_norm`` or
@@ -944,21 +948,16 @@ class BesoAgent(BaseAgent):
         self.model.load_state_dict(state)
         self.ema_helper = ExponentialMovingAverage(self.model.get_params(), self.decay, self.device)
         self._ema_packed_key = None
-        self._load_encoder_weights(weights_path)
-        log.info('Loaded pre-trained model parameters')
-
-    def _load_encoder_weights(self, weights_path: str) -> None:
-        """``encoder_state_dict.pth`` (the EMA weights) into a trainable encoder, its EMA shadow re-seeded from them.  A
-        directory without the file loads into a ``NoEncoder`` agent as before; into an agent with an encoder it raises."""
         enc = self._trainable_encoder()
-        if enc is None:
-            return
-        path = os.path.join(weights_path, "encoder_state_dict.pth")
-        if not os.path.exists(path):
-            raise FileNotFoundError(f"{path}: the agent has a trainable input encoder ({type(enc).__name__}) but the "
-                                    "checkpoint directory holds no encoder weights")
-        enc.network.load_state_dict(torch.load(path, map_location=self.device))
-        self.encoder_ema = ExponentialMovingAverage(enc.get_params(), self.decay, self.device)
+        if enc is not None:
+            # ``encoder_state_dict.pth`` (the EMA weights) likewise; a directory without it loads into a ``NoEncoder`` agent only
+            path = os.path.join(weights_path, "encoder_state_dict.pth")
+            if not os.path.exists(path):
+                raise FileNotFoundError(f"{path}: the agent has a trainable input encoder ({type(enc).__name__}) but the "
+                                        "checkpoint directory holds no encoder weights")
+            enc.network.load_state_dict(torch.load(path, map_location=self.device))
+            self.encoder_ema = ExponentialMovingAverage(enc.get_params(), self.decay, self.device)
+        log.info('Loaded pre-trained model parameters')
 
     def store_model_weights(self, store_path: str) -> None:
         """EMA weights -> model_state_dict.pth, raw weights -> non_ema_model_state_dict.pth
@@ -966,25 +965,25 @@ class BesoAgent(BaseAgent):
         self._complete_ema()
         if bdist.rank() != 0:
             return
-        raw = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
-        ema = dict(raw)
-        if self.use_ema:
-            names = [n for n, p in self.model.named_parameters() if p.requires_grad]
-            for n, s in zip(names, self.ema_helper.shadow_params):
-                ema[n] = s.detach().clone()
+        ema, raw = self._state_pair(self.model, self.ema_helper)
         torch.save(ema, os.path.join(store_path, "model_state_dict.pth"))
         torch.save(raw, os.path.join(store_path, "non_ema_model_state_dict.pth"))
         enc = self._trainable_encoder()
         if enc is not None:
             # the encoder beside them: encoder_state_dict.pth (EMA) and non_ema_encoder_state_dict.pth
-            raw = {k: v.detach().clone() for k, v in enc.network.state_dict().items()}
-            ema = dict(raw)
-            if self.use_ema:
-                names = [n for n, p in enc.network.named_parameters() if p.requires_grad]
-                for n, s in zip(names, self.encoder_ema.shadow_params):
-                    ema[n] = s.detach().clone()
+            ema, raw = self._state_pair(enc.network, self.encoder_ema)
             torch.save(ema, os.path.join(store_path, "encoder_state_dict.pth"))
             torch.save(raw, os.path.join(store_path, "non_ema_encoder_state_dict.pth"))
+
+    def _state_pair(self, module, ema_helper):
+        """(EMA, raw) state dicts of ``module``: the EMA one holds ``ema_helper``'s shadow (without ``use_ema``: the raw values)."""
+        raw = {k: v.detach().clone() for k, v in module.state_dict().items()}
+        ema = dict(raw)
+        if self.use_ema:
+            names = [n for n, p in module.named_parameters() if p.requires_grad]
+            for n, s in zip(names, ema_helper.shadow_params):
+                ema[n] = s.detach().clone()
+        return ema, raw
 
     # ------------------------------------------------------------------ exact resume
     def _training_state_guard(self):

@@ -167,13 +167,13 @@ def main():
     input_grads = "--input-grads" in sys.argv
     if input_grads:                             # the agent's HIP step with the state / goal gradients asked for (and dropped)
         sys.argv.remove("--input-grads")
-        # (BesoAgent._loss_backward calls step.loss_backward(state, action, goal, noise, sigma, **keywords); the counter below
+        # (BesoAgent._hip_loss_backward calls step.loss_backward(state, action, goal, noise, sigma, **keywords); the counter below
         #  is checked after the timed window, so a changed call site cannot turn this into a silent flag-off run)
         from beso_amd.training import HipTrainStep
         plain, taken = HipTrainStep.loss_backward, [0]
 
         def with_input_grads(self, *a, **k):
-            loss, state_grad, goal_grad = plain(self, *a, input_grads=True, **k)
+            loss, state_grad, goal_grad = plain(self, *a, **dict(k, input_grads=True))
             assert state_grad is not None
             taken[0] += 1
             return loss
