@@ -11,7 +11,7 @@
 #endif
 
 // Compile-time variants -- ablations that produce wrong results for timing, phase stamps (the `#ifndef BESO_... / #define`
-// blocks in fused.hip and train.hip document each) -- exist in VARIANT builds only
+// blocks in fused.hip, train.hip and train_gemm.h document each) -- exist in VARIANT builds only
 // (tools/variants.py passes -DBESO_VARIANTS=1): the product sources refuse every override, so the shipped binary is the one
 // configuration the tests run.
 #ifndef BESO_VARIANTS
@@ -30,6 +30,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 constexpr int kWave = 64;
 constexpr int kTileMN = 128;   // generic GEMM block tile (M and N)
@@ -212,7 +213,7 @@ __device__ __forceinline__ float step_noise(int mode_bits, float o, const float*
 }
 
 // Training-mode dropout: keep-scale of one element from a counter-based hash of (seed, site, element index) -- the
-// backward pass recomputes the mask.  p = 0 never reaches this function.  (train.hip; the attention core of the one-launch
+// backward pass recomputes the mask.  p = 0 never reaches this function.  (train.hip's headers; the attention core of the one-launch
 // training forward in fused.hip draws the same mask as attn_small_kernel.)
 __device__ __forceinline__ float drop_scale(uint32_t seed, uint32_t site, size_t idx, float p, float inv_keep) {
     uint32_t h = (uint32_t)idx * 0x9E3779B1u + (uint32_t)(idx >> 32) * 0x7FEB352Du + site * 0x85EBCA77u + seed;
@@ -220,7 +221,7 @@ __device__ __forceinline__ float drop_scale(uint32_t seed, uint32_t site, size_t
     return ((float)(h >> 8) * (1.0f / 16777216.0f)) >= p ? inv_keep : 0.f;
 }
 
-// Sites and element counters of the training dropouts, in one place for the kernels that apply a mask (train.hip, the one-launch
+// Sites and element counters of the training dropouts, in one place for the kernels that apply a mask (train.hip's headers, the one-launch
 // training forward of fused.hip), the backward kernels that recompute it and the exporter (dropout_mask_kernel):
 //   attention probabilities of layer l   site 4 l       counter ((b H + h) T + i) T + j   (query i, key j: the causally masked
 //                                                       pairs own counters too, nothing consumes them)

@@ -9,7 +9,7 @@
 // F(c_in * noised) is compared with the target, the reference's operation order: forming (D - action) / c_out from the
 // preconditioned output would subtract two numbers that agree to several digits at sigma ~ sigma_min and divide by c_out ~ 1e-3.
 // The target is not stored: loss_rows_kernel recomputes noised and target from action, noise and sigma with the expressions of
-// prep_kernel (train.hip), every product, quotient and sum rounded on its own as torch rounds them.  Both reductions run in a
+// prep_kernel (train_rows.h), every product, quotient and sum rounded on its own as torch rounds them.  Both reductions run in a
 // fixed order and there is no atomic: two runs give equal bits wherever the forward does, and per_sample[b] depends on sample
 // b's values only.
 #include "common.h"

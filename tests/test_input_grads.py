@@ -1,5 +1,5 @@
 """The gradient of the training loss, and of the denoiser output, with respect to the ``state`` and ``goal`` inputs
-(``beso_loss_grad_inputs`` / ``beso_denoise_vjp_inputs``, ``input_grad_kernel`` of train.hip).
+(``beso_loss_grad_inputs`` / ``beso_denoise_vjp_inputs``, ``input_grad_kernel`` of train_rows.h).
 
 Comparator: tests/autograd_reference.py (``loss_autograd`` / ``forward_autograd``) with ``state`` / ``goal`` as leaf tensors
 that require grad; the masked cases inject the library's own masks the way tests/test_dropout_parity.py does.
