@@ -18,6 +18,7 @@ GUIDEFIT_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_guidefit.so")   # the gu
 SELECT_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_select.so")   # best-of-K action selection (include/beso_select.h)
 SCALE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_scale.so")     # MinMaxScaler's scalings (include/beso_scale.h)
 NOISE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_noise.so")     # the rollout's keyed noise (include/beso_noise.h)
+RANK_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_rank.so")       # value-ranked best-of-K selection (include/beso_rank.h)
 
 # Every upper-case integer below is BESO_<name> of include/beso_hip.h, and every table one of its enums
 # (tests/test_cabi.py compares the values, and SIGNATURES with the prototypes, against the header's text).
@@ -204,6 +205,16 @@ NOISE_SIGNATURES = {
 }
 NOISE_EXPORTS = list(NOISE_SIGNATURES)
 
+# include/beso_rank.h (libbeso_rank.so): its limits and every function it declares, in its order; the dims struct and the
+# activations are include/beso_mlp.h's
+RANK_LIMITS = {"max_k": 256, "max_act": 64}          # BESO_RANK_MAX_K, BESO_RANK_MAX_ACT
+RANK_SIGNATURES = {
+    "beso_rank_last_error": (cstr, []),
+    "beso_rank_supported": (i32, [dimsp, i32, i32, i32]),
+    "beso_rank_candidates": (i32, [vpp, i32, dimsp, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+}
+RANK_EXPORTS = list(RANK_SIGNATURES)
+
 
 class BesoHipError(RuntimeError):
     pass
@@ -258,7 +269,9 @@ _SIDE = {"mlp": (MLP_LIB_PATH, MLP_SIGNATURES, "beso_mlp.h", "the encoder", None
          "scale": (SCALE_LIB_PATH, SCALE_SIGNATURES, "beso_scale.h", "MinMaxScaler's one-launch scalings",
                    "beso_scale_last_error", "beso_scale"),
          "noise": (NOISE_LIB_PATH, NOISE_SIGNATURES, "beso_noise.h", "the rollout's keyed noise",
-                   "beso_noise_last_error", "beso_noise")}
+                   "beso_noise_last_error", "beso_noise"),
+         "rank": (RANK_LIB_PATH, RANK_SIGNATURES, "beso_rank.h", "value-ranked best-of-K action selection",
+                  "beso_rank_last_error", "beso_rank")}
 _side = {}
 
 
@@ -277,7 +290,7 @@ def _load_side(name: str) -> C.CDLL:
 
 
 def check_side(name: str, status: int, what: str) -> None:
-    """check() for a library of _SIDE that keeps its own message (select, scale, noise): the message names what was refused."""
+    """check() for a library of _SIDE that keeps its own message (select, scale, noise, rank): the message names what was refused."""
     if status == OK:
         return
     last_error, prefix = _SIDE[name][4:]
@@ -290,6 +303,7 @@ def check_side(name: str, status: int, what: str) -> None:
 check_select = functools.partial(check_side, "select")
 check_scale = functools.partial(check_side, "scale")
 check_noise_status = functools.partial(check_side, "noise")
+check_rank = functools.partial(check_side, "rank")
 
 
 def load_mlp() -> C.CDLL:
@@ -327,6 +341,11 @@ def load_scale() -> C.CDLL:
 def load_noise() -> C.CDLL:
     """The library of the rollout's keyed noise (include/beso_noise.h)."""
     return _load_side("noise")
+
+
+def load_rank() -> C.CDLL:
+    """The value-ranked best-of-K selection library of the rollout (include/beso_rank.h)."""
+    return _load_side("rank")
 
 
 _dev = None

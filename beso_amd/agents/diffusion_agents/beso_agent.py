@@ -785,7 +785,7 @@ class BesoAgent(BaseAgent):
 
     @torch.no_grad()
     def predict_best_of(self, batch: dict, k: int, select=None, bandwidth=None, new_sampler_type=None, new_sampling_steps=None,
-                        noise_scheduler=None, extra_args=None, noise=None) -> torch.Tensor:
+                        noise_scheduler=None, extra_args=None, noise=None, guide=None) -> torch.Tensor:
         """``predict`` with ``k`` action candidates per environment, reduced to ONE action each: ``select='mean'`` acts on the
         candidates' sample mean, ``'kde'`` on the candidate of the highest diagonal Gaussian kernel density among its
         siblings (``bandwidth=None``: Scott's rule); the default is 'kde' with ``use_kde``, else 'mean'.  The window
@@ -794,14 +794,18 @@ class BesoAgent(BaseAgent):
         beso_amd/candidates.py (include/beso_select.h), and the selected, clipped action is what ``action_context`` remembers.
         ``noise`` [B, k, act] is the x_T draw of the newest action (None: ``torch.randn``); with k = 1 the call returns
         ``predict``'s bits for the same draw, in ``predict``'s shape (a one-slot window gives [B, 1, act], as there).
-        ``last_best_of`` holds the call's ``candidates`` [B, k, act], ``scores`` and ``index``.  ``predict(get_mean=...)`` is
-        the reference's call and stays what it is: it draws the extra rows and reduces nothing.  Needs the GPU."""
+        ``last_best_of`` holds the call's ``candidates`` [B, k, act], ``scores`` and ``index``.  ``select='value', guide=g`` acts
+        on the candidate the ``MLPGuide`` g scores highest, q of ``[newest observation | candidate | goal]`` as the sampler sees
+        them, in ONE launch behind the sampler (include/beso_rank.h); ``scores`` are then the q values, and a bad guide is refused
+        before a context changes.  ``predict(get_mean=...)`` is the reference's call and stays what it is: it draws the extra rows
+        and reduces nothing.  Needs the GPU."""
         from ... import candidates as best_of
         k, select, bandwidth = best_of.check_arguments(k, select, bandwidth, bool(self.use_kde))
         noise_scheduler = self.noise_scheduler if noise_scheduler is None else noise_scheduler
         state, goal, _ = self.process_batch(batch, predict=True)
         state, goal = self._encode_eval(state, goal)
         act_dim = self.scaler.y_bounds.shape[1]
+        guide = best_of.check_guide(select, guide, state.shape[-1], act_dim, goal is not None, state.device, "predict_best_of")
         noise = best_of.check_noise(noise, len(state), k, act_dim, self.device)
         windowed = state.dim() == 2 and self.window_size > 1
         if windowed:
@@ -830,11 +834,15 @@ class BesoAgent(BaseAgent):
             state_k, x_k = best_of.expand(state3, x.contiguous(), lengths, noise, self.sigma_max)
             if input_state.dim() == 2:
                 state_k = state_k[:, 0].contiguous()
+            goal_n = goal if goal.dim() == 3 else goal.unsqueeze(0)          # what the ranking reads: one goal per environment, or one
             if goal.dim() == 3 and goal.shape[0] == B and B > 1:
                 goal = torch.repeat_interleave(goal, k, dim=0)
             x0_k = self.sample_loop(sigmas, x_k, state_k, goal, sampler_type, extra_args)
             x0_k = x0_k.reshape(B * k, t, act_dim).to(torch.float32).contiguous()
-            x_0, index, scores = best_of.select(x0_k, lengths, k, select, bandwidth)
+            if guide is not None:
+                x_0, index, scores = best_of.rank(state3, goal_n, x0_k, lengths, k, guide)
+            else:
+                x_0, index, scores = best_of.select(x0_k, lengths, k, select, bandwidth)
             if t > 1:
                 x_0 = x_0[:, -1, :]
             x_0 = self.scaler.clip_action(x_0)

@@ -26,7 +26,7 @@ _Tail = namedtuple("_Tail", "kind lo hi stats")
 _TAIL_ENTRY = {"zscore": ("hip", "beso_rollout_end"), "minmax": ("scale", "beso_rollout_end_minmax")}
 # A step's checked arguments (``VectorRollout._arguments``).  ``K`` is None without candidates; ``sigmas`` is the host-side schedule
 # of the sampler settings; ``slabs`` counts the step-noise slabs a seeded step draws (0: none).
-_StepArgs = namedtuple("_StepArgs", "obs K select bandwidth sampler_type sigmas slabs")
+_StepArgs = namedtuple("_StepArgs", "obs K select bandwidth sampler_type sigmas slabs guide", defaults=(None,))
 
 
 def _ptr(v):
@@ -231,7 +231,7 @@ class VectorRollout:
     # ------------------------------------------------------------------ one environment step
     @torch.no_grad()
     def step(self, obs, new_sampler_type=None, new_sampling_steps=None, noise_scheduler=None, noise=None, candidates=None,
-             select=None, bandwidth=None) -> torch.Tensor:
+             select=None, bandwidth=None, guide=None) -> torch.Tensor:
         """Raw observations ``[N, obs]`` (device or host) -> actions ``[N, act]``.  ``noise`` ``[N, 1, act]`` is the x_T draw
         of the newest action; None draws ``torch.randn((N, 1, act), device=...)``, the draw ``predict`` makes.
 
@@ -243,10 +243,15 @@ class VectorRollout:
         ``[N, K, act]`` (the newest-slot actions before the clip), ``scores`` ``[N, K]`` and ``index`` ``[N]``, and the
         sampler call's ``state_k`` / ``x_k`` / ``x0_k`` on N K rows.
 
+        ``select='value', guide=g``: the candidate the ``MLPGuide`` g scores highest -- q of ``[newest observation | candidate's
+        newest action | goal]`` as the sampler sees them (scaled) -- in ONE launch behind the sampler (include/beso_rank.h);
+        ``scores`` are then the q values.  Every sampler works: nothing is differentiated.  g (without ``use_sigma``, on the
+        model's device) may be the ``cond_func`` of the agent's ``ClassifierGuidedSampleModel`` as well.
+
         Seeded (``seed``): ``noise=None`` is the keyed draw -- x_T, the K candidates and the step noise of 'euler_ancestral',
         'ancestral' and 'dpmpp_2s_ancestral' on their one-launch path, all from one launch -- and a sampler that would draw
         from the global generator inside a Python loop is a ValueError.  An explicit ``noise`` still wins."""
-        a = self._arguments(obs, noise, new_sampler_type, new_sampling_steps, noise_scheduler, candidates, select, bandwidth)
+        a = self._arguments(obs, noise, new_sampler_type, new_sampling_steps, noise_scheduler, candidates, select, bandwidth, guide)
         xs, ys = self._scaler_plan()
         noise, noise_k, step_noise = self._draws(a, noise)
         state, x = self._begin(a.obs, noise, xs)
@@ -259,10 +264,12 @@ class VectorRollout:
         self.last = _Last({"state": state, "x": x, "lengths": self.lengths, "x0": x0, **picked})
         return pred
 
-    def _arguments(self, obs, noise, new_sampler_type, new_sampling_steps, noise_scheduler, candidates, select, bandwidth):
-        """Phase 1: every refusal of a step -- the best-of-K arguments, the shapes of ``obs`` and of an explicit ``noise``, the
-        goal, the schedule, what a seeded step can serve (_keyed_step_slabs) -- as a ValueError, and the sampler settings
-        resolved.  Touches no device state and enqueues nothing: after a refusal no window, counter or reset flag has changed."""
+    def _arguments(self, obs, noise, new_sampler_type, new_sampling_steps, noise_scheduler, candidates, select, bandwidth,
+                   guide=None):
+        """Phase 1: every refusal of a step -- the best-of-K arguments and the guide of ``select='value'``, the shapes of ``obs``
+        and of an explicit ``noise``, the goal, the schedule, what a seeded step can serve (_keyed_step_slabs) -- as a ValueError
+        (a guide of the wrong type: TypeError), and the sampler settings resolved.  Touches no device state and enqueues nothing:
+        after a refusal no window, counter or reset flag has changed."""
         agent, N = self.agent, self.n_envs
         K = None
         if candidates is not None:
@@ -270,8 +277,10 @@ class VectorRollout:
             max_act = _lib.SELECT_LIMITS["max_act"]
             if self.act_dim > max_act:
                 raise ValueError(f"candidates: act_dim {self.act_dim} exceeds the {max_act} components the selection takes")
-        elif select is not None or bandwidth is not None:
-            raise ValueError("select and bandwidth belong to candidates=K")
+            guide = best_of.check_guide(select, guide, self.obs_dim, self.act_dim, getattr(self, "goal", None) is not None,
+                                        self.device, "VectorRollout.step")
+        elif select is not None or bandwidth is not None or guide is not None:
+            raise ValueError("select, bandwidth and guide belong to candidates=K")
         if noise is not None and tuple(torch.as_tensor(noise).shape) != (N, K or 1, self.act_dim):
             raise ValueError(f"noise must be [{N}, {K or 1}, {self.act_dim}], got {tuple(torch.as_tensor(noise).shape)}")
         if self.goal_len and self.goal is None:
@@ -283,7 +292,7 @@ class VectorRollout:
         n_steps = agent.num_sampling_steps if new_sampling_steps is None else new_sampling_steps
         sigmas = agent.get_noise_schedule(n_steps, agent.noise_scheduler if noise_scheduler is None else noise_scheduler)
         slabs = 0 if self._keyed is None else self._keyed_step_slabs(sampler_type, sigmas, N * (K or 1))
-        return _StepArgs(obs, K, select, bandwidth, sampler_type, sigmas, slabs)
+        return _StepArgs(obs, K, select, bandwidth, sampler_type, sigmas, slabs, guide)
 
     def _draws(self, a, noise):
         """Phase 2, the one place that says where a step's draws come from -> (noise [N, 1, act] for begin's newest slot, noise_k
@@ -329,9 +338,11 @@ class VectorRollout:
 
     def _sample(self, a, state, x, noise_k, step_noise):
         """Phase 4: ONE sampler call on the EMA weights in eval mode -> (x0 [N, W, act], the best-of-K entries of ``last``).
-        With candidates the N windows are expanded to N K rows in front of it and the selection picks N of them behind it; a
-        seeded step hands its keyed step noise to the sampler (gc_sampling.keyed_step_noise)."""
+        With candidates the N windows are expanded to N K rows in front of it and the selection picks N of them behind it
+        ('value': the ranking, which reads the un-expanded state and goal); a seeded step hands its keyed step noise to the
+        sampler (gc_sampling.keyed_step_noise)."""
         agent, N, W, K = self.agent, self.n_envs, self.window, a.K
+        state_n = state
         with agent._ema_scope():
             if agent.model.training:
                 agent.model.eval()
@@ -352,7 +363,10 @@ class VectorRollout:
         if K is None:
             return x0, {}
         x0_k = x0
-        x0, index, scores = best_of.select(x0_k, self.lengths, K, a.select, a.bandwidth)
+        if a.select == best_of.VALUE:
+            x0, index, scores = best_of.rank(state_n, self.goal, x0_k, self.lengths, K, a.guide)
+        else:
+            x0, index, scores = best_of.select(x0_k, self.lengths, K, a.select, a.bandwidth)
         return x0, {"scores": scores, "index": index, "state_k": state, "x_k": x, "x0_k": x0_k}
 
     def _end(self, x0, ys):

@@ -13,7 +13,18 @@ divided by `steps`, the record holds the median over the repetitions and the ext
   launches      beso_candidates_expand + beso_candidates_select on the step's own buffers
   torch_ops     repeat_interleave x 3 + indexed write, then gather + mean / (std, cdist, logsumexp, argmax) + gather -- this
                 form lives here, not in the package
-One JSON line per configuration is appended to --out."""
+One JSON line per configuration is appended to --out.
+
+    python tools/bench_candidates.py --select value --guide 69,256,2 [--cands 8,32] [--out profiles/value_select_bench.jsonl]
+
+measures value-ranked selection (include/beso_rank.h) with a guide MLPNetwork IN -> HIDDEN x LAYERS -> 1 (Mish) instead, the
+forms alternating in the same way:
+  step          roll.step(obs, candidates=K, select='value', guide=g)
+  plain_step    roll.step(obs) on a second rollout of the same N
+  kde_step      roll.step(obs, candidates=K, select='kde') on a third
+  launch        beso_rank_candidates alone on the step's own buffers
+  torch_ops     the same ranking with torch ops: repeat_interleave / cat rows, guide.network(...) (beso_mlp_fwd), argmax,
+                gather -- this form lives here, not in the package"""
 import argparse
 import json
 import os
@@ -59,14 +70,85 @@ def torch_select(x0_k, lengths, K, select):
     return win[rows, index], scores
 
 
+@torch.no_grad()
+def torch_rank(guide, state, goal, x0_k, lengths, K):
+    NK, W, act = x0_k.shape
+    N = NK // K
+    rows, slot = torch.arange(N, device=x0_k.device), lengths.long() - 1
+    win = x0_k.view(N, K, W, act)
+    parts = [torch.repeat_interleave(state[rows, slot], K, dim=0), win[rows, :, slot].reshape(NK, act)]
+    if goal is not None:
+        parts.append(torch.repeat_interleave(goal[:, -1], K, dim=0))
+    scores = guide.network(torch.cat(parts, dim=-1)).view(N, K)
+    index = scores.argmax(dim=1)
+    return win[rows, index], index, scores
+
+
+def main_value(a, cfg, agent, goal, box):
+    """--select value: see the module docstring."""
+    from beso_amd.agents.diffusion_agents.k_diffusion.guides import MLPGuide
+    from beso_amd.networks.mlps.mlps import MLPNetwork
+    in_dim, hidden, layers = (int(v) for v in a.guide.split(","))
+    torch.manual_seed(0)
+    guide = MLPGuide(MLPNetwork(in_dim, hidden, layers, 1, activation="Mish", device=DEV))
+    warm = max(20, 3 * cfg.obs_seq_len)
+    for N in [int(v) for v in a.envs.split(",")]:
+        obs = [torch.randn(N, cfg.obs_dim) for _ in range(a.steps)]
+        for K in [int(v) for v in a.cands.split(",")]:
+            roll, plain, kde = (agent.vector_rollout(N) for _ in range(3))
+            for r in (roll, plain, kde):
+                r.set_goal(goal)
+            forms = {"step": lambda i: roll.step(obs[i], candidates=K, select="value", guide=guide),
+                     "plain_step": lambda i: plain.step(obs[i]),
+                     "kde_step": lambda i: kde.step(obs[i], candidates=K, select="kde")}
+            for i in range(warm):
+                for fn in forms.values():
+                    fn(i % a.steps)
+            last = dict(roll.last)
+            lengths = roll.lengths.clone()
+            forms["launch"] = lambda i: best_of.rank(last["state"], roll.goal, last["x0_k"], lengths, K, guide)
+            forms["torch_ops"] = lambda i: torch_rank(guide, last["state"], roll.goal, last["x0_k"], lengths, K)
+            got, ref = forms["launch"](0), forms["torch_ops"](0)
+            agree = float((got[2] - ref[2]).abs().max())
+            same_index = bool((got[1].long() == ref[1]).all())
+            for i in range(5):
+                forms["launch"](i)
+                forms["torch_ops"](i)
+            t = {k: [] for k in forms}
+            for _ in range(a.reps):
+                for k, fn in forms.items():
+                    t[k].append(timed(fn, a.steps))
+            r = {"bench": "value_select", "config": "kitchen", "precision": "bf16", "sampler": "ddim", "sampling_steps": 3,
+                 "n_envs": N, "candidates": K, "select": "value", "guide": [in_dim, hidden, layers, 1], "sampler_rows": N * K,
+                 "steps_per_rep": a.steps, "reps": a.reps, "max_abs_score_diff_to_torch_ops": agree, "same_index_as_torch_ops": same_index}
+            for k in forms:
+                r[k + "_wall_ms"] = stats([v[0] for v in t[k]])
+                r[k + "_event_ms"] = stats([v[1] for v in t[k]])
+            med = lambda k: r[k + "_wall_ms"]["median"]                                  # noqa: E731
+            r["step_over_plain"] = round(med("step") / med("plain_step"), 3)
+            r["step_over_kde_step"] = round(med("step") / med("kde_step"), 3)
+            r["torch_ops_over_launch"] = round(med("torch_ops") / med("launch"), 2)
+            r.update(box)
+            line = json.dumps(r)
+            print(line, flush=True)
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", default="1,16,100")
     ap.add_argument("--cands", default="1,8,32")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "candidates_bench.jsonl"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--select", default=None, choices=("value",), help="measure value-ranked selection (needs --guide)")
+    ap.add_argument("--guide", default=None, help="IN,HIDDEN,LAYERS of the ranking guide's MLPNetwork")
     a = ap.parse_args()
+    if (a.select is None) != (a.guide is None):
+        raise SystemExit("--select value and --guide IN,HIDDEN,LAYERS go together")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "value_select_bench.jsonl" if a.select else "candidates_bench.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("bench_candidates.py measures on the GPU; none found")
     cfg = O.SHAPES["kitchen"]
@@ -80,6 +162,8 @@ def main():
     goal = torch.randn(cfg.goal_seq_len, cfg.obs_dim)
     warm = max(20, 3 * cfg.obs_seq_len)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.select == "value":
+        return main_value(a, cfg, agent, goal, box)
     for N in [int(v) for v in a.envs.split(",")]:
         obs = [torch.randn(N, cfg.obs_dim) for _ in range(a.steps)]
         for K in [int(v) for v in a.cands.split(",")]:
