@@ -19,6 +19,7 @@ SELECT_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_select.so")   # best-of-K 
 SCALE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_scale.so")     # MinMaxScaler's scalings (include/beso_scale.h)
 NOISE_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_noise.so")     # the rollout's keyed noise (include/beso_noise.h)
 RANK_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_rank.so")       # value-ranked best-of-K selection (include/beso_rank.h)
+CRITIC_LIB_PATH = os.path.join(_HERE, "lib", "libbeso_critic.so")   # the IQL critic's fit step (include/beso_critic_fit.h)
 
 # Every upper-case integer below is BESO_<name> of include/beso_hip.h, and every table one of its enums
 # (tests/test_cabi.py compares the values, and SIGNATURES with the prototypes, against the header's text).
@@ -215,6 +216,14 @@ RANK_SIGNATURES = {
 }
 RANK_EXPORTS = list(RANK_SIGNATURES)
 
+# include/beso_critic_fit.h (libbeso_critic.so): every function it declares, in its order
+CRITIC_SIGNATURES = {
+    "beso_critic_last_error": (cstr, []),
+    "beso_critic_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "beso_critic_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+CRITIC_EXPORTS = list(CRITIC_SIGNATURES)
+
 
 class BesoHipError(RuntimeError):
     pass
@@ -271,7 +280,9 @@ _SIDE = {"mlp": (MLP_LIB_PATH, MLP_SIGNATURES, "beso_mlp.h", "the encoder", None
          "noise": (NOISE_LIB_PATH, NOISE_SIGNATURES, "beso_noise.h", "the rollout's keyed noise",
                    "beso_noise_last_error", "beso_noise"),
          "rank": (RANK_LIB_PATH, RANK_SIGNATURES, "beso_rank.h", "value-ranked best-of-K action selection",
-                  "beso_rank_last_error", "beso_rank")}
+                  "beso_rank_last_error", "beso_rank"),
+         "critic": (CRITIC_LIB_PATH, CRITIC_SIGNATURES, "beso_critic_fit.h", "the IQL critic's fit step",
+                    "beso_critic_last_error", "beso_critic")}
 _side = {}
 
 
@@ -290,7 +301,7 @@ def _load_side(name: str) -> C.CDLL:
 
 
 def check_side(name: str, status: int, what: str) -> None:
-    """check() for a library of _SIDE that keeps its own message (select, scale, noise, rank): the message names what was refused."""
+    """check() for a library of _SIDE that keeps its own message (select, scale, noise, rank, critic): the message names what was refused."""
     if status == OK:
         return
     last_error, prefix = _SIDE[name][4:]
@@ -304,6 +315,7 @@ check_select = functools.partial(check_side, "select")
 check_scale = functools.partial(check_side, "scale")
 check_noise_status = functools.partial(check_side, "noise")
 check_rank = functools.partial(check_side, "rank")
+check_critic = functools.partial(check_side, "critic")
 
 
 def load_mlp() -> C.CDLL:
@@ -346,6 +358,11 @@ def load_noise() -> C.CDLL:
 def load_rank() -> C.CDLL:
     """The value-ranked best-of-K selection library of the rollout (include/beso_rank.h)."""
     return _load_side("rank")
+
+
+def load_critic() -> C.CDLL:
+    """The library of the IQL critic's fit step (include/beso_critic_fit.h)."""
+    return _load_side("critic")
 
 
 _dev = None

@@ -25,7 +25,8 @@ UNITS = ["api", "elementwise", "attention", "gemm", "fused", "fused_f16", "optim
 # Every library: (path, units, public header under include/).  The MLP observation / goal encoder, the residual MLP encoder and
 # the guide gradient of classifier-guided sampling (they share csrc/mlp_tile.h), the guide's fit step (it shares
 # csrc/guide_tile.h with the guide gradient), the best-of-K action selection of the
-# rollout, MinMaxScaler's scalings, the rollout's keyed noise, and the value-ranked selection (it shares csrc/mlp_tile.h too), are
+# rollout, MinMaxScaler's scalings, the rollout's keyed noise, the value-ranked selection (it shares csrc/mlp_tile.h too), and the
+# IQL critic's fit step, are
 # libraries of their own, built with the product library and under the same stamp: libbeso_hip.so's dynamic symbol table stays exactly include/beso_hip.h
 LIBS = [(LIB, UNITS, "beso_hip.h"),
         (DEV_LIB, UNITS, "beso_hip_debug.h"),
@@ -36,7 +37,8 @@ LIBS = [(LIB, UNITS, "beso_hip.h"),
         (os.path.join(LIBDIR, "libbeso_select.so"), ["select"], "beso_select.h"),
         (os.path.join(LIBDIR, "libbeso_scale.so"), ["scale"], "beso_scale.h"),
         (os.path.join(LIBDIR, "libbeso_noise.so"), ["noise"], "beso_noise.h"),
-        (os.path.join(LIBDIR, "libbeso_rank.so"), ["rank"], "beso_rank.h")]
+        (os.path.join(LIBDIR, "libbeso_rank.so"), ["rank"], "beso_rank.h"),
+        (os.path.join(LIBDIR, "libbeso_critic.so"), ["critic_fit"], "beso_critic_fit.h")]
 PRODUCT_LIBS = [lib for lib in LIBS if lib[0] != DEV_LIB]     # what a plain build makes and is_current() asks for
 ARCH = "gfx950"
 # -fvisibility=hidden: the dynamic symbol table is exactly include/beso_hip.h (its declarations carry default visibility)

@@ -1,0 +1,418 @@
+"""``StateValue``, ``CriticTrainer`` (k_diffusion/critic_fit.py) and the C ABI of libbeso_critic.so (include/beso_critic_fit.h), as far
+as they go without a GPU: the float32 numpy re-statements of ``beso_critic_loss``'s rounding order and of ``beso_critic_rows`` that
+tests/test_critic_fit_gpu.py compares bits with, every refusal by name, and the binding table against the header."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from beso_amd import _lib
+from beso_amd.agents.diffusion_agents.k_diffusion.critic_fit import CriticTrainer, StateValue
+from beso_amd.agents.diffusion_agents.k_diffusion.guides import MLPGuide
+from beso_amd.networks.mlps.mlps import MLPNetwork
+from test_guide_fit import lane_order_sum
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+EPS = 2.0 ** -24        # one fp32 rounding
+GAMMA, EXPECTILE = 0.99, 0.7
+SIZES = [1, 255, 256, 257, 1000]        # one lane; one short of, exactly and one past a pass of the 256 lanes; lanes of 4 and 3 rows
+
+
+# -------------------------------------------------------------------------------------------------
+# the re-statements the GPU tests share
+# -------------------------------------------------------------------------------------------------
+def restated_losses(q, q_target, v, v_next, reward, done, w=None, gamma=GAMMA, expectile=EXPECTILE):
+    """-> dict(loss_q, loss_v, per_row_q, per_row_v, dq, dv, adv) of ``beso_critic_loss`` in float32 numpy, rounding by rounding as
+    include/beso_critic_fit.h states them (numpy rounds every elementwise float32 operation on its own)."""
+    q, q_target, v, v_next, reward, done = (np.asarray(a, dtype=f32) for a in (q, q_target, v, v_next, reward, done))
+    gamma, tau = f32(gamma), f32(expectile)
+    om = f32(f32(1.0) - tau)
+    with np.errstate(invalid="ignore", over="ignore"):
+        u = q_target - v
+        e = np.where(u < 0, om, tau).astype(f32)
+        uu = u * u
+        l_v = e * uu
+        nd = f32(1.0) - done
+        gn = gamma * nd
+        p = gn * v_next
+        y = reward + p
+        d = q - y
+        l_q = d * d
+        eu = e * u
+        g_v = f32(-2.0) * eu
+        g_q = f32(2.0) * d
+        if w is None:
+            S, A, B = f32(len(q)), lane_order_sum(l_v), lane_order_sum(l_q)
+        else:
+            w = np.asarray(w, dtype=f32)
+            S, A, B = lane_order_sum(w), lane_order_sum(w * l_v), lane_order_sum(w * l_q)
+            g_v, g_q = w * g_v, w * g_q
+        zero = S == 0
+        return dict(loss_q=f32(0.0) if zero else f32(B / S), loss_v=f32(0.0) if zero else f32(A / S), per_row_q=l_q, per_row_v=l_v,
+                    dq=np.zeros_like(g_q) if zero else (g_q / S).astype(f32), dv=np.zeros_like(g_v) if zero else (g_v / S).astype(f32),
+                    adv=u)
+
+
+def autograd_losses(q, q_target, v, v_next, reward, done, w=None, gamma=GAMMA, expectile=EXPECTILE):
+    """The same two losses by float64 torch autograd (gamma and expectile as the fp32 values the C ABI takes): q_target and v_next
+    are constants.  -> dict(loss_q, loss_v, dq, dv), and the float64 terms (w, S, e, u, d, y, p) [M] that the bounds are taken of."""
+    t = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64))                        # noqa: E731
+    q, v = t(q).requires_grad_(True), t(v).requires_grad_(True)
+    q_target, v_next, reward, done = t(q_target), t(v_next), t(reward), t(done)
+    w = torch.ones_like(reward) if w is None else t(w)
+    gamma, tau = float(f32(gamma)), float(f32(expectile))
+    u = q_target - v
+    e = torch.where(u < 0, torch.full_like(u, 1.0 - tau), torch.full_like(u, tau))
+    p = gamma * (1.0 - done) * v_next
+    y = reward + p
+    d = q - y
+    S = w.sum()
+    loss_v, loss_q = (w * e * u * u).sum() / S, (w * d * d).sum() / S
+    (dv_q, dv), (dq, dq_v) = torch.autograd.grad(loss_v, (q, v), allow_unused=True), torch.autograd.grad(loss_q, (q, v), allow_unused=True)
+    assert dv_q is None and dq_v is None                    # L_V does not reach q, L_Q does not reach v
+    out = dict(loss_q=loss_q.item(), loss_v=loss_v.item(), dq=dq.numpy(), dv=dv.numpy())
+    return out, {k: x.detach().numpy() for k, x in dict(w=w, S=S, e=e, u=u, d=d, y=y, p=p).items()}
+
+
+def loss_inputs(M, seed=3):
+    """q, q_target, v, v_next, reward, done, w [M] in float32: about every fifth row terminal, every third weight (rows 1, 4, ...) zero."""
+    rng = np.random.default_rng(seed)
+    n = lambda s=1.0: (s * rng.standard_normal(M)).astype(f32)                              # noqa: E731
+    q, q_target, v, v_next, reward = n(2.0), n(2.0), n(2.0), n(2.0), n()
+    done = (rng.random(M) < 0.2).astype(f32)
+    w = rng.random(M).astype(f32)
+    w[1::3] = 0.0                     # (row 0 counts: M = 1 has a weight sum)
+    return q, q_target, v, v_next, reward, done, w
+
+
+def _deviations(M, weighted):
+    q, q_target, v, v_next, reward, done, w = loss_inputs(M)
+    w = w if weighted else None
+    got = restated_losses(q, q_target, v, v_next, reward, done, w)
+    want, terms = autograd_losses(q, q_target, v, v_next, reward, done, w)
+    assert all(np.asarray(a).dtype == f32 for a in got.values())
+    errs = {name: float(np.abs(np.asarray(got[name], dtype=np.float64) - want[name]).max()) for name in ("loss_q", "loss_v", "dq", "dv")}
+    return got, want, terms, errs
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weights_with_zeros"])
+@pytest.mark.parametrize("M", SIZES[1:])
+def test_float32_restatement_agrees_with_float64_autograd(M, weighted):
+    """Both losses and both gradients of the sequential float32 re-statement against float64 autograd at M = 255, 256, 257, 1000:
+    every deviation within M 2^-24 of the largest summand -- for a loss the largest w_m l_m / S, for a gradient its largest entry
+    (what the weight sum S, an fp32 sum of M terms, moves it by).  The bound of an fp32 sum of M terms: derived, not measured;
+    the test prints what it measured."""
+    got, want, t, errs = _deviations(M, weighted)
+    largest = dict(loss_v=(t["w"] * t["e"] * t["u"] ** 2).max() / t["S"], loss_q=(t["w"] * t["d"] ** 2).max() / t["S"],
+                   dv=np.abs(want["dv"]).max(), dq=np.abs(want["dq"]).max())
+    for name, err in errs.items():
+        bound = M * EPS * largest[name]
+        print(f"M={M} {'weighted' if weighted else 'unweighted'} {name}: |float32 - float64| {err:.3e}, bound {bound:.3e} ({err / bound:.3f} of it)")
+        assert err <= bound, (name, err, bound)
+    assert got["loss_q"] > 0 and got["loss_v"] > 0
+    if weighted:
+        assert not got["dq"][1::3].any() and not got["dv"][1::3].any()
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
+def test_float32_restatement_of_one_row_agrees_with_float64_autograd(weighted):
+    """M = 1: nothing is summed, so the bound of a sum says nothing -- 1 x 2^-24 is less than forming the one summand in fp32 costs.
+    Every rounding of the header's order is counted instead, each at most 2^-24 of its own result, to first order (one more
+    rounding is allowed for the second-order terms):
+      l_v = e (u u), times w, over S     u, om = 1 - tau, u u, e (u u), w l, / S: 6 roundings, each relative to l_v  ->  7 x 2^-24 |loss_v|
+      dv = w (-2 (e u)) / S              u, om, e u, w g, / S: 5 roundings relative to dv                               ->  6 x 2^-24 |dv|
+      d = q - (reward + p), p = gn v'    p, y and d are rounded once each: |delta d| <= 2^-24 (|p| + |y| + |d|) =: 2^-24 D (a difference
+                                         may cancel; the roundings of what it is taken of do not shrink with it)
+      l_q = d d, times w, over S         2 |d| |delta d|, then 3 roundings relative to l_q              ->  2^-24 (2 |d| D + 4 d^2) w / S
+      dq = w (2 d) / S                   2 |delta d|, then 2 roundings relative to dq                   ->  2^-24 (2 D + 6 |d|) w / S"""
+    got, want, t, errs = _deviations(1, weighted)
+    w_over_s = float(t["w"][0] / t["S"])
+    d, D = abs(float(t["d"][0])), abs(float(t["p"][0])) + abs(float(t["y"][0])) + abs(float(t["d"][0]))
+    bounds = dict(loss_v=7 * EPS * abs(want["loss_v"]), dv=6 * EPS * abs(want["dv"][0]),
+                  loss_q=EPS * (2 * d * D + 4 * d * d) * w_over_s, dq=EPS * (2 * D + 6 * d) * w_over_s)
+    for name, err in errs.items():
+        print(f"M=1 {'weighted' if weighted else 'unweighted'} {name}: |float32 - float64| {err:.3e}, bound {bounds[name]:.3e} ({err / bounds[name]:.3f} of it)")
+        assert err <= bounds[name], (name, err, bounds[name])
+    assert got["loss_q"] > 0 and got["loss_v"] > 0
+
+
+def test_expectile_branch_at_zero_and_terminal_rows():
+    one = lambda x: np.array([x], dtype=f32)                                                 # noqa: E731
+    tau, om = f32(EXPECTILE), f32(f32(1.0) - f32(EXPECTILE))
+    # u = +0 and u = -0 take `expectile` (u < 0 is false for both); the loss and the gradient are zero either way
+    for qt, v in ((1.5, 1.5), (-0.0, 0.0), (0.0, -0.0)):
+        r = restated_losses(one(0), one(qt), one(v), one(0), one(0), one(0))
+        assert r["adv"][0] == 0 and r["per_row_v"][0] == 0 and r["dv"][0] == 0
+    neg = restated_losses(one(0), one(-0.0), one(0.0), one(0), one(0), one(0))
+    assert np.signbit(neg["adv"][0]) and not np.signbit(neg["dv"][0])                        # -2 * (tau * -0) = +0: the tau branch
+    # either side of zero: u = 2 weighs tau, u = -2 weighs 1 - tau
+    up, down = (restated_losses(one(0), one(qt), one(0), one(0), one(0), one(0)) for qt in (2.0, -2.0))
+    assert up["per_row_v"][0] == tau * f32(4.0) and down["per_row_v"][0] == om * f32(4.0)
+    assert up["dv"][0] == f32(-2.0) * (tau * f32(2.0)) and down["dv"][0] == f32(-2.0) * (om * f32(-2.0))
+    assert up["loss_v"] == up["per_row_v"][0] and up["adv"][0] == 2.0
+    # done = 1 removes v_next exactly, whatever finite value it holds; done = 0 keeps it
+    q, reward = np.array([0.3, 0.3], dtype=f32), np.array([0.7, 0.7], dtype=f32)
+    for v_next in (3.0, -1e30, 250.0):
+        r = restated_losses(q, q, q, np.array([v_next, v_next], dtype=f32), reward, np.array([1.0, 0.0], dtype=f32))
+        d = f32(0.3) - f32(0.7)
+        assert r["per_row_q"][0] == d * d and r["dq"][0] == (f32(2.0) * d) / f32(2.0)
+        assert r["per_row_q"][1] != r["per_row_q"][0]
+    # all-zero weights: exact zeros, each row's loss still reported; a NaN reward stays in L_Q and in its own row
+    q, q_target, v, v_next, reward, done, _ = loss_inputs(33)
+    z = restated_losses(q, q_target, v, v_next, reward, done, np.zeros(33))
+    assert z["loss_q"] == 0 and z["loss_v"] == 0 and not z["dq"].any() and not z["dv"].any() and (z["per_row_q"] > 0).all()
+    reward[5] = np.nan
+    n = restated_losses(q, q_target, v, v_next, reward, done)
+    assert np.isnan(n["loss_q"]) and np.isfinite(n["loss_v"]) and np.isnan(n["dq"][5]) and np.isfinite(np.delete(n["dq"], 5)).all()
+    assert np.isfinite(n["dv"]).all()
+
+
+def restated_rows(state, action, goal, next_state=None):
+    """-> (q_rows [M, obs + act (+ obs)], v_rows [2 M, obs (+ obs)]) of ``beso_critic_rows`` in numpy, element by element from its
+    sources: the V' rows stand behind the V rows."""
+    state, action = np.asarray(state, dtype=f32), np.asarray(action, dtype=f32)
+    B, T, act = action.shape
+    obs = state.shape[2]
+    gw = 0 if goal is None else obs
+    M = B * T
+    q_rows, v_rows = np.empty((M, obs + act + gw), dtype=f32), np.empty((2 * M, obs + gw), dtype=f32)
+    for b in range(B):
+        g = None if goal is None else np.asarray(goal, dtype=f32)[b if goal.shape[0] == B and B > 1 else 0, -1]
+        for t in range(T):
+            m = b * T + t
+            nxt = state[b, t + 1] if next_state is None else np.asarray(next_state, dtype=f32)[b, t]
+            q_rows[m, :obs], q_rows[m, obs:obs + act] = state[b, t], action[b, t]
+            v_rows[m, :obs], v_rows[M + m, :obs] = state[b, t], nxt
+            if g is not None:
+                q_rows[m, obs + act:], v_rows[m, obs:], v_rows[M + m, obs:] = g, g, g
+    return q_rows, v_rows
+
+
+def torch_rows(state, action, goal, next_state=None):
+    """The same three blocks by ``torch.cat``."""
+    B, T, _ = action.shape
+    nxt = state[:, 1:T + 1] if next_state is None else next_state
+    g = [] if goal is None else [goal[:, -1:, :].expand(B, T, -1)]
+    q_rows = torch.cat([state[:, :T], action, *g], dim=-1).reshape(B * T, -1)
+    v_rows = torch.cat([torch.cat([state[:, :T], *g], dim=-1).reshape(B * T, -1), torch.cat([nxt, *g], dim=-1).reshape(B * T, -1)])
+    return q_rows, v_rows
+
+
+@pytest.mark.parametrize("given_next", [False, True], ids=["next_from_state", "next_state_given"])
+@pytest.mark.parametrize("goal", [None, "shared", "own"])
+@pytest.mark.parametrize("B", [1, 3])
+def test_rows_restatement_is_torch_cat(B, goal, given_next):
+    g = torch.Generator().manual_seed(2)
+    state, action, goals, nxt = (torch.randn(*s, generator=g) for s in ((B, 5, 3), (B, 3, 2), (B, 2, 3), (B, 3, 3)))
+    goal = None if goal is None else goals[:1] if goal == "shared" else goals
+    nxt = nxt if given_next else None
+    got = restated_rows(state.numpy(), action.numpy(), None if goal is None else goal.numpy(), None if nxt is None else nxt.numpy())
+    want = torch_rows(state, action, goal, nxt)
+    for a, b in zip(got, want):
+        assert a.shape == tuple(b.shape) and np.array_equal(a.view(np.int32), b.numpy().view(np.int32))
+    M = B * 3
+    assert np.array_equal(got[1][M:, :3], (state[:, 1:4] if nxt is None else nxt).reshape(M, 3).numpy())
+
+
+# -------------------------------------------------------------------------------------------------
+# StateValue and CriticTrainer: every refusal by name
+# -------------------------------------------------------------------------------------------------
+def _net(input_dim, hidden=16, out=1):
+    return MLPNetwork(input_dim, hidden, 1, out, device="cpu")
+
+
+def _trainer(q_in=8, v_in=6, **kw):
+    """obs 3, act 2, goal: Q reads 3 + 2 + 3, V reads 3 + 3."""
+    return CriticTrainer(MLPGuide(_net(q_in)), StateValue(_net(v_in)), **kw)
+
+
+def test_state_value_checks_its_dimensions_as_mlp_guide_does():
+    state, goal = torch.zeros(4, 3, 5), torch.zeros(4, 2, 5)
+    with pytest.raises(TypeError, match="StateValue: network must be an MLPNetwork"):
+        StateValue(torch.nn.Linear(10, 1))
+    with pytest.raises(ValueError, match="output_dim must be 1"):
+        StateValue(_net(10, out=2))
+    v = StateValue(_net(10))
+    assert v.use_goal and not StateValue(_net(5), use_goal=False).use_goal
+    with pytest.raises(ValueError, match=r"input_dim=10, but obs = 5 \(use_goal=True\)"):
+        v(state, None)
+    with pytest.raises(ValueError, match=r"input_dim=5, but obs \+ obs = 10"):
+        StateValue(_net(5))(state, goal)
+    for bad in (torch.zeros(3, 2, 5), torch.zeros(4, 2, 4), torch.zeros(4, 5)):
+        with pytest.raises(ValueError, match=r"goal .* must be \[B or 1, G, obs=5\]"):
+            v(state, bad)
+    with pytest.raises(ValueError, match=r"state \(4, 5\) must be \[B, steps, obs\]"):
+        v(torch.zeros(4, 5), goal)
+    for value, goal_arg in ((v, goal), (v, goal[:1]), (StateValue(_net(5), use_goal=False), goal), (StateValue(_net(5)), None)):
+        with pytest.raises(RuntimeError, match="GPU"):                                   # the shapes pass; the network has no CPU evaluation
+            value(state, goal_arg)
+
+
+def test_trainer_constructor_refuses_by_name():
+    q, v = MLPGuide(_net(8)), StateValue(_net(6))
+    with pytest.raises(TypeError, match="q must be an MLPGuide, got MLPNetwork"):
+        CriticTrainer(_net(8), v)
+    with pytest.raises(TypeError, match="v must be a StateValue, got MLPGuide"):
+        CriticTrainer(q, MLPGuide(_net(6)))
+    with pytest.raises(ValueError, match="use_sigma"):
+        CriticTrainer(MLPGuide(_net(9), use_sigma=True), v)
+    with pytest.raises(ValueError, match=r"disagree on use_goal \(q: True, v: False\)"):
+        CriticTrainer(q, StateValue(_net(3), use_goal=False))
+    with pytest.raises(ValueError, match="disagree on obs_dim"):
+        CriticTrainer(MLPGuide(_net(6)), v)
+    for kw, word in ((dict(gamma=1.5), "gamma=1.5"), (dict(gamma=-0.1), "gamma=-0.1"), (dict(expectile=0.0), "expectile=0.0"),
+                     (dict(expectile=1.0), "expectile=1.0"), (dict(tau=-0.5), "tau=-0.5"), (dict(tau=2), "tau=2"),
+                     (dict(gamma=float("nan")), "gamma=nan")):
+        with pytest.raises(ValueError, match=word):
+            CriticTrainer(q, v, **kw)
+    tr = CriticTrainer(q, v, gamma=0.9, expectile=0.8, tau=0.01, lr=1e-3, betas=(0.9, 0.99), weight_decay=0.1, decoupled_weight_decay=True)
+    assert (tr.gamma, tr.expectile, tr.tau) == (0.9, 0.8, 0.01) and tr.q is q and tr.v is v
+    for opt in (tr.q_optimizer, tr.v_optimizer):
+        group = opt.param_groups[0]
+        assert (group["lr"], group["betas"], group["weight_decay"], group["decoupled_weight_decay"]) == (1e-3, (0.9, 0.99), 0.1, True)
+    # the target: a copy (not a view) of q's parameters, with a constant decay 1 - tau
+    assert [t.shape for t in tr.q_target_params] == [p.shape for p in tr.q_params]
+    assert all(torch.equal(t, p) and t.data_ptr() != p.data_ptr() for t, p in zip(tr.q_target_params, tr.q_params))
+    assert [tr.target.next_decay() for _ in range(3)] == [1.0 - 0.01] * 3
+
+
+def _untouched(tr, before):
+    assert tr._bufs == {} and tr._flat == {} and tr.per_row_q is None and tr.per_row_v is None and tr.advantage is None
+    assert tr.q_optimizer._groups == [None] and tr.v_optimizer._groups == [None] and tr.target.version == 0
+    assert all(p.grad is None for p in (*tr.q_params, *tr.v_params))
+    assert all(torch.equal(a, b) for a, b in zip(before, (*tr.q_params, *tr.v_params, *tr.q_target_params)))
+
+
+def test_train_step_refuses_by_name_and_changes_nothing():
+    B, T = 4, 3
+    state, action, goal = torch.zeros(B, T + 1, 3), torch.zeros(B, T, 2), torch.zeros(B, 2, 3)
+    reward, done = torch.zeros(B, T), torch.zeros(B, T)
+    tr = _trainer()
+    before = [t.detach().clone() for t in (*tr.q_params, *tr.v_params, *tr.q_target_params)]
+    step = lambda **kw: tr.train_step(**{**dict(state=state, action=action, goal=goal, reward=reward, done=done), **kw})   # noqa: E731
+    for name in ("reward", "done", "weight"):
+        for bad in (torch.zeros(B), torch.zeros(B, T, 1), torch.zeros(T, B), torch.zeros(B * T), 0.5):
+            with pytest.raises(ValueError, match=rf"{name} must be \[B=4, T=3\]"):
+                step(**{name: bad})
+    for name in ("reward", "done"):
+        with pytest.raises(ValueError, match=rf"{name} must be \[B=4, T=3\], got NoneType"):
+            step(**{name: None})
+    with pytest.raises(ValueError, match=r"state has 3 steps, but next_state=None .* T \+ 1 = 4"):
+        step(state=state[:, :T])
+    for bad in (torch.zeros(B, T, 2), torch.zeros(B, T + 1, 3), torch.zeros(B * T, 3)):
+        with pytest.raises(ValueError, match=r"next_state must be \[B=4, T=3, obs=3\]"):
+            step(state=state[:, :T], next_state=bad)
+    with pytest.raises(ValueError, match="MLPGuide: state has 2 steps, fewer than a's 3"):
+        step(state=state[:, :2], next_state=torch.zeros(B, T, 3))
+    with pytest.raises(ValueError, match="input_dim=8"):                                    # no goal: q's rows would be 3 + 2 wide
+        step(goal=None)
+    with pytest.raises(ValueError, match=r"goal .* must be \[B or 1, G, obs=3\]"):
+        step(goal=torch.zeros(3, 2, 3))
+    for ok in (dict(), dict(state=state[:, :T], next_state=torch.zeros(B, T, 3)), dict(weight=torch.ones(B, T)),
+               dict(done=torch.zeros(B, T, dtype=torch.bool)), dict(goal=goal[:1])):
+        with pytest.raises(RuntimeError, match="GPU only .* no CPU"):                        # everything else passes: there is no CPU path
+            step(**ok)
+    _untouched(tr, before)
+    # q and v that agree on use_goal and on the difference of their widths, but not on obs_dim: obs 4 + act 2 + 4 against 3 + 3
+    other = _trainer(q_in=10, v_in=6)
+    before = [t.detach().clone() for t in (*other.q_params, *other.v_params, *other.q_target_params)]
+    with pytest.raises(ValueError, match=r"q and v disagree on obs_dim: v's input_dim=6, but obs \+ obs = 8"):
+        other.train_step(torch.zeros(B, T + 1, 4), action, torch.zeros(B, 2, 4), reward, done)
+    _untouched(other, before)
+
+
+def test_state_dict_round_trip_on_the_host():
+    tr = _trainer(tau=0.01)
+    sd = tr.state_dict()
+    assert sorted(sd) == ["expectile", "gamma", "q", "q_optimizer", "q_target", "tau", "v", "v_optimizer", "version"]
+    assert sorted(sd["q"]) == sorted(tr.q.network.state_dict()) and sorted(sd["v"]) == sorted(tr.v.network.state_dict())
+    assert [t.shape for t in sd["q_target"]] == [p.shape for p in tr.q_params] and not any(t.is_cuda for t in sd["q_target"])
+    torch.manual_seed(5)
+    other = _trainer(tau=0.01)
+    assert not torch.equal(other.q_params[0], tr.q_params[0])
+    other.load_state_dict(sd)
+    for a, b in zip((*other.q_params, *other.v_params, *other.q_target_params), (*tr.q_params, *tr.v_params, *tr.q_target_params)):
+        assert torch.equal(a, b)
+    for name, kw in (("tau", dict(tau=0.02)), ("gamma", dict(tau=0.01, gamma=0.9)), ("expectile", dict(tau=0.01, expectile=0.6))):
+        with pytest.raises(ValueError, match=f"saved with {name}="):
+            _trainer(**kw).load_state_dict(sd)
+
+
+# -------------------------------------------------------------------------------------------------
+# the library
+# -------------------------------------------------------------------------------------------------
+def test_header_binding_table_and_library_name_the_same_symbols():
+    """include/beso_critic_fit.h, _lib.CRITIC_SIGNATURES and the library's dynamic symbol table name the same three functions, in the
+    header's order and with its argument counts, and so has what load_critic() bound; build.LIBS makes the library from the unit
+    critic_fit; libbeso_hip.so exports what include/beso_hip.h declares and nothing of this."""
+    from beso_amd.build import LIBS, build
+    build(verbose=False)
+    assert any(path == _lib.CRITIC_LIB_PATH and units == ["critic_fit"] and header == "beso_critic_fit.h" for path, units, header in LIBS)
+    assert os.path.basename(_lib.CRITIC_LIB_PATH) == "libbeso_critic.so"
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "beso_critic_fit.h")).read(), flags=re.S)
+    protos = {fn: [a for a in args.split(",") if a.strip() != "void"]
+              for fn, args in re.findall(r"\b(beso_critic_[a-z_]+)\s*\(([^()]*)\)\s*;", text)}
+    assert sorted(protos) == sorted(_lib.CRITIC_SIGNATURES) == sorted(_lib.CRITIC_EXPORTS) and len(protos) == 3
+    assert list(protos) == list(_lib.CRITIC_SIGNATURES), "the table keeps the header's order"
+
+    def exported(path):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        return sorted(ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("beso_"))
+
+    assert exported(_lib.CRITIC_LIB_PATH) == sorted(protos)
+    bound = _lib.load_critic()
+    for fn, args in protos.items():
+        assert len(_lib.CRITIC_SIGNATURES[fn][1]) == len(args) == len(getattr(bound, fn).argtypes), fn
+    side = _lib._SIDE["critic"]
+    assert side[0] == _lib.CRITIC_LIB_PATH and side[1] is _lib.CRITIC_SIGNATURES and side[2] == "beso_critic_fit.h"
+    assert side[4] == "beso_critic_last_error" and side[4] in _lib.CRITIC_SIGNATURES
+    assert exported(_lib.LIB_PATH) == sorted(_lib.SIGNATURES)
+
+
+def test_the_entry_points_refuse_by_name_without_a_launch():
+    """Dummy non-NULL pointers: a call that got past its checks would read and write through them."""
+    from beso_amd.build import build
+    build(verbose=False)
+    lib = _lib.load_critic()
+    one, odd = C.c_void_p(0x1000), C.c_void_p(0x1002)
+    msg = lambda: lib.beso_critic_last_error().decode()                                     # noqa: E731
+    loss_args = ("q", "q_target", "v", "v_next", "reward", "done", "weight", "loss_q", "loss_v", "per_row_q", "per_row_v", "dq", "dv", "adv")
+
+    def loss(M=6, gamma=0.99, expectile=0.7, **ptrs):
+        p = {name: ptrs.get(name, one) for name in loss_args}
+        return lib.beso_critic_loss(*(p[n] for n in loss_args[:7]), M, gamma, expectile, *(p[n] for n in loss_args[7:]), None)
+
+    cases = [(dict(M=0), _lib.ERR_BAD_SHAPE, "M = 0"), (dict(M=-3), _lib.ERR_BAD_SHAPE, "M = -3"), (dict(M=1 << 31), _lib.ERR_BAD_SHAPE, "M = "),
+             (dict(gamma=1.5), _lib.ERR_BAD_ARG, "gamma = 1.5"), (dict(gamma=-0.5), _lib.ERR_BAD_ARG, "gamma = -0.5"),
+             (dict(gamma=float("nan")), _lib.ERR_BAD_ARG, "gamma = "), (dict(expectile=0.0), _lib.ERR_BAD_ARG, "expectile = 0"),
+             (dict(expectile=1.0), _lib.ERR_BAD_ARG, "expectile = 1"), (dict(expectile=float("nan")), _lib.ERR_BAD_ARG, "expectile = ")]
+    cases += [({name: None}, _lib.ERR_BAD_ARG, f"{name} is NULL") for name in loss_args if name != "weight"]
+    cases += [({name: odd}, _lib.ERR_BAD_ARG, f"{name} is not 4-byte aligned") for name in loss_args]
+    for bad, status, word in cases:
+        assert loss(**bad) == status, bad
+        assert word in msg() and msg().startswith("beso_critic_loss: "), (bad, msg())
+    with pytest.raises(ValueError, match="beso_critic: critic_loss: beso_critic_loss: dv is NULL"):
+        _lib.check_critic(loss(dv=None), "critic_loss")
+
+    def rows(state=one, next_state=None, action=one, goal=one, B=4, T=3, steps=4, G=2, grows=4, obs=5, act=3, q_rows=one, v_rows=one):
+        return lib.beso_critic_rows(state, next_state, action, goal, B, T, steps, G, grows, obs, act, q_rows, v_rows, None)
+
+    for bad, status, word in ((dict(obs=0), _lib.ERR_BAD_SHAPE, "obs_dim = 0"), (dict(act=0), _lib.ERR_BAD_SHAPE, "act_dim = 0"),
+                              (dict(obs=513), _lib.ERR_BAD_SHAPE, "obs_dim = 513"), (dict(obs=250, act=13), _lib.ERR_BAD_SHAPE, "= 513 floats per Q row"),
+                              (dict(B=0), _lib.ERR_BAD_SHAPE, "B = 0"), (dict(T=0), _lib.ERR_BAD_SHAPE, "T = 0"),
+                              (dict(steps=3), _lib.ERR_BAD_SHAPE, "state_steps = 3"), (dict(steps=2, next_state=one), _lib.ERR_BAD_SHAPE, "state_steps = 2"),
+                              (dict(G=0), _lib.ERR_BAD_SHAPE, "goal_steps = 0"), (dict(grows=3), _lib.ERR_BAD_SHAPE, "goal_rows = 3"),
+                              (dict(goal=None), _lib.ERR_BAD_SHAPE, "goal_steps = 2"),
+                              (dict(B=1 << 20, T=1 << 12, steps=(1 << 12) + 1, grows=1), _lib.ERR_BAD_SHAPE, "rows"),
+                              (dict(state=None), _lib.ERR_BAD_ARG, "state is NULL"), (dict(action=None), _lib.ERR_BAD_ARG, "action is NULL"),
+                              (dict(q_rows=None), _lib.ERR_BAD_ARG, "q_rows is NULL"), (dict(v_rows=None), _lib.ERR_BAD_ARG, "v_rows is NULL"),
+                              (dict(next_state=odd), _lib.ERR_BAD_ARG, "next_state is not 4-byte aligned"),
+                              (dict(goal=odd), _lib.ERR_BAD_ARG, "goal is not 4-byte aligned"),
+                              (dict(v_rows=odd), _lib.ERR_BAD_ARG, "v_rows is not 4-byte aligned")):
+        assert rows(**bad) == status, bad
+        assert word in msg() and msg().startswith("beso_critic_rows: "), (bad, msg())
