@@ -22,7 +22,7 @@ from .... import _lib
 from ...._instantiate import instantiate
 from ....networks.ema_helper.ema import ExponentialMovingAverage
 from ....networks.mlps.mlps import MLPNetwork
-from ....optim import FusedAdam
+from .fit_common import FitNet, check_bt, f32c, goal_args, ptr, require_gpu, row_dims, shape_of
 from .guides import MLPGuide, _stream
 
 
@@ -44,16 +44,7 @@ class StateValue(nn.Module):
 
     def _dims(self, state, goal):
         """(B, steps, obs, goal or None) of a call, refusing by name what the network cannot read."""
-        if state.dim() != 3:
-            raise ValueError(f"StateValue: state {tuple(state.shape)} must be [B, steps, obs]")
-        B, S, obs = state.shape
-        goal = goal if self.use_goal and goal is not None else None
-        if goal is not None and (goal.dim() != 3 or goal.shape[2] != obs or goal.shape[0] not in (1, B)):
-            raise ValueError(f"StateValue: goal {tuple(goal.shape)} must be [B or 1, G, obs={obs}]")
-        want = obs + (obs if goal is not None else 0)
-        if self.network.input_dim != want:
-            raise ValueError(f"StateValue: the network's input_dim={self.network.input_dim}, but obs"
-                             f"{' + obs' if goal is not None else ''} = {want} (use_goal={self.use_goal})")
+        B, S, obs, _, goal = row_dims("StateValue", self.network.input_dim, state, None, goal, self.use_goal)
         return B, S, obs, goal
 
     def forward(self, state, goal=None) -> torch.Tensor:
@@ -63,10 +54,6 @@ class StateValue(nn.Module):
         if goal is not None:
             parts.append(goal[:, -1:, :].to(torch.float32).expand(B, S, obs))
         return self.network(torch.cat(parts, dim=-1)).squeeze(-1)
-
-
-def _shape(t):
-    return tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
 
 
 class CriticTrainer:
@@ -104,47 +91,17 @@ class CriticTrainer:
             raise ValueError(f"CriticTrainer: tau={tau} must lie in [0, 1]")
         self.q, self.v = q, v
         self.gamma, self.expectile, self.tau = float(gamma), float(expectile), float(tau)
-        self.q_params = list(q.network.layers.parameters())
-        self.v_params = list(v.network.layers.parameters())
         adam = dict(lr=lr, betas=betas, weight_decay=weight_decay, decoupled_weight_decay=decoupled_weight_decay)
-        self.q_optimizer = FusedAdam(self.q_params, **adam)
-        self.v_optimizer = FusedAdam(self.v_params, **adam)
+        self._q, self._v = FitNet(q.network, adam), FitNet(v.network, adam)          # Q over M rows, V over 2 M
+        self.q_params, self.q_optimizer = self._q.params, self._q.optimizer
+        self.v_params, self.v_optimizer = self._v.params, self._v.optimizer
         # the Polyak target as the shadow of an EMA helper without its warm-up rule: next_decay() is 1 - tau at every step
         self.target = ExponentialMovingAverage(self.q_params, decay=1.0 - self.tau, use_num_updates=False)
         self.per_row_q = self.per_row_v = self.advantage = None         # [B, T] of the last step (device)
-        self._flat = {}                 # 'q' / 'v' -> the flat gradient; every parameter's .grad is a view of it
-        self._bufs = {}                 # M -> the step's buffers
 
     @property
     def q_target_params(self):
         return self.target.shadow_params
-
-    # ------------------------------------------------------------------ buffers
-    def _grads(self, which: str, dev):
-        net, params = (self.q.network, self.q_params) if which == "q" else (self.v.network, self.v_params)
-        flat = self._flat.get(which)
-        if flat is None or flat.device != dev:
-            flat = self._flat[which] = torch.empty(net.num_param_floats(), dtype=torch.float32, device=dev)
-        off = 0
-        for p in params:                    # (re-attached every step: zero_grad(set_to_none=True) elsewhere may have dropped them)
-            view = flat[off:off + p.numel()].view(p.shape)
-            if p.grad is None or p.grad.data_ptr() != view.data_ptr():
-                p.grad = view
-            off += p.numel()
-        return flat
-
-    def _buffers(self, M: int, dev):
-        hit = self._bufs.get(M)
-        if hit is None or hit["q_rows"].device != dev:
-            qn, vn = self.q.network, self.v.network
-            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)                  # noqa: E731
-            u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)                       # noqa: E731
-            hit = self._bufs[M] = dict(
-                q_rows=f32(M, qn.input_dim), v_rows=f32(2 * M, vn.input_dim), q=f32(M, 1), q_target=f32(M, 1), v=f32(2 * M, 1),
-                keep_q=f32(qn.keep_floats(M)), keep_v=f32(vn.keep_floats(2 * M)), dq=f32(M),
-                dv=torch.zeros(2 * M, dtype=torch.float32, device=dev),        # [dv ; M zeros]: only the first M are ever written
-                ws_q=u8(qn.workspace_bytes(M)), ws_v=u8(vn.workspace_bytes(2 * M)))
-        return hit
 
     # ------------------------------------------------------------------ the step
     def _check(self, state, action, goal, reward, done, next_state, weight):
@@ -157,20 +114,15 @@ class CriticTrainer:
         if self.v.network.input_dim != want:
             raise ValueError(f"CriticTrainer: q and v disagree on obs_dim: v's input_dim={self.v.network.input_dim}, but obs"
                              f"{' + obs' if goal is not None else ''} = {want} by q's rows")
-        for name, t in (("reward", reward), ("done", done), ("weight", weight)):
-            if (t is None and name != "weight") or (t is not None and (not torch.is_tensor(t) or t.shape != (B, T))):
-                raise ValueError(f"CriticTrainer: {name} must be [B={B}, T={T}], got {_shape(t)}")
+        check_bt("CriticTrainer", B, T, (("reward", reward), ("done", done), ("weight", weight)), required=("reward", "done"))
         if next_state is None:
             if state.shape[1] < T + 1:
                 raise ValueError(f"CriticTrainer: state has {state.shape[1]} steps, but next_state=None reads state[:, 1 : T + 1] "
                                  f"and needs T + 1 = {T + 1}")
         elif not torch.is_tensor(next_state) or next_state.shape != (B, T, obs):
-            raise ValueError(f"CriticTrainer: next_state must be [B={B}, T={T}, obs={obs}], got {_shape(next_state)}")
-        on_gpu = (state, action, reward, done, *(t for t in (goal, next_state, weight) if t is not None), *self.q_params,
-                  *self.v_params, *self.q_target_params)
-        if not all(t.is_cuda for t in on_gpu):
-            raise RuntimeError("CriticTrainer runs on the GPU only (HIP kernels, no CPU or eager fallback): q, v, the target and "
-                               "every tensor of a step must be on it")
+            raise ValueError(f"CriticTrainer: next_state must be [B={B}, T={T}, obs={obs}], got {shape_of(next_state)}")
+        require_gpu("CriticTrainer", "q, v, the target", (state, action, reward, done, *(t for t in (goal, next_state, weight) if t is not None),
+                                                           *self.q_params, *self.v_params, *self.q_target_params))
         return B, T, obs, act, goal
 
     def train_step(self, state, action, goal, reward, done, next_state=None, weight=None):
@@ -181,33 +133,33 @@ class CriticTrainer:
         -> ``(loss_q, loss_v)`` before the update, 0-dim device tensors."""
         B, T, obs, act, goal = self._check(state, action, goal, reward, done, next_state, weight)
         dev = action.device
-        f32c = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
-        state, action, goal, reward, done, next_state, weight = (f32c(t) for t in (state, action, goal, reward, done, next_state, weight))
-        ptr = lambda t: None if t is None else t.data_ptr()                                      # noqa: E731
+        state, action, goal, reward, done, next_state, weight = (f32c(t, dev) for t in (state, action, goal, reward, done, next_state, weight))
+        goal_steps, goal_rows = goal_args(goal)
 
         M = B * T
-        b = self._buffers(M, dev)
-        flat_q, flat_v = self._grads("q", dev), self._grads("v", dev)
+        fq, fv = self._q, self._v
+        bq = fq.buffers(M, dev, spare_out=True)                       # (the spare out: q_target)
+        bv = fv.buffers(2 * M, dev, zero_d_out=True)                  # [dv ; M zeros]: only the first M are ever written
+        flat_q, flat_v = fq.grads(dev), fv.grads(dev)
+        (q_rows, q, _, dq, _, q_target), (v_rows, v, _, dv, _) = bq, bv
         loss_q, loss_v = (torch.empty((), dtype=torch.float32, device=dev) for _ in range(2))
         self.per_row_q, self.per_row_v, self.advantage = (torch.empty(B, T, dtype=torch.float32, device=dev) for _ in range(3))
-        qn, vn = self.q.network, self.v.network
         lib = _lib.load_critic()
         with torch.cuda.device(dev):
             stream = _stream(action)
             _lib.check_critic(lib.beso_critic_rows(
-                state.data_ptr(), ptr(next_state), action.data_ptr(), ptr(goal), B, T, state.shape[1],
-                0 if goal is None else goal.shape[1], 0 if goal is None else goal.shape[0], obs, act, b["q_rows"].data_ptr(),
-                b["v_rows"].data_ptr(), stream), "critic_rows")
-            qn.run_forward(b["q_rows"], keep=True, params=self.q_params, out=b["q"], keep_out=b["keep_q"])
-            qn.run_forward(b["q_rows"], keep=False, params=self.q_target_params, out=b["q_target"])
-            vn.run_forward(b["v_rows"], keep=True, params=self.v_params, out=b["v"], keep_out=b["keep_v"])
+                state.data_ptr(), ptr(next_state), action.data_ptr(), ptr(goal), B, T, state.shape[1], goal_steps, goal_rows, obs, act,
+                q_rows.data_ptr(), v_rows.data_ptr(), stream), "critic_rows")
+            fq.forward(bq)
+            fq.forward(bq, params=self.q_target_params, keep=False, out=q_target)
+            fv.forward(bv)
             _lib.check_critic(lib.beso_critic_loss(
-                b["q"].data_ptr(), b["q_target"].data_ptr(), b["v"].data_ptr(), b["v"].data_ptr() + 4 * M, reward.data_ptr(),
+                q.data_ptr(), q_target.data_ptr(), v.data_ptr(), v.data_ptr() + 4 * M, reward.data_ptr(),
                 done.data_ptr(), ptr(weight), M, self.gamma, self.expectile, loss_q.data_ptr(), loss_v.data_ptr(),
-                self.per_row_q.data_ptr(), self.per_row_v.data_ptr(), b["dq"].data_ptr(), b["dv"].data_ptr(),
+                self.per_row_q.data_ptr(), self.per_row_v.data_ptr(), dq.data_ptr(), dv.data_ptr(),
                 self.advantage.data_ptr(), stream), "critic_loss")
-            qn.run_backward(b["keep_q"], b["dq"], flat_q, params=self.q_params, workspace=b["ws_q"])
-            vn.run_backward(b["keep_v"], b["dv"], flat_v, params=self.v_params, workspace=b["ws_v"])
+            fq.backward(bq, flat_q)
+            fv.backward(bv, flat_v)
             self.q_optimizer.step(ema=self.target)
             self.v_optimizer.step()
         return loss_q, loss_v
@@ -216,11 +168,10 @@ class CriticTrainer:
     def state_dict(self) -> dict:
         """Both networks, the target and both optimizers' moments and step counts (``FusedAdam.export_state``), as CPU tensors:
         loaded into a trainer around equally shaped networks, the next step's bits are those of the uninterrupted run."""
-        cpu = lambda sd: {k: t.detach().cpu().clone() for k, t in sd.items()}                  # noqa: E731
-        return dict(version=1, gamma=self.gamma, expectile=self.expectile, tau=self.tau,
-                    q=cpu(self.q.network.state_dict()), v=cpu(self.v.network.state_dict()),
+        (q, q_optimizer), (v, v_optimizer) = self._q.export(), self._v.export()
+        return dict(version=1, gamma=self.gamma, expectile=self.expectile, tau=self.tau, q=q, v=v,
                     q_target=[t.detach().cpu().clone() for t in self.target.state_dict()["shadow_params"]],
-                    q_optimizer=self.q_optimizer.export_state(), v_optimizer=self.v_optimizer.export_state())
+                    q_optimizer=q_optimizer, v_optimizer=v_optimizer)
 
     def load_state_dict(self, d: dict) -> None:
         for name in ("gamma", "expectile", "tau"):
@@ -230,9 +181,7 @@ class CriticTrainer:
         if [t.shape for t in d["q_target"]] != [t.shape for t in self.q_target_params]:
             raise ValueError(f"CriticTrainer.load_state_dict: the saved target's shapes {[tuple(t.shape) for t in d['q_target']]} "
                              f"are not this trainer's {[tuple(t.shape) for t in self.q_target_params]}")
-        self.q.network.load_state_dict(d["q"])                         # in place: the parameters keep their storage
-        self.v.network.load_state_dict(d["v"])
+        self._q.load(d["q"], d["q_optimizer"])
+        self._v.load(d["v"], d["v_optimizer"])
         # (in place as well: the shadow stays the flat buffer Q's optimizer launch updates; the decay stays constant)
         self.target.load_state_dict(dict(decay=1.0 - self.tau, num_updates=None, shadow_params=d["q_target"]))
-        self.q_optimizer.import_state(d["q_optimizer"])
-        self.v_optimizer.import_state(d["v_optimizer"])

@@ -12,12 +12,10 @@ One ``train_step`` is five enqueues and no torch-op evaluation of the network (i
   5. ``FusedAdam.step``
 
 Nothing reads the device: the loss comes back as a 0-dim device tensor.  Equal inputs, seed and state give equal bits."""
-import ctypes as C
-
 import torch
 
 from .... import _lib
-from ....optim import FusedAdam
+from .fit_common import FitNet, check_bt, f32c, goal_args, ptr, require_gpu
 from .guides import MLPGuide, _stream
 
 
@@ -40,39 +38,15 @@ class GuideTrainer:
         if loss not in _lib.GUIDEFIT_LOSSES:
             raise ValueError(f"GuideTrainer: loss {loss!r} has no HIP kernel (supported: {', '.join(sorted(_lib.GUIDEFIT_LOSSES))})")
         self.guide, self.loss, self.sample_density = guide, loss, sample_density
-        self.params = list(guide.network.layers.parameters())
-        self.optimizer = FusedAdam(self.params, lr=lr, betas=betas, weight_decay=weight_decay,
-                                   decoupled_weight_decay=decoupled_weight_decay)
+        self._net = FitNet(guide.network, dict(lr=lr, betas=betas, weight_decay=weight_decay,
+                                                 decoupled_weight_decay=decoupled_weight_decay))
+        self.params, self.optimizer = self._net.params, self._net.optimizer
         self.generator = torch.Generator(device=self.params[0].device)
         if seed is None:
             self.generator.seed()
         else:
             self.generator.manual_seed(int(seed))
         self.per_row = None             # [B, T]: each row's loss of the last step (device)
-        self._flat = None               # the flat gradient; every parameter's .grad is a view of it
-        self._bufs = {}                 # M -> (rows, q, keep, dq, workspace)
-
-    # ------------------------------------------------------------------ buffers
-    def _grads(self, dev):
-        if self._flat is None or self._flat.device != dev:
-            net = self.guide.network
-            self._flat = torch.empty(net.num_param_floats(), dtype=torch.float32, device=dev)
-        off = 0
-        for p in self.params:               # (re-attached every step: zero_grad(set_to_none=True) elsewhere may have dropped them)
-            view = self._flat[off:off + p.numel()].view(p.shape)
-            if p.grad is None or p.grad.data_ptr() != view.data_ptr():
-                p.grad = view
-            off += p.numel()
-        return self._flat
-
-    def _buffers(self, M: int, dev):
-        hit = self._bufs.get(M)
-        if hit is None or hit[0].device != dev:
-            net = self.guide.network
-            f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)                  # noqa: E731
-            hit = self._bufs[M] = (f32(M, net.input_dim), f32(M, 1), f32(net.keep_floats(M)), f32(M),
-                                   torch.empty(net.workspace_bytes(M), dtype=torch.uint8, device=dev))
-        return hit
 
     # ------------------------------------------------------------------ the step
     def train_step(self, state, action, goal, target, weight=None, sigma=None, noise=None) -> torch.Tensor:
@@ -81,18 +55,13 @@ class GuideTrainer:
         ``sigma [B]``: None draws it from ``sample_density``; without one (and without ``use_sigma``) the rows hold the clean
         action.  ``noise [B, T, act]``: None draws ``randn`` from the trainer's generator.  -> the loss before the update, a
         0-dim device tensor; ``per_row`` holds each row's loss."""
-        guide, net = self.guide, self.guide.network
+        guide = self.guide
         B, T, obs, act, goal = guide._dims(state, action, goal)
-        for name, t in (("target", target), ("weight", weight)):
-            if t is not None and (not torch.is_tensor(t) or t.shape != (B, T)):
-                raise ValueError(f"GuideTrainer: {name} must be [B={B}, T={T}], got "
-                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        check_bt("GuideTrainer", B, T, (("target", target), ("weight", weight)))
         if target is None:
             raise ValueError(f"GuideTrainer: target must be [B={B}, T={T}], got None")
         dev = action.device
-        if not all(t.is_cuda for t in (state, action, target, *self.params)):
-            raise RuntimeError("GuideTrainer runs on the GPU only (HIP kernels, no CPU or eager fallback): the guide and every "
-                               "tensor of a step must be on it")
+        require_gpu("GuideTrainer", "the guide", (state, action, target, *self.params))
         if sigma is None and self.sample_density is not None:
             sigma = self.sample_density((B,), device=dev)
         if sigma is None and guide.use_sigma:
@@ -105,14 +74,15 @@ class GuideTrainer:
             noise = torch.randn(B, T, act, generator=self.generator, device=dev, dtype=torch.float32)
         if noise is not None and noise.shape != (B, T, act):
             raise ValueError(f"GuideTrainer: noise must be [B={B}, T={T}, act={act}], got {tuple(noise.shape)}")
-        f32c = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
-        state, action, goal, target, weight, sigma, noise = (f32c(t) for t in (state, action, goal, target, weight, sigma, noise))
+        state, action, goal, target, weight, sigma, noise = (f32c(t, dev) for t in (state, action, goal, target, weight, sigma, noise))
         c_noise = guide.c_noise(sigma, B, "GuideTrainer") if guide.use_sigma else None         # torch's log, as MLPGuide.apply's
-        ptr = lambda t: None if t is None else t.data_ptr()                                      # noqa: E731
+        goal_steps, goal_rows = goal_args(goal)
 
         M = B * T
-        rows, q, keep, dq, workspace = self._buffers(M, dev)
-        flat = self._grads(dev)
+        fit = self._net
+        b = fit.buffers(M, dev)
+        rows, q, _, dq, _ = b
+        flat = fit.grads(dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         self.per_row = torch.empty(B, T, dtype=torch.float32, device=dev)
         lib = _lib.load_guidefit()
@@ -120,13 +90,13 @@ class GuideTrainer:
             stream = _stream(action)
             _lib.check(lib.beso_guide_fit_rows(
                 state.data_ptr(), action.data_ptr(), ptr(goal), ptr(sigma), ptr(noise), ptr(c_noise), B, T, state.shape[1],
-                0 if goal is None else goal.shape[1], 0 if goal is None else goal.shape[0], obs, act, rows.data_ptr(), stream),
+                goal_steps, goal_rows, obs, act, rows.data_ptr(), stream),
                 "beso_guide_fit_rows")
-            net.run_forward(rows, keep=True, params=self.params, out=q, keep_out=keep)
+            fit.forward(b)
             _lib.check(lib.beso_guide_fit_loss(q.data_ptr(), target.data_ptr(), ptr(weight), M, _lib.GUIDEFIT_LOSSES[self.loss],
                                                loss.data_ptr(), self.per_row.data_ptr(), dq.data_ptr(), stream),
                        "beso_guide_fit_loss")
-            net.run_backward(keep, dq, flat, params=self.params, workspace=workspace)
+            fit.backward(b, flat)
             self.optimizer.step()
         return loss
 
@@ -134,13 +104,11 @@ class GuideTrainer:
     def state_dict(self) -> dict:
         """The network, the optimizer's moments and step count (``FusedAdam.export_state``) and the noise generator, as CPU
         tensors: loaded into a trainer around an equally shaped guide, the next step's bits are those of the uninterrupted run."""
-        return dict(version=1, loss=self.loss,
-                    network={k: v.detach().cpu().clone() for k, v in self.guide.network.state_dict().items()},
-                    optimizer=self.optimizer.export_state(), generator=self.generator.get_state().clone())
+        network, optimizer = self._net.export()
+        return dict(version=1, loss=self.loss, network=network, optimizer=optimizer, generator=self.generator.get_state().clone())
 
     def load_state_dict(self, d: dict) -> None:
         if d.get("loss") != self.loss:
             raise ValueError(f"GuideTrainer.load_state_dict: saved with loss {d.get('loss')!r}, this trainer has {self.loss!r}")
-        self.guide.network.load_state_dict(d["network"])               # in place: the parameters keep their storage
-        self.optimizer.import_state(d["optimizer"])
+        self._net.load(d["network"], d["optimizer"])
         self.generator.set_state(d["generator"])

@@ -10,6 +10,7 @@ import torch.nn as nn
 from .... import _lib
 from ...._instantiate import instantiate
 from ....networks.mlps.mlps import MLPNetwork
+from .fit_common import row_dims
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -48,21 +49,8 @@ class MLPGuide(nn.Module):
     # ------------------------------------------------------------------ shapes
     def _dims(self, state, a, goal):
         """(B, T, obs, act, goal or None) of a call, refusing by name what the guide cannot read."""
-        if state.dim() != 3 or a.dim() != 3 or state.shape[0] != a.shape[0]:
-            raise ValueError(f"MLPGuide: state {tuple(state.shape)} and a {tuple(a.shape)} must be [B, steps, dim] with one B")
-        B, T, act = a.shape
-        if state.shape[1] < T:
-            raise ValueError(f"MLPGuide: state has {state.shape[1]} steps, fewer than a's {T}")
-        obs = state.shape[2]
-        goal = goal if self.use_goal and goal is not None else None
-        if goal is not None and (goal.dim() != 3 or goal.shape[2] != obs or goal.shape[0] not in (1, B)):
-            raise ValueError(f"MLPGuide: goal {tuple(goal.shape)} must be [B or 1, G, obs={obs}]")
-        want = obs + act + (obs if goal is not None else 0) + (1 if self.use_sigma else 0)
-        if self.network.input_dim != want:
-            raise ValueError(f"MLPGuide: the network's input_dim={self.network.input_dim}, but obs + act"
-                             f"{' + obs' if goal is not None else ''}{' + 1' if self.use_sigma else ''} = {want} "
-                             f"(use_goal={self.use_goal}, use_sigma={self.use_sigma})")
-        return B, T, obs, act, goal
+        return row_dims("MLPGuide", self.network.input_dim, state, a, goal, self.use_goal, extra=int(self.use_sigma),
+                        use_sigma=self.use_sigma)
 
     def c_noise(self, sigma, B: int, who: str = "MLPGuide"):
         """``log(sigma) / 4`` [B] in fp32 torch ops (None without ``use_sigma``), refusing by name a ``sigma`` the guide cannot

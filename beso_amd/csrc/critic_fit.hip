@@ -5,14 +5,13 @@
 //   critic_loss_kernel   ONE workgroup, two passes over the M rows: the per-row expectile and TD losses, the advantage and the
 //                        lane sums, then dv = w dl_v/dv / S and dq = w dl_q/dq / S
 // The loss kernel is fp32 with every product and sum rounded on its own (fp contraction off): the header states the order.
-#include "common.h"
+#include "side_host.h"
 #include "../../include/beso_critic_fit.h"
-
-#include <cstdio>
 
 namespace beso_critic {
 
 using beso::launch_plain;
+using namespace beso_side;
 
 constexpr int kThreads = 256;
 constexpr int kMaxDim = 512;
@@ -133,33 +132,9 @@ __global__ __launch_bounds__(kThreads) void critic_loss_kernel(Loss a) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------ host
-static thread_local char g_error[224] = "";
-
-template <typename... A>
-static int refuse(int status, const char* fmt, A... a) {
-    snprintf(g_error, sizeof(g_error), fmt, a...);
-    return status;
-}
-
-struct Named {
-    const char* name;
-    const void* p;
-    bool optional;
-};
-
-// the first NULL (unless optional) or misaligned pointer of `args`, by name
-template <size_t N>
-static int check_pointers(const char* fn, const Named (&args)[N]) {
-    for (const Named& a : args) {
-        if (!a.p && !a.optional) return refuse(BESO_ERR_BAD_ARG, "%s: %s is NULL", fn, a.name);
-        if ((uintptr_t)a.p & 3) return refuse(BESO_ERR_BAD_ARG, "%s: %s is not 4-byte aligned", fn, a.name);
-    }
-    return BESO_OK;
-}
-
 }  // namespace beso_critic
 
+// ------------------------------------------------------------------------------------------------------------ host
 using namespace beso_critic;
 
 extern "C" const char* beso_critic_last_error(void) { return g_error; }
@@ -184,7 +159,7 @@ extern "C" int beso_critic_rows(const float* state, const float* next_state, con
     const long long total = M * qw + 2 * M * vw;
     if (M > 0x7fffffffLL || total > kMaxElements)
         return refuse(BESO_ERR_BAD_SHAPE, "%s: B T = %lld rows (at most 2^31 - 1) with %lld output elements (at most (2^31 - 1) 256)", fn, M, total);
-    if (goal ? (goal_steps < 1 || (goal_rows != B && goal_rows != 1)) : (goal_steps != 0 || goal_rows != 0))
+    if (!GoalRows::valid(goal, goal_steps, goal_rows, B))
         return refuse(BESO_ERR_BAD_SHAPE, "%s: goal_steps = %d, goal_rows = %d: a goal is [B = %d or 1, goal_steps >= 1, obs_dim], and both are 0 without one",
                       fn, goal_steps, goal_rows, B);
     const Named ptrs[] = {{"state", state, false}, {"next_state", next_state, true}, {"action", action, false}, {"goal", goal, true},
@@ -203,8 +178,9 @@ extern "C" int beso_critic_rows(const float* state, const float* next_state, con
     rw.obs = obs_dim;
     rw.adim = act_dim;
     rw.gw = gw;
-    rw.goal_stride = goal && goal_rows == B && B > 1 ? (long long)goal_steps * obs_dim : 0;
-    rw.goal_off = goal ? (long long)(goal_steps - 1) * obs_dim : 0;
+    const GoalRows g(goal, goal_steps, goal_rows, B, obs_dim);
+    rw.goal_stride = g.stride;
+    rw.goal_off = g.off;
     rw.M = M;
     rw.q_total = M * qw;
     rw.total = total;

@@ -10,6 +10,7 @@ namespace beso_guide_fit {
 
 using beso::launch_plain;
 using beso::to_status;
+using namespace beso_side;
 
 constexpr int kThreads = 256;
 constexpr int kMaxDim = 512;
@@ -107,8 +108,6 @@ __global__ __launch_bounds__(kThreads) void fit_loss_kernel(const float* __restr
     }
 }
 
-static bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
-
 }  // namespace beso_guide_fit
 
 using namespace beso_guide_fit;
@@ -122,10 +121,10 @@ extern "C" int beso_guide_fit_rows(const float* state, const float* action, cons
     if (B < 1 || T < 1 || state_steps < T) return BESO_ERR_BAD_SHAPE;
     const long long M = (long long)B * T;
     if (M > 0x7fffffffLL || M * in_dim >= (1LL << 39)) return BESO_ERR_BAD_SHAPE;
-    if (goal ? (goal_steps < 1 || (goal_rows != B && goal_rows != 1)) : (goal_steps != 0 || goal_rows != 0)) return BESO_ERR_BAD_SHAPE;
+    if (!GoalRows::valid(goal, goal_steps, goal_rows, B)) return BESO_ERR_BAD_SHAPE;
     if (!state || !action || !rows || (sigma == nullptr) != (noise == nullptr)) return BESO_ERR_BAD_ARG;
-    if (misaligned(state) || misaligned(action) || misaligned(goal) || misaligned(sigma) || misaligned(noise) ||
-        misaligned(c_noise) || misaligned(rows))
+    if (misaligned(state, 4) || misaligned(action, 4) || misaligned(goal, 4) || misaligned(sigma, 4) || misaligned(noise, 4) ||
+        misaligned(c_noise, 4) || misaligned(rows, 4))
         return BESO_ERR_BAD_ARG;
 
     Rows rw{};
@@ -141,8 +140,9 @@ extern "C" int beso_guide_fit_rows(const float* state, const float* action, cons
     rw.obs = obs_dim;
     rw.adim = act_dim;
     rw.in_dim = in_dim;
-    rw.goal_stride = goal && goal_rows == B && B > 1 ? (long long)goal_steps * obs_dim : 0;
-    rw.goal_off = goal ? (long long)(goal_steps - 1) * obs_dim : 0;
+    const GoalRows g(goal, goal_steps, goal_rows, B, obs_dim);
+    rw.goal_stride = g.stride;
+    rw.goal_off = g.off;
     rw.total = M * in_dim;
     return to_status(launch_plain<fit_rows_kernel>(dim3((unsigned)((rw.total + kThreads - 1) / kThreads)), dim3(kThreads),
                                                    (hipStream_t)stream, rw));
@@ -153,7 +153,7 @@ extern "C" int beso_guide_fit_loss(const float* q, const float* target, const fl
     if (M < 1 || M > 0x7fffffffLL) return BESO_ERR_BAD_SHAPE;
     if (kind != BESO_GUIDE_FIT_MSE && kind != BESO_GUIDE_FIT_BCE) return BESO_ERR_BAD_ARG;
     if (!q || !target || !loss || !per_row || !dq) return BESO_ERR_BAD_ARG;
-    if (misaligned(q) || misaligned(target) || misaligned(weight) || misaligned(loss) || misaligned(per_row) || misaligned(dq))
+    if (misaligned(q, 4) || misaligned(target, 4) || misaligned(weight, 4) || misaligned(loss, 4) || misaligned(per_row, 4) || misaligned(dq, 4))
         return BESO_ERR_BAD_ARG;
     return to_status(launch_plain<fit_loss_kernel>(dim3(1), dim3(kThreads), (hipStream_t)stream, q, target, weight, M, kind, loss,
                                                    per_row, dq));

@@ -8,10 +8,13 @@
 // is, instruction for instruction, the kernel guide.hip held before the column existed.
 #pragma once
 #include "mlp_tile.h"
+#include "side_host.h"
 
 namespace beso_guide {
 
 using namespace beso_mlp;
+using beso_side::GoalRows;
+using beso_side::misaligned;
 
 constexpr int kMaxLinear = 5;                  // n_hidden <= 4
 constexpr size_t kMaxLds = 160 * 1024;         // what one workgroup may declare on gfx950
@@ -135,12 +138,12 @@ static int guide_apply(const float* const* params, int n_params, const beso_mlp_
     if (B < 1 || T < 1 || state_steps < T) return BESO_ERR_BAD_SHAPE;
     const long long M = (long long)B * T;
     if (M > 0x7fffffffLL) return BESO_ERR_BAD_SHAPE;
-    if (goal ? (goal_steps < 1 || (goal_rows != B && goal_rows != 1)) : (goal_steps != 0 || goal_rows != 0)) return BESO_ERR_BAD_SHAPE;
+    if (!GoalRows::valid(goal, goal_steps, goal_rows, B)) return BESO_ERR_BAD_SHAPE;
     if (check_params(params, n_params, 2 * (dims->n_hidden + 1)) != BESO_OK) return BESO_ERR_BAD_ARG;
-    if (!state || !pred || !sigma || !out || ((uintptr_t)state & 3) || ((uintptr_t)goal & 3) || ((uintptr_t)pred & 3) ||
-        ((uintptr_t)sigma & 3) || ((uintptr_t)out & 3))
+    if (!state || !pred || !sigma || !out || misaligned(state, 4) || misaligned(goal, 4) || misaligned(pred, 4) ||
+        misaligned(sigma, 4) || misaligned(out, 4))
         return BESO_ERR_BAD_ARG;
-    if (SIGMA && (!c_noise || ((uintptr_t)c_noise & 3))) return BESO_ERR_BAD_ARG;
+    if (SIGMA && (!c_noise || misaligned(c_noise, 4))) return BESO_ERR_BAD_ARG;
 
     Guide gd{};
     for (int l = 0; l <= dims->n_hidden; ++l) {
@@ -160,8 +163,9 @@ static int guide_apply(const float* const* params, int n_params, const beso_mlp_
     gd.state_steps = state_steps;
     gd.obs = obs_dim;
     gd.adim = act_dim;
-    gd.goal_stride = goal && goal_rows == B && B > 1 ? (long long)goal_steps * obs_dim : 0;
-    gd.goal_off = goal ? (long long)(goal_steps - 1) * obs_dim : 0;
+    const GoalRows g(goal, goal_steps, goal_rows, B, obs_dim);
+    gd.goal_stride = g.stride;
+    gd.goal_off = g.off;
     gd.lam = lam;
 
     return to_status(launch_lds_attr<guide_apply_kernel<SIGMA>>(kMaxLds, dim3(tile_grid(M)), dim3(kThreads), lds_bytes(dims),

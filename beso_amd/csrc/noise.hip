@@ -3,13 +3,14 @@
 //                        advances the per-environment counters, from one pair of arrays into another
 // A value depends on (key, episode, step, purpose, slab, element) only: no thread reads what another wrote.  Plain loads and
 // stores, no MFMA, no LDS, no atomics, no workspace.  The launch is bound by its round trip, not by its arithmetic.
-#include "common.h"
+#include "side_host.h"
 #include "../../include/beso_noise.h"
 
 #include <cmath>
-#include <cstdio>
 
 namespace beso_noise {
+
+using namespace beso_side;
 
 using beso::f32x4;
 using beso::u32x4;
@@ -128,15 +129,6 @@ __global__ __launch_bounds__(kThreads) void keyed_noise_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-static thread_local char g_error[192] = "";
-
-template <typename... A>
-static int refuse(int status, const char* fmt, A... a) {
-    snprintf(g_error, sizeof(g_error), fmt, a...);
-    return status;
-}
-
-static bool misaligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
 static bool overlap(const void* a, const void* b, size_t bytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + bytes && y < x + bytes;

@@ -6,13 +6,13 @@
 //                            writes the chosen window (the write-back of candidates_select_kernel, select.hip)
 // fp32 on v_mfma_f32_16x16x4_f32 through tile_xwt of mlp_tile.h.  Forward only: no keep buffer, no workspace, no atomics.
 #include "mlp_tile.h"
+#include "side_host.h"
 #include "../../include/beso_rank.h"
-
-#include <cstdio>
 
 namespace beso_rank {
 
 using namespace beso_mlp;
+using namespace beso_side;
 
 constexpr int kMaxLinear = 5;      // n_hidden <= 4
 
@@ -127,16 +127,6 @@ __global__ __launch_bounds__(kThreads) void rank_candidates_kernel(Rank rk, int 
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-static thread_local char g_error[224] = "";
-
-template <typename... A>
-static int refuse(int status, const char* fmt, A... a) {
-    snprintf(g_error, sizeof(g_error), fmt, a...);
-    return status;
-}
-
-static bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
-
 static int pitch_of(const beso_mlp_dims* d) { return tile_pitch(std::max(d->in_dim, d->hidden_dim)); }
 
 constexpr size_t kLdsMax = 2 * kTileBytes + (BESO_RANK_MAX_K + 4) * sizeof(float);
@@ -185,15 +175,15 @@ extern "C" int beso_rank_candidates(const float* const* params, int n_params, co
     if ((long long)W * act_dim > 0x7fffffffLL || (long long)W * obs_dim > 0x7fffffffLL || (long long)N * K > 0x7fffffffLL)
         return refuse(BESO_ERR_BAD_SHAPE, "%s: W act_dim = %lld / W obs_dim = %lld floats per row or N K = %lld rows exceed the int range", fn,
                       (long long)W * act_dim, (long long)W * obs_dim, (long long)N * K);
-    if (goal ? (goal_steps < 1 || (goal_rows != N && goal_rows != 1)) : (goal_steps != 0 || goal_rows != 0))
+    if (!GoalRows::valid(goal, goal_steps, goal_rows, N))
         return refuse(BESO_ERR_BAD_SHAPE, "%s: goal_steps = %d, goal_rows = %d: a goal is [N = %d or 1, goal_steps >= 1, obs_dim], and both are 0 without one",
                       fn, goal_steps, goal_rows, N);
     if (check_params(params, n_params, 2 * (dims->n_hidden + 1)) != BESO_OK)
         return refuse(BESO_ERR_BAD_ARG, "%s: params must be %d non-NULL 4-byte aligned device pointers, n_params = %d", fn,
                       2 * (dims->n_hidden + 1), n_params);
     if (!state || !x0_k || !lengths || !x0 || !index || !scores) return refuse(BESO_ERR_BAD_ARG, "%s: a NULL pointer", fn);
-    if (misaligned4(state) || misaligned4(goal) || misaligned4(x0_k) || misaligned4(lengths) || misaligned4(x0) || misaligned4(index) ||
-        misaligned4(scores))
+    if (misaligned(state, 4) || misaligned(goal, 4) || misaligned(x0_k, 4) || misaligned(lengths, 4) || misaligned(x0, 4) || misaligned(index, 4) ||
+        misaligned(scores, 4))
         return refuse(BESO_ERR_BAD_ARG, "%s: a pointer that is not 4-byte aligned", fn);
 
     Rank rk{};
@@ -216,8 +206,9 @@ extern "C" int beso_rank_candidates(const float* const* params, int n_params, co
     rk.obs = obs_dim;
     rk.adim = act_dim;
     rk.K = K;
-    rk.goal_stride = goal && goal_rows == N && N > 1 ? (long long)goal_steps * obs_dim : 0;
-    rk.goal_off = goal ? (long long)(goal_steps - 1) * obs_dim : 0;
+    const GoalRows g(goal, goal_steps, goal_rows, N, obs_dim);
+    rk.goal_stride = g.stride;
+    rk.goal_off = g.off;
 
     const int pitch = pitch_of(dims);
     const hipError_t e = launch_lds_attr<rank_candidates_kernel>(kLdsMax, dim3((unsigned)N), dim3(kThreads),

@@ -3,12 +3,12 @@
 //   rollout_end_minmax_kernel   a thread per (environment, action component): newest action, clip, remember, min-max un-scale
 // Copy work of a few KiB with two to four arithmetic operations per element, each stated on its own so that the bits are those of
 // the reference's torch expressions: no MFMA, no LDS, no atomics, no workspace.
-#include "common.h"
+#include "side_host.h"
 #include "../../include/beso_scale.h"
 
-#include <cstdio>
-
 namespace beso_scale {
+
+using namespace beso_side;
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 2048;
@@ -83,15 +83,6 @@ __global__ __launch_bounds__(kThreads) void rollout_end_minmax_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-static thread_local char g_error[192] = "";
-
-template <typename... A>
-static int refuse(int status, const char* fmt, A... a) {
-    snprintf(g_error, sizeof(g_error), fmt, a...);
-    return status;
-}
-
-static bool misaligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
 }  // namespace beso_scale
 

@@ -5,13 +5,14 @@
 //   candidates_select_kernel   a workgroup per environment holds its K newest-slot actions in LDS, forms their mean or their
 //                              kernel-density scores and argmax, and writes the chosen window
 // Copy work and a K x K x act loop: no MFMA, no atomics, no workspace, every sum sequential in a fixed order.
-#include "common.h"
+#include "side_host.h"
 #include "../../include/beso_select.h"
 
 #include <cmath>
-#include <cstdio>
 
 namespace beso_select {
+
+using namespace beso_side;
 
 using beso::f32x4;
 
@@ -175,16 +176,7 @@ __global__ __launch_bounds__(kThreads) void candidates_select_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-static thread_local char g_error[192] = "";
-
-template <typename... A>
-static int refuse(int status, const char* fmt, A... a) {
-    snprintf(g_error, sizeof(g_error), fmt, a...);
-    return status;
-}
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
+static bool aligned16(const void* p) { return !misaligned(p, 16); }
 
 }  // namespace beso_select
 
@@ -203,7 +195,7 @@ extern "C" int beso_candidates_expand(const float* state, const float* x, const 
         return refuse(BESO_ERR_BAD_SHAPE, "%s: N K = %lld rows or W obs_dim = %lld / W act_dim = %lld floats per row exceed the int range",
                       fn, (long long)N * K, (long long)W * obs_dim, (long long)W * act_dim);
     if (!state || !x || !lengths || !noise || !state_k || !x_k) return refuse(BESO_ERR_BAD_ARG, "%s: a NULL pointer", fn);
-    if (misaligned4(state) || misaligned4(x) || misaligned4(lengths) || misaligned4(noise) || misaligned4(state_k) || misaligned4(x_k))
+    if (misaligned(state, 4) || misaligned(x, 4) || misaligned(lengths, 4) || misaligned(noise, 4) || misaligned(state_k, 4) || misaligned(x_k, 4))
         return refuse(BESO_ERR_BAD_ARG, "%s: a pointer that is not 4-byte aligned", fn);
     const bool vs = (W * obs_dim) % 4 == 0 && aligned16(state) && aligned16(state_k);
     const bool vx = (W * act_dim) % 4 == 0 && aligned16(x) && aligned16(x_k);
@@ -237,7 +229,7 @@ extern "C" int beso_candidates_select(const float* x0_k, const int32_t* lengths,
         return refuse(BESO_ERR_BAD_ARG, "%s: mode %d is neither BESO_SELECT_MEAN nor BESO_SELECT_KDE", fn, mode);
     if (mode == BESO_SELECT_KDE && std::isnan(bandwidth)) return refuse(BESO_ERR_BAD_ARG, "%s: the bandwidth is NaN", fn);
     if (!x0_k || !lengths || !x0 || !index || !scores) return refuse(BESO_ERR_BAD_ARG, "%s: a NULL pointer", fn);
-    if (misaligned4(x0_k) || misaligned4(lengths) || misaligned4(x0) || misaligned4(index) || misaligned4(scores))
+    if (misaligned(x0_k, 4) || misaligned(lengths, 4) || misaligned(x0, 4) || misaligned(index, 4) || misaligned(scores, 4))
         return refuse(BESO_ERR_BAD_ARG, "%s: a pointer that is not 4-byte aligned", fn);
     const double scott = std::pow((double)K, -1.0 / (double)(act_dim + 4));
     const size_t lds = select_lds_floats(K, act_dim) * sizeof(float);

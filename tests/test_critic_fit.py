@@ -282,7 +282,8 @@ def test_trainer_constructor_refuses_by_name():
 
 
 def _untouched(tr, before):
-    assert tr._bufs == {} and tr._flat == {} and tr.per_row_q is None and tr.per_row_v is None and tr.advantage is None
+    assert all(net.bufs == {} and net.flat is None for net in (tr._q, tr._v))
+    assert tr.per_row_q is None and tr.per_row_v is None and tr.advantage is None
     assert tr.q_optimizer._groups == [None] and tr.v_optimizer._groups == [None] and tr.target.version == 0
     assert all(p.grad is None for p in (*tr.q_params, *tr.v_params))
     assert all(torch.equal(a, b) for a, b in zip(before, (*tr.q_params, *tr.v_params, *tr.q_target_params)))

@@ -64,12 +64,13 @@ def torch_ops_step(tr, state, action, goal, reward, done, weight):
     g = goal[:, -1:, :].expand(B, T, -1)
     q_rows = torch.cat([state[:, :T], action, g], dim=-1).reshape(M, -1)
     v_rows = torch.cat([torch.cat([state[:, :T], g], dim=-1).reshape(M, -1), torch.cat([state[:, 1:T + 1], g], dim=-1).reshape(M, -1)])
-    b = tr._buffers(M, q_rows.device)
-    flat_q, flat_v = tr._grads("q", q_rows.device), tr._grads("v", q_rows.device)
-    qn.run_forward(q_rows, keep=True, params=tr.q_params, out=b["q"], keep_out=b["keep_q"])
-    qn.run_forward(q_rows, keep=False, params=tr.q_target_params, out=b["q_target"])
-    vn.run_forward(v_rows, keep=True, params=tr.v_params, out=b["v"], keep_out=b["keep_v"])
-    q, q_target, v, v_next = b["q"].view(-1), b["q_target"].view(-1), b["v"].view(-1)[:M], b["v"].view(-1)[M:]
+    (_, q, keep_q, _, ws_q, q_target) = tr._q.buffers(M, q_rows.device, spare_out=True)
+    (_, v, keep_v, _, ws_v) = tr._v.buffers(2 * M, q_rows.device, zero_d_out=True)
+    flat_q, flat_v = tr._q.grads(q_rows.device), tr._v.grads(q_rows.device)
+    qn.run_forward(q_rows, keep=True, params=tr.q_params, out=q, keep_out=keep_q)
+    qn.run_forward(q_rows, keep=False, params=tr.q_target_params, out=q_target)
+    vn.run_forward(v_rows, keep=True, params=tr.v_params, out=v, keep_out=keep_v)
+    q, q_target, v, v_next = q.view(-1), q_target.view(-1), v.view(-1)[:M], v.view(-1)[M:]
     w = torch.ones_like(q) if weight is None else weight.reshape(-1)
     S = w.sum()
     u = q_target - v
@@ -79,8 +80,8 @@ def torch_ops_step(tr, state, action, goal, reward, done, weight):
     dq = w * (2.0 * d) / S
     dv = torch.cat([w * (-2.0 * e * u) / S, torch.zeros_like(u)])
     tr.advantage = u.view(B, T)
-    qn.run_backward(b["keep_q"], dq, flat_q, params=tr.q_params, workspace=b["ws_q"])
-    vn.run_backward(b["keep_v"], dv, flat_v, params=tr.v_params, workspace=b["ws_v"])
+    qn.run_backward(keep_q, dq, flat_q, params=tr.q_params, workspace=ws_q)
+    vn.run_backward(keep_v, dv, flat_v, params=tr.v_params, workspace=ws_v)
     tr.q_optimizer.step(ema=tr.target)
     tr.v_optimizer.step()
     return loss_q, loss_v

@@ -63,8 +63,8 @@ def torch_ops_step(tr, state, action, goal, target, weight, sigma, noise):
     if guide.use_sigma:
         parts.append((sigma.log() / 4).view(B, 1, 1).expand(B, T, 1))
     rows = torch.cat(parts, dim=-1).reshape(B * T, -1)
-    _, q, keep, _, workspace = tr._buffers(B * T, rows.device)
-    flat = tr._grads(rows.device)
+    _, q, keep, _, workspace = tr._net.buffers(B * T, rows.device)
+    flat = tr._net.grads(rows.device)
     net.run_forward(rows, keep=True, params=tr.params, out=q, keep_out=keep)
     d = q.view(-1) - target.reshape(-1)
     w = weight.reshape(-1)
